@@ -21,13 +21,23 @@ receiver on its own 16.368 Msps int8 IQ stream in HBM, one 1-ms correlator
 call per step (NCO words replayed from a command schedule: the DLL/PLL is
 host code and not part of the hot path).
 
-Run: python bench.py [--gpus N --steps K --warmup W].  For N>1 under
+Run: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].
+A plain run times the primary line alone: set-up, W warm-up steps, K timed steps,
+the result line with the contract's keys (`ms_per_step`: milliseconds per timed
+step).  --full adds everything else: the one-record search, the fp32 path, every
+secondary section, the CPU baselines (--no-cpu-baseline leaves those out) and the
+detail file; those sections follow --steps up to 50 and --warmup up to 10 (several
+keep distinct IF for every call resident), the primary line takes both as given.
+--dump-outputs DIR writes what the primary line's last timed step
+left in the caller's buffers, every field of the per-PRN results and of the
+per-(PRN, bin) rows as DIR/<name>.npy (float64); the inputs are seeded, so two
+builds can be compared array by array.  For N>1 under
 torch.distributed.run the launcher's RANK/WORLD_SIZE env is used; without it
 bench.py starts the N rank processes itself (launch_ranks).  Ranks synchronise
 over a host socket (gnsscorr/hostgroup.py, no torch.distributed) only for the
 barrier, the max-over-ranks time and a small result gather.
 
-Output: ONE JSON line on rank 0 -- the contract's keys first, then every
+Output: ONE JSON line on rank 0 -- the contract's keys first, then (--full) every
 secondary section without its descriptive strings (floats to 4 significant
 digits), tracking lines last; the full result, descriptions included, goes to
 gpurun_out/bench_detail.json.
@@ -73,6 +83,7 @@ SGT_RX, SGT_FS = 256, 16.0e6                   # GLONASS records: initSettings.s
 SGT_DP_PER_SAMPLE = 27                         # fp64 ops/sample of sgt_track_kernel
 PEAK_FP64_TFLOPS = 78.6                        # MI355X FP64 vector (AMD spec; not in the guide)
 TRACK_OPS_PER_SAMPLE = 20                      # SURVEY 8d integer-op model
+FULL_MAX_STEPS, FULL_MAX_WARMUP = 50, 10      # --full: caps of the secondary sections' counts
 EV_EVERY = 1                                   # kernel-timed steps: 1 of EV_EVERY (every step)
 METRIC = "1ms E/P/L correlations/sec + acquisition cells/sec @16.368Msps; 1/2/4/8 GPU"
 
@@ -152,7 +163,7 @@ def acq_step(ctx, b, ev=None):
                    b["d_res"].ptr)
 
 
-def run_acq(dist, dev, steps, warmup, precision=gc.ACQ_F64, records=None):
+def run_acq(dist, dev, steps, warmup, precision=gc.ACQ_F64, records=None, keep_outputs=False):
     if records is None:
         records = ACQ_RECORDS if precision == gc.ACQ_F64 else 1
     ctx, b, meta = acq_setup(dev, dist.rank, precision, records)
@@ -180,6 +191,12 @@ def run_acq(dist, dev, steps, warmup, precision=gc.ACQ_F64, records=None):
     dist.barrier()
     dt = dist.max(t1 - t0)
     corr_ms = float(np.mean([a.elapsed_ms(z) for a, z in evs.values()]))
+    outputs = None
+    if keep_outputs:
+        # what the last timed step left for the caller: results and rows
+        outputs = dict(
+            result=b["d_res"].download(gc.ACQ_RESULT).reshape(records, N_PRN),
+            row=b["d_rows"].download(gc.ACQ_ROW).reshape(records, N_PRN, N_BINS))
     with_codes = None
     if records == 1:
         # the cold start with the code spectra inside it (acquisition.sci:91-95 per
@@ -210,7 +227,20 @@ def run_acq(dist, dev, steps, warmup, precision=gc.ACQ_F64, records=None):
             found=sum(1 for p in meta["planted"] if res[0][p - 1]["metric"] > 2.5))
     return dict(dt=dt, corr_ms=dist.max(corr_ms), found=found,
                 n_planted=len(meta["planted"]) * records, records=records, meta=meta,
-                with_codes=with_codes)
+                with_codes=with_codes, outputs=outputs)
+
+
+def dump_outputs(path, outputs, rank):
+    """--dump-outputs: every named field of the result and row records as
+    <path>/<array>_<field>.npy in float64 (the int32 fields are exact there); ranks
+    above 0 add _rank<r> to the name."""
+    os.makedirs(path, exist_ok=True)
+    tail = f"_rank{rank}" if rank else ""
+    for name, arr in outputs.items():
+        for field in arr.dtype.names:
+            if not field.startswith("pad"):
+                np.save(os.path.join(path, f"{name}_{field}{tail}.npy"),
+                        np.ascontiguousarray(arr[field], dtype=np.float64))
 
 
 GENERIC_FS = 38.192e6   # the classic SoftGNSS front end (acquisition.sci: samplesPerCode 38192)
@@ -1438,7 +1468,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--skip-track", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the one-record search, the fp32 path, every secondary "
+                         "section and the CPU baselines, and write the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's results and rows as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no external launcher: one child process per rank, before any HIP call
         raise SystemExit(launch_ranks(a.gpus, sys.argv[1:]))
@@ -1451,25 +1488,34 @@ def main():
         raise SystemExit("bench.py: no HIP device visible")
     dev = dist.local % n_dev     # one rank per GPU; wraps only when rehearsing on fewer GPUs
 
-    acq = run_acq(dist, dev, a.steps, a.warmup, gc.ACQ_F64)
+    acq = run_acq(dist, dev, a.steps, a.warmup, gc.ACQ_F64, keep_outputs=bool(a.dump_outputs))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, acq["outputs"], dist.rank)
+    # everything below the primary line runs with --full only
+    if not a.full:
+        a.skip_track = True
+    # their step counts follow --steps up to the default's 50 (--warmup up to 10): several
+    # sections keep distinct IF for every call resident (run_track_io: 0.4 GB per step), so
+    # a long primary run would otherwise not fit the device
+    s2, w2 = min(a.steps, FULL_MAX_STEPS), min(a.warmup, FULL_MAX_WARMUP)
     # one search alone per launch: the cold-start latency north_star asks for (< 1 ms wall)
-    acq1 = run_acq(dist, dev, max(a.steps, 20), a.warmup, gc.ACQ_F64, records=1)
-    acq32 = None if a.skip_track else run_acq(dist, dev, a.steps, a.warmup, gc.ACQ_F32)
+    acq1 = run_acq(dist, dev, max(s2, 20), w2, gc.ACQ_F64, records=1) if a.full else None
+    acq32 = None if a.skip_track else run_acq(dist, dev, s2, w2, gc.ACQ_F32)
     rank_info = dist.gather(dict(rank=dist.rank, device=dev, pci_bus_id=gc.pci_bus_id(dev),
                                  hip_runtime=gc.hip_runtime()))
-    trk = None if a.skip_track else run_track(dist, dev, max(a.steps, 20), a.warmup)
-    tio = None if a.skip_track else run_track_io(dist, dev, max(a.steps, 20), a.warmup)
-    sgt = None if a.skip_track else run_sgt(dist, dev, max(a.steps, 20), a.warmup)
-    sgt_c4 = None if a.skip_track else run_sgt(dist, dev, max(a.steps, 20), a.warmup, FS)
+    trk = None if a.skip_track else run_track(dist, dev, max(s2, 20), w2)
+    tio = None if a.skip_track else run_track_io(dist, dev, max(s2, 20), w2)
+    sgt = None if a.skip_track else run_sgt(dist, dev, max(s2, 20), w2)
+    sgt_c4 = None if a.skip_track else run_sgt(dist, dev, max(s2, 20), w2, FS)
     # (20 timed searches after 5 warmups: 5 timed after 2 read 1.44 ms against 1.37-1.39
     # in steady state, profiles/r6/fullsky_generic_steps_r7o.log)
-    sky = None if a.skip_track else run_fullsky(dist, dev, max(a.steps, 10), 5)
-    sdr = None if a.skip_track else run_sdr(dist, dev, max(a.steps // 2, 10), 2)
-    gco = None if a.skip_track else run_glo_coherent(dist, dev, max(a.steps, 10), 5)
+    sky = None if a.skip_track else run_fullsky(dist, dev, max(s2, 10), 5)
+    sdr = None if a.skip_track else run_sdr(dist, dev, max(s2 // 2, 10), 2)
+    gco = None if a.skip_track else run_glo_coherent(dist, dev, max(s2, 10), 5)
     # (20 timed searches after 5 warmups: 10 timed after 3 read 0.99-1.00 ms against
     # 0.94-0.95 at 20, profiles/r6/fullsky_generic_steps_r7o.log)
-    gen = None if a.skip_track else run_acq_generic(dist, dev, max(a.steps, 10), 5)
-    gsc = None if a.skip_track else run_gps_scilab(dist, dev, max(a.steps, 10), 5)
+    gen = None if a.skip_track else run_acq_generic(dist, dev, max(s2, 10), 5)
+    gsc = None if a.skip_track else run_gps_scilab(dist, dev, max(s2, 10), 5)
 
     if dist.rank == 0:
         W = dist.world
@@ -1501,7 +1547,8 @@ def main():
                          **hbm_fields(pmc_traffic(ACQ64_KERNEL, "acq"), acq["corr_ms"] * 1e-3),
                          "hbm_algorithmic_bytes_per_launch": acq_alg_bytes(R)},
             "ms_per_search": acq["dt"] / a.steps / R * 1e3,
-            "single_search": {"ms_per_search": acq1["dt"] / max(a.steps, 20) * 1e3,
+            "single_search": None if acq1 is None else {
+                              "ms_per_search": acq1["dt"] / max(s2, 20) * 1e3,
                               "corr_kernel_ms": acq1["corr_ms"],
                               "with_codes": acq1["with_codes"],
                               "note": "one 2-ms record per launch (records_per_step = 1): the "
@@ -1521,12 +1568,12 @@ def main():
             "ranks": rank_info,
         }
         if acq32:
-            cells = CELLS_PER_SEARCH * a.steps * W
+            cells = CELLS_PER_SEARCH * s2 * W
             a32 = flop_launch / R / (acq32["corr_ms"] * 1e-3) / 1e12
             out["acquisition_f32"] = {
                 "metric": "acquisition cells/sec (config 2, single-precision fast path)",
                 "value": cells / acq32["dt"], "unit": "cells/s", "dtype": "f32",
-                "ms_per_step": acq32["dt"] / a.steps * 1e3,
+                "ms_per_step": acq32["dt"] / s2 * 1e3,
                 "note": "rows within 2e-5 of the row max of fp64 (tests/test_acq_gpu.py[f32]); "
                         "not the reference's precision",
                 "roofline": {"bound": "valu", "kernel": "acq_corr_pipe_kernel", "achieved": a32,
@@ -1840,7 +1887,9 @@ def main():
                              "frac": fe_bytes / (sdr["ms_fe"] * 1e-3) / 1e9 / PEAK_HBM_GBS,
                              **pmc_hbm("sdr", "gn3s_kernel", sdr["ms_fe"] * 1e-3)},
             }
-        if W == 1 and not a.no_cpu_baseline:
+        if not a.full:
+            del out["single_search"]
+        if a.full and W == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_acq(acq["meta"])
             if trk:
                 tb = cpu_baseline_track()
@@ -1862,7 +1911,8 @@ def main():
                 cb = cpu_baseline_sdr_channel(sdr["ch_corr"])
                 if cb:
                     out["sdr_channel"]["cpu_baseline"] = cb
-        write_detail(out)
+        if a.full:
+            write_detail(out)
         print(json.dumps(result_line(out), separators=(",", ":")), flush=True)
     dist.close()
 

@@ -8,6 +8,8 @@ import os
 import sys
 from contextlib import redirect_stdout
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -40,7 +42,8 @@ class _Dist:
 def test_bench_main_assembles_the_json_line(monkeypatch):
     sys.path.insert(0, ROOT)
     import bench
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--no-cpu-baseline"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline",
+                                      "--steps", "4000", "--warmup", "100"])
     monkeypatch.setattr(bench.gc, "lib", lambda: None)
     monkeypatch.setattr(bench.gc, "device_count", lambda: 1)
     monkeypatch.setattr(bench.gc, "pci_bus_id", lambda d: "0000:00:00.0")
@@ -61,14 +64,26 @@ def test_bench_main_assembles_the_json_line(monkeypatch):
         run_glo_coherent=lambda *a, **k: _D(found=4, n_planted=4),
         run_gps_scilab=lambda *a, **k: _D(found=6, n_planted=6, nb=113, n=16000),
         run_acq_generic=lambda *a, **k: _D(found=8, n_planted=8, fs=38.192e6, n=38192))
+    given = []   # (section, steps, warmup) as main() calls them
+
+    def recorded(name, fn):
+        def run(dist, dev, steps, warmup, *a, **k):
+            given.append((name, steps, warmup))
+            return fn(dist, dev, steps, warmup, *a, **k)
+        return run
     for k, v in stubs.items():
-        monkeypatch.setattr(bench, k, v)
+        monkeypatch.setattr(bench, k, recorded(k, v))
     buf = io.StringIO()
     with redirect_stdout(buf):
         bench.main()
     lines = [ln for ln in buf.getvalue().splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
+    # the primary line takes --steps as given; every other section stays within the
+    # default's counts, whose resident IF (0.4 GB per step in run_track_io) fits the device
+    assert given[0] == ("run_acq", 4000, 100) and d["steps"] == 4000
+    assert {name for name, _, _ in given} == set(stubs)
+    assert all(s <= bench.FULL_MAX_STEPS and w <= bench.FULL_MAX_WARMUP for _, s, w in given[1:])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
                 "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
                 "roofline"):
@@ -88,6 +103,58 @@ def test_bench_main_assembles_the_json_line(monkeypatch):
     assert len(lines[0]) < 6800, len(lines[0])
     assert list(d)[-1] == "tracking"
     assert "glonass_tracking" in d and "fullsky" in d and "shard_projection" in d["fullsky"]
+
+
+def test_plain_run_is_the_primary_line_alone(monkeypatch, tmp_path):
+    """Without --full only the config-2 fp64 search runs, once, with --steps timed
+    steps; the line keeps the contract's keys and --dump-outputs writes every field
+    of the results and rows as float64 .npy files."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2",
+                                      "--dump-outputs", str(tmp_path / "out")])
+    monkeypatch.setattr(bench.gc, "lib", lambda: None)
+    monkeypatch.setattr(bench.gc, "device_count", lambda: 1)
+    monkeypatch.setattr(bench.gc, "pci_bus_id", lambda d: "0000:00:00.0")
+    monkeypatch.setattr(bench.gc, "hip_runtime", lambda: "stub")
+    monkeypatch.setattr(bench, "Dist", _Dist)
+    monkeypatch.setattr(bench, "write_detail", lambda out: pytest.fail("detail file in a plain run"))
+    calls = []
+    res = np.zeros((16, 32), bench.gc.ACQ_RESULT)
+    res["code_phase"] = np.arange(16 * 32).reshape(16, 32)
+    rows = np.zeros((16, 32, 41), bench.gc.ACQ_ROW)
+    rows["peak"] = 0.5
+
+    def run_acq(dist, dev, steps, warmup, precision, records=None, keep_outputs=False):
+        calls.append((steps, warmup, precision, records, keep_outputs))
+        return _D(records=16, dt=0.014, meta=_D(set_codes_ms=1.0), found=8, n_planted=8,
+                  outputs=dict(result=res, row=rows))
+    monkeypatch.setattr(bench, "run_acq", run_acq)
+    for name in ("run_track", "run_track_io", "run_sgt", "run_fullsky", "run_sdr",
+                 "run_glo_coherent", "run_gps_scilab", "run_acq_generic", "cpu_baseline_acq"):
+        monkeypatch.setattr(bench, name, lambda *a, _n=name, **k: pytest.fail(_n + " in a plain run"))
+    buf = io.StringIO()
+    with redirect_stdout(buf):
+        bench.main()
+    assert calls == [(7, 2, bench.gc.ACQ_F64, None, True)]
+    lines = [ln for ln in buf.getvalue().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+                "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
+                "roofline"):
+        assert key in d, key
+    assert d["steps"] == 7 and d["ms_per_step"] == pytest.approx(2.0)
+    assert d["value"] == pytest.approx(bench.CELLS_PER_SEARCH * 7 * 16 / 0.014)
+    assert not set(bench.SECTION_ORDER) & set(d) - {"executed_fp64", "ranks"}
+    got = sorted(os.listdir(tmp_path / "out"))
+    assert got == sorted([f"result_{f}.npy" for f in ("peak", "second", "metric", "bin",
+                                                       "code_phase", "carr_freq")] +
+                         [f"row_{f}.npy" for f in ("peak", "second", "argmax", "block")])
+    cp = np.load(tmp_path / "out" / "result_code_phase.npy")
+    assert cp.dtype == np.float64 and np.array_equal(cp, res["code_phase"])
+    assert np.load(tmp_path / "out" / "row_peak.npy").shape == (16, 32, 41)
 
 
 def test_bench_launches_n_ranks_itself():

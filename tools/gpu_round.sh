@@ -23,22 +23,22 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.
 tail -1 $O/smoke.log
 echo "== bench (the driver's command, wall-timed)"
 s0=$(date +%s.%N)
-timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+timeout -k 10 500 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 s1=$(date +%s.%N)
 python3 -c "print('wall_s', round($s1-$s0, 1))" | tee $O/bench.wall
 cp gpurun_out/bench_detail.json $O/bench_detail.json   # (the profiled run below rewrites it)
 cut -c1-400 $O/bench.json
 echo "== rocprofv3 kernel-trace stats"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- \
-  python3 bench.py --no-cpu-baseline > $O/prof.log 2>&1
+  python3 bench.py --full --no-cpu-baseline > $O/prof.log 2>&1
 python3 tools/trace_by_grid.py $O/prof acq64_corr_kernel $O/acq64_trace_by_grid.json \
-  "rocprofv3 --kernel-trace of python3 bench.py --no-cpu-baseline ($TAG)"
+  "rocprofv3 --kernel-trace of python3 bench.py --full --no-cpu-baseline ($TAG)"
 fi
 if [ $PART = main ]; then echo "== done (main)"; exit 0; fi
 echo "== pmc"
 # the committed traffic file is the base: every pass below updates its entries
 cp profiles/pmc_traffic.json $O/pmc_traffic.json
-B="python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline"
+B="python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline"
 if [ $PART != pmcB ]; then
 i=0
 for C in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_BUSY_CYCLES" \
