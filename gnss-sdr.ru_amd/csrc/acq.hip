@@ -1506,9 +1506,10 @@ __global__ __launch_bounds__(256) void acq_symmetrize_kernel(float2* __restrict_
     Fc[(sn / M16) * kPlane + sn % M16] = make_float2(v.x, -v.y);
 }
 
-// spectra of the n_codes int8 replicas at d (device), kept resident
-static int codes_spectra(gnsscorr_acq_ctx* c, const int8_t* d, int n_codes) {
-  if (c->prec == GNSSCORR_ACQ_F64) return acq64_set_codes(c, d, n_codes);
+// spectra of the n_codes int8 replicas at d (device), kept resident; code_len < n_samples:
+// the replicas are zero from code_len on (set_codes_padded)
+static int codes_spectra(gnsscorr_acq_ctx* c, const int8_t* d, int n_codes, int code_len) {
+  if (c->prec == GNSSCORR_ACQ_F64) return acq64_set_codes(c, d, n_codes, code_len);
   int rc = forward_launch(c, d, 0, 1, nullptr, 1, n_codes, c->d_F, nullptr, nullptr);
   if (rc) return rc;
   hipLaunchKernelGGL(acq_symmetrize_kernel, dim3((n_codes * N + 255) / 256), dim3(256), 0,
@@ -1528,7 +1529,45 @@ extern "C" int gnsscorr_acq_set_codes(gnsscorr_acq_ctx* c, int n_codes, const in
   int rc = acq_grow((void**)&c->d_codes8, &c->cap_codes8, bytes, 1);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(c->d_codes8, h_codes, bytes, hipMemcpyHostToDevice, c->stream));
-  rc = codes_spectra(c, c->d_codes8, n_codes);
+  rc = codes_spectra(c, c->d_codes8, n_codes, c->cfg.n_samples);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->n_codes = n_codes;
+  return GNSSCORR_OK;
+}
+
+// replica r: its code_len chips, then zeros up to L
+__global__ __launch_bounds__(256) void pad_codes_kernel(const int8_t* __restrict__ chips,
+                                                        int code_len, int L, long total,
+                                                        int8_t* __restrict__ out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const long r = i / L;
+  const int n = (int)(i - r * L);
+  out[i] = n < code_len ? chips[r * code_len + n] : (int8_t)0;
+}
+
+extern "C" int gnsscorr_acq_set_codes_padded(gnsscorr_acq_ctx* c, int n_codes,
+                                             const int8_t* h_codes, int code_len) {
+  if (!c || !h_codes || n_codes < 1 || n_codes > c->cfg.max_codes || code_len < 1 ||
+      code_len > c->cfg.n_samples) {
+    gnsscorr_set_error("gnsscorr_acq_set_codes_padded: bad arguments (n_codes %d, max %d, "
+                       "code_len %d, n_samples %d)", n_codes, c ? c->cfg.max_codes : 0, code_len,
+                       c ? c->cfg.n_samples : 0);
+    return GNSSCORR_EINVAL;
+  }
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  // d_codes8: the zero-extended replicas, then the chips as uploaded
+  const size_t L = (size_t)c->cfg.n_samples, ext = (size_t)n_codes * L;
+  int rc = acq_grow((void**)&c->d_codes8, &c->cap_codes8, ext + (size_t)n_codes * code_len, 1);
+  if (rc) return rc;
+  int8_t* d_chips = c->d_codes8 + ext;
+  HIP_TRY(hipMemcpyAsync(d_chips, h_codes, (size_t)n_codes * code_len, hipMemcpyHostToDevice,
+                         c->stream));
+  hipLaunchKernelGGL(pad_codes_kernel, dim3((unsigned)((ext + 255) / 256)), dim3(256), 0,
+                     c->stream, d_chips, code_len, (int)L, (long)ext, c->d_codes8);
+  HIP_TRY(hipGetLastError());
+  rc = codes_spectra(c, c->d_codes8, n_codes, code_len);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->n_codes = n_codes;
@@ -1606,7 +1645,7 @@ extern "C" int gnsscorr_acq_set_prn_codes(gnsscorr_acq_ctx* c, int n_codes,
                        n, c->cfg.samp_rate, c->d_codes8 + (size_t)b * n);
     HIP_TRY(hipGetLastError());
   }
-  rc = codes_spectra(c, c->d_codes8, n_codes);
+  rc = codes_spectra(c, c->d_codes8, n_codes, c->cfg.n_samples);
   if (rc) return rc;
   c->n_codes = n_codes;
   return GNSSCORR_OK;
@@ -1682,6 +1721,12 @@ static int forward_launch(gnsscorr_acq_ctx* c, const int8_t* src, int iq, int n_
 }
 
 static int check_search(gnsscorr_acq_ctx* c, int n_blocks, int n_freqs, int mode) {
+  if (c->keep && (c->prec != GNSSCORR_ACQ_F64 || c->plan64 != 3 || c->coh > 1 || c->recs > 1 ||
+                  c->d_group_rec)) {
+    gnsscorr_set_error("gnsscorr_acq: a zero-padded search needs the fp64 generic engine, one "
+                       "code period per block, one record and no group-record table");
+    return GNSSCORR_EINVAL;
+  }
   if (n_blocks < 1 || n_blocks * c->coh * c->recs > c->cfg.max_blocks || n_freqs < 1 ||
       n_freqs > c->cfg.max_freqs || c->n_codes < 1 ||
       (mode != GNSSCORR_ACQ_BEST_OF_BLOCKS && mode != GNSSCORR_ACQ_NONCOHERENT)) {
@@ -1734,7 +1779,8 @@ static int correlate_launch(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_g
                             gnsscorr_acq_result* d_res, double* d_dump, int dump_block) {
   int rc = check_search(c, n_blocks, c->spec_freqs > 0 ? c->spec_freqs : 1, mode);
   if (rc) return rc;
-  if (n_groups < 1 || n_bins < 1 || spc < 1 || spc > c->cfg.n_samples / 2 ||
+  if (n_groups < 1 || n_bins < 1 || spc < 1 ||
+      spc > (c->keep ? c->keep : c->cfg.n_samples) / 2 ||
       n_blocks != c->spec_blocks ||
       (c->prec == GNSSCORR_ACQ_F64 && c->spec_recs != c->recs)) {
     gnsscorr_set_error("gnsscorr_acq_correlate: bad arguments (groups %d, bins %d, spc %d, "
@@ -1947,8 +1993,10 @@ extern "C" int gnsscorr_acq_power_row(gnsscorr_acq_ctx* c, const int8_t* h_if, i
   const int32_t gc = code, gf = 0;
   const int recs = c->recs;   // one record, whatever set_records says
   const int32_t* grec = c->d_group_rec;   // and no per-group records
+  const int keep = c->keep;   // and the full row of a zero-padded context
   c->recs = 1;
   c->d_group_rec = nullptr;
+  c->keep = 0;
   int rc = stage_host(c, h_if, iq, n_blocks, 1, &freq, 1, 1, &gc, &gf);
   if (!rc && !c->d_dump && hipMalloc(&c->d_dump, sizeof(double) * c->cfg.n_samples) != hipSuccess) {
     gnsscorr_set_error("gnsscorr_acq_power_row: out of device memory");
@@ -1959,6 +2007,7 @@ extern "C" int gnsscorr_acq_power_row(gnsscorr_acq_ctx* c, const int8_t* h_if, i
                        1, c->d_gcode, c->d_gfreq, 16, c->d_rows, nullptr, c->d_dump, block);
   c->recs = recs;
   c->d_group_rec = grec;
+  c->keep = keep;
   c->spec_blocks = 0;   // its one-record spectra must not serve a later multi-record correlate
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(h_power, c->d_dump, sizeof(double) * c->cfg.n_samples,
@@ -1972,6 +2021,11 @@ extern "C" int gnsscorr_acq_set_coherent(gnsscorr_acq_ctx* c, int coh_ms) {
     gnsscorr_set_error("gnsscorr_acq_set_coherent: need 1 <= coh_ms <= max_blocks");
     return GNSSCORR_EINVAL;
   }
+  if (coh_ms > 1 && c->keep) {
+    gnsscorr_set_error("gnsscorr_acq_set_coherent: a zero-padded search (set_zero_padded) takes "
+                       "one code period per block");
+    return GNSSCORR_EINVAL;
+  }
   c->coh = coh_ms;
   c->spec_blocks = 0;   // resident spectra were made with the previous setting
   return GNSSCORR_OK;
@@ -1982,6 +2036,11 @@ extern "C" int gnsscorr_acq_set_group_records(gnsscorr_acq_ctx* c, const int32_t
   if (d_group_rec && (c->prec != GNSSCORR_ACQ_F64 || c->plan64 == 3)) {
     gnsscorr_set_error("gnsscorr_acq_set_group_records: needs the fp64 precision and a compiled "
                        "plan (N = 16368 or 16000)");
+    return GNSSCORR_EINVAL;
+  }
+  if (d_group_rec && c->keep) {
+    gnsscorr_set_error("gnsscorr_acq_set_group_records: not with a zero-padded search "
+                       "(set_zero_padded)");
     return GNSSCORR_EINVAL;
   }
   // the caller keeps it alive; values outside [0, records) are clamped into that range
@@ -2003,10 +2062,40 @@ extern "C" int gnsscorr_acq_set_records(gnsscorr_acq_ctx* c, int n_records) {
                        "generic plan (no prime factor above 31)", 16368, 16000);
     return GNSSCORR_EINVAL;
   }
+  if (n_records > 1 && c->keep) {
+    gnsscorr_set_error("gnsscorr_acq_set_records: a zero-padded search (set_zero_padded) takes "
+                       "one record");
+    return GNSSCORR_EINVAL;
+  }
   // a per-group record table was made for the previous record count: set it again
   if (n_records != c->recs) c->d_group_rec = nullptr;
   c->recs = n_records;
   c->spec_blocks = 0;   // resident spectra were made with the previous setting
+  return GNSSCORR_OK;
+}
+
+extern "C" int gnsscorr_acq_set_zero_padded(gnsscorr_acq_ctx* c, int keep) {
+  if (!c || keep < 0 || keep > c->cfg.n_samples) {
+    gnsscorr_set_error("gnsscorr_acq_set_zero_padded: need 0 <= keep <= n_samples");
+    return GNSSCORR_EINVAL;
+  }
+  if (keep > 0) {
+    const char* why = c->prec != GNSSCORR_ACQ_F64 ? "the fp64 precision"
+                      : c->plan64 != 3 ? "the generic engine (not the compiled plans of "
+                                         "n_samples 16368 and 16000)"
+                      : c->coh > 1     ? "one code period per block (set_coherent(1))"
+                      : c->recs > 1    ? "one record per search (set_records(1))"
+                      : c->d_group_rec ? "no group-record table"
+                                       : nullptr;
+    if (why) {
+      gnsscorr_set_error("gnsscorr_acq_set_zero_padded: a zero-padded search needs %s", why);
+      return GNSSCORR_EINVAL;
+    }
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    const int rc = acq64_set_zero_padded(c, keep);
+    if (rc) return rc;
+  }
+  c->keep = keep;
   return GNSSCORR_OK;
 }
 

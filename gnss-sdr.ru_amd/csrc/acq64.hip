@@ -326,6 +326,24 @@ __device__ __forceinline__ void dft(v2d (&x)[R]) {
   }
 }
 
+// outputs 0 .. R/2-1 of an even-length DFT, by decimation in time: X_k = E_k + W_R^k O_k
+// (E, O the R/2-point DFTs of the even and the odd inputs); the other half,
+// X_{k+R/2} = E_k - W_R^k O_k, is not formed
+template <int R>
+__device__ __forceinline__ void dft_first_half(const v2d (&x)[R], v2d (&o)[R / 2]) {
+  static_assert(R % 2 == 0, "even length");
+  v2d e[R / 2], d[R / 2];
+#pragma unroll
+  for (int n = 0; n < R / 2; n++) {
+    e[n] = x[2 * n];
+    d[n] = x[2 * n + 1];
+  }
+  dft<R / 2>(e);
+  dft<R / 2>(d);
+#pragma unroll
+  for (int k = 0; k < R / 2; k++) o[k] = e[k] + twc<R>(d[k], k);
+}
+
 // ---- plans -----------------------------------------------------------------------
 // N = R1 R2 R3.  Positions between stages (same for both kinds):
 //   after stage 1: k1*G1 + g,       g = n2*R3 + n3   (G1 = R2*R3 = stage-1 groups)
@@ -1472,12 +1490,13 @@ __global__ __launch_bounds__(kGThreads) void g_post_kernel(const v2d* __restrict
   out[(long)blockIdx.y * rs + k] = cmul((v2d){d.x * inv, -d.y * inv}, chirp[k]);
 }
 
-// powers |DFT_N(Y)|^2 / N^2 = |D_k|^2 / (M N)^2, stored or added
+// powers |DFT_N(Y)|^2 / N^2 = |D_k|^2 / (M N)^2, stored or added; lags k < n_out
+// (N, or the kept lags of a zero-padded search) of rows of stride N
 __global__ __launch_bounds__(kGThreads) void g_power_kernel(const v2d* __restrict__ D, int N,
                                                             int M, int acc,
-                                                            double* __restrict__ pw) {
+                                                            double* __restrict__ pw, int n_out) {
   const int k = blockIdx.x * kGThreads + threadIdx.x;
-  if (k >= N) return;
+  if (k >= n_out) return;
   const v2d d = D[(long)blockIdx.y * M + k];
   const double sc = 1.0 / ((double)M * (double)N);
   const double p = fma(d.x * sc, d.x * sc, (d.y * sc) * (d.y * sc));
@@ -1486,16 +1505,18 @@ __global__ __launch_bounds__(kGThreads) void g_power_kernel(const v2d* __restric
 }
 
 // row statistics of a power row (acq64_corr_kernel's: first natural index of
-// the maximum, max outside the open circular window (argmax - spc, argmax + spc))
+// the maximum, max outside the open circular window (argmax - spc, argmax + spc)).
+// N: the lags searched, circular in N (the row length, or the kept lags of a
+// zero-padded search: E1/acquisition.sci:121-145); rs: the stride of the rows of pw
 __global__ __launch_bounds__(kGThreads) void g_stats_kernel(const double* __restrict__ pw, int N,
                                                             int u0, int n_blocks, int nc, int spc,
                                                             gnsscorr_acq_row* __restrict__ stats,
                                                             double* __restrict__ dump,
-                                                            int dump_block) {
+                                                            int dump_block, int rs) {
   __shared__ double s_v[kGThreads / 64], s_m[kGThreads / 64];
   __shared__ int s_k[kGThreads / 64];
   const int unit = u0 + blockIdx.x;
-  const double* row = pw + (long)blockIdx.x * N;
+  const double* row = pw + (long)blockIdx.x * rs;
   const int rowid = nc ? unit : unit / n_blocks;
   const int blk0 = nc ? 0 : unit % n_blocks;
   double bv = -1.0;
@@ -1541,11 +1562,11 @@ static inline bool stats1_exact(int N, int spc) {
 }
 __global__ __launch_bounds__(kStatsThreads) void g_stats1_kernel(
     const double* __restrict__ pw, int N, int u0, int n_blocks, int nc, int spc,
-    gnsscorr_acq_row* __restrict__ stats, double* __restrict__ dump, int dump_block) {
+    gnsscorr_acq_row* __restrict__ stats, double* __restrict__ dump, int dump_block, int rs) {
   __shared__ double s_v[kStatsThreads / 64], s_m[kStatsThreads / 64];
   __shared__ int s_k[kStatsThreads / 64];
   const int unit = u0 + blockIdx.x;
-  const double* row = pw + (long)blockIdx.x * N;
+  const double* row = pw + (long)blockIdx.x * rs;   // N, rs as in g_stats_kernel
   const int rowid = nc ? unit : unit / n_blocks;
   const int blk0 = nc ? 0 : unit % n_blocks;
   double a1 = -1.0, a2 = -1.0;
@@ -1723,23 +1744,28 @@ int g_init(gnsscorr_acq_ctx* c) {
   return GNSSCORR_OK;
 }
 
-int mx_dft_rows(gnsscorr_acq_ctx* c, const v2d* a, int src_rs, int rows, v2d* out, int rs);
+int mx_dft_rows(gnsscorr_acq_ctx* c, const v2d* a, int src_rs, int rows, v2d* out, int rs,
+                int n_in);
 int mx_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int n_bins,
                  const int32_t* d_gcode, const int32_t* d_gfreq, int spc, double* d_dump,
                  int dump_block);
 
-// DFT_N of natural rows: the mixed-radix plan where N has one, else Bluestein
-int gen_dft_rows(gnsscorr_acq_ctx* c, const v2d* a, int src_rs, int rows, v2d* out, int rs) {
-  return c->mix_nr ? mx_dft_rows(c, a, src_rs, rows, out, rs)
+// DFT_N of natural rows: the mixed-radix plan where N has one, else Bluestein.  n_in:
+// the rows are zero from that element on (the mixed-radix first pass skips those loads)
+int gen_dft_rows(gnsscorr_acq_ctx* c, const v2d* a, int src_rs, int rows, v2d* out, int rs,
+                 int n_in) {
+  return c->mix_nr ? mx_dft_rows(c, a, src_rs, rows, out, rs, n_in)
                    : g_dft_rows(c, a, src_rs, rows, out, rs);
 }
 
-int g_set_codes(gnsscorr_acq_ctx* c, const int8_t* d_codes, int n_codes) {
+// d_codes: n_codes replicas of N int8 values, zero from code_len on (set_codes_padded)
+int g_set_codes(gnsscorr_acq_ctx* c, const int8_t* d_codes, int n_codes, int code_len) {
   const long n = (long)n_codes * c->cfg.n_samples;
   hipLaunchKernelGGL(g_codes_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_codes, n,
                      (v2d*)c->d_in64);
   HIP_TRY(hipGetLastError());
-  return gen_dft_rows(c, (const v2d*)c->d_in64, c->cfg.n_samples, n_codes, (v2d*)c->d_F64, c->rs64);
+  return gen_dft_rows(c, (const v2d*)c->d_in64, c->cfg.n_samples, n_codes, (v2d*)c->d_F64,
+                      c->rs64, code_len);
 }
 
 int g_spectra(gnsscorr_acq_ctx* c, const int8_t* d_if, int iq, int n_blocks, int n_freqs,
@@ -1761,7 +1787,7 @@ int g_spectra(gnsscorr_acq_ctx* c, const int8_t* d_if, int iq, int n_blocks, int
   int n_cls = 0;
   HIP_TRY(hipMemcpyAsync(&n_cls, c->d_nclass, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  return gen_dft_rows(c, (const v2d*)c->d_in64, N, n_cls * n_blocks, (v2d*)c->d_X64, c->rs64);
+  return gen_dft_rows(c, (const v2d*)c->d_in64, N, n_cls * n_blocks, (v2d*)c->d_X64, c->rs64, N);
 }
 
 int g_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int n_bins,
@@ -1771,6 +1797,7 @@ int g_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int n
     return mx_correlate(c, n_blocks, mode, n_groups, n_bins, d_gcode, d_gfreq, spc, d_dump,
                         dump_block);
   const int N = c->cfg.n_samples, M = c->gM;
+  const int NK = c->keep ? c->keep : N;   // lags searched (zero-padded search: the kept ones)
   const bool nc = mode == GNSSCORR_ACQ_NONCOHERENT;
   const int n_units = n_groups * n_bins * (nc ? 1 : n_blocks);
   for (int u0 = 0; u0 < n_units; u0 += c->g_chunk) {
@@ -1790,18 +1817,18 @@ int g_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int n
       HIP_TRY(hipGetLastError());
       rc = g_fft(c, E, D, nu, &D);
       if (rc) return rc;
-      hipLaunchKernelGGL(g_power_kernel, dim3((N + kGThreads - 1) / kGThreads, nu),
-                         dim3(kGThreads), 0, c->stream, D, N, M, b > 0, c->d_gpw);
+      hipLaunchKernelGGL(g_power_kernel, dim3((NK + kGThreads - 1) / kGThreads, nu),
+                         dim3(kGThreads), 0, c->stream, D, N, M, b > 0, c->d_gpw, NK);
       HIP_TRY(hipGetLastError());
     }
-    if (stats1_exact(N, spc))
+    if (stats1_exact(NK, spc))
       hipLaunchKernelGGL(g_stats1_kernel, dim3(nu), dim3(kStatsThreads), 0, c->stream,
-                         (const double*)c->d_gpw, N, u0, n_blocks, (int)nc, spc, c->d_stats,
-                         d_dump, dump_block);
+                         (const double*)c->d_gpw, NK, u0, n_blocks, (int)nc, spc, c->d_stats,
+                         d_dump, dump_block, N);
     else
       hipLaunchKernelGGL(g_stats_kernel, dim3(nu), dim3(kGThreads), 0, c->stream,
-                         (const double*)c->d_gpw, N, u0, n_blocks, (int)nc, spc, c->d_stats,
-                         d_dump, dump_block);
+                         (const double*)c->d_gpw, NK, u0, n_blocks, (int)nc, spc, c->d_stats,
+                         d_dump, dump_block, N);
     HIP_TRY(hipGetLastError());
   }
   return GNSSCORR_OK;
@@ -1835,6 +1862,7 @@ struct MixCorr {
   // records (gnsscorr_acq_set_records): virtual group g = rec * n_groups + g0 searches
   // group g0 on record rec, whose blocks are rec * n_blocks ... of the spectra's nbT
   int n_groups = 1 << 30, nbT = 0;
+  int keep = 0;   // zero-padded search: the lags kept by the last pass (MODE 3 / 4)
 };
 
 // a correlation unit's class spectrum row and code spectrum row (MODE 1 of the passes)
@@ -1854,6 +1882,15 @@ __device__ __forceinline__ void mix_unit_rows(const MixCorr& cp, int unit, const
 // MODE 1: first pass of a correlation chunk: the input is y[n] = conj(X[n - m]) F[n] of
 //         unit u0 + row (its bin's class spectrum shifted by m, acquisition.sci:116)
 // MODE 2: last pass of a correlation chunk: |.|^2 / N^2 into pw (added when acc)
+// MODE 3: MODE 2 of a zero-padded search: only lags < cp.keep are squared, stored or
+//         added (a bound check per output; any keep)
+// MODE 4: MODE 2 of a zero-padded search with keep = N/2 and an even last radix: Ns = N/R,
+//         output r of butterfly k lands at lag k + r Ns, so the kept lags are the outputs
+//         r < R/2 and only those are formed (dft_first_half); even R only
+// MODE 5: MODE 0 as the first pass (Ns = 1) of rows that are zero from element n_in on
+//         (zero-extended codes; n_in is passed in `acc`): input r of every butterfly is
+//         element j + r N/R, so the inputs r >= ceil(n_in / (N/R)) are zero for every j
+//         and are not loaded
 // occupancy: a pass is latency bound (strided row loads, one butterfly per thread),
 // so the register allocator is held to 3 waves per SIMD up to radix 16 (the fused
 // first pass otherwise keeps all 2R complex loads in flight: 244 VGPRs, 2 waves;
@@ -1883,6 +1920,11 @@ __global__ __launch_bounds__(kMixThreads, mx_waves<R>()) void mx_pass(const v2d*
       const v2d x = Xr[s], f = Fr[n];
       v[r] = (v2d){fma(x.x, f.x, x.y * f.y), fma(x.x, f.y, -(x.y * f.x))};
     }
+  } else if constexpr (MODE == 5) {
+    const int nz = (acc + NR - 1) / NR;   // inputs r >= nz are zero
+#pragma unroll
+    for (int r = 0; r < R; r++)
+      v[r] = r < nz ? in[row * in_rs + j + r * NR] : (v2d){0.0, 0.0};
   } else {
 #pragma unroll
     for (int r = 0; r < R; r++) v[r] = in[row * in_rs + j + r * NR];
@@ -1891,9 +1933,33 @@ __global__ __launch_bounds__(kMixThreads, mx_waves<R>()) void mx_pass(const v2d*
   const int ts = k * (N / (Ns * R));   // r ts < N
 #pragma unroll
   for (int r = 1; r < R; r++) v[r] = cmul(v[r], tw[r * ts]);
+  if constexpr (MODE == 4) {
+    // Ns = N/R: k = j is the butterfly's first output lag, and the kept lags
+    // k + r Ns < N/2 are r < R/2
+    static_assert(R % 2 == 0, "the half last pass needs an even radix");
+    v2d h[R / 2];
+    dft_first_half<R>(v, h);
+    const double sc = 1.0 / ((double)N * (double)N);
+    double* o = pw + row * N + k;
+#pragma unroll
+    for (int r = 0; r < R / 2; r++) {
+      const double q = fma(h[r].x, h[r].x, h[r].y * h[r].y) * sc;
+      o[r * Ns] = acc ? o[r * Ns] + q : q;
+    }
+    return;
+  }
   dft<R>(v);
   const int d = (j / Ns) * Ns * R + k;
-  if constexpr (MODE == 2) {
+  if constexpr (MODE == 3) {
+    const double sc = 1.0 / ((double)N * (double)N);
+    double* o = pw + row * N + d;
+#pragma unroll
+    for (int r = 0; r < R; r++)
+      if (d + r * Ns < cp.keep) {
+        const double q = fma(v[r].x, v[r].x, v[r].y * v[r].y) * sc;
+        o[r * Ns] = acc ? o[r * Ns] + q : q;
+      }
+  } else if constexpr (MODE == 2) {
     const double sc = 1.0 / ((double)N * (double)N);
     double* o = pw + row * N + d;
 #pragma unroll
@@ -1933,6 +1999,29 @@ int mix_factor(int N, int* r) {
   return n;
 }
 
+// the order of a zero-padded search's correlation passes (set_zero_padded): the smallest
+// even radix last, so that with keep = N/2 the last pass forms half of its outputs
+// (mx_pass MODE 4); the first pass keeps the smallest of the others; r unchanged for an
+// odd N.  128000 -> 5, 5, 5, 16, 16, 4 (unpadded: 4, 5, 5, 16, 16, 5).
+void mix_order_padded(const int* r, int n, int* rp) {
+  int t[24];
+  for (int a = 0; a < n; a++) t[a] = r[a];
+  for (int a = 0; a < n; a++)
+    for (int b = a + 1; b < n; b++)
+      if (t[b] < t[a]) { const int x = t[a]; t[a] = t[b]; t[b] = x; }
+  int e = -1;
+  for (int a = 0; a < n && e < 0; a++)
+    if (t[a] % 2 == 0) e = a;
+  if (e < 0) {
+    for (int a = 0; a < n; a++) rp[a] = r[a];
+    return;
+  }
+  int m = 0;
+  for (int a = 0; a < n; a++)
+    if (a != e) rp[m++] = t[a];
+  rp[n - 1] = t[e];
+}
+
 template <int MODE>
 int mx_launch(gnsscorr_acq_ctx* c, int R, const v2d* in, int in_rs, v2d* out, int out_rs, int rows,
               int Ns, const MixCorr& cp, double* pw, int acc) {
@@ -1940,10 +2029,12 @@ int mx_launch(gnsscorr_acq_ctx* c, int R, const v2d* in, int in_rs, v2d* out, in
   const dim3 grid((N / R + kMixThreads - 1) / kMixThreads, rows);
   const v2d* tw = (const v2d*)c->d_twN;
   switch (R) {
+    // (MODE 4 exists for even radices; mx_correlate asks for it only with one)
 #define MIX_CASE(RR)                                                                           \
   case RR:                                                                                     \
-    hipLaunchKernelGGL((mx_pass<RR, MODE>), grid, dim3(kMixThreads), 0, c->stream, in, in_rs, \
-                       out, out_rs, N, Ns, tw, cp, pw, acc);                                   \
+    hipLaunchKernelGGL((mx_pass<RR, (MODE == 4 && RR % 2) ? 3 : MODE>), grid,                  \
+                       dim3(kMixThreads), 0, c->stream, in, in_rs, out, out_rs, N, Ns, tw, cp, \
+                       pw, acc);                                                               \
     break;
     MIX_RADICES(MIX_CASE)
 #undef MIX_CASE
@@ -2384,8 +2475,10 @@ int m4_launch(gnsscorr_acq_ctx* c, const v2d* in, int in_rs, v2d* out, int out_r
   return GNSSCORR_OK;
 }
 
-// DFT_N of `rows` natural rows a (stride src_rs) -> out (stride rs), chunked
-int mx_dft_rows(gnsscorr_acq_ctx* c, const v2d* a, int src_rs, int rows, v2d* out, int rs) {
+// DFT_N of `rows` natural rows a (stride src_rs) -> out (stride rs), chunked; the rows
+// are zero from element n_in on (n_in = N: nothing known)
+int mx_dft_rows(gnsscorr_acq_ctx* c, const v2d* a, int src_rs, int rows, v2d* out, int rs,
+                int n_in) {
   const int N = c->cfg.n_samples, P = c->mix_nr;
   const MixCorr none{};
   for (int r0 = 0; r0 < rows; r0 += c->g_chunk) {
@@ -2402,7 +2495,11 @@ int mx_dft_rows(gnsscorr_acq_ctx* c, const v2d* a, int src_rs, int rows, v2d* ou
     for (int i = 0; i < P; i++) {
       const bool last = i + 1 == P;
       v2d* dst = last ? out + (long)r0 * rs : (i % 2 == 0 ? A : B);
-      int rc = mx_launch<0>(c, c->mix_r[i], src, srs, dst, last ? rs : N, nr, Ns, none, nullptr, 0);
+      int rc = i == 0 && n_in < N
+                   ? mx_launch<5>(c, c->mix_r[i], src, srs, dst, last ? rs : N, nr, Ns, none,
+                                  nullptr, n_in)
+                   : mx_launch<0>(c, c->mix_r[i], src, srs, dst, last ? rs : N, nr, Ns, none,
+                                  nullptr, 0);
       if (rc) return rc;
       src = dst;
       srs = N;
@@ -2416,6 +2513,13 @@ int mx_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int 
                  const int32_t* d_gcode, const int32_t* d_gfreq, int spc, double* d_dump,
                  int dump_block) {
   const int N = c->cfg.n_samples, P = c->mix_nr;
+  // zero-padded search (set_zero_padded): the plain passes in the padded order, the last
+  // one pruned to the kept lags (the four-step plans are not used while it is on), and
+  // the statistics over those lags
+  const int keep = c->keep, NK = keep ? keep : N;
+  const int m4 = keep ? 0 : c->m4;
+  const int* const radix = keep ? c->mix_rp : c->mix_r;
+  const bool half = keep && 2 * keep == N && radix[P - 1] % 2 == 0;
   const bool nc = mode == GNSSCORR_ACQ_NONCOHERENT;
   // records: every group on every record of the resident spectra (virtual groups)
   const int nrec = c->spec_recs;
@@ -2423,12 +2527,12 @@ int mx_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int 
   // four-step plans: the row statistics ride on the last block's m4_rows2 (per-column
   // top-2; its power rows are then not stored) unless the window can hold two samples
   // of a column or the power rows are dumped
-  const int N1 = c->m4 ? kM4Plans[c->m4][0] * kM4Plans[c->m4][1] : 0;
-  const bool fused = c->m4 && c->d_m4top && 2 * spc - 1 <= N1 && !d_dump;
+  const int N1 = m4 ? kM4Plans[m4][0] * kM4Plans[m4][1] : 0;
+  const bool fused = m4 && c->d_m4top && 2 * spc - 1 <= N1 && !d_dump;
   // equal chunks (7 x 375 rows rather than 6 x 385 + 314 at the bench's 2 624); with
   // two lanes an even count, chunk i on lane i % 2 (stream, Y, power rows, top-2 of
   // its own), forked from and joined back to the context stream
-  const int lanes = c->m4 ? c->m4_lanes : 1;
+  const int lanes = m4 ? c->m4_lanes : 1;
   int n_ch = (n_units + c->g_chunk - 1) / c->g_chunk;
   if (lanes == 2 && n_ch > 1 && n_ch % 2) n_ch++;
   const int step = n_ch > 0 ? (n_units + n_ch - 1) / n_ch : c->g_chunk;
@@ -2448,8 +2552,8 @@ int mx_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int 
     for (int b = 0; b < nb; b++) {
       MixCorr cp{(const v2d*)c->d_X64, (const v2d*)c->d_F64, c->rs64, n_blocks, nc ? b : -1,
                  n_bins, u0, d_gcode, d_gfreq, (const int2*)c->d_fmap64, n_groups,
-                 n_blocks * nrec};
-      if (c->m4) {
+                 n_blocks * nrec, keep};
+      if (m4) {
         const M4StatsJob* sj = b == 0 && pend.n > 0 ? &pend : nullptr;
         hipEvent_t const fork = lanes == 2 && ci == 0 && b == 0 ? c->m4_ev[0] : nullptr;
         const int rc =
@@ -2465,13 +2569,17 @@ int mx_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int 
       int Ns = 1;
       for (int i = 0; i < P; i++) {
         v2d* dst = i % 2 == 0 ? A : B;
-        int rc = i == 0 ? mx_launch<1>(c, c->mix_r[i], nullptr, 0, dst, N, nu, Ns, cp, nullptr, 0)
-                 : i + 1 == P ? mx_launch<2>(c, c->mix_r[i], src, N, nullptr, 0, nu, Ns, cp,
-                                             c->d_gpw, b > 0)
-                              : mx_launch<0>(c, c->mix_r[i], src, N, dst, N, nu, Ns, cp, nullptr, 0);
+        int rc = i == 0 ? mx_launch<1>(c, radix[i], nullptr, 0, dst, N, nu, Ns, cp, nullptr, 0)
+                 : i + 1 < P ? mx_launch<0>(c, radix[i], src, N, dst, N, nu, Ns, cp, nullptr, 0)
+                 : !keep     ? mx_launch<2>(c, radix[i], src, N, nullptr, 0, nu, Ns, cp, c->d_gpw,
+                                            b > 0)
+                 : half      ? mx_launch<4>(c, radix[i], src, N, nullptr, 0, nu, Ns, cp, c->d_gpw,
+                                            b > 0)
+                             : mx_launch<3>(c, radix[i], src, N, nullptr, 0, nu, Ns, cp, c->d_gpw,
+                                            b > 0);
         if (rc) return rc;
         src = dst;
-        Ns *= c->mix_r[i];
+        Ns *= radix[i];
       }
     }
     if (fused) {   // carried by the lane's next column pass, or launched below
@@ -2483,14 +2591,14 @@ int mx_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int 
       pend.n_blocks = n_blocks;
       pend.nc = (int)nc;
       pend.spc = spc;
-    } else if (stats1_exact(N, spc))
+    } else if (stats1_exact(NK, spc))
       hipLaunchKernelGGL(g_stats1_kernel, dim3(nu), dim3(kStatsThreads), 0, st,
-                         (const double*)pw, N, u0, n_blocks, (int)nc, spc, c->d_stats,
-                         d_dump, dump_block);
+                         (const double*)pw, NK, u0, n_blocks, (int)nc, spc, c->d_stats,
+                         d_dump, dump_block, N);
     else
       hipLaunchKernelGGL(g_stats_kernel, dim3(nu), dim3(kGThreads), 0, st,
-                         (const double*)pw, N, u0, n_blocks, (int)nc, spc, c->d_stats,
-                         d_dump, dump_block);
+                         (const double*)pw, NK, u0, n_blocks, (int)nc, spc, c->d_stats,
+                         d_dump, dump_block, N);
     HIP_TRY(hipGetLastError());
   }
   for (int l = 0; l < 2; l++)
@@ -2589,6 +2697,7 @@ int acq64_plan_for(int n_samples) {
 
 namespace {
 int mix_factor(int N, int* r);
+void mix_order_padded(const int* r, int n, int* rp);
 int m4_plan(int N);
 int mx_init(gnsscorr_acq_ctx* c);
 }  // namespace
@@ -2611,6 +2720,7 @@ int acq64_init(gnsscorr_acq_ctx* c) {
     // GNSSCORR_ACQ_BLUESTEIN=1: the chirp-z engine, for cross-checks)
     const char* fb = getenv("GNSSCORR_ACQ_BLUESTEIN");
     c->mix_nr = (fb && atoi(fb)) ? 0 : mix_factor(N, c->mix_r);
+    mix_order_padded(c->mix_r, c->mix_nr, c->mix_rp);
     // the four-step plan where one is compiled for N (GNSSCORR_ACQ_MIX4=0: the
     // mixed-radix passes, for cross-checks)
     const char* f4 = getenv("GNSSCORR_ACQ_MIX4");
@@ -2704,13 +2814,21 @@ int acq64_preload(gnsscorr_acq_ctx* c) {
   return GNSSCORR_OK;
 }
 
-int acq64_set_codes(gnsscorr_acq_ctx* c, const int8_t* d_codes, int n_codes) {
+int acq64_set_codes(gnsscorr_acq_ctx* c, const int8_t* d_codes, int n_codes, int code_len) {
   int rc = acq_grow((void**)&c->d_in64, &c->cap_in64, (size_t)n_codes * c->cfg.n_samples,
                     sizeof(double2));
   if (rc) return rc;
-  if (c->plan64 == 3) return g_set_codes(c, d_codes, n_codes);
+  if (c->plan64 == 3) return g_set_codes(c, d_codes, n_codes, code_len);
   return c->plan64 == 1 ? set_codes_launch<PlanA>(c, d_codes, n_codes)
                         : set_codes_launch<PlanB>(c, d_codes, n_codes);
+}
+
+// A zero-padded search runs the plain mixed-radix passes; a context on a four-step plan
+// has one work buffer (Y) and gets the passes' second one here, once.
+int acq64_set_zero_padded(gnsscorr_acq_ctx* c, int keep) {
+  if (keep > 0 && c->mix_nr && c->m4 && !c->d_gB)
+    HIP_TRY(hipMalloc(&c->d_gB, sizeof(double2) * (size_t)c->cfg.n_samples * c->g_chunk));
+  return GNSSCORR_OK;
 }
 
 int acq64_spectra(gnsscorr_acq_ctx* c, const int8_t* d_if, int iq, int n_blocks, int n_freqs,

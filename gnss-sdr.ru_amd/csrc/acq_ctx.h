@@ -42,6 +42,10 @@ struct gnsscorr_acq_ctx {
   // mix_nr passes of radix mix_r[i] in global memory, twiddles d_twN (W_N^j)
   int mix_nr = 0;
   int mix_r[24] = {};
+  // the same radices in the order of a zero-padded search's correlation passes
+  // (set_zero_padded): an even radix last where N has one, so that with keep = N/2 the
+  // last pass forms only the kept half of its outputs
+  int mix_rp[24] = {};
   // four-step plan of the generic path (N = N1 N2, N1 = A B and N2 = C D two-radix
   // sub-transforms in LDS, two passes over the rows): 0 none, else its plan index
   int m4 = 0;
@@ -71,6 +75,7 @@ struct gnsscorr_acq_ctx {
   int n_cu = 256;                       // persistent grid of the pipelined kernel
   int coh = 1;                          // code periods per coherent block (set_coherent)
   int recs = 1;                         // records per search (set_records, fp64 plans)
+  int keep = 0;                         // zero-padded search: lags kept (set_zero_padded; 0: off)
   const int32_t* d_group_rec = nullptr; // per group: its IF record (set_group_records; NULL: every
                                         // group on every record)
   int spec_recs = 1;                    // records of the resident IF spectra
@@ -101,7 +106,9 @@ int acq64_plan_for(int n_samples);
 int acq64_init(gnsscorr_acq_ctx* c);             // device tables for the plan
 void acq64_free(gnsscorr_acq_ctx* c);
 int acq64_preload(gnsscorr_acq_ctx* c);   // code spectra buffers + code-object load
-int acq64_set_codes(gnsscorr_acq_ctx* c, const int8_t* d_codes, int n_codes);
+// code_len < n_samples: the replicas are zero above code_len (set_codes_padded)
+int acq64_set_codes(gnsscorr_acq_ctx* c, const int8_t* d_codes, int n_codes, int code_len);
+int acq64_set_zero_padded(gnsscorr_acq_ctx* c, int keep);   // buffers of the padded passes
 int acq64_spectra(gnsscorr_acq_ctx* c, const int8_t* d_if, int iq, int n_blocks, int n_freqs,
                   const double* d_freqs);
 int acq64_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int n_bins,

@@ -10,6 +10,7 @@
  *  gnsscorr_ca_code          SoftGNSS generateCAcode.sci:42-87 (ICD G2 delays)
  *  gnsscorr_st_code          SoftGNSS GLONASS generateSTcode.sci:35-42
  *  gnsscorr_sample_code      makeCaTable.sci:64-72 / makeStTable.sci:60-67
+ *  gnsscorr_sample_boc_code  GALILEO/E1/include/makeE1BCodesTable.sci:56-78
  *  gnsscorr_ifgen            int8 IQ at {-3,-1,1,3} (gps_source.cpp:692 levels)
  */
 #include "gnsscorr_internal.h"
@@ -128,6 +129,24 @@ int gnsscorr_sample_code(const int8_t *chips, int code_len, double code_rate, do
     if (k == n) idx = code_len;                     /* codeValueIndex($) = codeLength */
     long j = ((idx - 1) % code_len + code_len) % code_len;
     out[k - 1] = chips[j];
+  }
+  return GNSSCORR_OK;
+}
+
+/* makeE1BCodesTable.sci:56-78: kron(code, [1 1]) .* meander, sampled at index
+ * ceil((ts k) / tc * 2) (1-based) of the 2 code_len half chips; the last sample takes
+ * index code_len (:73 as written, not 2 code_len). */
+int gnsscorr_sample_boc_code(const int8_t *chips, int code_len, double code_rate, double fs,
+                             int n, int8_t *out)
+{
+  if (!chips || !out || code_len <= 0 || n <= 0 || fs <= 0 || code_rate <= 0) return GNSSCORR_EINVAL;
+  double ts = 1.0 / fs, tc = 1.0 / code_rate;
+  const long len2 = 2L * code_len;
+  for (int k = 1; k <= n; k++) {
+    long idx = (long)ceil((ts * (double)k) / tc * 2.0);   /* 1-based half-chip index */
+    if (k == n) idx = code_len;                           /* codeValueIndex($) = codeLength */
+    long j = ((idx - 1) % len2 + len2) % len2;
+    out[k - 1] = (int8_t)((j & 1) ? -chips[j / 2] : chips[j / 2]);
   }
   return GNSSCORR_OK;
 }

@@ -173,6 +173,7 @@ EXPORTED_FUNCTIONS = [
     "gnsscorr_acq_spectra_dev", "gnsscorr_acq_correlate_dev", "gnsscorr_acq_select_dev",
     "gnsscorr_acq_sync", "gnsscorr_acq_stream", "gnsscorr_acq_set_coherent",
     "gnsscorr_acq_set_records", "gnsscorr_acq_set_group_records", "gnsscorr_acq_set_prn_codes",
+    "gnsscorr_acq_set_zero_padded", "gnsscorr_acq_set_codes_padded",
     "gnsscorr_sgt_loop_coefs", "gnsscorr_sgt_init_chan", "gnsscorr_sgt_create",
     "gnsscorr_sgt_destroy", "gnsscorr_sgt_track_dev", "gnsscorr_sgt_track", "gnsscorr_sgt_sync",
     "gnsscorr_sgt_stream", "gnsscorr_sgt_replay", "gnsscorr_sgt_replay_dev",
@@ -194,6 +195,7 @@ EXPORTED_FUNCTIONS = [
     "gnsscorr_stream_wait_event",
     "gnsscorr_event_elapsed_ms", "gnsscorr_event_destroy", "gnsscorr_dev_fill_if2",
     "gnsscorr_ifgen", "gnsscorr_ca_code", "gnsscorr_st_code", "gnsscorr_sample_code",
+    "gnsscorr_sample_boc_code",
     "correlator_init", "Sim_GP2021_int", "gnsscorr_osg_configure", "gnsscorr_osg_get_state",
 ]
 EXPORTED_DATA = ["REG_read", "REG_write", "Carrier_DCO_Delta", "Code_DCO_Delta",
@@ -251,6 +253,8 @@ def lib() -> C.CDLL:
         "gnsscorr_acq_set_records": (I, [P, I]),
         "gnsscorr_acq_set_group_records": (I, [P, P]),
         "gnsscorr_acq_set_prn_codes": (I, [P, I, P]),
+        "gnsscorr_acq_set_zero_padded": (I, [P, I]),
+        "gnsscorr_acq_set_codes_padded": (I, [P, I, P, I]),
         "gnsscorr_acq_stream": (P, [P]),
         "gnsscorr_sgt_loop_coefs": (None, [C.POINTER(SgtCfg)] + [C.POINTER(D)] * 5),
         "gnsscorr_sgt_init_chan": (I, [C.POINTER(SgtCfg), I, I, I64, I64, D, P]),
@@ -313,6 +317,7 @@ def lib() -> C.CDLL:
         "gnsscorr_ca_code": (I, [I, P]),
         "gnsscorr_st_code": (I, [P]),
         "gnsscorr_sample_code": (I, [P, I, D, D, I, P]),
+        "gnsscorr_sample_boc_code": (I, [P, I, D, D, I, P]),
         "correlator_init": (None, [D]),
         "Sim_GP2021_int": (None, [P, C.c_long]),
         "gnsscorr_osg_configure": (I, [D, D, D, D, I, I, I, I, D, I]),
@@ -487,6 +492,24 @@ def sample_code(chips: np.ndarray, code_rate: float, fs: float, n: int) -> np.nd
     return out
 
 
+def sample_boc_code(chips: np.ndarray, code_rate: float, fs: float, n: int) -> np.ndarray:
+    """gnsscorr_sample_boc_code: +-1 chips sampled as BOC(1,1) by the
+    makeE1BCodesTable.sci:56-78 rule (the last sample takes half-chip index code_len)."""
+    chips = np.ascontiguousarray(chips, np.int8)
+    out = np.empty(n, np.int8)
+    _check(lib().gnsscorr_sample_boc_code(_ptr(chips), len(chips), code_rate, fs, n, _ptr(out)),
+           "gnsscorr_sample_boc_code")
+    return out
+
+
+def e1b_bins(if_freq: float, band_khz: float, ms_code_len: int) -> np.ndarray:
+    """The frequency grid of GALILEO/E1/acquisition.sci:61, 94-96: round(band * 2 * ms) + 1
+    bins from IF - band/2 kHz in steps of 1000 / (2 * ms) Hz."""
+    nb = int(round(band_khz * 2 * ms_code_len)) + 1
+    k = np.arange(1, nb + 1)
+    return if_freq - (band_khz / 2) * 1000 + (1000 / (2 * ms_code_len)) * (k - 1)
+
+
 def make_sigs(sigs) -> np.ndarray:
     """sigs: list of dicts with keys of SIG (missing keys default to 0)."""
     a = np.zeros(len(sigs), SIG)
@@ -610,6 +633,22 @@ class AcqCtx:
         codes = np.ascontiguousarray(codes, np.int8).reshape(-1, self.n)
         _check(lib().gnsscorr_acq_set_codes(self.h, codes.shape[0], _ptr(codes)),
                "gnsscorr_acq_set_codes")
+
+    def set_codes_padded(self, codes: np.ndarray):
+        """gnsscorr_acq_set_codes_padded: (n_codes, code_len) +-1 chips with code_len <=
+        n_samples, zero-extended to n_samples on the device ([code zeros],
+        E1/acquisition.sci:88)."""
+        codes = np.ascontiguousarray(codes, np.int8)
+        codes = codes.reshape(1, -1) if codes.ndim == 1 else codes
+        _check(lib().gnsscorr_acq_set_codes_padded(self.h, codes.shape[0], _ptr(codes),
+                                                   codes.shape[1]),
+               "gnsscorr_acq_set_codes_padded")
+
+    def set_zero_padded(self, keep: int):
+        """gnsscorr_acq_set_zero_padded: row statistics over the first `keep` lags only,
+        the second-peak window circular in keep (E1/acquisition.sci:112-145); 0: off."""
+        _check(lib().gnsscorr_acq_set_zero_padded(self.h, int(keep)),
+               "gnsscorr_acq_set_zero_padded")
 
     def set_prn_codes(self, code_ids):
         """gnsscorr_acq_set_prn_codes: replicas generated on the device from code ids

@@ -379,6 +379,34 @@ int gnsscorr_acq_set_records(gnsscorr_acq_ctx *ctx, int n_records);
  * into that range; gnsscorr_acq_set_records with another count turns the table
  * off (set it again after).  (No reference counterpart: batching.) */
 int gnsscorr_acq_set_group_records(gnsscorr_acq_ctx *ctx, const int32_t *d_group_rec);
+/* Zero-padded long-code search (Galileo E1B, GALILEO/E1/acquisition.sci:45-165):
+ * the context is created with n_samples = L, the transform length (E1: twice
+ * samplesPerCode), the codes are one period followed by zeros
+ * (gnsscorr_acq_set_codes_padded; conj(fft([code zeros(1,S)])), :88), so the L-point
+ * product is a linear correlation, and only the first `keep` lags count (:112).
+ * With keep > 0 the per-unit row statistics of both search modes (peak, argmax, the
+ * block choice of best-of-blocks, the non-coherent sums) cover lags 0 .. keep-1 only,
+ * the second peak is the maximum outside the open window (argmax - spc, argmax + spc)
+ * circular in keep (:129-145 with samplesPerCode = keep; spc <= keep / 2), and
+ * code_phase is 1-based within keep.  Powers keep the scale of an L-point ifft.
+ * keep = 0 turns the mode off; 0 < keep <= n_samples otherwise.
+ * fp64 generic engine only, one code period per block and one record per search:
+ * GNSSCORR_EINVAL for keep > 0 on a context of F32 precision, on one of the compiled
+ * register-resident plans (n_samples 16368 or 16000), with set_coherent(> 1),
+ * set_records(> 1) or a group-record table; while the mode is on those three setters
+ * return GNSSCORR_EINVAL for such values.  gnsscorr_acq_power_row is not affected: it
+ * returns the full row of n_samples powers.  (No reference counterpart for n_blocks
+ * > 1: acquisition.sci searches one 2 x samplesPerCode block.) */
+int gnsscorr_acq_set_zero_padded(gnsscorr_acq_ctx *ctx, int keep);
+/* gnsscorr_acq_set_codes for codes shorter than the transform: n_codes x code_len
+ * int8 chips of +-1 (code_len <= n_samples), zero-extended to n_samples on the
+ * device; their spectra are computed there and kept resident.  Like
+ * gnsscorr_acq_set_codes it is synchronous: it returns after the spectra are
+ * complete on the context stream, and h_codes may be reused at once.  With code_len
+ * = n_samples it computes exactly what gnsscorr_acq_set_codes does.  Works with the
+ * mode above on or off. */
+int gnsscorr_acq_set_codes_padded(gnsscorr_acq_ctx *ctx, int n_codes, const int8_t *h_codes,
+                                  int code_len);
 /* Debug/parity: full |ifft|^2 power row for (code, freq, block): n_samples doubles. */
 int gnsscorr_acq_power_row(gnsscorr_acq_ctx *ctx, const int8_t *h_if, int iq, int n_blocks,
                            int block, double freq, int code, double *h_power);
@@ -802,6 +830,14 @@ int gnsscorr_st_code(int8_t *h_chips511);
  * out[k-1] = chips[ceil(k*ts/tc)-1], last index forced to code_len. */
 int gnsscorr_sample_code(const int8_t *h_chips, int code_len, double code_rate, double fs,
                          int n_samples, int8_t *h_out);
+/* Sample a +-1 chip sequence as BOC(1,1) with the makeE1BCodesTable.sci:56-78 rule:
+ * every chip is doubled and multiplied by the +1/-1 meander (2 code_len half chips),
+ * out[k-1] = halfchips[ceil(k*ts/tc*2)-1].  The last sample takes index code_len of
+ * the half-chip array -- not 2 code_len, its natural value: makeE1BCodesTable.sci:73
+ * writes codeValueIndex($) = settings.codeLength, and that line is reproduced as it
+ * stands (the last sample is the second half of chip code_len / 2). */
+int gnsscorr_sample_boc_code(const int8_t *h_chips, int code_len, double code_rate, double fs,
+                             int n_samples, int8_t *h_out);
 
 #ifdef __cplusplus
 }
