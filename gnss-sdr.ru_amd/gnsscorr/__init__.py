@@ -71,6 +71,23 @@ SGT_EPOCH = np.dtype([("I_E", "<f8"), ("I_P", "<f8"), ("I_L", "<f8"), ("Q_E", "<
                       ("pllDiscr", "<f8"), ("pllDiscrFilt", "<f8"), ("blksize", "<i4"),
                       ("status", "<i4")])
 assert SGT_CHAN.itemsize == 128 and SGT_EPOCH.itemsize == 112
+E1T_SUMS = ("I_E_P", "I_P_E", "I_P_P", "I_P_L", "I_L_P", "Q_E_P", "Q_P_E", "Q_P_P", "Q_P_L",
+            "Q_L_P")   # first letter: subcarrier arm, second: code arm
+E1T_CHAN = np.dtype([("code_id", "<i4"), ("stream", "<i4"), ("status", "<i4"),
+                     ("n_epochs", "<i4"), ("segment", "<i4"), ("pad", "<i4"), ("pos", "<i8"),
+                     ("rem_code", "<f8"), ("rem_meandr", "<f8"), ("rem_carr", "<f8"),
+                     ("code_freq", "<f8"), ("meandr_freq", "<f8"), ("carr_freq", "<f8"),
+                     ("carr_freq_basis", "<f8"), ("old_code_nco", "<f8"),
+                     ("old_code_error", "<f8"), ("old_meandr_nco", "<f8"),
+                     ("old_meandr_error", "<f8"), ("old_carr_nco", "<f8"),
+                     ("old_carr_error", "<f8"), ("i1", "<f8"), ("q1", "<f8"), ("pad2", "<f8")])
+E1T_EPOCH = np.dtype([(f, "<f8") for f in E1T_SUMS] +
+                     [("carrFreq", "<f8"), ("codeFreq", "<f8"), ("meandrFreq", "<f8"),
+                      ("absoluteSample", "<f8"), ("dllDiscr", "<f8"), ("dllDiscrFilt", "<f8"),
+                      ("sllDiscr", "<f8"), ("sllDiscrFilt", "<f8"), ("pllDiscr", "<f8"),
+                      ("pllDiscrFilt", "<f8"), ("blksize", "<i4"), ("status", "<i4"),
+                      ("segment", "<i4"), ("pad", "<i4")])
+assert E1T_CHAN.itemsize == 160 and E1T_EPOCH.itemsize == 176
 SDR_CHAN = np.dtype([("code_phase", "<f8"), ("carrier_phase", "<f8"),
                      ("carrier_phase_prev", "<f8"), ("code_phase_mod", "<f8"),
                      ("carrier_phase_mod", "<f8"), ("code_nco", "<f8"), ("carrier_nco", "<f8"),
@@ -150,6 +167,18 @@ class SgtCfg(C.Structure):
                 ("code_nco_variant", C.c_int32), ("abs_sample_variant", C.c_int32)]
 
 
+class E1tCfg(C.Structure):
+    _fields_ = [("file_type", C.c_int32), ("device", C.c_int32), ("max_channels", C.c_int32),
+                ("max_codes", C.c_int32), ("code_length", C.c_int32),
+                ("meandr_length", C.c_int32), ("samp_rate", C.c_double),
+                ("code_freq_basis", C.c_double), ("meandr_freq_basis", C.c_double),
+                ("if_freq", C.c_double), ("dll_spacing", C.c_double),
+                ("dll_noise_bw", C.c_double), ("dll_damping", C.c_double),
+                ("sll_spacing", C.c_double), ("sll_noise_bw", C.c_double),
+                ("sll_damping", C.c_double), ("pll_noise_bw", C.c_double),
+                ("fll_noise_bw", C.c_double)]
+
+
 class SdrCorrCfg(C.Structure):
     _fields_ = [("device", C.c_int32), ("saturate", C.c_int32)]
 
@@ -177,6 +206,10 @@ EXPORTED_FUNCTIONS = [
     "gnsscorr_sgt_loop_coefs", "gnsscorr_sgt_init_chan", "gnsscorr_sgt_create",
     "gnsscorr_sgt_destroy", "gnsscorr_sgt_track_dev", "gnsscorr_sgt_track", "gnsscorr_sgt_sync",
     "gnsscorr_sgt_stream", "gnsscorr_sgt_replay", "gnsscorr_sgt_replay_dev",
+    "gnsscorr_e1t_loop_coefs", "gnsscorr_e1t_init_chan", "gnsscorr_e1t_create",
+    "gnsscorr_e1t_destroy", "gnsscorr_e1t_set_codes", "gnsscorr_e1t_track_dev",
+    "gnsscorr_e1t_track", "gnsscorr_e1t_replay_dev", "gnsscorr_e1t_replay", "gnsscorr_e1t_sync",
+    "gnsscorr_e1t_stream",
     "gnsscorr_sdr_prn_codes", "gnsscorr_sdr_sine_gen", "gnsscorr_sdr_acq_create",
     "gnsscorr_sdr_acq_destroy", "gnsscorr_sdr_acq_strong", "gnsscorr_sdr_acq_strong_dev",
     "gnsscorr_sdr_channel_start", "gnsscorr_sdr_channel_accum_dev", "gnsscorr_sdr_track_dev",
@@ -266,6 +299,17 @@ def lib() -> C.CDLL:
         "gnsscorr_sgt_replay_dev": (I, [P, I, P, I, P, P]),
         "gnsscorr_sgt_sync": (I, [P]),
         "gnsscorr_sgt_stream": (P, [P]),
+        "gnsscorr_e1t_loop_coefs": (None, [C.POINTER(E1tCfg)] + [C.POINTER(D)] * 7),
+        "gnsscorr_e1t_init_chan": (I, [C.POINTER(E1tCfg), I, I, I64, I64, D, P]),
+        "gnsscorr_e1t_create": (I, [C.POINTER(P), C.POINTER(E1tCfg)]),
+        "gnsscorr_e1t_destroy": (I, [P]),
+        "gnsscorr_e1t_set_codes": (I, [P, I, P]),
+        "gnsscorr_e1t_track_dev": (I, [P, P, I64, I64, I, P, I, I, P]),
+        "gnsscorr_e1t_track": (I, [P, P, I64, I64, I, P, I, I, P]),
+        "gnsscorr_e1t_replay": (I, [P, I, P, I, P, P]),
+        "gnsscorr_e1t_replay_dev": (I, [P, I, P, I, P, P]),
+        "gnsscorr_e1t_sync": (I, [P]),
+        "gnsscorr_e1t_stream": (P, [P]),
         "gnsscorr_sdr_prn_codes": (I, [P]),
         "gnsscorr_sdr_sine_gen": (None, [P, D, D, I]),
         "gnsscorr_sdr_acq_create": (I, [C.POINTER(P), C.POINTER(SdrAcqCfg)]),
@@ -820,6 +864,113 @@ class SgtCtx:
     @property
     def stream(self) -> int:
         return lib().gnsscorr_sgt_stream(self.h)
+
+
+# ---------------------------------------------------------------- Galileo E1B float tracking
+def e1t_cfg(device: int = 0, **kw) -> E1tCfg:
+    """GALILEO/E1/initSettings.sci:65-107 defaults; keyword overrides use the Scilab
+    names (samplingFreq, IF, sllCorrelatorSpacing, fileType, ...) plus maxCodes."""
+    d = dict(fileType=2, samplingFreq=16e6, codeFreqBasis=1.023e6, meandrFreqBasis=2.046e6,
+             IF=2.42e6, codeLength=4092, meandrLength=8184, dllDampingRatio=0.7,
+             dllNoiseBandwidth=0.5, dllCorrelatorSpacing=0.25, sllDampingRatio=0.7,
+             sllNoiseBandwidth=0.5, sllCorrelatorSpacing=0.1, pllNoiseBandwidth=25.0,
+             fllNoiseBandwidth=250.0, maxCodes=50)
+    unknown = set(kw) - set(d)
+    if unknown:
+        raise ValueError(f"unknown settings {sorted(unknown)}")
+    d.update(kw)
+    return E1tCfg(d["fileType"], device, 0, d["maxCodes"], d["codeLength"], d["meandrLength"],
+                  d["samplingFreq"], d["codeFreqBasis"], d["meandrFreqBasis"], d["IF"],
+                  d["dllCorrelatorSpacing"], d["dllNoiseBandwidth"], d["dllDampingRatio"],
+                  d["sllCorrelatorSpacing"], d["sllNoiseBandwidth"], d["sllDampingRatio"],
+                  d["pllNoiseBandwidth"], d["fllNoiseBandwidth"])
+
+
+def e1t_loop_coefs(cfg: E1tCfg):
+    """(tau1code, tau2code, tau1meandr, tau2meandr, k1, k2, k3) of a configuration (host only)."""
+    v = [C.c_double() for _ in range(7)]
+    lib().gnsscorr_e1t_loop_coefs(C.byref(cfg), *[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def e1t_init_chan(cfg: E1tCfg, code_id, code_phase_1b, acq_freq, stream=0, skip=0) -> np.ndarray:
+    """One E1T_CHAN (shape (1,)) from an acquisition result (host only)."""
+    out = np.zeros(1, E1T_CHAN)
+    _check(lib().gnsscorr_e1t_init_chan(C.byref(cfg), int(code_id), int(stream), int(skip),
+                                        int(code_phase_1b), float(acq_freq), out.ctypes.data),
+           "gnsscorr_e1t_init_chan")
+    return out
+
+
+class E1tCtx:
+    """Galileo E1B float tracking (GALILEO/E1/tracking.sci) for many channels over
+    HBM-resident records: code and subcarrier NCOs, five arms, PLL/FLL + DLL + SLL."""
+
+    def __init__(self, device: int = 0, **settings):
+        self.cfg = e1t_cfg(device, **settings)
+        h = C.c_void_p()
+        _check(lib().gnsscorr_e1t_create(C.byref(h), C.byref(self.cfg)), "gnsscorr_e1t_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().gnsscorr_e1t_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def loop_coefs(self):
+        return e1t_loop_coefs(self.cfg)
+
+    def set_codes(self, chips):
+        """chips: (n_codes, 4092) of +-1; channel code_id is the row."""
+        chips = np.ascontiguousarray(chips, np.int8)
+        assert chips.ndim == 2 and chips.shape[1] == 4092
+        _check(lib().gnsscorr_e1t_set_codes(self.h, chips.shape[0], _ptr(chips)),
+               "gnsscorr_e1t_set_codes")
+
+    def init_chan(self, code_id, code_phase_1b, acq_freq, stream=0, skip=0):
+        return e1t_init_chan(self.cfg, code_id, code_phase_1b, acq_freq, stream, skip)
+
+    def init_chans(self, code_ids, code_phases_1b, acq_freqs, streams=None, skip=0):
+        n = len(code_ids)
+        streams = np.zeros(n, np.int64) if streams is None else np.asarray(streams)
+        return np.concatenate([self.init_chan(code_ids[i], code_phases_1b[i], acq_freqs[i],
+                                              streams[i], skip) for i in range(n)])
+
+    def track(self, d_if, stride, n_samples, chans, n_epochs, closed_loop=True):
+        """Host channel array in/out; returns epochs [n_ch, n_epochs]."""
+        assert chans.dtype == E1T_CHAN and chans.flags.c_contiguous
+        ep = np.zeros((len(chans), n_epochs), E1T_EPOCH)
+        _check(lib().gnsscorr_e1t_track(self.h, d_if, stride, n_samples, len(chans),
+                                        _ptr(chans), n_epochs, int(closed_loop), _ptr(ep)),
+               "gnsscorr_e1t_track")
+        return ep
+
+    def track_dev(self, d_if, stride, n_samples, n_ch, d_chan, n_epochs, d_epochs,
+                  closed_loop=True):
+        _check(lib().gnsscorr_e1t_track_dev(self.h, d_if, stride, n_samples, n_ch, d_chan,
+                                            n_epochs, int(closed_loop), d_epochs),
+               "gnsscorr_e1t_track_dev")
+
+    def replay(self, chans, sums):
+        """The loop half on given sums [n_ch, n_epochs, 10] (E1T_SUMS order); host
+        channel array in/out; returns epochs [n_ch, n_epochs]."""
+        assert chans.dtype == E1T_CHAN and chans.flags.c_contiguous
+        sums = np.ascontiguousarray(sums, dtype=np.float64)
+        n_ch, n_ep = sums.shape[0], sums.shape[1]
+        assert sums.shape == (len(chans), n_ep, 10)
+        ep = np.zeros((n_ch, n_ep), E1T_EPOCH)
+        _check(lib().gnsscorr_e1t_replay(self.h, n_ch, _ptr(chans), n_ep, _ptr(sums), _ptr(ep)),
+               "gnsscorr_e1t_replay")
+        return ep
+
+    def sync(self):
+        _check(lib().gnsscorr_e1t_sync(self.h), "gnsscorr_e1t_sync")
+
+    @property
+    def stream(self) -> int:
+        return lib().gnsscorr_e1t_stream(self.h)
 
 
 # ---------------------------------------------------------------- GPS-SDR integer acquisition

@@ -511,6 +511,107 @@ int gnsscorr_sgt_sync(gnsscorr_sgt_ctx *ctx);
 void *gnsscorr_sgt_stream(gnsscorr_sgt_ctx *ctx);
 
 /* ======================================================================
+ * Galileo E1B float tracking ("e1t"): the Scilab receiver's per-channel loop
+ *   POSTPROCESSING_SCILAB_RECEIVERS/GALILEO/E1/tracking.sci:95-455
+ *   settings: GALILEO/E1/initSettings.sci:65-107
+ * One epoch = 1 ms = one quarter of the 4092-chip primary code:
+ * blksize = ceil((codeLength/4 - remCode)/codeStep) samples.  Two NCOs run
+ * over the epoch, the code (1.023 MHz, over the padded 1025-entry row of the
+ * current quarter, :157-160) and the subcarrier "meandr" (2.046 MHz, over the
+ * alternating 2050-entry table of :164-168, two-entry front pad kept).  Five
+ * arms, subcarrier x code: E-P, P-E, P-P, P-L, L-P, ten fp64 sums.  Closed loop:
+ * the FLL-assisted PLL (:371-389), the DLL on P-E / P-L (:394-407) and the SLL
+ * on E-P / L-P (:412-425).  Indices are fp64 without contraction: bit-exact.
+ * The records stay resident in HBM as for the sgt family above.
+ * ==================================================================== */
+typedef struct gnsscorr_e1t_ctx gnsscorr_e1t_ctx;
+
+typedef struct {          /* initSettings.sci fields used by tracking.sci     */
+  int32_t file_type;      /* settings.fileType: 1 = int8 real, 2 = int8 interleaved I,Q */
+  int32_t device;
+  int32_t max_channels;
+  int32_t max_codes;      /* rows gnsscorr_e1t_set_codes may upload (0 = 50)   */
+  int32_t code_length;    /* settings.codeLength: 4092 only                    */
+  int32_t meandr_length;  /* settings.meandrLength: 8184 only                  */
+  double  samp_rate;      /* settings.samplingFreq                             */
+  double  code_freq_basis;/* settings.codeFreqBasis                            */
+  double  meandr_freq_basis; /* settings.meandrFreqBasis                       */
+  double  if_freq;        /* settings.IF                                       */
+  double  dll_spacing;    /* settings.dllCorrelatorSpacing [chips]             */
+  double  dll_noise_bw, dll_damping;   /* calcLoopCoef(dll.., dll.., 1)        */
+  double  sll_spacing;    /* settings.sllCorrelatorSpacing [subcarrier half-cycles] */
+  double  sll_noise_bw, sll_damping;   /* calcLoopCoef(sll.., sll.., 1)        */
+  double  pll_noise_bw, fll_noise_bw;  /* calcFLLPLLLoopCoef(pll, fll, PDIcarr=0.001) */
+} gnsscorr_e1t_cfg;
+
+typedef struct {          /* one tracking channel (tracking.sci:150-205 + loop state) */
+  int32_t code_id;        /* row of the table uploaded by gnsscorr_e1t_set_codes */
+  int32_t stream;         /* which IF record (stride given per call)           */
+  int32_t status;         /* 0 tracking; 1 out of data (:282-286); 2 subcarrier index
+                             outside the 2050-entry table (Scilab would abort on it);
+                             3 code_id outside the uploaded table (track_dev only) */
+  int32_t n_epochs;       /* epochs processed so far                           */
+  int32_t segment;        /* currE1BCodeSegment - 1: 0..3 (:312-315)           */
+  int32_t pad;
+  int64_t pos;            /* next sample (complex or real) of the record       */
+  double  rem_code, rem_meandr, rem_carr;
+  double  code_freq, meandr_freq, carr_freq, carr_freq_basis;
+  double  old_code_nco, old_code_error, old_meandr_nco, old_meandr_error;
+  double  old_carr_nco, old_carr_error, i1, q1;
+  double  pad2;
+} gnsscorr_e1t_chan;      /* 160 bytes */
+
+typedef struct {          /* trackResults(ch).* for one epoch (tracking.sci:433-454) */
+  double  i_e_p, i_p_e, i_p_p, i_p_l, i_l_p;   /* first letter: subcarrier arm, */
+  double  q_e_p, q_p_e, q_p_p, q_p_l, q_l_p;   /* second letter: code arm       */
+  double  carr_freq, code_freq, meandr_freq, absolute_sample;
+  double  dll_discr, dll_discr_filt, sll_discr, sll_discr_filt, pll_discr, pll_discr_filt;
+  int32_t blksize;        /* samples of the epoch; on a stop record the blksize that did
+                             not fit (status 1) or whose subcarrier range left the table
+                             (status 2), or -1 if it is not a representable count */
+  int32_t status;         /* 0 ok; else the channel's stop status: not processed */
+  int32_t segment;        /* the quarter (0..3) this epoch correlated against   */
+  int32_t pad;
+} gnsscorr_e1t_epoch;     /* 176 bytes */
+
+/* calcLoopCoef.sci:39-43 for the DLL and the SLL (k = 1.0), calcFLLPLLLoopCoef.sci:36-38. */
+void gnsscorr_e1t_loop_coefs(const gnsscorr_e1t_cfg *cfg, double *tau1code, double *tau2code,
+                             double *tau1meandr, double *tau2meandr, double *k1, double *k2,
+                             double *k3);
+/* Channel initialisation from an acquisition result (tracking.sci:150-205):
+ * pos = skip_samples + code_phase_1b - 1, segment 0, codeFreq / meandrFreq at
+ * their bases, carrFreq = carrFreqBasis = acquired_freq, I1 = Q1 = 0.001. */
+int gnsscorr_e1t_init_chan(const gnsscorr_e1t_cfg *cfg, int code_id, int stream,
+                           int64_t skip_samples, int64_t code_phase_1b, double acquired_freq,
+                           gnsscorr_e1t_chan *out);
+int gnsscorr_e1t_create(gnsscorr_e1t_ctx **out, const gnsscorr_e1t_cfg *cfg);
+int gnsscorr_e1t_destroy(gnsscorr_e1t_ctx *ctx);
+/* Upload n_codes primary codes, chips[n_codes][4092] of +-1 (anything else:
+ * GNSSCORR_EINVAL, checked before any device call).  The four padded 1025-entry
+ * rows of tracking.sci:157-160 are built here, once per code. */
+int gnsscorr_e1t_set_codes(gnsscorr_e1t_ctx *ctx, int n_codes, const int8_t *chips);
+/* Run n_epochs epochs of n_ch channels (state in d_chan, updated in place);
+ * arguments as gnsscorr_sgt_track_dev.  closed_loop=0 holds the three
+ * frequencies.  Tracking before gnsscorr_e1t_set_codes is GNSSCORR_EINVAL. */
+int gnsscorr_e1t_track_dev(gnsscorr_e1t_ctx *ctx, const int8_t *d_if, int64_t stream_stride,
+                           int64_t n_samples, int n_ch, gnsscorr_e1t_chan *d_chan,
+                           int n_epochs, int closed_loop, gnsscorr_e1t_epoch *d_epochs);
+/* Same with host channel state / results (synchronous); a code_id outside the
+ * uploaded table is GNSSCORR_EINVAL. */
+int gnsscorr_e1t_track(gnsscorr_e1t_ctx *ctx, const int8_t *d_if, int64_t stream_stride,
+                       int64_t n_samples, int n_ch, gnsscorr_e1t_chan *h_chan, int n_epochs,
+                       int closed_loop, gnsscorr_e1t_epoch *h_epochs);
+/* The loop half alone, driven by given sums[(ch*n_epochs + e)*10 + j], j in the
+ * record's order (I_E_P .. I_L_P, Q_E_P .. Q_L_P): the same device code as the
+ * closed-loop tracker's epoch end.  No record, so no status 1 or 2. */
+int gnsscorr_e1t_replay_dev(gnsscorr_e1t_ctx *ctx, int n_ch, gnsscorr_e1t_chan *d_chan,
+                            int n_epochs, const double *d_sums, gnsscorr_e1t_epoch *d_epochs);
+int gnsscorr_e1t_replay(gnsscorr_e1t_ctx *ctx, int n_ch, gnsscorr_e1t_chan *h_chan,
+                        int n_epochs, const double *h_sums, gnsscorr_e1t_epoch *h_epochs);
+int gnsscorr_e1t_sync(gnsscorr_e1t_ctx *ctx);
+void *gnsscorr_e1t_stream(gnsscorr_e1t_ctx *ctx);
+
+/* ======================================================================
  * GPS-SDR integer strong acquisition ("sdr"), bit-exact with the real-time
  * receiver's int16 path (REALTIME_RECEIVERS/GPS/GPS_SDR_REAL_TIME_GPS_RECEIVER):
  *   Acquisition::doPrepIF    objects/acquisition.cpp:191-236 (1 ms buffer)
