@@ -33,16 +33,6 @@
 #include "acq_ctx.h"
 #include "if2.h"
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) {                                                             \
-      gnsscorr_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
-                         __LINE__);                                                     \
-      return GNSSCORR_EDEVICE;                                                          \
-    }                                                                                   \
-  } while (0)
-
 // Diagnostic hook: tools/acq_stamps.hip defines ACQ_STAMP(i) to record
 // s_memtime at phase boundaries; in the library it compiles to nothing.
 // tools/acq_ablate.hip sets ACQ_SKIP to time the kernel with phases removed

@@ -47,16 +47,6 @@
 #include "acq_ctx.h"
 #include "if2.h"
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) {                                                             \
-      gnsscorr_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
-                         __LINE__);                                                     \
-      return GNSSCORR_EDEVICE;                                                          \
-    }                                                                                   \
-  } while (0)
-
 // Diagnostic hook: tools/acq64_stamps.hip defines ACQ64_STAMP(i) to record
 // s_memtime at the barriers of the correlation kernel; nothing in the library.
 #ifndef ACQ64_STAMP

@@ -6,16 +6,6 @@
 #include <hip/hip_runtime.h>
 #include "gnsscorr_internal.h"
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) {                                                             \
-      gnsscorr_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
-                         __LINE__);                                                     \
-      return GNSSCORR_EDEVICE;                                                          \
-    }                                                                                   \
-  } while (0)
-
 extern "C" int gnsscorr_device_pci_bus_id(int device, char* buf, int len) {
   if (!buf || len < 13) return GNSSCORR_EINVAL;
   HIP_TRY(hipDeviceGetPCIBusId(buf, len, device));

@@ -47,18 +47,10 @@
 #include <stdlib.h>
 #include <string.h>
 #include "gnsscorr_internal.h"
-
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) {                                                             \
-      gnsscorr_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
-                         __LINE__);                                                     \
-      return GNSSCORR_EDEVICE;                                                          \
-    }                                                                                   \
-  } while (0)
+#include "ftrack.h"
 
 namespace {
+using namespace ftrack;
 
 constexpr int kChips = 4092;
 constexpr int kQuarter = kChips / 4;        // 1023 chips per epoch
@@ -88,7 +80,6 @@ __device__ __forceinline__ gnsscorr_e1t_epoch e1t_epoch_end(const E1tParams& p,
 #pragma clang fp contract(off)
   const double I_E_P = S[0], I_P_E = S[1], I_P_P = S[2], I_P_L = S[3], I_L_P = S[4];
   const double Q_E_P = S[5], Q_P_E = S[6], Q_P_P = S[7], Q_P_L = S[8], Q_L_P = S[9];
-  const double twopi = 2.0 * M_PI;
   const double A = (c.carr_freq * 2.0) * M_PI;        // (carrFreq * 2.0 * %pi)
   const int seg = c.segment;
   const double tlast = c.rem_code + (double)(blk - 1) * cstep;     // tcode(blksize), prompt
@@ -96,39 +87,20 @@ __device__ __forceinline__ gnsscorr_e1t_epoch e1t_epoch_end(const E1tParams& p,
   c.segment = (c.segment + 1) & 3;                                 // :312-315
   const double mlast = c.rem_meandr + (double)(blk - 1) * mstep;   // tmeandr(blksize), prompt
   c.rem_meandr = (mlast + mstep) - 8184.0 / 4;                     // :338
-  const double last = A * ((double)blk / p.fs) + c.rem_carr;       // trigarg(blksize+1)
-  c.rem_carr = last - trunc(last / twopi) * twopi;                 // :345-346
+  carry_carrier(c, A, blk, p.fs);                                  // :341-346
   c.pos += blk;
   double code_err = 0, meandr_err = 0, carr_err = 0;
   if (CLOSED) {
-    // FLL-assisted PLL (:371-389)
-    const double I2 = c.i1, Q2 = c.q1;
-    c.i1 = I_P_P; c.q1 = Q_P_P;
-    const double cross = c.i1 * Q2 - I2 * c.q1;
-    const double dot = fabs(c.i1 * I2 + c.q1 * Q2);
-    const double freq_err = atan2(cross, dot) / M_PI;
-    carr_err = atan(Q_P_P / I_P_P) / (2.0 * M_PI);
-    const double carr_nco = c.old_carr_nco + p.k1 * carr_err - p.k2 * c.old_carr_error -
-                            p.k3 * freq_err;
-    c.old_carr_nco = carr_nco;
-    c.old_carr_error = carr_err;
-    c.carr_freq = c.carr_freq_basis + carr_nco;
+    carr_err = fll_pll_step(c, p.k1, p.k2, p.k3, I_P_P, Q_P_P);   // :371-389
     // DLL on P-E / P-L (:394-407)
-    const double cE = sqrt(I_P_E * I_P_E + Q_P_E * Q_P_E), cL = sqrt(I_P_L * I_P_L + Q_P_L * Q_P_L);
-    code_err = (cE - cL) / (cE + cL);
-    const double code_nco = c.old_code_nco + (p.tau2c / p.tau1c) * (code_err - c.old_code_error) +
-                            code_err * (0.001 / p.tau1c);
-    c.old_code_nco = code_nco;
-    c.old_code_error = code_err;
+    code_err = early_late_step(I_P_E, Q_P_E, I_P_L, Q_P_L, p.tau1c, p.tau2c, 0.001,
+                               c.old_code_nco, c.old_code_error);
+    const double code_nco = c.old_code_nco;
     c.code_freq = p.code_basis - code_nco + ((c.carr_freq - p.if_freq) / 1540);
     // SLL on E-P / L-P (:412-425)
-    const double mE = sqrt(I_E_P * I_E_P + Q_E_P * Q_E_P), mL = sqrt(I_L_P * I_L_P + Q_L_P * Q_L_P);
-    meandr_err = (mE - mL) / (mE + mL);
-    const double meandr_nco = c.old_meandr_nco +
-                              (p.tau2m / p.tau1m) * (meandr_err - c.old_meandr_error) +
-                              meandr_err * (0.001 / p.tau1m);
-    c.old_meandr_nco = meandr_nco;
-    c.old_meandr_error = meandr_err;
+    meandr_err = early_late_step(I_E_P, Q_E_P, I_L_P, Q_L_P, p.tau1m, p.tau2m, 0.001,
+                                 c.old_meandr_nco, c.old_meandr_error);
+    const double meandr_nco = c.old_meandr_nco;
     c.meandr_freq = p.meandr_basis - meandr_nco + ((c.carr_freq - p.if_freq) / 770);
   }
   c.n_epochs++;
@@ -159,36 +131,6 @@ __device__ __forceinline__ gnsscorr_e1t_epoch stop_record(int status, double blk
   z.blksize = blk_d >= 0.0 && blk_d < 2147483648.0 ? (int32_t)blk_d : -1;
   z.segment = seg;
   return z;
-}
-
-__device__ __forceinline__ int clampu(int i, int hi) { return (int)min((unsigned)i, (unsigned)hi); }
-
-// a value every lane of the workgroup holds: kept in scalar registers
-__device__ __forceinline__ double uni(double v) {
-  const long long b = __double_as_longlong(v);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((int)b);
-  const unsigned hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-// wave total, uniform (DPP row_shr scan per 16-lane row, the four rows added
-// in scalar registers); every lane must be active
-template <int CTRL>
-__device__ __forceinline__ double dpp_shr(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double lane_f64(double v, int l) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l),
-                          __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-__device__ __forceinline__ double wave_sum(double v) {
-  v += dpp_shr<0x111>(v);
-  v += dpp_shr<0x112>(v);
-  v += dpp_shr<0x114>(v);
-  v += dpp_shr<0x118>(v);
-  return (lane_f64(v, 15) + lane_f64(v, 31)) + (lane_f64(v, 47) + lane_f64(v, 63));
 }
 
 // v with its sign flipped where s (0 or 0x80000000) says so: exactly +-v
@@ -298,9 +240,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
           acc[a] += flip(ib, sg[a]);
           acc[5 + a] += flip(qb, sg[a]);
         }
-        const double c2 = fma(cs, cw, -(sn * sw));
-        sn = fma(sn, cw, cs * sw);
-        cs = c2;
+        rotate(sn, cs, sw, cw);
       };
       // kU samples per thread per pass, the next pass's IF words loaded during
       // this one; the last, partial pass is guarded per sample
@@ -339,16 +279,14 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
     // 16-byte grid of the stream), q = tid + it*T
     constexpr int kBps = FT == 2 ? 2 : 1;
     auto run_chunks = [&]() {
-      const int mis = (int)((uintptr_t)src & 15) / kBps;
-      const uint4* ab = reinterpret_cast<const uint4*>(src - mis * kBps);
-      const int nC = (blk + mis + kC - 1) / kC;
-      const int nIt = (nC + T - 1) / T;
+      using Grid = ChunkGrid<kBps, kC>;
+      const Grid grid(src, blk, T);
       const double cst = uni(cstep), mst = uni(mstep);
       const double inv_c = uni(1.0 / cstep), inv_m = uni(1.0 / mstep);
       const double aX[3] = {uni(aE), uni(aP), uni(aL)};
       const double bX[3] = {uni(bE), uni(bP), uni(bL)};
       double sb, cb, sR, cR;
-      sincos(A * ((double)(tid * kC - mis) / p.fs) + c.rem_carr, &sb, &cb);
+      sincos(A * ((double)(tid * kC - grid.mis) / p.fs) + c.rem_carr, &sb, &cb);
       if (tid < kC) {
         double swl, cwl;
         sincos(A * ((double)tid / p.fs), &swl, &cwl);
@@ -358,28 +296,28 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
       sR = uni(sR);
       cR = uni(cR);
       __syncthreads();
-      constexpr int kW = kC * kBps / 16;   // 16-byte words per chunk
+      constexpr int kW = Grid::kW;   // 16-byte words per chunk
       uint4 nx[kW];
       auto fetch = [&](int it, uint4 (&x)[kW]) {
         const int q = it * T + tid;
 #pragma unroll
         for (int u = 0; u < kW; u++) {
           // only words holding a sample of the epoch: none past the record's end
-          const int ks = q * kC - mis + u * (16 / kBps);
-          x[u] = ks < blk ? ab[(int64_t)q * kW + u] : make_uint4(0, 0, 0, 0);
+          const int ks = q * kC - grid.mis + u * (16 / kBps);
+          x[u] = ks < blk ? grid.ab[(int64_t)q * kW + u] : make_uint4(0, 0, 0, 0);
         }
       };
       fetch(0, nx);
-      for (int it = 0; it < nIt; it++) {
+      for (int it = 0; it < grid.nIt; it++) {
         uint32_t wd[4 * kW];
 #pragma unroll
         for (int u = 0; u < kW; u++) {
           wd[4 * u] = nx[u].x; wd[4 * u + 1] = nx[u].y;
           wd[4 * u + 2] = nx[u].z; wd[4 * u + 3] = nx[u].w;
         }
-        if (it + 1 < nIt) fetch(it + 1, nx);
+        if (it + 1 < grid.nIt) fetch(it + 1, nx);
         const int q = it * T + tid;
-        const int k0 = q * kC - mis;
+        const int k0 = q * kC - grid.mis;
         // the epoch's first and last chunks: samples outside [0, blk) count as 0
         if (k0 < 0 || k0 + kC > blk) {
 #pragma unroll
@@ -396,29 +334,20 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
         uint32_t mc[3], ms[3];
         bool risky = false;
         auto low = [](int b) -> uint32_t { return (1u << b) - 1u; };   // b <= kC < 32
-        // sample k has index > j iff a + k*step > j, i.e. k > d = (j - a)/step: the
-        // first such sample is floor(d) + 1
-        auto crossing = [&](double j, double a, double inv) -> int {
-          const double d = (j - a) * inv;
-          const double fd = floor(d);
-          const double fr = d - fd;
-          risky |= !(fr > 1e-6 && fr < 1.0 - 1e-6);
-          return min(max((int)fd + 1 - k0, 1), kC);
-        };
 #pragma unroll
         for (int x = 0; x < 3; x++) {
           const double jf = ceil(aX[x] + tc0);
           const int j0 = (int)jf;
-          const int beta = crossing(jf, aX[x], inv_c);          // at most one step: 15*cstep < 1
+          const int beta = Grid::crossing(jf, aX[x], inv_c, k0, risky);   // one step at most: 15*cstep < 1
           const uint32_t g0 = 0u - cbit(j0), g1 = 0u - cbit(j0 + 1);
           mc[x] = (g0 & low(beta)) | (g1 & ~low(beta));
           const double hf = ceil(bX[x] + tm0);
-          const int b1 = crossing(hf, bX[x], inv_m);            // at most two: 15*mstep < 2
-          const int b2 = max(crossing(hf + 1.0, bX[x], inv_m), b1);
+          const int b1 = Grid::crossing(hf, bX[x], inv_m, k0, risky);     // two at most: 15*mstep < 2
+          const int b2 = max(Grid::crossing(hf + 1.0, bX[x], inv_m, k0, risky), b1);
           const uint32_t flipd = low(b1) ^ low(b2);             // samples [b1, b2): the other sign
           ms[x] = ((int)hf & 1) ? ~flipd : flipd;
         }
-        if (risky && q < nC) {
+        if (risky && q < grid.nC) {
           // a crossing without margin: the chunk's masks from the exact indices
           for (int x = 0; x < 3; x++) mc[x] = ms[x] = 0;
 #pragma unroll 1
@@ -470,9 +399,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
           acc[a] = fma(sb, Ur[a], fma(cb, Ui[a], acc[a]));
           acc[5 + a] = fma(cb, Ur[a], fma(-sb, Ui[a], acc[5 + a]));
         }
-        const double cn = fma(cb, cR, -(sb * sR));
-        sb = fma(sb, cR, cb * sR);
-        cb = cn;
+        rotate(sb, cb, sR, cR);
       }
     };
     // chunks need every index inside its table without the clamp mattering
@@ -552,23 +479,12 @@ struct gnsscorr_e1t_ctx {
   size_t chan_cap = 0, ep_cap = 0;
 };
 
-static void loop_coef(double lbw, double z, double* tau1, double* tau2) {
-  // calcLoopCoef.sci:39-43 (k = 1.0)
-  const double wn = lbw * 8 * z / (4 * (z * z) + 1);
-  *tau1 = 1.0 / (wn * wn);
-  *tau2 = 2.0 * z / wn;
-}
-
 extern "C" void gnsscorr_e1t_loop_coefs(const gnsscorr_e1t_cfg* cfg, double* tau1c, double* tau2c,
                                         double* tau1m, double* tau2m, double* k1, double* k2,
                                         double* k3) {
-  loop_coef(cfg->dll_noise_bw, cfg->dll_damping, tau1c, tau2c);
-  loop_coef(cfg->sll_noise_bw, cfg->sll_damping, tau1m, tau2m);
-  // calcFLLPLLLoopCoef.sci:36-38 (T = PDIcarr = 0.001)
-  const double T = 0.001, b = cfg->pll_noise_bw / 0.53;
-  *k1 = T * (b * b) + 1.414 * b;
-  *k2 = 1.414 * b;
-  *k3 = T * (cfg->fll_noise_bw / 0.25);
+  calc_loop_coef(cfg->dll_noise_bw, cfg->dll_damping, tau1c, tau2c);
+  calc_loop_coef(cfg->sll_noise_bw, cfg->sll_damping, tau1m, tau2m);
+  calc_fll_pll_loop_coef(cfg->pll_noise_bw, cfg->fll_noise_bw, k1, k2, k3);
 }
 
 static int check_cfg(const gnsscorr_e1t_cfg* cfg) {
@@ -603,17 +519,7 @@ extern "C" int gnsscorr_e1t_init_chan(const gnsscorr_e1t_cfg* cfg, int code_id, 
   return GNSSCORR_OK;
 }
 
-extern "C" int gnsscorr_e1t_destroy(gnsscorr_e1t_ctx* c) {
-  if (!c) return GNSSCORR_OK;
-  (void)hipSetDevice(c->cfg.device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(c->d_codes);
-  (void)hipFree(c->d_chan);
-  (void)hipFree(c->d_ep);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-  return GNSSCORR_OK;
-}
+extern "C" int gnsscorr_e1t_destroy(gnsscorr_e1t_ctx* c) { return ftrack::destroy(c); }
 
 extern "C" int gnsscorr_e1t_create(gnsscorr_e1t_ctx** out, const gnsscorr_e1t_cfg* cfg) {
   if (!out) return GNSSCORR_EINVAL;
@@ -706,19 +612,14 @@ extern "C" int gnsscorr_e1t_set_codes(gnsscorr_e1t_ctx* c, int n_codes, const in
 extern "C" int gnsscorr_e1t_track_dev(gnsscorr_e1t_ctx* c, const int8_t* d_if, int64_t stride,
                                       int64_t n_samples, int n_ch, gnsscorr_e1t_chan* d_chan,
                                       int n_epochs, int closed_loop, gnsscorr_e1t_epoch* d_ep) {
-  if (!c || !d_if || !d_chan || !d_ep || n_ch < 1 || n_epochs < 1 || n_samples < 0 ||
-      stride < 0) {
-    gnsscorr_set_error("gnsscorr_e1t_track_dev: bad arguments");
-    return GNSSCORR_EINVAL;
-  }
+  int rc = check_track_dev(__func__, c, d_if, d_chan, d_ep, n_ch, n_epochs, n_samples, stride);
+  if (rc) return rc;
   if (c->p.n_codes < 1) {
     gnsscorr_set_error("gnsscorr_e1t_track_dev: no codes (call gnsscorr_e1t_set_codes first)");
     return GNSSCORR_EINVAL;
   }
-  if (c->cfg.file_type == 2 && ((uintptr_t)d_if & 1)) {
-    gnsscorr_set_error("gnsscorr_e1t_track_dev: IQ record must be 2-byte aligned");
-    return GNSSCORR_EINVAL;
-  }
+  rc = check_iq_aligned(__func__, c, d_if);
+  if (rc) return rc;
   HIP_TRY(hipSetDevice(c->cfg.device));
   // two launch shapes: one wave per channel for many channels (throughput),
   // 256-thread workgroups otherwise (epoch latency of a receiver's worth of
@@ -753,10 +654,7 @@ extern "C" int gnsscorr_e1t_track_dev(gnsscorr_e1t_ctx* c, const int8_t* d_if, i
 extern "C" int gnsscorr_e1t_track(gnsscorr_e1t_ctx* c, const int8_t* d_if, int64_t stride,
                                   int64_t n_samples, int n_ch, gnsscorr_e1t_chan* h_chan,
                                   int n_epochs, int closed_loop, gnsscorr_e1t_epoch* h_ep) {
-  if (!c || !h_chan || !h_ep || n_ch < 1 || n_epochs < 1) {
-    gnsscorr_set_error("gnsscorr_e1t_track: bad arguments");
-    return GNSSCORR_EINVAL;
-  }
+  if (!c || !h_chan || !h_ep || n_ch < 1 || n_epochs < 1) return bad_arguments(__func__);
   if (c->p.n_codes < 1) {
     gnsscorr_set_error("gnsscorr_e1t_track: no codes (call gnsscorr_e1t_set_codes first)");
     return GNSSCORR_EINVAL;
@@ -769,93 +667,27 @@ extern "C" int gnsscorr_e1t_track(gnsscorr_e1t_ctx* c, const int8_t* d_if, int64
       return GNSSCORR_EINVAL;
     }
   }
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  const size_t nc = (size_t)n_ch, ne = nc * (size_t)n_epochs;
-  if (nc > c->chan_cap) {
-    (void)hipFree(c->d_chan);
-    c->d_chan = nullptr;
-    c->chan_cap = 0;
-    HIP_TRY(hipMalloc(&c->d_chan, nc * sizeof(gnsscorr_e1t_chan)));
-    c->chan_cap = nc;
-  }
-  if (ne > c->ep_cap) {
-    (void)hipFree(c->d_ep);
-    c->d_ep = nullptr;
-    c->ep_cap = 0;
-    HIP_TRY(hipMalloc(&c->d_ep, ne * sizeof(gnsscorr_e1t_epoch)));
-    c->ep_cap = ne;
-  }
-  HIP_TRY(hipMemcpyAsync(c->d_chan, h_chan, nc * sizeof(gnsscorr_e1t_chan),
-                         hipMemcpyHostToDevice, c->stream));
-  int rc = gnsscorr_e1t_track_dev(c, d_if, stride, n_samples, n_ch, c->d_chan, n_epochs,
-                                  closed_loop, c->d_ep);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h_chan, c->d_chan, nc * sizeof(gnsscorr_e1t_chan),
-                         hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(h_ep, c->d_ep, ne * sizeof(gnsscorr_e1t_epoch), hipMemcpyDeviceToHost,
-                         c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GNSSCORR_OK;
+  return ftrack::track(c, n_ch, h_chan, n_epochs, h_ep,
+                       [&](gnsscorr_e1t_chan* d_chan, gnsscorr_e1t_epoch* d_ep) {
+                         return gnsscorr_e1t_track_dev(c, d_if, stride, n_samples, n_ch, d_chan,
+                                                       n_epochs, closed_loop, d_ep);
+                       });
 }
 
-extern "C" int gnsscorr_e1t_sync(gnsscorr_e1t_ctx* c) {
-  if (!c) return GNSSCORR_EINVAL;
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GNSSCORR_OK;
-}
+extern "C" int gnsscorr_e1t_sync(gnsscorr_e1t_ctx* c) { return ftrack::sync(c); }
 
-extern "C" void* gnsscorr_e1t_stream(gnsscorr_e1t_ctx* c) { return c ? (void*)c->stream : nullptr; }
+extern "C" void* gnsscorr_e1t_stream(gnsscorr_e1t_ctx* c) { return ftrack::stream(c); }
 
 extern "C" int gnsscorr_e1t_replay_dev(gnsscorr_e1t_ctx* c, int n_ch, gnsscorr_e1t_chan* d_chan,
                                        int n_epochs, const double* d_sums,
                                        gnsscorr_e1t_epoch* d_ep) {
-  if (!c || !d_chan || !d_sums || !d_ep || n_ch < 1 || n_epochs < 1) {
-    gnsscorr_set_error("gnsscorr_e1t_replay_dev: bad arguments");
-    return GNSSCORR_EINVAL;
-  }
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  hipLaunchKernelGGL(e1t_replay_kernel, dim3((n_ch + 63) / 64), dim3(64), 0, c->stream, c->p,
-                     d_chan, n_ch, n_epochs, d_sums, d_ep);
-  HIP_TRY(hipGetLastError());
-  return GNSSCORR_OK;
+  return ftrack::replay_dev(__func__, c, e1t_replay_kernel, n_ch, d_chan, n_epochs, d_sums, d_ep);
 }
 
 extern "C" int gnsscorr_e1t_replay(gnsscorr_e1t_ctx* c, int n_ch, gnsscorr_e1t_chan* h_chan,
                                    int n_epochs, const double* h_sums, gnsscorr_e1t_epoch* h_ep) {
-  if (!c || !h_chan || !h_sums || !h_ep || n_ch < 1 || n_epochs < 1) {
-    gnsscorr_set_error("gnsscorr_e1t_replay: bad arguments");
-    return GNSSCORR_EINVAL;
-  }
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  const size_t nc = (size_t)n_ch, ne = nc * (size_t)n_epochs;
-  gnsscorr_e1t_chan* d_chan = nullptr;
-  double* d_sums = nullptr;
-  gnsscorr_e1t_epoch* d_ep = nullptr;
-  hipError_t e = hipMalloc(&d_chan, nc * sizeof(gnsscorr_e1t_chan));
-  if (e == hipSuccess) e = hipMalloc(&d_sums, ne * 10 * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&d_ep, ne * sizeof(gnsscorr_e1t_epoch));
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(d_chan, h_chan, nc * sizeof(gnsscorr_e1t_chan), hipMemcpyHostToDevice,
-                       c->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(d_sums, h_sums, ne * 10 * sizeof(double), hipMemcpyHostToDevice,
-                       c->stream);
-  int rc = GNSSCORR_OK;
-  if (e == hipSuccess) rc = gnsscorr_e1t_replay_dev(c, n_ch, d_chan, n_epochs, d_sums, d_ep);
-  if (e == hipSuccess && rc == GNSSCORR_OK)
-    e = hipMemcpyAsync(h_chan, d_chan, nc * sizeof(gnsscorr_e1t_chan), hipMemcpyDeviceToHost,
-                       c->stream);
-  if (e == hipSuccess && rc == GNSSCORR_OK)
-    e = hipMemcpyAsync(h_ep, d_ep, ne * sizeof(gnsscorr_e1t_epoch), hipMemcpyDeviceToHost,
-                       c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d_chan);
-  (void)hipFree(d_sums);
-  (void)hipFree(d_ep);
-  if (e != hipSuccess) {
-    gnsscorr_set_error("gnsscorr_e1t_replay: %s", hipGetErrorString(e));
-    return GNSSCORR_EDEVICE;
-  }
-  return rc;
+  return ftrack::replay<10>(__func__, c, n_ch, h_chan, n_epochs, h_sums, h_ep,
+                            [&](gnsscorr_e1t_chan* d_chan, double* d_sums, gnsscorr_e1t_epoch* d_ep) {
+                              return gnsscorr_e1t_replay_dev(c, n_ch, d_chan, n_epochs, d_sums, d_ep);
+                            });
 }

@@ -1,0 +1,301 @@
+// ftrack.h -- what the two float trackers (sgt.hip, e1t.hip) share: lane
+// helpers and the carrier rotation, the chunk grid of the chunked paths
+// (geometry and the crossing estimate with its margin), the loop-filter steps
+// of the epoch end and the host scaffolding around a tracking context.
+// Everything on the device side is __forceinline__ and carries its own fp
+// contract(off): the code indices and the NCO carry-over are bit-exact
+// restatements of tracking.sci, whose line citations stay next to the call
+// sites in each tracker.
+// Deliberately not here, although the two kernels spell them alike: the
+// per-sample pass loop, the epoch reduction, and the chunk loop's fetch / unpack
+// / edge masking, W_n * raw product and opaque table offset.  Each was tried as
+// a shared function and each changed the instructions the compiler emits for at
+// least one tracking kernel (e1t: up to +6 VGPRs); both kernels sit on their
+// register bounds, so those pieces stay in the kernels.
+#ifndef GNSSCORR_FTRACK_H
+#define GNSSCORR_FTRACK_H
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include "gnsscorr_internal.h"
+
+namespace ftrack {
+
+// ============================================================================
+// lane helpers
+// ============================================================================
+// indices stay inside their table for every state the loop produces; the clamp
+// only keeps a corrupted state inside the LDS table, in one instruction: a
+// negative index wraps to a huge unsigned and lands on hi
+__device__ __forceinline__ int clampu(int i, int hi) { return (int)min((unsigned)i, (unsigned)hi); }
+
+// a value every lane of the workgroup holds (the channel's state is uniform):
+// held in scalar registers instead of a VGPR pair
+__device__ __forceinline__ double uni(double v) {
+  const long long b = __double_as_longlong(v);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((int)b);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// wave total, uniform: DPP row_shr 1/2/4/8 (a Hillis-Steele scan in each
+// 16-lane row, 0.0 shifted in) leaves each row's sum in its lane 15 and the
+// four rows add in scalar registers -- VALU only, where a 64-bit __shfl_xor
+// butterfly is two ds_bpermute round trips per step.  Every lane must be active.
+template <int CTRL>
+__device__ __forceinline__ double dpp_shr(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
+  return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double lane_f64(double v, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l),
+                          __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma clang fp contract(off)
+  v += dpp_shr<0x111>(v);
+  v += dpp_shr<0x112>(v);
+  v += dpp_shr<0x114>(v);
+  v += dpp_shr<0x118>(v);
+  return (lane_f64(v, 15) + lane_f64(v, 31)) + (lane_f64(v, 47) + lane_f64(v, 63));
+}
+
+// (sb, cb) <- (sb, cb) * (sR, cR): the carrier one rotation on (explicit fma:
+// the carrier only needs fp64 accuracy)
+__device__ __forceinline__ void rotate(double& sb, double& cb, double sR, double cR) {
+#pragma clang fp contract(off)
+  const double cn = fma(cb, cR, -(sb * sR));
+  sb = fma(sb, cR, cb * sR);
+  cb = cn;
+}
+
+// ============================================================================
+// chunked paths: the epoch's samples as chunks of kC on the 16-byte grid of the
+// stream.  Chunk q holds samples k0 = q*kC - mis .. k0 + kC - 1, thread tid takes
+// q = tid + it*T.  kBps: bytes per sample (2 = IQ records, 1 = real).
+// ============================================================================
+template <int kBps, int kC>
+struct ChunkGrid {
+  static constexpr int kW = kC * kBps / 16;   // 16-byte words per chunk
+  int mis;           // samples between the grid and the epoch's first
+  const uint4* ab;   // the grid word holding the epoch's first sample
+  int nC, nIt;       // chunks of the epoch, chunks per thread
+
+  __device__ __forceinline__ ChunkGrid(const int8_t* src, int blk, int T) {
+    mis = (int)((uintptr_t)src & 15) / kBps;
+    ab = reinterpret_cast<const uint4*>(src - mis * kBps);
+    nC = (blk + mis + kC - 1) / kC;
+    nIt = (nC + T - 1) / T;
+  }
+
+  // Where an index a + k*step next exceeds j: sample k has index > j iff
+  // a + k*step > j, i.e. k > d = (j - a)/step (inv = 1/step), so the first such
+  // sample is floor(d) + 1; returned as an offset into the chunk at k0, clamped
+  // to [1, kC].  When d lies within 1e-6 samples of an integer the real-valued
+  // estimate could round either way: risky is set and the caller recomputes the
+  // chunk with the exact fp64 indices, sample by sample.
+  static __device__ __forceinline__ int crossing(double j, double a, double inv, int k0,
+                                                 bool& risky) {
+#pragma clang fp contract(off)
+    const double d = (j - a) * inv;
+    const double fd = floor(d);
+    const double fr = d - fd;
+    risky |= !(fr > 1e-6 && fr < 1.0 - 1e-6);
+    return min(max((int)fd + 1 - k0, 1), kC);
+  }
+};
+
+// ============================================================================
+// epoch end.  Chan: any channel struct with the common field names
+// (gnsscorr_sgt_chan, gnsscorr_e1t_chan).
+// ============================================================================
+// remCarrPhase after blk samples at A = carrFreq*2*pi rad/s
+template <class Chan>
+__device__ __forceinline__ void carry_carrier(Chan& c, double A, int blk, double fs) {
+#pragma clang fp contract(off)
+  const double twopi = 2.0 * M_PI;
+  const double last = A * ((double)blk / fs) + c.rem_carr;   // trigarg(blksize+1)
+  c.rem_carr = last - trunc(last / twopi) * twopi;
+}
+
+// FLL-assisted PLL on the prompt sums: sets carr_freq, returns the PLL discriminator
+template <class Chan>
+__device__ __forceinline__ double fll_pll_step(Chan& c, double k1, double k2, double k3,
+                                               double I_P, double Q_P) {
+#pragma clang fp contract(off)
+  const double I2 = c.i1, Q2 = c.q1;
+  c.i1 = I_P; c.q1 = Q_P;
+  const double cross = c.i1 * Q2 - I2 * c.q1;
+  const double dot = fabs(c.i1 * I2 + c.q1 * Q2);
+  const double freq_err = atan2(cross, dot) / M_PI;
+  const double carr_err = atan(Q_P / I_P) / (2.0 * M_PI);
+  const double carr_nco = c.old_carr_nco + k1 * carr_err - k2 * c.old_carr_error - k3 * freq_err;
+  c.old_carr_nco = carr_nco;
+  c.old_carr_error = carr_err;
+  c.carr_freq = c.carr_freq_basis + carr_nco;
+  return carr_err;
+}
+
+// early-minus-late magnitude discriminator and its tau2/tau1 filter (pdi: the
+// loop's integration time): updates the NCO command and the kept error,
+// returns the discriminator
+__device__ __forceinline__ double early_late_step(double I_E, double Q_E, double I_L, double Q_L,
+                                                  double tau1, double tau2, double pdi,
+                                                  double& old_nco, double& old_error) {
+#pragma clang fp contract(off)
+  const double mE = sqrt(I_E * I_E + Q_E * Q_E), mL = sqrt(I_L * I_L + Q_L * Q_L);
+  const double err = (mE - mL) / (mE + mL);
+  const double nco = old_nco + (tau2 / tau1) * (err - old_error) + err * (pdi / tau1);
+  old_nco = nco;
+  old_error = err;
+  return err;
+}
+
+// ============================================================================
+// host side.  Ctx: a tracking context with cfg.device, p (the kernel's params),
+// stream, d_codes and the host wrappers' own d_chan / d_ep with their
+// capacities.  fn: the exported function's name, for its error texts.
+// ============================================================================
+inline int bad_arguments(const char* fn) {
+  gnsscorr_set_error("%s: bad arguments", fn);
+  return GNSSCORR_EINVAL;
+}
+
+// calcLoopCoef.sci:39-43 (k = 1.0)
+inline void calc_loop_coef(double lbw, double z, double* tau1, double* tau2) {
+  const double wn = lbw * 8 * z / (4 * (z * z) + 1);
+  *tau1 = 1.0 / (wn * wn);
+  *tau2 = 2.0 * z / wn;
+}
+
+// calcFLLPLLLoopCoef.sci:36-38 (T = PDIcarr = 0.001)
+inline void calc_fll_pll_loop_coef(double pll_bw, double fll_bw, double* k1, double* k2,
+                                   double* k3) {
+  const double T = 0.001, b = pll_bw / 0.53;
+  *k1 = T * (b * b) + 1.414 * b;
+  *k2 = 1.414 * b;
+  *k3 = T * (fll_bw / 0.25);
+}
+
+template <class Ctx>
+int destroy(Ctx* c) {
+  if (!c) return GNSSCORR_OK;
+  (void)hipSetDevice(c->cfg.device);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  (void)hipFree(c->d_codes);
+  (void)hipFree(c->d_chan);
+  (void)hipFree(c->d_ep);
+  if (c->stream) (void)hipStreamDestroy(c->stream);
+  delete c;
+  return GNSSCORR_OK;
+}
+
+template <class Ctx>
+int sync(Ctx* c) {
+  if (!c) return GNSSCORR_EINVAL;
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return GNSSCORR_OK;
+}
+
+template <class Ctx>
+void* stream(Ctx* c) { return c ? (void*)c->stream : nullptr; }
+
+// room for n elements; a failed growth leaves a null buffer of capacity 0
+template <class T>
+int ensure_capacity(T*& buf, size_t& cap, size_t n) {
+  if (n <= cap) return GNSSCORR_OK;
+  (void)hipFree(buf);
+  buf = nullptr;
+  cap = 0;
+  HIP_TRY(hipMalloc(&buf, n * sizeof(T)));
+  cap = n;
+  return GNSSCORR_OK;
+}
+
+// the checks *_track_dev share
+template <class Ctx>
+int check_track_dev(const char* fn, const Ctx* c, const int8_t* d_if, const void* d_chan,
+                    const void* d_ep, int n_ch, int n_epochs, int64_t n_samples, int64_t stride) {
+  if (!c || !d_if || !d_chan || !d_ep || n_ch < 1 || n_epochs < 1 || n_samples < 0 || stride < 0)
+    return bad_arguments(fn);
+  return GNSSCORR_OK;
+}
+template <class Ctx>
+int check_iq_aligned(const char* fn, const Ctx* c, const int8_t* d_if) {
+  if (c->cfg.file_type == 2 && ((uintptr_t)d_if & 1)) {
+    gnsscorr_set_error("%s: IQ record must be 2-byte aligned", fn);
+    return GNSSCORR_EINVAL;
+  }
+  return GNSSCORR_OK;
+}
+
+// host channels in, track_dev(d_chan, d_ep) on the context's own buffers, host
+// channels and epochs out, synchronised
+template <class Ctx, class Chan, class Epoch, class TrackDev>
+int track(Ctx* c, int n_ch, Chan* h_chan, int n_epochs, Epoch* h_ep, const TrackDev& track_dev) {
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  const size_t nc = (size_t)n_ch, ne = nc * (size_t)n_epochs;
+  int rc = ensure_capacity(c->d_chan, c->chan_cap, nc);
+  if (rc) return rc;
+  rc = ensure_capacity(c->d_ep, c->ep_cap, ne);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(c->d_chan, h_chan, nc * sizeof(Chan), hipMemcpyHostToDevice, c->stream));
+  rc = track_dev(c->d_chan, c->d_ep);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(h_chan, c->d_chan, nc * sizeof(Chan), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(h_ep, c->d_ep, ne * sizeof(Epoch), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return GNSSCORR_OK;
+}
+
+// the loop half on given sums: one thread per channel
+template <class Ctx, class Kernel, class Chan, class Epoch>
+int replay_dev(const char* fn, Ctx* c, Kernel kernel, int n_ch, Chan* d_chan, int n_epochs,
+               const double* d_sums, Epoch* d_ep) {
+  if (!c || !d_chan || !d_sums || !d_ep || n_ch < 1 || n_epochs < 1) return bad_arguments(fn);
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  hipLaunchKernelGGL(kernel, dim3((n_ch + 63) / 64), dim3(64), 0, c->stream, c->p, d_chan, n_ch,
+                     n_epochs, d_sums, d_ep);
+  HIP_TRY(hipGetLastError());
+  return GNSSCORR_OK;
+}
+
+// host channels and sums [n_ch, n_epochs, N] in, replay_dev(d_chan, d_sums,
+// d_ep) on buffers of this call's own, host channels and epochs out
+template <int N, class Ctx, class Chan, class Epoch, class ReplayDev>
+int replay(const char* fn, Ctx* c, int n_ch, Chan* h_chan, int n_epochs, const double* h_sums,
+           Epoch* h_ep, const ReplayDev& replay_dev) {
+  if (!c || !h_chan || !h_sums || !h_ep || n_ch < 1 || n_epochs < 1) return bad_arguments(fn);
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  const size_t nc = (size_t)n_ch, ne = nc * (size_t)n_epochs;
+  Chan* d_chan = nullptr;
+  double* d_sums = nullptr;
+  Epoch* d_ep = nullptr;
+  hipError_t e = hipMalloc(&d_chan, nc * sizeof(Chan));
+  if (e == hipSuccess) e = hipMalloc(&d_sums, ne * N * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&d_ep, ne * sizeof(Epoch));
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(d_chan, h_chan, nc * sizeof(Chan), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(d_sums, h_sums, ne * N * sizeof(double), hipMemcpyHostToDevice, c->stream);
+  int rc = GNSSCORR_OK;
+  if (e == hipSuccess) rc = replay_dev(d_chan, d_sums, d_ep);
+  if (e == hipSuccess && rc == GNSSCORR_OK)
+    e = hipMemcpyAsync(h_chan, d_chan, nc * sizeof(Chan), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && rc == GNSSCORR_OK)
+    e = hipMemcpyAsync(h_ep, d_ep, ne * sizeof(Epoch), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(d_chan);
+  (void)hipFree(d_sums);
+  (void)hipFree(d_ep);
+  if (e != hipSuccess) {
+    gnsscorr_set_error("%s: %s", fn, hipGetErrorString(e));
+    return GNSSCORR_EDEVICE;
+  }
+  return rc;
+}
+
+}  // namespace ftrack
+#endif

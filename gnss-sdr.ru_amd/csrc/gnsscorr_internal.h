@@ -42,4 +42,18 @@ void gnsscorr_sdr_post_dft(int16_t *out);
 #ifdef __cplusplus
 }
 #endif
+
+#ifdef __HIPCC__
+/* a failed HIP call: the error text names the call and its place, the
+ * enclosing function returns GNSSCORR_EDEVICE */
+#define HIP_TRY(expr)                                                                   \
+  do {                                                                                  \
+    hipError_t _e = (expr);                                                             \
+    if (_e != hipSuccess) {                                                             \
+      gnsscorr_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
+                         __LINE__);                                                     \
+      return GNSSCORR_EDEVICE;                                                          \
+    }                                                                                   \
+  } while (0)
+#endif
 #endif

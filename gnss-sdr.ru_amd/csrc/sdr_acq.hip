@@ -40,16 +40,6 @@
 #include <string.h>
 #include "gnsscorr_internal.h"
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) {                                                             \
-      gnsscorr_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
-                         __LINE__);                                                     \
-      return GNSSCORR_EDEVICE;                                                          \
-    }                                                                                   \
-  } while (0)
-
 namespace {
 
 constexpr int kN = 2048;

@@ -29,16 +29,6 @@
 
 #pragma clang fp contract(off)
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) {                                                             \
-      gnsscorr_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
-                         __LINE__);                                                     \
-      return GNSSCORR_EDEVICE;                                                          \
-    }                                                                                   \
-  } while (0)
-
 namespace {
 
 constexpr int kEmpty = 0, kNormal = 3;          // Channel_State (channel.h:33-39)

@@ -27,16 +27,6 @@
 #include "gnsscorr_internal.h"
 #include "sdr_corr_state.h"
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) {                                                             \
-      gnsscorr_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
-                         __LINE__);                                                     \
-      return GNSSCORR_EDEVICE;                                                          \
-    }                                                                                   \
-  } while (0)
-
 namespace {
 
 using namespace sdrc;

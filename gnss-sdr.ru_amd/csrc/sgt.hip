@@ -33,56 +33,26 @@
 #include <stdlib.h>
 #include <string.h>
 #include "gnsscorr_internal.h"
-
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) {                                                             \
-      gnsscorr_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
-                         __LINE__);                                                     \
-      return GNSSCORR_EDEVICE;                                                          \
-    }                                                                                   \
-  } while (0)
+#include "ftrack.h"
 
 namespace {
+using namespace ftrack;
 
 constexpr int kMaxCode = 1023;
 constexpr int kPadLen = kMaxCode + 2;
 constexpr int kMaxWaves = 16;
-#ifndef SGT_KC32
-#define SGT_KC32 1
-#endif
-#ifndef SGT_WPE
-#define SGT_WPE 3
-#endif
-#ifndef SGT_PREFIX
-#define SGT_PREFIX 1
-#endif
-// chunked path, SGT_PREFIX: per-lane prefix sums of W_n*raw over sub-blocks of
-// kSub samples staged in LDS (kSub x 64 x 16 B per wave), read back at each
+// wave mode asks for 3 waves per SIMD (<= 168 VGPRs): measured 3 % faster than 2
+constexpr int kWaveOcc = 3;
+// run_chunks with prefix columns: per-lane prefix sums of W_n*raw over sub-blocks
+// of kSub samples staged in LDS (kSub x 64 x 16 B per wave), read back at each
 // arm's crossing, instead of a code select and two FMAs per arm and sample
-#ifndef SGT_KSUB
-#define SGT_KSUB 16
-#endif
-// wave mode: chip-aligned chunks (run_chips) instead of the prefix columns,
-// which then stay out of the wave kernel's LDS
-#ifndef SGT_CHIPS
-#define SGT_CHIPS 1
-#endif
-#ifndef SGT_CHIP_GROUP
-#define SGT_CHIP_GROUP 4
-#endif
-#ifndef SGT_CHIP_FMA
-#define SGT_CHIP_FMA 1
-#endif
-#ifndef SGT_CHIP_PF
-#define SGT_CHIP_PF 1     // the next chunk's IF words loaded during this chunk
-#endif
-constexpr int kSub = SGT_KSUB;
+constexpr int kSub = 16;
 constexpr int kPfWaveBytes = kSub * 64 * 16;
-__host__ __device__ constexpr bool sgt_prefix(int maxt) {
-  return SGT_PREFIX && maxt <= 256 && !(SGT_CHIPS && maxt == 64);
-}
+// run_chips: samples per group of the sample loop (see there)
+constexpr int kChipGroup = 4;
+// the 256-thread shape has the prefix columns; the wave kernel (chip-aligned
+// chunks, its LDS the two tables only) and the 1024-thread one select per sample
+__host__ __device__ constexpr bool sgt_prefix(int maxt) { return maxt <= 256 && maxt != 64; }
 __host__ __device__ constexpr size_t sgt_tab_bytes(int code_length) {
   return ((size_t)(code_length + 3) * sizeof(double) + 15) & ~(size_t)15;   // s_sgn + guard
 }
@@ -106,35 +76,19 @@ __device__ __forceinline__ gnsscorr_sgt_epoch sgt_epoch_end(const SgtParams& p,
                                                             double step, const double (&S)[6]) {
 #pragma clang fp contract(off)
   const double I_E = S[0], I_P = S[1], I_L = S[2], Q_E = S[3], Q_P = S[4], Q_L = S[5];
-  const double dL = (double)p.code_length, twopi = 2.0 * M_PI;
+  const double dL = (double)p.code_length;
   const double A = (c.carr_freq * 2.0) * M_PI;        // (carrFreq * 2.0 * %pi)
   // carry-over (tracking.sci:301-313)
   const double tlast = c.rem_code + (double)(blk - 1) * step;   // tcode(blksize), prompt range
   c.rem_code = (tlast + step) - dL;
-  const double last = A * ((double)blk / p.fs) + c.rem_carr;
-  c.rem_carr = last - trunc(last / twopi) * twopi;
+  carry_carrier(c, A, blk, p.fs);
   c.pos += blk;
   double code_err = 0, carr_err = 0;
   if (CLOSED) {
-    // FLL-assisted PLL (tracking.sci:329-353)
-    const double I2 = c.i1, Q2 = c.q1;
-    c.i1 = I_P; c.q1 = Q_P;
-    const double cross = c.i1 * Q2 - I2 * c.q1;
-    const double dot = fabs(c.i1 * I2 + c.q1 * Q2);
-    const double freq_err = atan2(cross, dot) / M_PI;
-    carr_err = atan(Q_P / I_P) / (2.0 * M_PI);
-    const double carr_nco = c.old_carr_nco + p.k1 * carr_err - p.k2 * c.old_carr_error -
-                            p.k3 * freq_err;
-    c.old_carr_nco = carr_nco;
-    c.old_carr_error = carr_err;
-    c.carr_freq = c.carr_freq_basis + carr_nco;
-    // DLL (tracking.sci:355-374)
-    const double aEm = sqrt(I_E * I_E + Q_E * Q_E), aLm = sqrt(I_L * I_L + Q_L * Q_L);
-    code_err = (aEm - aLm) / (aEm + aLm);
-    const double code_nco = c.old_code_nco + (p.tau2 / p.tau1) * (code_err - c.old_code_error) +
-                            code_err * (p.pdi_code / p.tau1);
-    c.old_code_nco = code_nco;
-    c.old_code_error = code_err;
+    carr_err = fll_pll_step(c, p.k1, p.k2, p.k3, I_P, Q_P);   // tracking.sci:329-353
+    code_err = early_late_step(I_E, Q_E, I_L, Q_L, p.tau1, p.tau2, p.pdi_code, c.old_code_nco,
+                               c.old_code_error);             // DLL, tracking.sci:355-374
+    const double code_nco = c.old_code_nco;
     if (p.code_nco_variant == 1) {
       c.code_freq = p.code_basis - code_nco;               // :366, no carrier aiding
     } else if (p.system == 1) {
@@ -170,55 +124,14 @@ __device__ __forceinline__ int xcd_channel(int b, int G) {
   return x * q + (x < r ? x : r) + slot;
 }
 
-// indices are in [0, L+1] for every state the loop produces (remCode in
-// [0, step)); the clamp only keeps a corrupted state inside the LDS table, in
-// one instruction: a negative index wraps to a huge unsigned and lands on hi
-__device__ __forceinline__ int clampu(int i, int hi) { return (int)min((unsigned)i, (unsigned)hi); }
-
-// a value every lane of the workgroup holds (the channel's state is uniform):
-// held in scalar registers instead of a VGPR pair
-__device__ __forceinline__ double uni(double v) {
-  const long long b = __double_as_longlong(v);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((int)b);
-  const unsigned hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-// wave total, uniform: DPP row_shr 1/2/4/8 (a Hillis-Steele scan in each
-// 16-lane row, 0.0 shifted in) leaves each row's sum in its lane 15 and the
-// four rows add in scalar registers -- VALU only, where a 64-bit __shfl_xor
-// butterfly is two ds_bpermute round trips per step.  Every lane must be active.
-template <int CTRL>
-__device__ __forceinline__ double dpp_shr(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double lane_f64(double v, int l) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l),
-                          __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-__device__ __forceinline__ double wave_sum(double v) {
-  v += dpp_shr<0x111>(v);
-  v += dpp_shr<0x112>(v);
-  v += dpp_shr<0x114>(v);
-  v += dpp_shr<0x118>(v);
-  return (lane_f64(v, 15) + lane_f64(v, 31)) + (lane_f64(v, 47) + lane_f64(v, 63));
-}
-
 // WAVE: one wavefront per channel (many-channel launches): the butterfly sums
 // leave the totals in every lane, so an epoch needs no LDS partials and no
 // barrier, and the loop filters run once per wave instead of once per wave of
 // a 4-16-wave workgroup.
 // MAXT: the launch bound (64 = WAVE; 256 for the default small-receiver shape,
 // which then keeps its registers instead of fitting the 1024-thread budget).
-// Wave mode asks for 3 waves per SIMD (<= 168 VGPRs): measured 3 % faster than
-// the 2 the chunked path otherwise compiles to.
 template <int FT, bool CLOSED, int MAXT>
-// (with the prefix columns a wave-mode workgroup takes 16 KiB + the code table:
-// 7 fit a CU for GLONASS (511 chips, 4112 B table), 6 for GPS (1023 chips, 8208 B);
-// that is under 2 waves per SIMD, so the bound asks for 2)
-__global__ __launch_bounds__(MAXT, MAXT == 64 ? (sgt_prefix(64) ? 2 : SGT_WPE) : 1) void sgt_track_kernel(
+__global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_kernel(
     SgtParams p, const int8_t* __restrict__ ifbuf, int64_t stride, int64_t n_samples,
     const uint32_t* __restrict__ codes, gnsscorr_sgt_chan* __restrict__ chans, int n_epochs,
     gnsscorr_sgt_epoch* __restrict__ out) {
@@ -323,9 +236,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? (sgt_prefix(64) ? 2 : SGT_WPE) :
       const double ib = fma(cs, im, sn * re);      // imag(carrsig .* rawSignal)
       ie = fma(ib, gE, ie); ip = fma(ib, gP, ip); il = fma(ib, gL, il);   // +-ib exactly
       qe = fma(qb, gE, qe); qp = fma(qb, gP, qp); ql = fma(qb, gL, ql);
-      const double c2 = fma(cs, cw, -(sn * sw));
-      sn = fma(sn, cw, cs * sw);
-      cs = c2;
+      rotate(sn, cs, sw, cw);
     };
     const int n_full = blk / (kU * T);   // passes whose kU samples all exist for every thread
     int k0 = tid;
@@ -376,14 +287,12 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? (sgt_prefix(64) ? 2 : SGT_WPE) :
     constexpr int kBps = FT == 2 ? 2 : 1;
     auto run_chunks = [&](auto kc_tag) {
       constexpr int kC = decltype(kc_tag)::value;
-      const int mis = (int)((uintptr_t)src & 15) / kBps;
-      const uint4* ab = reinterpret_cast<const uint4*>(src - mis * kBps);
-      const int nC = (blk + mis + kC - 1) / kC;
-      const int nIt = (nC + T - 1) / T;
+      using Grid = ChunkGrid<kBps, kC>;
+      const Grid grid(src, blk, T);
       const double inv_step = uni(1.0 / step), stp = uni(step);
       const double aX[3] = {uni(aE), uni(aP), uni(aL)};
       double sb, cb, sR, cR;
-      sincos(A * ((double)(tid * kC - mis) / p.fs) + c.rem_carr, &sb, &cb);
+      sincos(A * ((double)(tid * kC - grid.mis) / p.fs) + c.rem_carr, &sb, &cb);
       double swl = 0.0, cwl = 1.0;
       if (WAVE || tid < kC) sincos(A * ((double)tid / p.fs), &swl, &cwl);   // W_tid
       if (tid < kC) s_w[tid] = make_double2(cwl, swl);
@@ -404,28 +313,28 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? (sgt_prefix(64) ? 2 : SGT_WPE) :
       }
       __syncthreads();
       double accI[3] = {0.0, 0.0, 0.0}, accQ[3] = {0.0, 0.0, 0.0};
-      constexpr int kW = kC * kBps / 16;   // 16-byte words per chunk
+      constexpr int kW = Grid::kW;   // 16-byte words per chunk
       uint4 nx[kW];
       auto fetch = [&](int it, uint4 (&x)[kW]) {
         const int q = it * T + tid;
 #pragma unroll
         for (int u = 0; u < kW; u++) {
           // only words holding a sample of the epoch: none past the stream's end
-          const int ks = q * kC - mis + u * (16 / kBps);
-          x[u] = ks < blk ? ab[q * kW + u] : make_uint4(0, 0, 0, 0);
+          const int ks = q * kC - grid.mis + u * (16 / kBps);
+          x[u] = ks < blk ? grid.ab[q * kW + u] : make_uint4(0, 0, 0, 0);
         }
       };
       fetch(0, nx);
-      for (int it = 0; it < nIt; it++) {
+      for (int it = 0; it < grid.nIt; it++) {
         uint32_t wd[4 * kW];
 #pragma unroll
         for (int u = 0; u < kW; u++) {
           wd[4 * u] = nx[u].x; wd[4 * u + 1] = nx[u].y;
           wd[4 * u + 2] = nx[u].z; wd[4 * u + 3] = nx[u].w;
         }
-        if (it + 1 < nIt) fetch(it + 1, nx);
+        if (it + 1 < grid.nIt) fetch(it + 1, nx);
         const int q = it * T + tid;
-        const int k0 = q * kC - mis;
+        const int k0 = q * kC - grid.mis;
         // the epoch's first and last chunks: samples outside [0, blk) count as 0
         if (k0 < 0 || k0 + kC > blk) {
 #pragma unroll
@@ -444,17 +353,13 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? (sgt_prefix(64) ? 2 : SGT_WPE) :
         for (int x = 0; x < 3; x++) {
           const double jf = ceil(aX[x] + t0);
           j0[x] = (int)jf;
-          const double d = (jf - aX[x]) * inv_step;
-          const double fd = floor(d);
-          const double fr = d - fd;
-          risky |= !(fr > 1e-6 && fr < 1.0 - 1e-6);
-          beta[x] = min(max((int)fd + 1 - k0, 1), kC);
+          beta[x] = Grid::crossing(jf, aX[x], inv_step, k0, risky);
           // the code as +-1.0: only the high word differs (the low one is 0)
           const uint32_t* sg = reinterpret_cast<const uint32_t*>(s_sgn) + 1;
           g0[x] = __longlong_as_double((long long)sg[2 * clampu(j0[x], L + 1)] << 32);
           g1[x] = __longlong_as_double((long long)sg[2 * clampu(j0[x] + 1, L + 1)] << 32);
         }
-        if (risky && q < nC) {
+        if (risky && q < grid.nC) {
           // exact crossings: the first sample whose index exceeds j0
 #pragma unroll 1
           for (int x = 0; x < 3; x++) {
@@ -466,8 +371,6 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? (sgt_prefix(64) ? 2 : SGT_WPE) :
           }
         }
         double Ur[3] = {0.0, 0.0, 0.0}, Ui[3] = {0.0, 0.0, 0.0};
-        // the W_n reads are loop invariant: an opaque offset per chunk keeps
-        // them from being hoisted out of the chunk loop (16 complex in VGPRs)
         int wo = 0;
         asm volatile("" : "+v"(wo));
         if constexpr (kPrefix) {
@@ -535,9 +438,6 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? (sgt_prefix(64) ? 2 : SGT_WPE) :
             Ur[x] = fma(ur, g, Ur[x]);
             Ui[x] = fma(ui, g, Ui[x]);
           }
-#ifdef SGT_SCHED
-          if (n % SGT_SCHED == SGT_SCHED - 1) __builtin_amdgcn_sched_barrier(0);
-#endif
         }
         // exp(i theta_k0) * U: real part -> Q (qBasebandSignal), imaginary -> I
 #pragma unroll
@@ -545,9 +445,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? (sgt_prefix(64) ? 2 : SGT_WPE) :
           accQ[x] = fma(cb, Ur[x], fma(-sb, Ui[x], accQ[x]));
           accI[x] = fma(sb, Ur[x], fma(cb, Ui[x], accI[x]));
         }
-        const double cn = fma(cb, cR, -(sb * sR));
-        sb = fma(sb, cR, cb * sR);
-        cb = cn;
+        rotate(sb, cb, sR, cR);   // the carrier T chunks on
       }
       ie = accI[0]; ip = accI[1]; il = accI[2];
       qe = accQ[0]; qp = accQ[1]; ql = accQ[2];
@@ -654,17 +552,16 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? (sgt_prefix(64) ? 2 : SGT_WPE) :
       double sb, cb;   // carrier at the chunk's first sample
       sincos(A * ((double)b.kS / p.fs) + c.rem_carr, &sb, &cb);
       uint32_t nx[kNW];
-      if (SGT_CHIP_PF) fetch(b, nx);
+      fetch(b, nx);   // the next chunk's IF words load during this chunk
       for (int it = 0; it < nIt; it++) {
         uint32_t w[kNW];
-        if (!SGT_CHIP_PF) fetch(b, nx);
 #pragma unroll
         for (int u = 0; u < kNW; u++) w[u] = nx[u];
         const int j = jF + it * T + tid;
         Bd bn = b;
         if (it + 1 < nIt) {
           bn = bounds(j + T);
-          if (SGT_CHIP_PF) fetch(bn, nx);
+          fetch(bn, nx);
         }
         const int len = b.kN - b.kS, bE = b.kE - b.kS, bL = b.kL - b.kS;
         const bool ok = len <= kC && len >= kC - 3 && bE >= 0 && bE <= kHW && bL - 1 >= kC - kTW &&
@@ -684,13 +581,13 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? (sgt_prefix(64) ? 2 : SGT_WPE) :
           asm volatile("" : "+v"(wo));
 #pragma unroll
           for (int n = 0; n < kC; n++) {
-            if (n % SGT_CHIP_GROUP == 0 && n > 0) {
+            if (n % kChipGroup == 0 && n > 0) {
               // groups of samples: the next group's W_n reads and IF words depend
               // on the running sum so far, so the compiler cannot hoist every
               // sample's table entry and conversion to the chunk's start
               asm volatile("" : "+v"(wo) : "v"(Tr));
 #pragma unroll
-              for (int u = n * kBps / 4; u < kNR && u < (n + SGT_CHIP_GROUP) * kBps / 4 + 1; u++)
+              for (int u = n * kBps / 4; u < kNR && u < (n + kChipGroup) * kBps / 4 + 1; u++)
                 asm volatile("" : "+v"(r[u]) : "v"(Ti));
             }
             int re, im = 0;
@@ -708,25 +605,12 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? (sgt_prefix(64) ? 2 : SGT_WPE) :
               im = v ? im : 0;
             }
             const double2 W = s_w[n + wo];   // broadcast read
-            if constexpr (SGT_CHIP_FMA) {
-              // T += W_n * raw as fused steps (fp64 rounding only)
-              Tr = fma(W.x, (double)re, Tr);
-              Ti = fma(W.y, (double)re, Ti);
-              if constexpr (FT == 2) {
-                Tr = fma(-W.y, (double)im, Tr);
-                Ti = fma(W.x, (double)im, Ti);
-              }
-            } else {
-              double ur, ui;
-              if constexpr (FT == 2) {
-                ur = fma(W.x, (double)re, -(W.y * (double)im));   // W_n * raw
-                ui = fma(W.x, (double)im, W.y * (double)re);
-              } else {
-                ur = W.x * (double)re;
-                ui = W.y * (double)re;
-              }
-              Tr += ur;
-              Ti += ui;
+            // T += W_n * raw as fused steps (fp64 rounding only)
+            Tr = fma(W.x, (double)re, Tr);
+            Ti = fma(W.y, (double)re, Ti);
+            if constexpr (FT == 2) {
+              Tr = fma(-W.y, (double)im, Tr);
+              Ti = fma(W.x, (double)im, Ti);
             }
             if (n < kHW) {
               const bool h = n == bE - 1;
@@ -788,9 +672,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? (sgt_prefix(64) ? 2 : SGT_WPE) :
               rc = fma(cR, W1.x, -(sR * W1.y));
               rs = fma(sR, W1.x, cR * W1.y);
             }
-            const double cn = fma(cb, rc, -(sb * rs));
-            sb = fma(sb, rc, cb * rs);
-            cb = cn;
+            rotate(sb, cb, rs, rc);
           } else {
             sincos(A * ((double)bn.kS / p.fs) + c.rem_carr, &sb, &cb);
           }
@@ -805,7 +687,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? (sgt_prefix(64) ? 2 : SGT_WPE) :
     const double invs = 1.0 / step, sps = floor(p.spc * invs);   // samples per chip, spc in samples
     // the longest chunk is floor(samples per chip) + 1 samples: kC = 16 / 17 (GPS
     // at 16 / 16.368 Msps), 32 / 33 (GLONASS); the loop masks its last 3 samples
-    const int ipc = (SGT_CHIPS && MAXT <= 256 && chunked && sps <= 3.0 && invs < 33.0) ? (int)invs : 0;
+    const int ipc = (MAXT <= 256 && chunked && sps <= 3.0 && invs < 33.0) ? (int)invs : 0;
     const int kcs = ipc >= 29 ? (ipc >= 32 ? 33 : 32) : (ipc >= 13 && ipc <= 16 ? (ipc >= 16 ? 17 : 16) : 0);
     if (kcs) {
       if (kcs == 33) run_chips(std::integral_constant<int, 33>{});
@@ -813,7 +695,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? (sgt_prefix(64) ? 2 : SGT_WPE) :
       else if (kcs == 17) run_chips(std::integral_constant<int, 17>{});
       else run_chips(std::integral_constant<int, 16>{});
     }
-    else if (chunked && SGT_KC32 && 31.0 * step < 0.999)
+    else if (chunked && 31.0 * step < 0.999)
       run_chunks(std::integral_constant<int, 32>{});
     else if (chunked)
       run_chunks(std::integral_constant<int, 16>{});
@@ -896,16 +778,8 @@ struct gnsscorr_sgt_ctx {
 
 extern "C" void gnsscorr_sgt_loop_coefs(const gnsscorr_sgt_cfg* cfg, double* tau1, double* tau2,
                                         double* k1, double* k2, double* k3) {
-  // calcLoopCoef.sci:39-43 (k = 1.0)
-  const double z = cfg->dll_damping;
-  const double wn = cfg->dll_noise_bw * 8 * z / (4 * (z * z) + 1);
-  *tau1 = 1.0 / (wn * wn);
-  *tau2 = 2.0 * z / wn;
-  // calcFLLPLLLoopCoef.sci:36-38 (T = PDIcarr = 0.001)
-  const double T = 0.001, b = cfg->pll_noise_bw / 0.53;
-  *k1 = T * (b * b) + 1.414 * b;
-  *k2 = 1.414 * b;
-  *k3 = T * (cfg->fll_noise_bw / 0.25);
+  calc_loop_coef(cfg->dll_noise_bw, cfg->dll_damping, tau1, tau2);
+  calc_fll_pll_loop_coef(cfg->pll_noise_bw, cfg->fll_noise_bw, k1, k2, k3);
 }
 
 static int check_cfg(const gnsscorr_sgt_cfg* cfg) {
@@ -944,17 +818,7 @@ extern "C" int gnsscorr_sgt_init_chan(const gnsscorr_sgt_cfg* cfg, int code_id, 
   return GNSSCORR_OK;
 }
 
-extern "C" int gnsscorr_sgt_destroy(gnsscorr_sgt_ctx* c) {
-  if (!c) return GNSSCORR_OK;
-  (void)hipSetDevice(c->cfg.device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(c->d_codes);
-  (void)hipFree(c->d_chan);
-  (void)hipFree(c->d_ep);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-  return GNSSCORR_OK;
-}
+extern "C" int gnsscorr_sgt_destroy(gnsscorr_sgt_ctx* c) { return ftrack::destroy(c); }
 
 extern "C" int gnsscorr_sgt_create(gnsscorr_sgt_ctx** out, const gnsscorr_sgt_cfg* cfg) {
   if (!out) return GNSSCORR_EINVAL;
@@ -1023,15 +887,9 @@ extern "C" int gnsscorr_sgt_create(gnsscorr_sgt_ctx** out, const gnsscorr_sgt_cf
 extern "C" int gnsscorr_sgt_track_dev(gnsscorr_sgt_ctx* c, const int8_t* d_if, int64_t stride,
                                       int64_t n_samples, int n_ch, gnsscorr_sgt_chan* d_chan,
                                       int n_epochs, int closed_loop, gnsscorr_sgt_epoch* d_ep) {
-  if (!c || !d_if || !d_chan || !d_ep || n_ch < 1 || n_epochs < 1 || n_samples < 0 ||
-      stride < 0) {
-    gnsscorr_set_error("gnsscorr_sgt_track_dev: bad arguments");
-    return GNSSCORR_EINVAL;
-  }
-  if (c->cfg.file_type == 2 && ((uintptr_t)d_if & 1)) {
-    gnsscorr_set_error("gnsscorr_sgt_track_dev: IQ record must be 2-byte aligned");
-    return GNSSCORR_EINVAL;
-  }
+  int rc = check_track_dev(__func__, c, d_if, d_chan, d_ep, n_ch, n_epochs, n_samples, stride);
+  if (!rc) rc = check_iq_aligned(__func__, c, d_if);
+  if (rc) return rc;
   HIP_TRY(hipSetDevice(c->cfg.device));
   // many channels: one wave per channel (throughput); fewer: 256-thread
   // workgroups, which also give the lowest epoch latency for the 14-channel
@@ -1045,7 +903,7 @@ extern "C" int gnsscorr_sgt_track_dev(gnsscorr_sgt_ctx* c, const int8_t* d_if, i
   }
   dim3 grid(n_ch), block(T);
   const size_t tab = sgt_tab_bytes(c->p.code_length);
-  // + the prefix columns of the chunked path (64- and 256-thread shapes)
+  // + the prefix columns of run_chunks (the 128- and 256-thread shapes; not wave mode)
   const size_t tab_pf = tab + (sgt_prefix(T) ? (size_t)(T / 64) * kPfWaveBytes : 0);
 #define SGT_LAUNCH(FT, CL)                                                                     \
   do {                                                                                         \
@@ -1075,10 +933,7 @@ extern "C" int gnsscorr_sgt_track_dev(gnsscorr_sgt_ctx* c, const int8_t* d_if, i
 extern "C" int gnsscorr_sgt_track(gnsscorr_sgt_ctx* c, const int8_t* d_if, int64_t stride,
                                   int64_t n_samples, int n_ch, gnsscorr_sgt_chan* h_chan,
                                   int n_epochs, int closed_loop, gnsscorr_sgt_epoch* h_ep) {
-  if (!c || !h_chan || !h_ep || n_ch < 1 || n_epochs < 1) {
-    gnsscorr_set_error("gnsscorr_sgt_track: bad arguments");
-    return GNSSCORR_EINVAL;
-  }
+  if (!c || !h_chan || !h_ep || n_ch < 1 || n_epochs < 1) return bad_arguments(__func__);
   for (int i = 0; i < n_ch; i++) {
     const int id = h_chan[i].code_id;
     if (c->cfg.system == 0 ? (id < 1 || id > 32) : (id < -7 || id > 6)) {
@@ -1086,91 +941,27 @@ extern "C" int gnsscorr_sgt_track(gnsscorr_sgt_ctx* c, const int8_t* d_if, int64
       return GNSSCORR_EINVAL;
     }
   }
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  const size_t nc = (size_t)n_ch, ne = nc * (size_t)n_epochs;
-  if (nc > c->chan_cap) {
-    (void)hipFree(c->d_chan);
-    c->d_chan = nullptr;
-    HIP_TRY(hipMalloc(&c->d_chan, nc * sizeof(gnsscorr_sgt_chan)));
-    c->chan_cap = nc;
-  }
-  if (ne > c->ep_cap) {
-    (void)hipFree(c->d_ep);
-    c->d_ep = nullptr;
-    HIP_TRY(hipMalloc(&c->d_ep, ne * sizeof(gnsscorr_sgt_epoch)));
-    c->ep_cap = ne;
-  }
-  HIP_TRY(hipMemcpyAsync(c->d_chan, h_chan, nc * sizeof(gnsscorr_sgt_chan),
-                         hipMemcpyHostToDevice, c->stream));
-  int rc = gnsscorr_sgt_track_dev(c, d_if, stride, n_samples, n_ch, c->d_chan, n_epochs,
-                                  closed_loop, c->d_ep);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h_chan, c->d_chan, nc * sizeof(gnsscorr_sgt_chan),
-                         hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(h_ep, c->d_ep, ne * sizeof(gnsscorr_sgt_epoch), hipMemcpyDeviceToHost,
-                         c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GNSSCORR_OK;
+  return ftrack::track(c, n_ch, h_chan, n_epochs, h_ep,
+                       [&](gnsscorr_sgt_chan* d_chan, gnsscorr_sgt_epoch* d_ep) {
+                         return gnsscorr_sgt_track_dev(c, d_if, stride, n_samples, n_ch, d_chan,
+                                                       n_epochs, closed_loop, d_ep);
+                       });
 }
 
-extern "C" int gnsscorr_sgt_sync(gnsscorr_sgt_ctx* c) {
-  if (!c) return GNSSCORR_EINVAL;
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GNSSCORR_OK;
-}
+extern "C" int gnsscorr_sgt_sync(gnsscorr_sgt_ctx* c) { return ftrack::sync(c); }
 
-extern "C" void* gnsscorr_sgt_stream(gnsscorr_sgt_ctx* c) { return c ? (void*)c->stream : nullptr; }
+extern "C" void* gnsscorr_sgt_stream(gnsscorr_sgt_ctx* c) { return ftrack::stream(c); }
 
 extern "C" int gnsscorr_sgt_replay_dev(gnsscorr_sgt_ctx* c, int n_ch, gnsscorr_sgt_chan* d_chan,
                                        int n_epochs, const double* d_sums,
                                        gnsscorr_sgt_epoch* d_ep) {
-  if (!c || !d_chan || !d_sums || !d_ep || n_ch < 1 || n_epochs < 1) {
-    gnsscorr_set_error("gnsscorr_sgt_replay_dev: bad arguments");
-    return GNSSCORR_EINVAL;
-  }
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  hipLaunchKernelGGL(sgt_replay_kernel, dim3((n_ch + 63) / 64), dim3(64), 0, c->stream, c->p,
-                     d_chan, n_ch, n_epochs, d_sums, d_ep);
-  HIP_TRY(hipGetLastError());
-  return GNSSCORR_OK;
+  return ftrack::replay_dev(__func__, c, sgt_replay_kernel, n_ch, d_chan, n_epochs, d_sums, d_ep);
 }
 
 extern "C" int gnsscorr_sgt_replay(gnsscorr_sgt_ctx* c, int n_ch, gnsscorr_sgt_chan* h_chan,
                                    int n_epochs, const double* h_sums, gnsscorr_sgt_epoch* h_ep) {
-  if (!c || !h_chan || !h_sums || !h_ep || n_ch < 1 || n_epochs < 1) {
-    gnsscorr_set_error("gnsscorr_sgt_replay: bad arguments");
-    return GNSSCORR_EINVAL;
-  }
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  const size_t nc = (size_t)n_ch, ne = nc * (size_t)n_epochs;
-  gnsscorr_sgt_chan* d_chan = nullptr;
-  double* d_sums = nullptr;
-  gnsscorr_sgt_epoch* d_ep = nullptr;
-  hipError_t e = hipMalloc(&d_chan, nc * sizeof(gnsscorr_sgt_chan));
-  if (e == hipSuccess) e = hipMalloc(&d_sums, ne * 6 * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&d_ep, ne * sizeof(gnsscorr_sgt_epoch));
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(d_chan, h_chan, nc * sizeof(gnsscorr_sgt_chan), hipMemcpyHostToDevice,
-                       c->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(d_sums, h_sums, ne * 6 * sizeof(double), hipMemcpyHostToDevice,
-                       c->stream);
-  int rc = GNSSCORR_OK;
-  if (e == hipSuccess) rc = gnsscorr_sgt_replay_dev(c, n_ch, d_chan, n_epochs, d_sums, d_ep);
-  if (e == hipSuccess && rc == GNSSCORR_OK)
-    e = hipMemcpyAsync(h_chan, d_chan, nc * sizeof(gnsscorr_sgt_chan), hipMemcpyDeviceToHost,
-                       c->stream);
-  if (e == hipSuccess && rc == GNSSCORR_OK)
-    e = hipMemcpyAsync(h_ep, d_ep, ne * sizeof(gnsscorr_sgt_epoch), hipMemcpyDeviceToHost,
-                       c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d_chan);
-  (void)hipFree(d_sums);
-  (void)hipFree(d_ep);
-  if (e != hipSuccess) {
-    gnsscorr_set_error("gnsscorr_sgt_replay: %s", hipGetErrorString(e));
-    return GNSSCORR_EDEVICE;
-  }
-  return rc;
+  return ftrack::replay<6>(__func__, c, n_ch, h_chan, n_epochs, h_sums, h_ep,
+                           [&](gnsscorr_sgt_chan* d_chan, double* d_sums, gnsscorr_sgt_epoch* d_ep) {
+                             return gnsscorr_sgt_replay_dev(c, n_ch, d_chan, n_epochs, d_sums, d_ep);
+                           });
 }

@@ -33,16 +33,6 @@
 #include "if2.h"
 #include "osg_isr.h"
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) {                                                             \
-      gnsscorr_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
-                         __LINE__);                                                     \
-      return GNSSCORR_EDEVICE;                                                          \
-    }                                                                                   \
-  } while (0)
-
 // Diagnostic hook (tools/trk_stamps.hip defines it; a no-op in the library)
 #ifndef TRACK_PSTAMP
 #define TRACK_PSTAMP(i) \

@@ -81,6 +81,52 @@ def test_open_loop_epoch_matches_oracle(gpu, system, file_type, switch, threads,
     assert (ch["code_freq"] == ch0["code_freq"]).all()
 
 
+@pytest.mark.parametrize("threads", [None, "64"])
+@pytest.mark.parametrize("system,file_type", [(0, 2), (1, 2), (1, 1)])
+def test_open_loop_wide_spacing_runs_chunk_grid(gpu, system, file_type, threads, monkeypatch):
+    """dllCorrelatorSpacing = 0.5 at 16 Msps: floor(spc/step) is 7 (GPS) or 15
+    (GLONASS) samples, above the chip-aligned path's limit of 3, so the 256-thread
+    shape (threads None, 96 channels) takes run_chunks with the prefix columns and
+    the wave shape (threads "64") run_chunks with the per-sample code select; kC =
+    16 for GPS, 32 for GLONASS (sgt.hip).  One open-loop epoch on random states
+    against the oracle: indices and state bit-exact, sums within 1e-6."""
+    gc = gpu
+    if threads:
+        monkeypatch.setenv("GNSSCORR_SGT_THREADS", threads)
+    rng = np.random.default_rng(29 + system + 3 * file_type)
+    n = 200000
+    IF = gc.ifgen(n, [], fs=FS, iq=file_type == 2, seed=23)
+    d_if = gc.DevBuf.from_array(IF)
+    kw = dict(fileType=file_type, samplingFreq=FS, dllCorrelatorSpacing=0.5)
+    ctx = gc.SgtCtx(system, **kw)
+    s = S.settings(system, **kw)
+    C = 96
+    ids = rng.integers(-7, 7, C) if system == 1 else rng.integers(1, 33, C)
+    ch = np.zeros(C, gc.SGT_CHAN)
+    ch["code_id"] = ids
+    ch["pos"] = rng.integers(0, n - 20000, C)
+    ch["code_freq"] = s["codeFreqBasis"] + rng.uniform(-40, 40, C)
+    step = ch["code_freq"] / FS
+    ch["rem_code"] = rng.uniform(0, 1, C) * step
+    ch["rem_carr"] = rng.uniform(-6.2, 6.2, C)
+    ch["carr_freq"] = rng.uniform(-3e6, 3e6, C)
+    ch0 = ch.copy()
+    ep = ctx.track(d_if.ptr, 0, n, ch, 1, closed_loop=False)[:, 0]
+    for i in range(C):
+        pad = S.padded_code(system, int(ids[i]))
+        sums, blk, pos, rc, rcar = S.correlate(IF, s, pad, int(ch0["pos"][i]),
+                                               float(ch0["rem_code"][i]),
+                                               float(ch0["rem_carr"][i]),
+                                               float(ch0["code_freq"][i]),
+                                               float(ch0["carr_freq"][i]))
+        assert ep["status"][i] == 0 and ep["blksize"][i] == blk
+        assert ch["pos"][i] == pos
+        assert ch["rem_code"][i] == rc, (i, ch["rem_code"][i], rc)
+        assert ch["rem_carr"][i] == rcar, (i, ch["rem_carr"][i], rcar)
+        got = np.array([ep[f][i] for f in SUMS])
+        assert _close(got, sums).all(), (i, got, sums)
+
+
 @pytest.mark.parametrize("fs", [4.096e6, 2.048e6])
 @pytest.mark.parametrize("system", [1, 0])
 def test_open_loop_low_rate_unclamped_path(gpu, system, fs):

@@ -33,7 +33,10 @@ def test_inline_asm_is_volatile():
 
 
 def test_measured_out_switches_are_gone():
-    gone = ("TRACK_ASM_MAD", "TRACK_SLOTS", "TRACK_DMA_AUX", "GNSSCORR_TRACK_V1", "TRACK_LOAD4")
+    gone = ("TRACK_ASM_MAD", "TRACK_SLOTS", "TRACK_DMA_AUX", "GNSSCORR_TRACK_V1", "TRACK_LOAD4",
+            # sgt.hip's compile-time switches, each measured and lost
+            "SGT_KC32", "SGT_WPE", "SGT_PREFIX", "SGT_KSUB", "SGT_CHIPS", "SGT_CHIP_GROUP",
+            "SGT_CHIP_FMA", "SGT_CHIP_PF", "SGT_SCHED")
     for f, lines in _sources():
         text = "\n".join(lines)
         for g in gone:

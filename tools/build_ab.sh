@@ -7,7 +7,8 @@ make -s -j8 -C gnss-sdr.ru_amd && mkdir -p gnss-sdr.ru_amd/ab
 B=gnss-sdr.ru_amd/build
 BASE=$(basename $SRC .hip)
 EXTRA=""
-[ "$BASE" = sgt ] && EXTRA="-mllvm -disable-promote-alloca-to-lds"
+# as the Makefile builds them (fp64 sincos: no promotion of its private struct to LDS)
+{ [ "$BASE" = sgt ] || [ "$BASE" = e1t ]; } && EXTRA="-mllvm -disable-promote-alloca-to-lds"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Iinclude -Ignss-sdr.ru_amd/csrc $EXTRA "$@" \
   -c gnss-sdr.ru_amd/csrc/$BASE.hip -o /tmp/ab_$BASE.o
 OBJS=$(ls $B/*.o | grep -v "/$BASE.o$")
