@@ -1351,17 +1351,46 @@ static int forward_launch(gnsscorr_acq_ctx* c, const int8_t* src, int iq, int n_
                           const double* d_freqs, int mode, int n_rows, float2* dst,
                           const double* d_cfreq, const int* d_nrows, int fuse_n = 0);
 
-int acq_grow(void** p, size_t* cap, size_t need, size_t elem) {
-  if (need <= *cap) return GNSSCORR_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  HIP_TRY(hipMalloc(p, need * elem));
-  *cap = need;
+static int codes_preload(gnsscorr_acq_ctx* c);
+
+// the stream and the buffers both precisions use
+static int init_shared(gnsscorr_acq_ctx* c) {
+  const gnsscorr_acq_cfg* cfg = &c->cfg;
+  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  HIP_TRY(hipMalloc(&c->d_if, (size_t)cfg->n_samples * 2 * cfg->max_blocks));
+  HIP_TRY(hipMalloc(&c->d_freqs, sizeof(double) * cfg->max_freqs));
+  HIP_TRY(hipMalloc(&c->d_cfreq, sizeof(double) * cfg->max_freqs));
+  HIP_TRY(hipMalloc(&c->d_resid, sizeof(double) * cfg->max_freqs));
+  HIP_TRY(hipMalloc(&c->d_nclass, sizeof(int)));
   return GNSSCORR_OK;
 }
 
-static int codes_preload(gnsscorr_acq_ctx* c);
+// the fp32 path's spectra and its store permutation
+static int init_f32(gnsscorr_acq_ctx* c) {
+  const gnsscorr_acq_cfg* cfg = &c->cfg;
+  const size_t nF = NPAD * (size_t)cfg->max_codes;
+  const size_t nX = NPAD * (size_t)cfg->max_freqs * cfg->max_blocks;
+  HIP_TRY(hipMalloc(&c->d_sigma, sizeof(int) * N));
+  HIP_TRY(hipMalloc(&c->d_F, sizeof(float2) * nF));
+  HIP_TRY(hipMalloc(&c->d_X, sizeof(float2) * nX));
+  HIP_TRY(hipMemset(c->d_F, 0, sizeof(float2) * nF));
+  HIP_TRY(hipMemset(c->d_X, 0, sizeof(float2) * nX));
+  HIP_TRY(hipMalloc(&c->d_fmap, sizeof(int4) * cfg->max_freqs));
+  // sigma(p) = n^-1(k(p)): where the forward FFT's output k(p) must be stored
+  // so that the correlation kernel reads its input n(p') linearly
+  int* inv_in = (int*)malloc(sizeof(int) * 2 * N);
+  if (!inv_in) return GNSSCORR_ENOMEM;
+  int* sigma = inv_in + N;
+  for (int p = 0; p < N; p++) inv_in[host_in_index(p)] = p;
+  for (int p = 0; p < N; p++) {
+    const int q = inv_in[host_out_index(p)];          // LDS position in the correlation kernel
+    sigma[p] = (q / M16) * kPlane + q % M16;          // padded HBM index
+  }
+  const hipError_t e = hipMemcpy(c->d_sigma, sigma, sizeof(int) * N, hipMemcpyHostToDevice);
+  free(inv_in);
+  HIP_TRY(e);
+  return GNSSCORR_OK;
+}
 
 extern "C" int gnsscorr_acq_create(gnsscorr_acq_ctx** out, const gnsscorr_acq_cfg* cfg) {
   if (!out || !cfg || cfg->max_freqs < 1 || cfg->max_blocks < 1 || cfg->max_codes < 1 ||
@@ -1386,6 +1415,7 @@ extern "C" int gnsscorr_acq_create(gnsscorr_acq_ctx** out, const gnsscorr_acq_cf
     static int checked = 0;
     if (!checked) {
       char* seen = (char*)calloc(2 * N, 1);
+      if (!seen) return GNSSCORR_ENOMEM;
       for (int p = 0; p < N; p++) { seen[host_in_index(p)]++; seen[N + host_out_index(p)]++; }
       for (int i = 0; i < 2 * N; i++)
         if (seen[i] != 1) { free(seen); gnsscorr_set_error("PFA map check failed"); return GNSSCORR_EINVAL; }
@@ -1393,88 +1423,34 @@ extern "C" int gnsscorr_acq_create(gnsscorr_acq_ctx** out, const gnsscorr_acq_cf
       checked = 1;
     }
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    gnsscorr_set_error("gnsscorr_acq_create: no HIP device");
-    return GNSSCORR_ENODEV;
-  }
-  if (cfg->device < 0 || cfg->device >= ndev) {
-    gnsscorr_set_error("gnsscorr_acq_create: device %d out of range", cfg->device);
-    return GNSSCORR_EINVAL;
-  }
-  HIP_TRY(hipSetDevice(cfg->device));
+  int rc = hostctx::open_device(__func__, cfg->device);
+  if (rc) return rc;
   auto* c = new gnsscorr_acq_ctx();
   c->cfg = *cfg;
   c->prec = cfg->precision;
-  const int ns = cfg->n_samples;
   if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, cfg->device) !=
           hipSuccess || c->n_cu < 1)
     c->n_cu = 256;
   if (const char* e = getenv("GNSSCORR_ACQ_PIPE")) c->pipe = atoi(e) != 0;
-  auto fail = [&](int code) {
+  rc = init_shared(c);
+  if (!rc) rc = c->prec == GNSSCORR_ACQ_F64 ? acq64_init(c) : init_f32(c);
+  if (!rc && c->prec == GNSSCORR_ACQ_F64) rc = acq64_preload(c);
+  if (!rc) rc = codes_preload(c);
+  if (rc) {
     gnsscorr_acq_destroy(c);
-    return code;
-  };
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc(&c->d_if, (size_t)ns * 2 * cfg->max_blocks) != hipSuccess ||
-      hipMalloc(&c->d_freqs, sizeof(double) * cfg->max_freqs) != hipSuccess ||
-      hipMalloc(&c->d_cfreq, sizeof(double) * cfg->max_freqs) != hipSuccess ||
-      hipMalloc(&c->d_resid, sizeof(double) * cfg->max_freqs) != hipSuccess ||
-      hipMalloc(&c->d_nclass, sizeof(int)) != hipSuccess) {
-    gnsscorr_set_error("gnsscorr_acq_create: device allocation failed");
-    return fail(GNSSCORR_ENOMEM);
+    return rc;
   }
-  if (c->prec == GNSSCORR_ACQ_F64) {
-    int rc = acq64_init(c);
-    if (!rc) rc = acq64_preload(c);
-    if (!rc) rc = codes_preload(c);
-    if (rc) return fail(rc);
-    *out = c;
-    return GNSSCORR_OK;
-  }
-  if (hipMalloc(&c->d_sigma, sizeof(int) * N) != hipSuccess ||
-      hipMalloc(&c->d_F, sizeof(float2) * NPAD * (size_t)cfg->max_codes) != hipSuccess ||
-      hipMalloc(&c->d_X, sizeof(float2) * NPAD * (size_t)cfg->max_freqs * cfg->max_blocks) != hipSuccess ||
-      hipMemset(c->d_F, 0, sizeof(float2) * NPAD * (size_t)cfg->max_codes) != hipSuccess ||
-      hipMemset(c->d_X, 0, sizeof(float2) * NPAD * (size_t)cfg->max_freqs * cfg->max_blocks) != hipSuccess ||
-      hipMalloc(&c->d_fmap, sizeof(int4) * cfg->max_freqs) != hipSuccess) {
-    gnsscorr_set_error("gnsscorr_acq_create: device allocation failed");
-    return fail(GNSSCORR_ENOMEM);
-  }
-  // sigma(p) = n^-1(k(p)): where the forward FFT's output k(p) must be stored
-  // so that the correlation kernel reads its input n(p') linearly
-  int* inv_in = (int*)malloc(sizeof(int) * N);
-  int* sigma = (int*)malloc(sizeof(int) * N);
-  for (int p = 0; p < N; p++) inv_in[host_in_index(p)] = p;
-  for (int p = 0; p < N; p++) {
-    const int q = inv_in[host_out_index(p)];          // LDS position in the correlation kernel
-    sigma[p] = (q / M16) * kPlane + q % M16;          // padded HBM index
-  }
-  hipError_t e = hipMemcpy(c->d_sigma, sigma, sizeof(int) * N, hipMemcpyHostToDevice);
-  free(inv_in);
-  free(sigma);
-  if (e != hipSuccess) {
-    gnsscorr_set_error("gnsscorr_acq_create: %s", hipGetErrorString(e));
-    return fail(GNSSCORR_EDEVICE);
-  }
-  if (const int rc = codes_preload(c)) return fail(rc);
   *out = c;
   return GNSSCORR_OK;
 }
 
 extern "C" int gnsscorr_acq_destroy(gnsscorr_acq_ctx* c) {
-  if (!c) return GNSSCORR_OK;
-  (void)hipSetDevice(c->cfg.device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  acq64_free(c);
-  void* bufs[] = {c->d_sigma, c->d_F, c->d_X, c->d_if, c->d_freqs, c->d_gcode, c->d_gfreq,
-                  c->d_rows, c->d_res, c->d_dump, c->d_order, c->d_stage, c->d_stats,
-                  c->d_fmap, c->d_cfreq, c->d_resid, c->d_nclass, c->d_codes8, c->d_chips};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-  return GNSSCORR_OK;
+  return hostctx::destroy(c, [&] {
+    acq64_free(c);
+    hostctx::release(c->d_sigma, c->d_F, c->d_X, c->d_if, c->d_freqs, c->d_gcode, c->d_gfreq,
+                     c->d_rows, c->d_res, c->d_dump, c->d_order, c->d_stage, c->d_stats, c->d_fmap,
+                     c->d_cfreq, c->d_resid, c->d_nclass, c->d_codes8, c->d_chips);
+  });
 }
 
 // Code spectra are spectra of real sequences; make them exactly
@@ -1516,10 +1492,10 @@ extern "C" int gnsscorr_acq_set_codes(gnsscorr_acq_ctx* c, int n_codes, const in
   }
   HIP_TRY(hipSetDevice(c->cfg.device));
   const size_t bytes = (size_t)n_codes * c->cfg.n_samples;
-  int rc = acq_grow((void**)&c->d_codes8, &c->cap_codes8, bytes, 1);
+  int rc = hostctx::grow(c->d_codes8, bytes);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(c->d_codes8, h_codes, bytes, hipMemcpyHostToDevice, c->stream));
-  rc = codes_spectra(c, c->d_codes8, n_codes, c->cfg.n_samples);
+  HIP_TRY(hipMemcpyAsync(c->d_codes8.p, h_codes, bytes, hipMemcpyHostToDevice, c->stream));
+  rc = codes_spectra(c, c->d_codes8.p, n_codes, c->cfg.n_samples);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->n_codes = n_codes;
@@ -1549,15 +1525,15 @@ extern "C" int gnsscorr_acq_set_codes_padded(gnsscorr_acq_ctx* c, int n_codes,
   HIP_TRY(hipSetDevice(c->cfg.device));
   // d_codes8: the zero-extended replicas, then the chips as uploaded
   const size_t L = (size_t)c->cfg.n_samples, ext = (size_t)n_codes * L;
-  int rc = acq_grow((void**)&c->d_codes8, &c->cap_codes8, ext + (size_t)n_codes * code_len, 1);
+  int rc = hostctx::grow(c->d_codes8, ext + (size_t)n_codes * code_len);
   if (rc) return rc;
-  int8_t* d_chips = c->d_codes8 + ext;
+  int8_t* d_chips = c->d_codes8.p + ext;
   HIP_TRY(hipMemcpyAsync(d_chips, h_codes, (size_t)n_codes * code_len, hipMemcpyHostToDevice,
                          c->stream));
   hipLaunchKernelGGL(pad_codes_kernel, dim3((unsigned)((ext + 255) / 256)), dim3(256), 0,
-                     c->stream, d_chips, code_len, (int)L, (long)ext, c->d_codes8);
+                     c->stream, d_chips, code_len, (int)L, (long)ext, c->d_codes8.p);
   HIP_TRY(hipGetLastError());
-  rc = codes_spectra(c, c->d_codes8, n_codes, code_len);
+  rc = codes_spectra(c, c->d_codes8.p, n_codes, code_len);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->n_codes = n_codes;
@@ -1600,8 +1576,7 @@ static int codes_preload(gnsscorr_acq_ctx* c) {
   gnsscorr_st_code(h + 32 * 1023);
   HIP_TRY(hipMalloc(&c->d_chips, sizeof h));
   HIP_TRY(hipMemcpy(c->d_chips, h, sizeof h, hipMemcpyHostToDevice));
-  const int rc = acq_grow((void**)&c->d_codes8, &c->cap_codes8,
-                          (size_t)c->cfg.max_codes * c->cfg.n_samples, 1);
+  const int rc = hostctx::grow(c->d_codes8, (size_t)c->cfg.max_codes * c->cfg.n_samples);
   if (rc) return rc;
   hipFuncAttributes a;
   HIP_TRY(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&prn_codes_kernel)));
@@ -1623,7 +1598,7 @@ extern "C" int gnsscorr_acq_set_prn_codes(gnsscorr_acq_ctx* c, int n_codes,
     }
   HIP_TRY(hipSetDevice(c->cfg.device));
   const int n = c->cfg.n_samples;
-  int rc = acq_grow((void**)&c->d_codes8, &c->cap_codes8, (size_t)n_codes * n, 1);
+  int rc = hostctx::grow(c->d_codes8, (size_t)n_codes * n);
   if (rc) return rc;
   for (int b = 0; b < n_codes; b += kIdBatch) {
     CodeIds ids;
@@ -1632,10 +1607,10 @@ extern "C" int gnsscorr_acq_set_prn_codes(gnsscorr_acq_ctx* c, int n_codes,
     const long total = (long)nb * n;
     const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
     hipLaunchKernelGGL(prn_codes_kernel, dim3(grid), dim3(256), 0, c->stream, c->d_chips, ids, nb,
-                       n, c->cfg.samp_rate, c->d_codes8 + (size_t)b * n);
+                       n, c->cfg.samp_rate, c->d_codes8.p + (size_t)b * n);
     HIP_TRY(hipGetLastError());
   }
-  rc = codes_spectra(c, c->d_codes8, n_codes, c->cfg.n_samples);
+  rc = codes_spectra(c, c->d_codes8.p, n_codes, c->cfg.n_samples);
   if (rc) return rc;
   c->n_codes = n_codes;
   return GNSSCORR_OK;
@@ -1666,15 +1641,16 @@ static void build_tile_order(int n_groups, int n_bins, int units_per_row, int* p
 }
 
 static int ensure_order(gnsscorr_acq_ctx* c, int n_groups, int n_bins, int units_per_row) {
-  if (c->d_order && c->order_groups == n_groups && c->order_bins == n_bins &&
+  if (c->d_order.p && c->order_groups == n_groups && c->order_bins == n_bins &&
       c->order_units == units_per_row)
     return GNSSCORR_OK;
   const int R = n_groups * n_bins * units_per_row;
   int* perm = (int*)malloc(sizeof(int) * R);
   build_tile_order(n_groups, n_bins, units_per_row, perm);
-  int rc = acq_grow((void**)&c->d_order, &c->cap_order, R, sizeof(int));
+  int rc = hostctx::grow(c->d_order, R);
   if (rc) { free(perm); return rc; }
-  hipError_t e = hipMemcpyAsync(c->d_order, perm, sizeof(int) * R, hipMemcpyHostToDevice, c->stream);
+  hipError_t e =
+      hipMemcpyAsync(c->d_order.p, perm, sizeof(int) * R, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   free(perm);
   if (e != hipSuccess) {
@@ -1691,7 +1667,7 @@ static int ensure_order(gnsscorr_acq_ctx* c, int n_groups, int n_bins, int units
 static int forward_launch(gnsscorr_acq_ctx* c, const int8_t* src, int iq, int n_blocks,
                           const double* d_freqs, int mode, int n_rows, float2* dst,
                           const double* d_cfreq, const int* d_nrows, int fuse_n) {
-  int rc = acq_grow((void**)&c->d_stage, &c->cap_stage, (size_t)n_rows * NPAD, sizeof(float2));
+  int rc = hostctx::grow(c->d_stage, (size_t)n_rows * NPAD);
   if (rc) return rc;
   // grid-stride kernels: the device-side class count bounds the work, the grid
   // only the parallelism (n_rows is an upper bound of the rows)
@@ -1699,12 +1675,12 @@ static int forward_launch(gnsscorr_acq_ctx* c, const int8_t* src, int iq, int n_
   const int g1023 = min(n_rows * 16, 1024);
   hipLaunchKernelGGL(acq_fwd16_kernel, dim3(g16),
                      dim3(kFwd1Threads), 0, c->stream, src, iq,
-                     n_blocks, d_freqs, 1.0 / c->cfg.samp_rate, mode, c->d_stage, d_cfreq,
+                     n_blocks, d_freqs, 1.0 / c->cfg.samp_rate, mode, c->d_stage.p, d_cfreq,
                      d_nrows, mode == 0 ? c->coh : 1, n_rows, fuse_n, c->cfg.samp_rate / N,
                      c->d_fmap, c->d_cfreq, c->d_nclass);
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(acq_fwd1023_kernel, dim3(g1023), dim3(kFwd2Threads), 0, c->stream,
-                     c->d_stage,
+                     c->d_stage.p,
                      c->d_sigma, dst, n_blocks, d_nrows, n_rows);
   HIP_TRY(hipGetLastError());
   return GNSSCORR_OK;
@@ -1788,8 +1764,7 @@ static int correlate_launch(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_g
   const int gall = n_groups * nrec;   // virtual groups rec * n_groups + g
   rc = ensure_order(c, gall, n_bins, upr);
   if (rc) return rc;
-  rc = acq_grow((void**)&c->d_stats, &c->cap_stats, (size_t)gall * n_bins * n_blocks,
-            sizeof(gnsscorr_acq_row));
+  rc = hostctx::grow(c->d_stats, (size_t)gall * n_bins * n_blocks);
   if (rc) return rc;
   const int n_units = n_groups * n_bins * upr;
   if (c->prec == GNSSCORR_ACQ_F64) {
@@ -1799,8 +1774,8 @@ static int correlate_launch(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_g
   } else {
 #define ACQ_CORR_LAUNCH(M, D)                                                                \
   hipLaunchKernelGGL((acq_corr_kernel<M, D>), dim3(n_units), dim3(kThreads), 0, c->stream,    \
-                     c->d_X, c->d_F, n_blocks, d_gcode, d_gfreq, n_bins, spc, c->d_stats,      \
-                     d_dump, dump_block, c->d_order, c->d_fmap)
+                     c->d_X, c->d_F, n_blocks, d_gcode, d_gfreq, n_bins, spc, c->d_stats.p,    \
+                     d_dump, dump_block, c->d_order.p, c->d_fmap)
   if (d_dump)
     ACQ_CORR_LAUNCH(GNSSCORR_ACQ_BEST_OF_BLOCKS, true);
   else if (mode == GNSSCORR_ACQ_NONCOHERENT)
@@ -1808,7 +1783,7 @@ static int correlate_launch(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_g
   else if (c->pipe) {
     hipLaunchKernelGGL(acq_corr_pipe_kernel, dim3(n_units < c->n_cu ? n_units : c->n_cu),
                        dim3(kPipeThreads), 0, c->stream, c->d_X, c->d_F, n_blocks, d_gcode,
-                       d_gfreq, n_bins, spc, c->d_stats, c->d_order, c->d_fmap, n_units);
+                       d_gfreq, n_bins, spc, c->d_stats.p, c->d_order.p, c->d_fmap, n_units);
   } else
     ACQ_CORR_LAUNCH(GNSSCORR_ACQ_BEST_OF_BLOCKS, false);
 #undef ACQ_CORR_LAUNCH
@@ -1824,7 +1799,7 @@ static int correlate_launch(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_g
       gnsscorr_set_error("gnsscorr_acq_correlate: d_res needs d_rows and d_freqs");
       return GNSSCORR_EINVAL;
     }
-    hipLaunchKernelGGL(acq_select_kernel, dim3(gall), dim3(64), 0, c->stream, c->d_stats,
+    hipLaunchKernelGGL(acq_select_kernel, dim3(gall), dim3(64), 0, c->stream, c->d_stats.p,
                        gall, n_bins, n_blocks, mode, d_gfreq, d_freqs, d_rows, d_res, n_groups);
     HIP_TRY(hipGetLastError());
   }
@@ -1878,7 +1853,7 @@ extern "C" int gnsscorr_acq_select_dev(gnsscorr_acq_ctx* c, int n_groups, int n_
   }
   HIP_TRY(hipSetDevice(c->cfg.device));
   const int gall = n_groups * c->stat_recs;
-  hipLaunchKernelGGL(acq_select_kernel, dim3(gall), dim3(64), 0, c->stream, c->d_stats, gall,
+  hipLaunchKernelGGL(acq_select_kernel, dim3(gall), dim3(64), 0, c->stream, c->d_stats.p, gall,
                      n_bins, c->stat_blocks, c->stat_mode, d_group_freq, d_freqs, d_rows, d_res,
                      n_groups);
   HIP_TRY(hipGetLastError());
@@ -1922,14 +1897,11 @@ static int stage_host(gnsscorr_acq_ctx* c, const int8_t* h_if, int iq, int n_blo
     }
   }
   const size_t R = (size_t)n_groups * n_bins;
-  int rc;
-  if ((rc = acq_grow((void**)&c->d_rows, &c->cap_rows, R * c->recs, sizeof(gnsscorr_acq_row))))
-    return rc;
-  if ((rc = acq_grow((void**)&c->d_res, &c->cap_res, (size_t)n_groups * c->recs,
-                     sizeof(gnsscorr_acq_result))))
-    return rc;
-  if ((rc = acq_grow((void**)&c->d_gcode, &c->cap_gcode, n_groups, sizeof(int)))) return rc;
-  if ((rc = acq_grow((void**)&c->d_gfreq, &c->cap_gfreq, R, sizeof(int)))) return rc;
+  int rc = hostctx::grow(c->d_rows, R * c->recs);
+  if (!rc) rc = hostctx::grow(c->d_res, (size_t)n_groups * c->recs);
+  if (!rc) rc = hostctx::grow(c->d_gcode, n_groups);
+  if (!rc) rc = hostctx::grow(c->d_gfreq, R);
+  if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(c->d_if, h_if,
                          (size_t)if_bytes((int64_t)c->recs * n_blocks * c->coh * c->cfg.n_samples *
                                               ((iq & GNSSCORR_IF_IQ) ? 2 : 1),
@@ -1937,9 +1909,10 @@ static int stage_host(gnsscorr_acq_ctx* c, const int8_t* h_if, int iq, int n_blo
                          hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->d_freqs, h_freqs, sizeof(double) * n_freqs, hipMemcpyHostToDevice,
                          c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_gcode, h_gcode, sizeof(int) * n_groups, hipMemcpyHostToDevice,
+  HIP_TRY(hipMemcpyAsync(c->d_gcode.p, h_gcode, sizeof(int) * n_groups, hipMemcpyHostToDevice,
                          c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_gfreq, h_gfreq, sizeof(int) * R, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_gfreq.p, h_gfreq, sizeof(int) * R, hipMemcpyHostToDevice,
+                         c->stream));
   return GNSSCORR_OK;
 }
 
@@ -1957,15 +1930,15 @@ extern "C" int gnsscorr_acq_search(gnsscorr_acq_ctx* c, const int8_t* h_if, int 
                       h_group_freq);
   if (rc) return rc;
   rc = search_launch(c, c->d_if, iq, n_blocks, mode, n_freqs, c->d_freqs, n_groups, n_bins,
-                     c->d_gcode, c->d_gfreq, spc, c->d_rows, c->d_res, nullptr, -1);
+                     c->d_gcode.p, c->d_gfreq.p, spc, c->d_rows.p, c->d_res.p, nullptr, -1);
   if (rc) return rc;
   const int nro = c->d_group_rec ? 1 : c->recs;   // per-group records: one result per group
   if (h_rows)
-    HIP_TRY(hipMemcpyAsync(h_rows, c->d_rows,
+    HIP_TRY(hipMemcpyAsync(h_rows, c->d_rows.p,
                            sizeof(gnsscorr_acq_row) * nro * n_groups * n_bins,
                            hipMemcpyDeviceToHost, c->stream));
   if (h_res)
-    HIP_TRY(hipMemcpyAsync(h_res, c->d_res, sizeof(gnsscorr_acq_result) * nro * n_groups,
+    HIP_TRY(hipMemcpyAsync(h_res, c->d_res.p, sizeof(gnsscorr_acq_result) * nro * n_groups,
                            hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return GNSSCORR_OK;
@@ -1994,7 +1967,7 @@ extern "C" int gnsscorr_acq_power_row(gnsscorr_acq_ctx* c, const int8_t* h_if, i
   }
   if (!rc)
     rc = search_launch(c, c->d_if, iq, n_blocks, GNSSCORR_ACQ_BEST_OF_BLOCKS, 1, c->d_freqs, 1,
-                       1, c->d_gcode, c->d_gfreq, 16, c->d_rows, nullptr, c->d_dump, block);
+                       1, c->d_gcode.p, c->d_gfreq.p, 16, c->d_rows.p, nullptr, c->d_dump, block);
   c->recs = recs;
   c->d_group_rec = grec;
   c->keep = keep;

@@ -1371,8 +1371,8 @@ int corr_launch(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_units, int n_
 
 #define ACQ64_LAUNCH(M, D)                                                                  \
   hipLaunchKernelGGL((acq64_corr_kernel<P, M, D>), dim3(n_units), dim3(P::TB), 0, c->stream, \
-                     (const v2d*)c->d_X64, (const v2d*)c->d_F64, c->rs64, n_blocks, d_gcode,   \
-                     d_gfreq, n_bins, spc, c->d_stats, d_dump, dump_block, c->d_order,         \
+                     (const v2d*)c->d_X64.p, (const v2d*)c->d_F64, c->rs64, n_blocks, d_gcode, \
+                     d_gfreq, n_bins, spc, c->d_stats.p, d_dump, dump_block, c->d_order.p,     \
                      c->d_fmap64, (const v2d*)c->d_twN, gpr, nbT, c->d_group_rec)
   if (d_dump)
     ACQ64_LAUNCH(GNSSCORR_ACQ_BEST_OF_BLOCKS, true);
@@ -1752,9 +1752,9 @@ int gen_dft_rows(gnsscorr_acq_ctx* c, const v2d* a, int src_rs, int rows, v2d* o
 int g_set_codes(gnsscorr_acq_ctx* c, const int8_t* d_codes, int n_codes, int code_len) {
   const long n = (long)n_codes * c->cfg.n_samples;
   hipLaunchKernelGGL(g_codes_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_codes, n,
-                     (v2d*)c->d_in64);
+                     (v2d*)c->d_in64.p);
   HIP_TRY(hipGetLastError());
-  return gen_dft_rows(c, (const v2d*)c->d_in64, c->cfg.n_samples, n_codes, (v2d*)c->d_F64,
+  return gen_dft_rows(c, (const v2d*)c->d_in64.p, c->cfg.n_samples, n_codes, (v2d*)c->d_F64,
                       c->rs64, code_len);
 }
 
@@ -1770,14 +1770,14 @@ int g_spectra(gnsscorr_acq_ctx* c, const int8_t* d_if, int iq, int n_blocks, int
   const int grid = (int)((work + 255) / 256 < 2048 ? (work + 255) / 256 : 2048);
   hipLaunchKernelGGL(g_wipe_kernel, dim3(grid), dim3(256), 0, c->stream, d_if, iq, n_blocks,
                      c->coh, (const double*)c->d_cfreq, (const int*)c->d_nclass,
-                     1.0 / c->cfg.samp_rate, N, (v2d*)c->d_in64);
+                     1.0 / c->cfg.samp_rate, N, (v2d*)c->d_in64.p);
   HIP_TRY(hipGetLastError());
   // transform only the class rows (the count is on the device: one small read
   // back; this generic path is synchronous here anyway)
   int n_cls = 0;
   HIP_TRY(hipMemcpyAsync(&n_cls, c->d_nclass, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  return gen_dft_rows(c, (const v2d*)c->d_in64, N, n_cls * n_blocks, (v2d*)c->d_X64, c->rs64, N);
+  return gen_dft_rows(c, (const v2d*)c->d_in64.p, N, n_cls * n_blocks, (v2d*)c->d_X64.p, c->rs64, N);
 }
 
 int g_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int n_bins,
@@ -1795,7 +1795,7 @@ int g_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int n
     for (int b = 0; b < (nc ? n_blocks : 1); b++) {
       v2d *A = (v2d*)c->d_gA, *B = (v2d*)c->d_gB, *D;
       hipLaunchKernelGGL(g_corr_pre_kernel, dim3((M + kGThreads - 1) / kGThreads, nu),
-                         dim3(kGThreads), 0, c->stream, (const v2d*)c->d_X64,
+                         dim3(kGThreads), 0, c->stream, (const v2d*)c->d_X64.p,
                          (const v2d*)c->d_F64, c->rs64, n_blocks, nc ? b : -1, d_gcode, d_gfreq,
                          n_bins, (const int2*)c->d_fmap64, u0, (const v2d*)c->d_chirp, N, M, A);
       HIP_TRY(hipGetLastError());
@@ -1813,11 +1813,11 @@ int g_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int n
     }
     if (stats1_exact(NK, spc))
       hipLaunchKernelGGL(g_stats1_kernel, dim3(nu), dim3(kStatsThreads), 0, c->stream,
-                         (const double*)c->d_gpw, NK, u0, n_blocks, (int)nc, spc, c->d_stats,
+                         (const double*)c->d_gpw, NK, u0, n_blocks, (int)nc, spc, c->d_stats.p,
                          d_dump, dump_block, N);
     else
       hipLaunchKernelGGL(g_stats_kernel, dim3(nu), dim3(kGThreads), 0, c->stream,
-                         (const double*)c->d_gpw, NK, u0, n_blocks, (int)nc, spc, c->d_stats,
+                         (const double*)c->d_gpw, NK, u0, n_blocks, (int)nc, spc, c->d_stats.p,
                          d_dump, dump_block, N);
     HIP_TRY(hipGetLastError());
   }
@@ -2540,7 +2540,7 @@ int mx_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int 
     hipStream_t const st = lane ? c->m4_s2 : c->stream;
     if (lanes == 2 && ci == 1) HIP_TRY(hipStreamWaitEvent(c->m4_s2, c->m4_ev[0], 0));
     for (int b = 0; b < nb; b++) {
-      MixCorr cp{(const v2d*)c->d_X64, (const v2d*)c->d_F64, c->rs64, n_blocks, nc ? b : -1,
+      MixCorr cp{(const v2d*)c->d_X64.p, (const v2d*)c->d_F64, c->rs64, n_blocks, nc ? b : -1,
                  n_bins, u0, d_gcode, d_gfreq, (const int2*)c->d_fmap64, n_groups,
                  n_blocks * nrec, keep};
       if (m4) {
@@ -2574,7 +2574,7 @@ int mx_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int 
     }
     if (fused) {   // carried by the lane's next column pass, or launched below
       pend.top = (const M4Top*)(lane ? c->d_m4top2 : c->d_m4top);
-      pend.stats = c->d_stats;
+      pend.stats = c->d_stats.p;
       pend.n = nu;
       pend.u0 = u0;
       pend.N1 = N1;
@@ -2583,11 +2583,11 @@ int mx_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int 
       pend.spc = spc;
     } else if (stats1_exact(NK, spc))
       hipLaunchKernelGGL(g_stats1_kernel, dim3(nu), dim3(kStatsThreads), 0, st,
-                         (const double*)pw, NK, u0, n_blocks, (int)nc, spc, c->d_stats,
+                         (const double*)pw, NK, u0, n_blocks, (int)nc, spc, c->d_stats.p,
                          d_dump, dump_block, N);
     else
       hipLaunchKernelGGL(g_stats_kernel, dim3(nu), dim3(kGThreads), 0, st,
-                         (const double*)pw, NK, u0, n_blocks, (int)nc, spc, c->d_stats,
+                         (const double*)pw, NK, u0, n_blocks, (int)nc, spc, c->d_stats.p,
                          d_dump, dump_block, N);
     HIP_TRY(hipGetLastError());
   }
@@ -2595,7 +2595,7 @@ int mx_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int 
     if (pends[l].n > 0) {   // each lane's last chunk's statistics
       hipLaunchKernelGGL(m4_stats_kernel, dim3(pends[l].n), dim3(64), 0,
                          l ? c->m4_s2 : c->stream, pends[l].top, N1, N, pends[l].u0, n_blocks,
-                         (int)nc, spc, c->d_stats);
+                         (int)nc, spc, c->d_stats.p);
       HIP_TRY(hipGetLastError());
     }
   if (lanes == 2) {
@@ -2719,6 +2719,7 @@ int acq64_init(gnsscorr_acq_ctx* c) {
   }
   HIP_TRY(hipMalloc(&c->d_twN, sizeof(double2) * N));
   double2* tw = (double2*)malloc(sizeof(double2) * N);
+  if (!tw) return GNSSCORR_ENOMEM;
   for (int j = 0; j < N; j++) {
     // W_N^j = exp(-2 pi i j / N), argument reduced to [0, pi/4]-accurate libm calls
     const double a = 2.0 * M_PI * ((double)j / (double)N);
@@ -2731,14 +2732,9 @@ int acq64_init(gnsscorr_acq_ctx* c) {
 }
 
 void acq64_free(gnsscorr_acq_ctx* c) {
-  void* bufs[] = {c->d_F64, c->d_X64,   c->d_in64, c->d_twN, c->d_fmap64, c->d_lead64,
-                  c->d_chirp, c->d_vf, c->d_twM, c->d_gA,  c->d_gB,     c->d_gpw,
-                  c->d_m4top, c->d_twm4, c->d_gA2, c->d_gpw2, c->d_m4top2};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  c->d_gA2 = nullptr;
-  c->d_gpw2 = nullptr;
-  c->d_m4top2 = nullptr;
+  hostctx::release(c->d_F64, c->d_X64, c->d_in64, c->d_twN, c->d_fmap64, c->d_lead64, c->d_chirp,
+                   c->d_vf, c->d_twM, c->d_gA, c->d_gB, c->d_gpw, c->d_m4top, c->d_twm4, c->d_gA2,
+                   c->d_gpw2, c->d_m4top2);
   for (hipEvent_t& ev : c->m4_ev)
     if (ev) {
       (void)hipEventDestroy(ev);
@@ -2746,13 +2742,6 @@ void acq64_free(gnsscorr_acq_ctx* c) {
     }
   if (c->m4_s2) (void)hipStreamDestroy(c->m4_s2);
   c->m4_s2 = nullptr;
-  c->d_chirp = c->d_vf = c->d_twM = c->d_gA = c->d_gB = nullptr;
-  c->d_gpw = nullptr;
-  c->d_m4top = nullptr;
-  c->d_twm4 = nullptr;
-  c->d_F64 = c->d_X64 = c->d_in64 = c->d_twN = nullptr;
-  c->d_fmap64 = nullptr;
-  c->d_lead64 = nullptr;
 }
 
 namespace {
@@ -2761,9 +2750,9 @@ template <class P>
 int set_codes_launch(gnsscorr_acq_ctx* c, const int8_t* d_codes, int n_codes) {
   const long n = (long)n_codes * P::N;
   hipLaunchKernelGGL(acq64_codes_kernel<P>, dim3((n + 255) / 256), dim3(256), 0, c->stream,
-                     d_codes, n, (v2d*)c->d_in64);
+                     d_codes, n, (v2d*)c->d_in64.p);
   HIP_TRY(hipGetLastError());
-  return fwd_launch<P>(c, (const v2d*)c->d_in64, nullptr, 1, n_codes, (v2d*)c->d_F64);
+  return fwd_launch<P>(c, (const v2d*)c->d_in64.p, nullptr, 1, n_codes, (v2d*)c->d_F64);
 }
 
 template <class P>
@@ -2783,10 +2772,10 @@ int spectra_launch(gnsscorr_acq_ctx* c, const int8_t* d_if, int iq, int n_blocks
   const int grid = (int)((work + 255) / 256 < 2048 ? (work + 255) / 256 : 2048);
   hipLaunchKernelGGL(acq64_wipe_kernel<P>, dim3(grid), dim3(256), 0, c->stream, d_if, iq,
                      n_blocks, c->coh, c->d_cfreq, c->d_nclass, 1.0 / c->cfg.samp_rate,
-                     (v2d*)c->d_in64, fuse, d_freqs, delta, c->d_fmap64, c->d_cfreq,
+                     (v2d*)c->d_in64.p, fuse, d_freqs, delta, c->d_fmap64, c->d_cfreq,
                      c->d_nclass);
   HIP_TRY(hipGetLastError());
-  return fwd_launch<P>(c, (const v2d*)c->d_in64, c->d_nclass, n_blocks, rows, (v2d*)c->d_X64);
+  return fwd_launch<P>(c, (const v2d*)c->d_in64.p, c->d_nclass, n_blocks, rows, (v2d*)c->d_X64.p);
 }
 
 }  // namespace
@@ -2796,8 +2785,7 @@ int spectra_launch(gnsscorr_acq_ctx* c, const int8_t* d_if, int iq, int n_blocks
 // translation unit's kernels on their first use: ~3 ms on the first
 // set_prn_codes of a process otherwise; hipFuncGetAttributes loads it).
 int acq64_preload(gnsscorr_acq_ctx* c) {
-  int rc = acq_grow((void**)&c->d_in64, &c->cap_in64, (size_t)c->cfg.max_codes * c->cfg.n_samples,
-                    sizeof(double2));
+  int rc = hostctx::grow(c->d_in64, (size_t)c->cfg.max_codes * c->cfg.n_samples);
   if (rc) return rc;
   hipFuncAttributes a;
   HIP_TRY(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&acq64_classify_kernel)));
@@ -2805,8 +2793,7 @@ int acq64_preload(gnsscorr_acq_ctx* c) {
 }
 
 int acq64_set_codes(gnsscorr_acq_ctx* c, const int8_t* d_codes, int n_codes, int code_len) {
-  int rc = acq_grow((void**)&c->d_in64, &c->cap_in64, (size_t)n_codes * c->cfg.n_samples,
-                    sizeof(double2));
+  int rc = hostctx::grow(c->d_in64, (size_t)n_codes * c->cfg.n_samples);
   if (rc) return rc;
   if (c->plan64 == 3) return g_set_codes(c, d_codes, n_codes, code_len);
   return c->plan64 == 1 ? set_codes_launch<PlanA>(c, d_codes, n_codes)
@@ -2824,9 +2811,9 @@ int acq64_set_zero_padded(gnsscorr_acq_ctx* c, int keep) {
 int acq64_spectra(gnsscorr_acq_ctx* c, const int8_t* d_if, int iq, int n_blocks, int n_freqs,
                   const double* d_freqs) {
   const size_t rows = (size_t)n_freqs * n_blocks;
-  int rc = acq_grow((void**)&c->d_in64, &c->cap_in64, rows * c->cfg.n_samples, sizeof(double2));
+  int rc = hostctx::grow(c->d_in64, rows * c->cfg.n_samples);
   if (rc) return rc;
-  rc = acq_grow((void**)&c->d_X64, &c->cap_X64, rows * c->rs64, sizeof(double2));
+  rc = hostctx::grow(c->d_X64, rows * c->rs64);
   if (rc) return rc;
   if (c->plan64 == 3) return g_spectra(c, d_if, iq, n_blocks, n_freqs, d_freqs);
   return c->plan64 == 1 ? spectra_launch<PlanA>(c, d_if, iq, n_blocks, n_freqs, d_freqs)

@@ -1,9 +1,12 @@
 // acq_ctx.h -- the acquisition context shared by the fp32 (acq.hip) and the
 // reference-precision fp64 (acq64.hip) kernels.  Internal to libgnsscorr.
+// Buffers of a size fixed at create are raw pointers; the ones a call may grow
+// are DevBufs (hostctx.h).
 #ifndef GNSSCORR_ACQ_CTX_H
 #define GNSSCORR_ACQ_CTX_H
 #include <hip/hip_runtime.h>
 #include "gnsscorr_internal.h"
+#include "hostctx.h"
 
 struct gnsscorr_acq_ctx {
   gnsscorr_acq_cfg cfg;
@@ -14,16 +17,13 @@ struct gnsscorr_acq_ctx {
   float2* d_F = nullptr;     // code spectra, permuted, [max_codes][N]
   float2* d_X = nullptr;     // IF spectra, permuted, [max_freqs*max_blocks][N]
   int4* d_fmap = nullptr;               // per frequency: spectrum class + PFA shift coordinates
-  float2* d_stage = nullptr;            // forward-FFT staging rows
-  size_t cap_stage = 0;
+  hostctx::DevBuf<float2> d_stage;      // forward-FFT staging rows
   int pipe = 1;                         // GNSSCORR_ACQ_PIPE=0: one-unit-per-workgroup kernel
   // ---- fp64 path (prec == GNSSCORR_ACQ_F64)
   int plan64 = 0;                       // acq64 plan id (acq64_plan_for)
   double2* d_F64 = nullptr;             // code spectra, storage order of the plan, [max_codes][rs64]
-  double2* d_X64 = nullptr;             // IF class spectra [rows][rs64] (grown per search)
-  size_t cap_X64 = 0;
-  double2* d_in64 = nullptr;            // natural-order forward-FFT inputs [rows][N] (grown)
-  size_t cap_in64 = 0;
+  hostctx::DevBuf<double2> d_X64;       // IF class spectra [rows][rs64] (grown per search)
+  hostctx::DevBuf<double2> d_in64;      // natural-order forward-FFT inputs [rows][N] (grown)
   double2* d_twN = nullptr;             // W_N^j, j < N (Cooley-Tukey plans)
   int2* d_fmap64 = nullptr;             // per frequency: {class, shift m mod N}
   int* d_lead64 = nullptr;              // classify scratch: per frequency, its class leader
@@ -66,9 +66,8 @@ struct gnsscorr_acq_ctx {
   // ---- shared
   int n_codes = 0;
   int spec_blocks = 0, spec_freqs = 0;  // shape of the resident IF spectra
-  int* d_order = nullptr;               // workgroup -> work-unit permutation (XCD tiles)
+  hostctx::DevBuf<int> d_order;         // workgroup -> work-unit permutation (XCD tiles)
   int order_groups = 0, order_bins = 0, order_units = 0;
-  size_t cap_order = 0;
   double* d_cfreq = nullptr;            // per class: the residue frequency whose spectrum is computed
   double* d_resid = nullptr;            // per frequency: its fs/N-grid residue (classify scratch)
   int* d_nclass = nullptr;
@@ -79,26 +78,19 @@ struct gnsscorr_acq_ctx {
   const int32_t* d_group_rec = nullptr; // per group: its IF record (set_group_records; NULL: every
                                         // group on every record)
   int spec_recs = 1;                    // records of the resident IF spectra
-  gnsscorr_acq_row* d_stats = nullptr;  // per (row, block) statistics
-  size_t cap_stats = 0;
+  hostctx::DevBuf<gnsscorr_acq_row> d_stats;   // per (row, block) statistics
   int stat_groups = 0, stat_bins = 0, stat_blocks = 0, stat_mode = 0, stat_recs = 1;
   // host-API staging
-  int8_t* d_codes8 = nullptr;           // sampled code replicas, int8 [n_codes][N] (grown)
-  size_t cap_codes8 = 0;
+  hostctx::DevBuf<int8_t> d_codes8;     // sampled code replicas, int8 [n_codes][N] (grown)
   int8_t* d_chips = nullptr;            // chip table: rows 0..31 GPS C/A PRN 1..32, row 32 the
                                         // GLONASS ST code (511 chips), 1023 B each (set_prn_codes)
   int8_t* d_if = nullptr;
   double* d_freqs = nullptr;
-  int* d_gcode = nullptr;
-  int* d_gfreq = nullptr;
-  gnsscorr_acq_row* d_rows = nullptr;
-  gnsscorr_acq_result* d_res = nullptr;
+  hostctx::DevBuf<int> d_gcode, d_gfreq;
+  hostctx::DevBuf<gnsscorr_acq_row> d_rows;
+  hostctx::DevBuf<gnsscorr_acq_result> d_res;
   double* d_dump = nullptr;
-  size_t cap_rows = 0, cap_res = 0, cap_gcode = 0, cap_gfreq = 0;
 };
-
-// grow a device buffer to hold `need` elements of `elem` bytes (contents lost)
-int acq_grow(void** p, size_t* cap, size_t need, size_t elem);
 
 // ---- acq64.hip: the fp64 engine behind the same context
 // plan id for N (0: N not supported by a compiled plan)

@@ -474,9 +474,8 @@ struct gnsscorr_e1t_ctx {
   hipStream_t stream = nullptr;
   uint32_t* d_codes = nullptr;
   int max_codes = 0;
-  gnsscorr_e1t_chan* d_chan = nullptr;
-  gnsscorr_e1t_epoch* d_ep = nullptr;
-  size_t chan_cap = 0, ep_cap = 0;
+  hostctx::DevBuf<gnsscorr_e1t_chan> d_chan;   // the host wrappers' own
+  hostctx::DevBuf<gnsscorr_e1t_epoch> d_ep;
 };
 
 extern "C" void gnsscorr_e1t_loop_coefs(const gnsscorr_e1t_cfg* cfg, double* tau1c, double* tau2c,
@@ -521,21 +520,20 @@ extern "C" int gnsscorr_e1t_init_chan(const gnsscorr_e1t_cfg* cfg, int code_id, 
 
 extern "C" int gnsscorr_e1t_destroy(gnsscorr_e1t_ctx* c) { return ftrack::destroy(c); }
 
+// the stream and room for the code rows (gnsscorr_e1t_set_codes fills them)
+static int init_device(gnsscorr_e1t_ctx* c) {
+  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  HIP_TRY(hipMalloc(&c->d_codes, sizeof(uint32_t) * (size_t)c->max_codes * kCodeWords));
+  return GNSSCORR_OK;
+}
+
 extern "C" int gnsscorr_e1t_create(gnsscorr_e1t_ctx** out, const gnsscorr_e1t_cfg* cfg) {
   if (!out) return GNSSCORR_EINVAL;
   *out = nullptr;
   int rc = check_cfg(cfg);
   if (rc) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    gnsscorr_set_error("gnsscorr_e1t_create: no HIP device");
-    return GNSSCORR_ENODEV;
-  }
-  if (cfg->device < 0 || cfg->device >= ndev) {
-    gnsscorr_set_error("gnsscorr_e1t_create: device %d out of range", cfg->device);
-    return GNSSCORR_EINVAL;
-  }
-  HIP_TRY(hipSetDevice(cfg->device));
+  rc = hostctx::open_device(__func__, cfg->device);
+  if (rc) return rc;
   auto* c = new gnsscorr_e1t_ctx();
   c->cfg = *cfg;
   c->max_codes = cfg->max_codes > 0 ? cfg->max_codes : 50;   // settings.NumberOfE1BCodes
@@ -553,13 +551,10 @@ extern "C" int gnsscorr_e1t_create(gnsscorr_e1t_ctx** out, const gnsscorr_e1t_cf
   p.sspc = cfg->sll_spacing;
   p.code_len = (double)cfg->code_length;
   gnsscorr_e1t_loop_coefs(cfg, &p.tau1c, &p.tau2c, &p.tau1m, &p.tau2m, &p.k1, &p.k2, &p.k3);
-  hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e == hipSuccess)
-    e = hipMalloc(&c->d_codes, sizeof(uint32_t) * (size_t)c->max_codes * kCodeWords);
-  if (e != hipSuccess) {
-    gnsscorr_set_error("gnsscorr_e1t_create: %s", hipGetErrorString(e));
+  rc = init_device(c);
+  if (rc) {
     gnsscorr_e1t_destroy(c);
-    return GNSSCORR_EDEVICE;
+    return rc;
   }
   *out = c;
   return GNSSCORR_OK;
@@ -674,9 +669,9 @@ extern "C" int gnsscorr_e1t_track(gnsscorr_e1t_ctx* c, const int8_t* d_if, int64
                        });
 }
 
-extern "C" int gnsscorr_e1t_sync(gnsscorr_e1t_ctx* c) { return ftrack::sync(c); }
+extern "C" int gnsscorr_e1t_sync(gnsscorr_e1t_ctx* c) { return hostctx::sync(c); }
 
-extern "C" void* gnsscorr_e1t_stream(gnsscorr_e1t_ctx* c) { return ftrack::stream(c); }
+extern "C" void* gnsscorr_e1t_stream(gnsscorr_e1t_ctx* c) { return hostctx::stream(c); }
 
 extern "C" int gnsscorr_e1t_replay_dev(gnsscorr_e1t_ctx* c, int n_ch, gnsscorr_e1t_chan* d_chan,
                                        int n_epochs, const double* d_sums,

@@ -1,7 +1,8 @@
 // ftrack.h -- what the two float trackers (sgt.hip, e1t.hip) share: lane
 // helpers and the carrier rotation, the chunk grid of the chunked paths
 // (geometry and the crossing estimate with its margin), the loop-filter steps
-// of the epoch end and the host scaffolding around a tracking context.
+// of the epoch end and the host wrappers around a tracking context (on the
+// shared host scaffolding of hostctx.h).
 // Everything on the device side is __forceinline__ and carries its own fp
 // contract(off): the code indices and the NCO carry-over are bit-exact
 // restatements of tracking.sci, whose line citations stay next to the call
@@ -18,6 +19,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "gnsscorr_internal.h"
+#include "hostctx.h"
 
 namespace ftrack {
 
@@ -154,8 +156,8 @@ __device__ __forceinline__ double early_late_step(double I_E, double Q_E, double
 
 // ============================================================================
 // host side.  Ctx: a tracking context with cfg.device, p (the kernel's params),
-// stream, d_codes and the host wrappers' own d_chan / d_ep with their
-// capacities.  fn: the exported function's name, for its error texts.
+// stream, d_codes and the host wrappers' own growable d_chan / d_ep.  fn: the
+// exported function's name, for its error texts.
 // ============================================================================
 inline int bad_arguments(const char* fn) {
   gnsscorr_set_error("%s: bad arguments", fn);
@@ -180,38 +182,7 @@ inline void calc_fll_pll_loop_coef(double pll_bw, double fll_bw, double* k1, dou
 
 template <class Ctx>
 int destroy(Ctx* c) {
-  if (!c) return GNSSCORR_OK;
-  (void)hipSetDevice(c->cfg.device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(c->d_codes);
-  (void)hipFree(c->d_chan);
-  (void)hipFree(c->d_ep);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-  return GNSSCORR_OK;
-}
-
-template <class Ctx>
-int sync(Ctx* c) {
-  if (!c) return GNSSCORR_EINVAL;
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GNSSCORR_OK;
-}
-
-template <class Ctx>
-void* stream(Ctx* c) { return c ? (void*)c->stream : nullptr; }
-
-// room for n elements; a failed growth leaves a null buffer of capacity 0
-template <class T>
-int ensure_capacity(T*& buf, size_t& cap, size_t n) {
-  if (n <= cap) return GNSSCORR_OK;
-  (void)hipFree(buf);
-  buf = nullptr;
-  cap = 0;
-  HIP_TRY(hipMalloc(&buf, n * sizeof(T)));
-  cap = n;
-  return GNSSCORR_OK;
+  return hostctx::destroy(c, [&] { hostctx::release(c->d_codes, c->d_chan, c->d_ep); });
 }
 
 // the checks *_track_dev share
@@ -237,15 +208,14 @@ template <class Ctx, class Chan, class Epoch, class TrackDev>
 int track(Ctx* c, int n_ch, Chan* h_chan, int n_epochs, Epoch* h_ep, const TrackDev& track_dev) {
   HIP_TRY(hipSetDevice(c->cfg.device));
   const size_t nc = (size_t)n_ch, ne = nc * (size_t)n_epochs;
-  int rc = ensure_capacity(c->d_chan, c->chan_cap, nc);
+  int rc = hostctx::grow(c->d_chan, nc);
+  if (!rc) rc = hostctx::grow(c->d_ep, ne);
   if (rc) return rc;
-  rc = ensure_capacity(c->d_ep, c->ep_cap, ne);
+  HIP_TRY(hipMemcpyAsync(c->d_chan.p, h_chan, nc * sizeof(Chan), hipMemcpyHostToDevice, c->stream));
+  rc = track_dev(c->d_chan.p, c->d_ep.p);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(c->d_chan, h_chan, nc * sizeof(Chan), hipMemcpyHostToDevice, c->stream));
-  rc = track_dev(c->d_chan, c->d_ep);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h_chan, c->d_chan, nc * sizeof(Chan), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(h_ep, c->d_ep, ne * sizeof(Epoch), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(h_chan, c->d_chan.p, nc * sizeof(Chan), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(h_ep, c->d_ep.p, ne * sizeof(Epoch), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return GNSSCORR_OK;
 }
@@ -270,31 +240,22 @@ int replay(const char* fn, Ctx* c, int n_ch, Chan* h_chan, int n_epochs, const d
   if (!c || !h_chan || !h_sums || !h_ep || n_ch < 1 || n_epochs < 1) return bad_arguments(fn);
   HIP_TRY(hipSetDevice(c->cfg.device));
   const size_t nc = (size_t)n_ch, ne = nc * (size_t)n_epochs;
-  Chan* d_chan = nullptr;
-  double* d_sums = nullptr;
-  Epoch* d_ep = nullptr;
-  hipError_t e = hipMalloc(&d_chan, nc * sizeof(Chan));
-  if (e == hipSuccess) e = hipMalloc(&d_sums, ne * N * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&d_ep, ne * sizeof(Epoch));
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(d_chan, h_chan, nc * sizeof(Chan), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(d_sums, h_sums, ne * N * sizeof(double), hipMemcpyHostToDevice, c->stream);
-  int rc = GNSSCORR_OK;
-  if (e == hipSuccess) rc = replay_dev(d_chan, d_sums, d_ep);
-  if (e == hipSuccess && rc == GNSSCORR_OK)
-    e = hipMemcpyAsync(h_chan, d_chan, nc * sizeof(Chan), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess && rc == GNSSCORR_OK)
-    e = hipMemcpyAsync(h_ep, d_ep, ne * sizeof(Epoch), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d_chan);
-  (void)hipFree(d_sums);
-  (void)hipFree(d_ep);
-  if (e != hipSuccess) {
-    gnsscorr_set_error("%s: %s", fn, hipGetErrorString(e));
-    return GNSSCORR_EDEVICE;
-  }
-  return rc;
+  hostctx::TempBuf<Chan> d_chan;
+  hostctx::TempBuf<double> d_sums;
+  hostctx::TempBuf<Epoch> d_ep;
+  int rc = hostctx::grow(d_chan, nc);
+  if (!rc) rc = hostctx::grow(d_sums, ne * N);
+  if (!rc) rc = hostctx::grow(d_ep, ne);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(d_chan.p, h_chan, nc * sizeof(Chan), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_sums.p, h_sums, ne * N * sizeof(double), hipMemcpyHostToDevice,
+                         c->stream));
+  rc = replay_dev(d_chan.p, d_sums.p, d_ep.p);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(h_chan, d_chan.p, nc * sizeof(Chan), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(h_ep, d_ep.p, ne * sizeof(Epoch), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return GNSSCORR_OK;
 }
 
 }  // namespace ftrack

@@ -39,6 +39,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "gnsscorr_internal.h"
+#include "hostctx.h"
 
 namespace {
 
@@ -613,11 +614,8 @@ struct gnsscorr_sdr_acq_ctx {
   gnsscorr_sdr_acq_cfg cfg;
   hipStream_t stream = nullptr;
   uint32_t *d_wipe = nullptr, *d_codes = nullptr, *d_twf = nullptr, *d_twi = nullptr;
-  uint32_t *d_X = nullptr, *d_buff = nullptr;
-  int32_t* d_svs = nullptr;
-  int2* d_rows = nullptr;
-  gnsscorr_sdr_acq_result* d_res = nullptr;
-  size_t cap_rec = 0, cap_rows = 0, cap_sv = 0;
+  hostctx::DevBuf<uint32_t> d_X;   // 4 x 2048 per record
+  hostctx::DevBuf<int2> d_rows;
   // medium / weak: 10-ms wipe-offs, post-correlation DFT rows, and the
   // per-record persistent baseband_rows store (kStoreRows x 2048 CPX)
   uint32_t *d_wipe10 = nullptr, *d_dft = nullptr, *d_store = nullptr;
@@ -625,104 +623,106 @@ struct gnsscorr_sdr_acq_ctx {
 };
 
 extern "C" int gnsscorr_sdr_acq_destroy(gnsscorr_sdr_acq_ctx* c) {
-  if (!c) return GNSSCORR_OK;
-  (void)hipSetDevice(c->cfg.device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  void* ps[] = {c->d_wipe, c->d_codes, c->d_twf,    c->d_twi, c->d_X,    c->d_buff,
-                c->d_svs,  c->d_rows,  c->d_res, c->d_wipe10, c->d_dft, c->d_store};
-  for (void* p : ps) (void)hipFree(p);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  return hostctx::destroy(c, [&] {
+    hostctx::release(c->d_wipe, c->d_codes, c->d_twf, c->d_twi, c->d_X, c->d_rows, c->d_wipe10,
+                     c->d_dft, c->d_store);
+  });
+}
+
+// host tables: wipe-offs (sine_gen, misc.cpp:95-115), Q14 twiddles (fft.cpp:114-147),
+// PRN spectra (gen_fft_codes.m).  h: 1-ms wipe-offs | spectra | twiddles; tmp:
+// scratch for the spectra; w10: 10-ms wipe-offs | post-correlation DFT rows
+static int host_tables(const gnsscorr_sdr_acq_cfg* cfg, uint32_t* h, int16_t* tmp, uint32_t* w10) {
+  if (!h || !tmp || !w10) return GNSSCORR_ENOMEM;
+  // sine_gen over 10 ms (acquisition.cpp:123-128); the 1-ms tables are its head
+  for (int j = 0; j < 4; j++) {
+    gnsscorr_sdr_sine_gen((int16_t*)(w10 + (size_t)j * kWipe), -cfg->fif - 250.0 * j, 2048000.0,
+                          kWipe);
+    memcpy(h + (size_t)j * kN, w10 + (size_t)j * kWipe, sizeof(uint32_t) * kN);
+  }
+  gnsscorr_sdr_post_dft((int16_t*)(w10 + 4 * (size_t)kWipe));
+  gnsscorr_sdr_prn_codes(tmp);
+  memcpy(h + 4 * kN, tmp, sizeof(uint32_t) * 51 * kN);
+  // cmulsc_d2 negates the code's Q component in int16 (sdr_strong_kernel):
+  // -32768 would not be representable (the table is within +-502,
+  // pinned by tests/test_codes_host.py)
+  for (size_t k = 1; k < (size_t)51 * kN * 2; k += 2)
+    if (((const int16_t*)tmp)[k] == -32768) {
+      gnsscorr_set_error("gnsscorr_sdr_acq_create: PRN spectrum Q == -32768 is not "
+                         "representable for the negated code product");
+      return GNSSCORR_EINVAL;
+    }
+  gnsscorr_sdr_twiddles((int16_t*)(h + 55 * kN), (int16_t*)(h + 55 * kN + kN / 2));
   return GNSSCORR_OK;
+}
+
+template <class T>
+static int upload(T*& d, const T* h, size_t n) {
+  HIP_TRY(hipMalloc(&d, sizeof(T) * n));
+  HIP_TRY(hipMemcpy(d, h, sizeof(T) * n, hipMemcpyHostToDevice));
+  return GNSSCORR_OK;
+}
+
+// the stream and the host tables on the device
+static int init_device(gnsscorr_sdr_acq_ctx* c, const uint32_t* h, const uint32_t* w10) {
+  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  int rc = upload(c->d_wipe, h, 4 * (size_t)kN);
+  if (!rc) rc = upload(c->d_codes, h + 4 * kN, 51 * (size_t)kN);
+  if (!rc) rc = upload(c->d_twf, h + 55 * kN, (size_t)kN / 2);
+  if (!rc) rc = upload(c->d_twi, h + 55 * kN + kN / 2, (size_t)kN / 2);
+  if (!rc) rc = upload(c->d_wipe10, w10, 4 * (size_t)kWipe);
+  if (!rc) rc = upload(c->d_dft, w10 + 4 * (size_t)kWipe, (size_t)200);
+  return rc;
 }
 
 extern "C" int gnsscorr_sdr_acq_create(gnsscorr_sdr_acq_ctx** out, const gnsscorr_sdr_acq_cfg* cfg) {
   if (!out || !cfg) return GNSSCORR_EINVAL;
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    gnsscorr_set_error("gnsscorr_sdr_acq_create: no HIP device");
-    return GNSSCORR_ENODEV;
-  }
-  if (cfg->device < 0 || cfg->device >= ndev) {
-    gnsscorr_set_error("gnsscorr_sdr_acq_create: device %d out of range", cfg->device);
-    return GNSSCORR_EINVAL;
-  }
-  HIP_TRY(hipSetDevice(cfg->device));
+  int rc = hostctx::open_device(__func__, cfg->device);
+  if (rc) return rc;
   auto* c = new gnsscorr_sdr_acq_ctx();
   c->cfg = *cfg;
-  // host tables: wipe-offs (sine_gen, misc.cpp:95-115), Q14 twiddles (fft.cpp:114-147),
-  // PRN spectra (gen_fft_codes.m)
   uint32_t* h = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)(4 * kN + 51 * kN + kN));
   int16_t* tmp = (int16_t*)malloc(sizeof(int16_t) * 2 * (size_t)51 * kN);
   uint32_t* w10 = (uint32_t*)malloc(sizeof(uint32_t) * (4 * (size_t)kWipe + 200));
-  int rc = (h && tmp && w10) ? GNSSCORR_OK : GNSSCORR_ENOMEM;
-  if (!rc) {
-    // sine_gen over 10 ms (acquisition.cpp:123-128); the 1-ms tables are its head
-    for (int j = 0; j < 4; j++) {
-      gnsscorr_sdr_sine_gen((int16_t*)(w10 + (size_t)j * kWipe), -cfg->fif - 250.0 * j, 2048000.0,
-                            kWipe);
-      memcpy(h + (size_t)j * kN, w10 + (size_t)j * kWipe, sizeof(uint32_t) * kN);
-    }
-    gnsscorr_sdr_post_dft((int16_t*)(w10 + 4 * (size_t)kWipe));
-    gnsscorr_sdr_prn_codes(tmp);
-    memcpy(h + 4 * kN, tmp, sizeof(uint32_t) * 51 * kN);
-    // cmulsc_d2 negates the code's Q component in int16 (sdr_strong_kernel):
-    // -32768 would not be representable (the table is within +-502,
-    // pinned by tests/test_codes_host.py)
-    for (size_t k = 1; k < (size_t)51 * kN * 2; k += 2)
-      if (((const int16_t*)tmp)[k] == -32768) {
-        gnsscorr_set_error("gnsscorr_sdr_acq_create: PRN spectrum Q == -32768 is not "
-                           "representable for the negated code product");
-        rc = GNSSCORR_EINVAL;
-        break;
-      }
-    gnsscorr_sdr_twiddles((int16_t*)(h + 55 * kN), (int16_t*)(h + 55 * kN + kN / 2));
-  }
-  hipError_t e = hipSuccess;
-  if (!rc) {
-    e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&c->d_wipe, sizeof(uint32_t) * 4 * kN);
-    if (e == hipSuccess) e = hipMalloc(&c->d_codes, sizeof(uint32_t) * 51 * kN);
-    if (e == hipSuccess) e = hipMalloc(&c->d_twf, sizeof(uint32_t) * kN / 2);
-    if (e == hipSuccess) e = hipMalloc(&c->d_twi, sizeof(uint32_t) * kN / 2);
-    if (e == hipSuccess)
-      e = hipMemcpy(c->d_wipe, h, sizeof(uint32_t) * 4 * kN, hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-      e = hipMemcpy(c->d_codes, h + 4 * kN, sizeof(uint32_t) * 51 * kN, hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-      e = hipMemcpy(c->d_twf, h + 55 * kN, sizeof(uint32_t) * kN / 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-      e = hipMemcpy(c->d_twi, h + 55 * kN + kN / 2, sizeof(uint32_t) * kN / 2,
-                    hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&c->d_wipe10, sizeof(uint32_t) * 4 * kWipe);
-    if (e == hipSuccess) e = hipMalloc(&c->d_dft, sizeof(uint32_t) * 200);
-    if (e == hipSuccess)
-      e = hipMemcpy(c->d_wipe10, w10, sizeof(uint32_t) * 4 * kWipe, hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-      e = hipMemcpy(c->d_dft, w10 + 4 * (size_t)kWipe, sizeof(uint32_t) * 200, hipMemcpyHostToDevice);
-  }
+  rc = host_tables(cfg, h, tmp, w10);
+  if (!rc) rc = init_device(c, h, w10);
   free(h);
   free(tmp);
   free(w10);
-  if (rc || e != hipSuccess) {
-    if (e != hipSuccess) gnsscorr_set_error("gnsscorr_sdr_acq_create: %s", hipGetErrorString(e));
+  if (rc) {
     gnsscorr_sdr_acq_destroy(c);
-    return rc ? rc : GNSSCORR_EDEVICE;
+    return rc;
   }
   *out = c;
   return GNSSCORR_OK;
 }
 
-static int grow(void** p, size_t* cap, size_t need, size_t elem) {
-  if (need <= *cap) return GNSSCORR_OK;
-  (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  HIP_TRY(hipMalloc(p, need * elem));
-  *cap = need;
-  return GNSSCORR_OK;
-}
+// device copies of one host call's records and satellite list and room for its
+// results, freed when the call returns
+struct HostStaging {
+  hostctx::TempBuf<int16_t> buff;   // records of (I, Q) pairs
+  hostctx::TempBuf<int32_t> svs;
+  hostctx::TempBuf<gnsscorr_sdr_acq_result> res;
+
+  int upload(gnsscorr_sdr_acq_ctx* c, const int16_t* h_buff, size_t n_pairs, const int32_t* h_svs,
+             int n_sv, size_t n_res) {
+    int rc = hostctx::grow(buff, 2 * n_pairs);
+    if (!rc) rc = hostctx::grow(svs, (size_t)n_sv);
+    if (!rc) rc = hostctx::grow(res, n_res);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(buff.p, h_buff, sizeof(uint32_t) * n_pairs, hipMemcpyHostToDevice,
+                           c->stream));
+    HIP_TRY(hipMemcpyAsync(svs.p, h_svs, sizeof(int32_t) * n_sv, hipMemcpyHostToDevice, c->stream));
+    return GNSSCORR_OK;
+  }
+  int download(gnsscorr_sdr_acq_ctx* c, gnsscorr_sdr_acq_result* h_res) {
+    HIP_TRY(hipMemcpyAsync(h_res, res.p, sizeof(gnsscorr_sdr_acq_result) * res.cap,
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return GNSSCORR_OK;
+  }
+};
 
 static int check_range(int n_rec, int n_sv, int doppmin, int doppmax) {
   const int lmin = doppmin / 1000, lmax = doppmax / 1000;   // C truncation, as the reference
@@ -743,17 +743,16 @@ extern "C" int gnsscorr_sdr_acq_strong_dev(gnsscorr_sdr_acq_ctx* c, const int16_
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->cfg.device));
   const int lmin = doppmin / 1000, n_rows = 4 * (doppmax / 1000 - lmin);
-  if ((rc = grow((void**)&c->d_X, &c->cap_rec, (size_t)n_rec, sizeof(uint32_t) * 4 * kN)))
-    return rc;
-  if ((rc = grow((void**)&c->d_rows, &c->cap_rows, (size_t)n_rec * n_sv * n_rows, sizeof(int2))))
-    return rc;
+  rc = hostctx::grow(c->d_X, (size_t)n_rec * 4 * kN);
+  if (!rc) rc = hostctx::grow(c->d_rows, (size_t)n_rec * n_sv * n_rows);
+  if (rc) return rc;
   hipLaunchKernelGGL(sdr_prep_kernel, dim3(4 * n_rec), dim3(kThreads), 0, c->stream,
-                     (const uint32_t*)d_buff, c->d_wipe, c->d_twf, c->d_X, c->cfg.saturate);
+                     (const uint32_t*)d_buff, c->d_wipe, c->d_twf, c->d_X.p, c->cfg.saturate);
   hipLaunchKernelGGL(sdr_strong_kernel, dim3(n_rec * n_sv * (n_rows / 4)), dim3(kThreads), 0, c->stream,
-                     c->d_X, c->d_codes, c->d_twi, d_svs, n_sv, lmin, n_rows, c->cfg.saturate,
-                     c->d_rows);
+                     c->d_X.p, c->d_codes, c->d_twi, d_svs, n_sv, lmin, n_rows, c->cfg.saturate,
+                     c->d_rows.p);
   const int G = n_rec * n_sv;
-  hipLaunchKernelGGL(sdr_select_kernel, dim3(G), dim3(64), 0, c->stream, c->d_rows,
+  hipLaunchKernelGGL(sdr_select_kernel, dim3(G), dim3(64), 0, c->stream, c->d_rows.p,
                      d_svs, n_sv, n_rec, lmin, n_rows, d_res);
   HIP_TRY(hipGetLastError());
   return GNSSCORR_OK;
@@ -772,55 +771,16 @@ extern "C" int gnsscorr_sdr_acq_strong(gnsscorr_sdr_acq_ctx* c, const int16_t* h
     }
   HIP_TRY(hipSetDevice(c->cfg.device));
   static_assert(sizeof(gnsscorr_sdr_acq_result) == 24, "result layout");
-  // staging buffers sized to this call
-  size_t cap_b = 0, cap_s = 0, cap_r = 0;
-  int16_t* d_b = nullptr;
-  int32_t* d_s = nullptr;
-  gnsscorr_sdr_acq_result* d_r = nullptr;
-  auto cleanup = [&]() {
-    (void)hipFree(d_b);
-    (void)hipFree(d_s);
-    (void)hipFree(d_r);
-  };
-  if ((rc = grow((void**)&d_b, &cap_b, (size_t)n_rec * kN, sizeof(uint32_t))) ||
-      (rc = grow((void**)&d_s, &cap_s, (size_t)n_sv, sizeof(int32_t))) ||
-      (rc = grow((void**)&d_r, &cap_r, (size_t)n_rec * n_sv, sizeof(gnsscorr_sdr_acq_result)))) {
-    cleanup();
-    return rc;
-  }
-  hipError_t e = hipMemcpyAsync(d_b, h_buff, sizeof(uint32_t) * (size_t)n_rec * kN,
-                                hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(d_s, h_svs, sizeof(int32_t) * n_sv, hipMemcpyHostToDevice, c->stream);
-  if (e != hipSuccess) {
-    cleanup();
-    gnsscorr_set_error("gnsscorr_sdr_acq_strong: %s", hipGetErrorString(e));
-    return GNSSCORR_EDEVICE;
-  }
-  rc = gnsscorr_sdr_acq_strong_dev(c, d_b, n_rec, n_sv, d_s, doppmin, doppmax, d_r);
-  if (!rc) {
-    e = hipMemcpyAsync(h_res, d_r, sizeof(gnsscorr_sdr_acq_result) * (size_t)n_rec * n_sv,
-                       hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-      gnsscorr_set_error("gnsscorr_sdr_acq_strong: %s", hipGetErrorString(e));
-      rc = GNSSCORR_EDEVICE;
-    }
-  }
-  cleanup();
-  return rc;
+  HostStaging st;
+  if ((rc = st.upload(c, h_buff, (size_t)n_rec * kN, h_svs, n_sv, (size_t)n_rec * n_sv))) return rc;
+  rc = gnsscorr_sdr_acq_strong_dev(c, st.buff.p, n_rec, n_sv, st.svs.p, doppmin, doppmax, st.res.p);
+  if (rc) return rc;
+  return st.download(c, h_res);
 }
 
-extern "C" int gnsscorr_sdr_acq_sync(gnsscorr_sdr_acq_ctx* c) {
-  if (!c) return GNSSCORR_EINVAL;
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GNSSCORR_OK;
-}
+extern "C" int gnsscorr_sdr_acq_sync(gnsscorr_sdr_acq_ctx* c) { return hostctx::sync(c); }
 
-extern "C" void* gnsscorr_sdr_acq_stream(gnsscorr_sdr_acq_ctx* c) {
-  return c ? (void*)c->stream : nullptr;
-}
+extern "C" void* gnsscorr_sdr_acq_stream(gnsscorr_sdr_acq_ctx* c) { return hostctx::stream(c); }
 
 // ============================================================================
 // medium / weak acquisition (Acquisition::doPrepIF at 10 / 310 ms,
@@ -903,19 +863,19 @@ extern "C" int gnsscorr_sdr_acq_search_dev(gnsscorr_sdr_acq_ctx* c, int type, in
     return GNSSCORR_EINVAL;
   }
   HIP_TRY(hipSetDevice(c->cfg.device));
-  int rc = grow((void**)&c->d_rows, &c->cap_rows, (size_t)n_rec * n_sv * n_rows, sizeof(int2));
+  int rc = hostctx::grow(c->d_rows, (size_t)n_rec * n_sv * n_rows);
   if (rc) return rc;
   const dim3 grid(n_rec * n_sv * n_rows);
   if (type == GNSSCORR_SDR_ACQ_WEAK)
     hipLaunchKernelGGL(sdr_coh_kernel<true>, grid, dim3(kCoh), 0, c->stream, c->d_store,
                        c->d_codes, c->d_twi, c->d_dft, d_svs, n_sv, lmin, n_rows,
-                       c->cfg.saturate, c->d_rows);
+                       c->cfg.saturate, c->d_rows.p);
   else
     hipLaunchKernelGGL(sdr_coh_kernel<false>, grid, dim3(kCoh), 0, c->stream, c->d_store,
                        c->d_codes, c->d_twi, c->d_dft, d_svs, n_sv, lmin, n_rows,
-                       c->cfg.saturate, c->d_rows);
+                       c->cfg.saturate, c->d_rows.p);
   const int G = n_rec * n_sv;
-  hipLaunchKernelGGL(sdr_select_mw_kernel, dim3(G), dim3(64), 0, c->stream, c->d_rows,
+  hipLaunchKernelGGL(sdr_select_mw_kernel, dim3(G), dim3(64), 0, c->stream, c->d_rows.p,
                      d_svs, n_sv, n_rec, lmin, n_rows, type == GNSSCORR_SDR_ACQ_WEAK ? 1 : 0,
                      d_res);
   HIP_TRY(hipGetLastError());
@@ -940,44 +900,12 @@ extern "C" int gnsscorr_sdr_acq_acquire(gnsscorr_sdr_acq_ctx* c, int type, const
     }
   HIP_TRY(hipSetDevice(c->cfg.device));
   const int ms = prep_ms(type);
-  size_t cap_b = 0, cap_s = 0, cap_r = 0;
-  int16_t* d_b = nullptr;
-  int32_t* d_s = nullptr;
-  gnsscorr_sdr_acq_result* d_r = nullptr;
-  auto cleanup = [&]() {
-    (void)hipFree(d_b);
-    (void)hipFree(d_s);
-    (void)hipFree(d_r);
-  };
-  int rc;
-  if ((rc = grow((void**)&d_b, &cap_b, (size_t)n_rec * ms * kN, sizeof(uint32_t))) ||
-      (rc = grow((void**)&d_s, &cap_s, (size_t)n_sv, sizeof(int32_t))) ||
-      (rc = grow((void**)&d_r, &cap_r, (size_t)n_rec * n_sv, sizeof(gnsscorr_sdr_acq_result)))) {
-    cleanup();
-    return rc;
-  }
-  hipError_t e = hipMemcpyAsync(d_b, h_buff, sizeof(uint32_t) * (size_t)n_rec * ms * kN,
-                                hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(d_s, h_svs, sizeof(int32_t) * n_sv, hipMemcpyHostToDevice, c->stream);
-  if (e != hipSuccess) {
-    cleanup();
-    gnsscorr_set_error("gnsscorr_sdr_acq_acquire: %s", hipGetErrorString(e));
-    return GNSSCORR_EDEVICE;
-  }
-  rc = gnsscorr_sdr_acq_prep_dev(c, type, d_b, n_rec);
-  if (!rc) rc = gnsscorr_sdr_acq_search_dev(c, type, n_rec, n_sv, d_s, doppmin, doppmax, d_r);
-  if (!rc) {
-    e = hipMemcpyAsync(h_res, d_r, sizeof(gnsscorr_sdr_acq_result) * (size_t)n_rec * n_sv,
-                       hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-      gnsscorr_set_error("gnsscorr_sdr_acq_acquire: %s", hipGetErrorString(e));
-      rc = GNSSCORR_EDEVICE;
-    }
-  } else {
-    (void)hipStreamSynchronize(c->stream);
-  }
-  cleanup();
-  return rc;
+  HostStaging st;
+  int rc = st.upload(c, h_buff, (size_t)n_rec * ms * kN, h_svs, n_sv, (size_t)n_rec * n_sv);
+  if (rc) return rc;
+  rc = gnsscorr_sdr_acq_prep_dev(c, type, st.buff.p, n_rec);
+  if (!rc)
+    rc = gnsscorr_sdr_acq_search_dev(c, type, n_rec, n_sv, st.svs.p, doppmin, doppmax, st.res.p);
+  if (rc) return rc;
+  return st.download(c, h_res);
 }

@@ -25,6 +25,7 @@
 #include <string.h>
 #include <vector>
 #include "gnsscorr_internal.h"
+#include "hostctx.h"
 #include "sdr_corr_state.h"
 
 namespace {
@@ -138,27 +139,40 @@ void dump(gnsscorr_sdr_chan* s, gnsscorr_sdr_corr* c, int ch, gnsscorr_sdr_dump_
 struct gnsscorr_sdr_corr_ctx {
   gnsscorr_sdr_corr_cfg cfg;
   hipStream_t stream = nullptr;
-  uint32_t *d_carrier = nullptr, *d_codebits = nullptr, *d_packets = nullptr;
+  uint32_t *d_carrier = nullptr, *d_codebits = nullptr;
+  hostctx::DevBuf<uint32_t> d_packets;
+  // per-job staging, grown together (ensure_jobs): cap_jobs entries each
   gnsscorr_sdr_accum_job* d_jobs = nullptr;
   gnsscorr_sdr_corr* d_out = nullptr;
-  size_t cap_packets = 0, cap_jobs = 0;
-  gnsscorr_sdr_accum_job* h_jobs = nullptr;   // pinned staging
+  gnsscorr_sdr_accum_job* h_jobs = nullptr;   // pinned
   gnsscorr_sdr_corr* h_out = nullptr;
+  size_t cap_jobs = 0;
 };
 
-extern "C" int gnsscorr_sdr_corr_destroy(gnsscorr_sdr_corr_ctx* c) {
-  if (!c) return GNSSCORR_OK;
-  (void)hipSetDevice(c->cfg.device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(c->d_carrier);
-  (void)hipFree(c->d_codebits);
-  (void)hipFree(c->d_packets);
-  (void)hipFree(c->d_jobs);
-  (void)hipFree(c->d_out);
+static void release_jobs(gnsscorr_sdr_corr_ctx* c) {
+  hostctx::release(c->d_jobs, c->d_out);
   (void)hipHostFree(c->h_jobs);
   (void)hipHostFree(c->h_out);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  c->h_jobs = nullptr;
+  c->h_out = nullptr;
+  c->cap_jobs = 0;
+}
+
+extern "C" int gnsscorr_sdr_corr_destroy(gnsscorr_sdr_corr_ctx* c) {
+  return hostctx::destroy(c, [&] {
+    hostctx::release(c->d_carrier, c->d_codebits, c->d_packets);
+    release_jobs(c);
+  });
+}
+
+// the stream and the two tables on the device
+static int init_device(gnsscorr_sdr_corr_ctx* c, const std::vector<uint32_t>& car,
+                       const std::vector<uint32_t>& bits) {
+  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  HIP_TRY(hipMalloc(&c->d_carrier, car.size() * 4));
+  HIP_TRY(hipMalloc(&c->d_codebits, bits.size() * 4));
+  HIP_TRY(hipMemcpy(c->d_carrier, car.data(), car.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(c->d_codebits, bits.data(), bits.size() * 4, hipMemcpyHostToDevice));
   return GNSSCORR_OK;
 }
 
@@ -166,16 +180,8 @@ extern "C" int gnsscorr_sdr_corr_create(gnsscorr_sdr_corr_ctx** out,
                                         const gnsscorr_sdr_corr_cfg* cfg) {
   if (!out || !cfg) return GNSSCORR_EINVAL;
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    gnsscorr_set_error("gnsscorr_sdr_corr_create: no HIP device");
-    return GNSSCORR_ENODEV;
-  }
-  if (cfg->device < 0 || cfg->device >= ndev) {
-    gnsscorr_set_error("gnsscorr_sdr_corr_create: device %d out of range", cfg->device);
-    return GNSSCORR_EINVAL;
-  }
-  HIP_TRY(hipSetDevice(cfg->device));
+  int rc = hostctx::open_device(__func__, cfg->device);
+  if (rc) return rc;
   auto* c = new gnsscorr_sdr_corr_ctx();
   c->cfg = *cfg;
   const size_t ncar = (size_t)kSBins * kRow;
@@ -202,16 +208,10 @@ extern "C" int gnsscorr_sdr_corr_create(gnsscorr_sdr_corr_ctx** out,
       }
     }
   }
-  hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipMalloc(&c->d_carrier, ncar * 4);
-  if (e == hipSuccess) e = hipMalloc(&c->d_codebits, nwords * 4);
-  if (e == hipSuccess) e = hipMemcpy(c->d_carrier, car.data(), ncar * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = hipMemcpy(c->d_codebits, bits.data(), nwords * 4, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    gnsscorr_set_error("gnsscorr_sdr_corr_create: %s", hipGetErrorString(e));
+  rc = init_device(c, car, bits);
+  if (rc) {
     gnsscorr_sdr_corr_destroy(c);
-    return GNSSCORR_EDEVICE;
+    return rc;
   }
   *out = c;
   return GNSSCORR_OK;
@@ -260,12 +260,7 @@ extern "C" int gnsscorr_sdr_accum_dev(gnsscorr_sdr_corr_ctx* c, const int16_t* d
 
 static int ensure_jobs(gnsscorr_sdr_corr_ctx* c, size_t n) {
   if (n <= c->cap_jobs) return GNSSCORR_OK;
-  (void)hipFree(c->d_jobs);
-  (void)hipFree(c->d_out);
-  (void)hipHostFree(c->h_jobs);
-  (void)hipHostFree(c->h_out);
-  c->d_jobs = nullptr; c->d_out = nullptr; c->h_jobs = nullptr; c->h_out = nullptr;
-  c->cap_jobs = 0;
+  release_jobs(c);
   HIP_TRY(hipMalloc(&c->d_jobs, n * sizeof(gnsscorr_sdr_accum_job)));
   HIP_TRY(hipMalloc(&c->d_out, n * sizeof(gnsscorr_sdr_corr)));
   HIP_TRY(hipHostMalloc(&c->h_jobs, n * sizeof(gnsscorr_sdr_accum_job), hipHostMallocDefault));
@@ -281,16 +276,10 @@ extern "C" int gnsscorr_sdr_correlate(gnsscorr_sdr_corr_ctx* c, const int16_t* h
   if (!c || !h_packets || !st || !corr || n_packets < 1 || n_ch < 0) return GNSSCORR_EINVAL;
   if (n_ch == 0) return GNSSCORR_OK;
   HIP_TRY(hipSetDevice(c->cfg.device));
-  int rc;
-  if ((size_t)n_packets > c->cap_packets) {
-    (void)hipFree(c->d_packets);
-    c->d_packets = nullptr;
-    c->cap_packets = 0;
-    HIP_TRY(hipMalloc(&c->d_packets, (size_t)n_packets * kN * 4));
-    c->cap_packets = (size_t)n_packets;
-  }
-  if ((rc = ensure_jobs(c, (size_t)n_ch))) return rc;
-  HIP_TRY(hipMemcpyAsync(c->d_packets, h_packets, (size_t)n_packets * kN * 4,
+  int rc = hostctx::grow(c->d_packets, (size_t)n_packets * kN);
+  if (!rc) rc = ensure_jobs(c, (size_t)n_ch);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(c->d_packets.p, h_packets, (size_t)n_packets * kN * 4,
                          hipMemcpyHostToDevice, c->stream));
   // per-channel progress through the packet (Correlate, correlator.cpp:183-235)
   std::vector<int32_t> off(n_ch, 0), left(n_ch, kN), dumps(n_ch, 0), job_of(n_ch, -1);
@@ -334,7 +323,7 @@ extern "C" int gnsscorr_sdr_correlate(gnsscorr_sdr_corr_ctx* c, const int16_t* h
     if (nj > 0) {
       HIP_TRY(hipMemcpyAsync(c->d_jobs, c->h_jobs, nj * sizeof(gnsscorr_sdr_accum_job),
                              hipMemcpyHostToDevice, c->stream));
-      if ((rc = gnsscorr_sdr_accum_dev(c, (const int16_t*)c->d_packets, nj, c->d_jobs, c->d_out)))
+      if ((rc = gnsscorr_sdr_accum_dev(c, (const int16_t*)c->d_packets.p, nj, c->d_jobs, c->d_out)))
         return rc;
       HIP_TRY(hipMemcpyAsync(c->h_out, c->d_out, nj * sizeof(gnsscorr_sdr_corr),
                              hipMemcpyDeviceToHost, c->stream));
@@ -373,16 +362,9 @@ extern "C" void gnsscorr_sdr_corr_tables(const gnsscorr_sdr_corr_ctx* c, const u
   *saturate = c->cfg.saturate;
 }
 
-extern "C" int gnsscorr_sdr_corr_sync(gnsscorr_sdr_corr_ctx* c) {
-  if (!c) return GNSSCORR_EINVAL;
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GNSSCORR_OK;
-}
+extern "C" int gnsscorr_sdr_corr_sync(gnsscorr_sdr_corr_ctx* c) { return hostctx::sync(c); }
 
-extern "C" void* gnsscorr_sdr_corr_stream(gnsscorr_sdr_corr_ctx* c) {
-  return c ? (void*)c->stream : nullptr;
-}
+extern "C" void* gnsscorr_sdr_corr_stream(gnsscorr_sdr_corr_ctx* c) { return hostctx::stream(c); }
 
 extern "C" int gnsscorr_sdr_corr_device(const gnsscorr_sdr_corr_ctx* c) {
   return c ? c->cfg.device : -1;

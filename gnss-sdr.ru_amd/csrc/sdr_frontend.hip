@@ -27,6 +27,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "gnsscorr_internal.h"
+#include "hostctx.h"
 
 namespace {
 
@@ -95,13 +96,22 @@ __global__ __launch_bounds__(kThreads) void downsample_kernel(const uint32_t* __
 }  // namespace
 
 struct gnsscorr_sdr_fe_ctx {
-  int device = 0;
+  struct { int device = 0; } cfg;   // where the shared host code looks for the device
   hipStream_t stream = nullptr;
   uint32_t* d_prod = nullptr;   // 4 x 1024 (I | Q << 16)
-  uint8_t* d_in = nullptr;      // host-API staging
-  uint32_t* d_out = nullptr;
-  size_t cap_in = 0, cap_out = 0;
+  hostctx::DevBuf<uint8_t> d_in;      // host-API staging
+  hostctx::DevBuf<uint32_t> d_out;
 };
+
+// the stream and the product table on the device
+static int init_device(gnsscorr_sdr_fe_ctx* c) {
+  int16_t prod[4 * 1024 * 2];
+  gnsscorr_sdr_gn3s_products(prod);
+  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  HIP_TRY(hipMalloc(&c->d_prod, sizeof(prod)));
+  HIP_TRY(hipMemcpy(c->d_prod, prod, sizeof(prod), hipMemcpyHostToDevice));
+  return GNSSCORR_OK;
+}
 
 extern "C" int gnsscorr_sdr_fe_create(gnsscorr_sdr_fe_ctx** out, int device) {
   if (!out) {
@@ -109,41 +119,21 @@ extern "C" int gnsscorr_sdr_fe_create(gnsscorr_sdr_fe_ctx** out, int device) {
     return GNSSCORR_EINVAL;
   }
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    gnsscorr_set_error("gnsscorr_sdr_fe_create: no HIP device");
-    return GNSSCORR_ENODEV;
-  }
-  if (device < 0 || device >= ndev) {
-    gnsscorr_set_error("gnsscorr_sdr_fe_create: device %d out of range", device);
-    return GNSSCORR_EINVAL;
-  }
-  HIP_TRY(hipSetDevice(device));
+  int rc = hostctx::open_device(__func__, device);
+  if (rc) return rc;
   auto* c = new gnsscorr_sdr_fe_ctx();
-  c->device = device;
-  int16_t prod[4 * 1024 * 2];
-  gnsscorr_sdr_gn3s_products(prod);
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc(&c->d_prod, sizeof(prod)) != hipSuccess ||
-      hipMemcpy(c->d_prod, prod, sizeof(prod), hipMemcpyHostToDevice) != hipSuccess) {
+  c->cfg.device = device;
+  rc = init_device(c);
+  if (rc) {
     gnsscorr_sdr_fe_destroy(c);
-    gnsscorr_set_error("gnsscorr_sdr_fe_create: device allocation failed");
-    return GNSSCORR_ENOMEM;
+    return rc;
   }
   *out = c;
   return GNSSCORR_OK;
 }
 
 extern "C" int gnsscorr_sdr_fe_destroy(gnsscorr_sdr_fe_ctx* c) {
-  if (!c) return GNSSCORR_OK;
-  (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->d_prod) (void)hipFree(c->d_prod);
-  if (c->d_in) (void)hipFree(c->d_in);
-  if (c->d_out) (void)hipFree(c->d_out);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-  return GNSSCORR_OK;
+  return hostctx::destroy(c, [&] { hostctx::release(c->d_prod, c->d_in, c->d_out); });
 }
 
 static size_t gn3s_in_bytes(int fmt, int n_blocks) {
@@ -162,7 +152,7 @@ extern "C" int gnsscorr_sdr_gn3s_dev(gnsscorr_sdr_fe_ctx* c, const uint8_t* d_in
     gnsscorr_set_error("gnsscorr_sdr_gn3s_dev: d_out must be 16-byte aligned");
     return GNSSCORR_EINVAL;
   }
-  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipSetDevice(c->cfg.device));
   static_assert(kQuads % kThreads == 0, "exact grid of 16-byte output stores");
   hipLaunchKernelGGL(gn3s_kernel, dim3(kQuads / kThreads,
                                        (unsigned)(n_blocks < kGridY ? n_blocks : kGridY)),
@@ -179,27 +169,16 @@ extern "C" int gnsscorr_sdr_gn3s(gnsscorr_sdr_fe_ctx* c, const uint8_t* h_in, in
     gnsscorr_set_error("gnsscorr_sdr_gn3s: bad arguments");
     return GNSSCORR_EINVAL;
   }
-  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipSetDevice(c->cfg.device));
   const size_t nb = gn3s_in_bytes(fmt, n_blocks);
   const size_t no = (size_t)n_blocks * kBlkOut * 4;
-  if (nb > c->cap_in) {
-    if (c->d_in) (void)hipFree(c->d_in);
-    c->d_in = nullptr;
-    c->cap_in = 0;
-    HIP_TRY(hipMalloc(&c->d_in, nb));
-    c->cap_in = nb;
-  }
-  if (no > c->cap_out) {
-    if (c->d_out) (void)hipFree(c->d_out);
-    c->d_out = nullptr;
-    c->cap_out = 0;
-    HIP_TRY(hipMalloc(&c->d_out, no));
-    c->cap_out = no;
-  }
-  HIP_TRY(hipMemcpyAsync(c->d_in, h_in, nb, hipMemcpyHostToDevice, c->stream));
-  const int rc = gnsscorr_sdr_gn3s_dev(c, c->d_in, fmt, n_blocks, phase, step, (int16_t*)c->d_out);
+  int rc = hostctx::grow(c->d_in, nb);
+  if (!rc) rc = hostctx::grow(c->d_out, (size_t)n_blocks * kBlkOut);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h_out, c->d_out, no, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_in.p, h_in, nb, hipMemcpyHostToDevice, c->stream));
+  rc = gnsscorr_sdr_gn3s_dev(c, c->d_in.p, fmt, n_blocks, phase, step, (int16_t*)c->d_out.p);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(h_out, c->d_out.p, no, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return GNSSCORR_OK;
 }
@@ -224,7 +203,7 @@ extern "C" int gnsscorr_sdr_downsample_dev(gnsscorr_sdr_fe_ctx* c, const int16_t
                        n_src, f_dest, f_source);
     return GNSSCORR_EINVAL;
   }
-  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipSetDevice(c->cfg.device));
   hipLaunchKernelGGL(downsample_kernel, dim3((k + kThreads - 1) / kThreads), dim3(kThreads), 0,
                      c->stream, (const uint32_t*)d_src, k, step, (uint32_t*)d_dest);
   HIP_TRY(hipGetLastError());
@@ -232,11 +211,6 @@ extern "C" int gnsscorr_sdr_downsample_dev(gnsscorr_sdr_fe_ctx* c, const int16_t
   return GNSSCORR_OK;
 }
 
-extern "C" int gnsscorr_sdr_fe_sync(gnsscorr_sdr_fe_ctx* c) {
-  if (!c) return GNSSCORR_EINVAL;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GNSSCORR_OK;
-}
+extern "C" int gnsscorr_sdr_fe_sync(gnsscorr_sdr_fe_ctx* c) { return hostctx::sync(c); }
 
-extern "C" void* gnsscorr_sdr_fe_stream(gnsscorr_sdr_fe_ctx* c) { return c ? c->stream : nullptr; }
+extern "C" void* gnsscorr_sdr_fe_stream(gnsscorr_sdr_fe_ctx* c) { return hostctx::stream(c); }

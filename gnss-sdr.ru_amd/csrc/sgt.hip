@@ -771,9 +771,8 @@ struct gnsscorr_sgt_ctx {
   SgtParams p;
   hipStream_t stream = nullptr;
   uint32_t* d_codes = nullptr;
-  gnsscorr_sgt_chan* d_chan = nullptr;
-  gnsscorr_sgt_epoch* d_ep = nullptr;
-  size_t chan_cap = 0, ep_cap = 0;
+  hostctx::DevBuf<gnsscorr_sgt_chan> d_chan;   // the host wrappers' own
+  hostctx::DevBuf<gnsscorr_sgt_epoch> d_ep;
 };
 
 extern "C" void gnsscorr_sgt_loop_coefs(const gnsscorr_sgt_cfg* cfg, double* tau1, double* tau2,
@@ -820,21 +819,21 @@ extern "C" int gnsscorr_sgt_init_chan(const gnsscorr_sgt_cfg* cfg, int code_id, 
 
 extern "C" int gnsscorr_sgt_destroy(gnsscorr_sgt_ctx* c) { return ftrack::destroy(c); }
 
+// the stream and the code rows h on the device
+static int init_device(gnsscorr_sgt_ctx* c, const uint32_t* h, size_t bytes) {
+  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  HIP_TRY(hipMalloc(&c->d_codes, bytes));
+  HIP_TRY(hipMemcpy(c->d_codes, h, bytes, hipMemcpyHostToDevice));
+  return GNSSCORR_OK;
+}
+
 extern "C" int gnsscorr_sgt_create(gnsscorr_sgt_ctx** out, const gnsscorr_sgt_cfg* cfg) {
   if (!out) return GNSSCORR_EINVAL;
   *out = nullptr;
   int rc = check_cfg(cfg);
   if (rc) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    gnsscorr_set_error("gnsscorr_sgt_create: no HIP device");
-    return GNSSCORR_ENODEV;
-  }
-  if (cfg->device < 0 || cfg->device >= ndev) {
-    gnsscorr_set_error("gnsscorr_sgt_create: device %d out of range", cfg->device);
-    return GNSSCORR_EINVAL;
-  }
-  HIP_TRY(hipSetDevice(cfg->device));
+  rc = hostctx::open_device(__func__, cfg->device);
+  if (rc) return rc;
   auto* c = new gnsscorr_sgt_ctx();
   c->cfg = *cfg;
   SgtParams& p = c->p;
@@ -870,15 +869,11 @@ extern "C" int gnsscorr_sgt_create(gnsscorr_sgt_ctx** out, const gnsscorr_sgt_cf
     for (int i = 0; i < L; i++) row[1 + i] = m(chips[i]);
     row[L + 1] = m(chips[0]);
   }
-  hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipMalloc(&c->d_codes, sizeof(uint32_t) * rows * kPadLen);
-  if (e == hipSuccess)
-    e = hipMemcpy(c->d_codes, h, sizeof(uint32_t) * rows * kPadLen, hipMemcpyHostToDevice);
+  rc = init_device(c, h, sizeof(uint32_t) * rows * kPadLen);
   free(h);
-  if (e != hipSuccess) {
-    gnsscorr_set_error("gnsscorr_sgt_create: %s", hipGetErrorString(e));
+  if (rc) {
     gnsscorr_sgt_destroy(c);
-    return GNSSCORR_EDEVICE;
+    return rc;
   }
   *out = c;
   return GNSSCORR_OK;
@@ -948,9 +943,9 @@ extern "C" int gnsscorr_sgt_track(gnsscorr_sgt_ctx* c, const int8_t* d_if, int64
                        });
 }
 
-extern "C" int gnsscorr_sgt_sync(gnsscorr_sgt_ctx* c) { return ftrack::sync(c); }
+extern "C" int gnsscorr_sgt_sync(gnsscorr_sgt_ctx* c) { return hostctx::sync(c); }
 
-extern "C" void* gnsscorr_sgt_stream(gnsscorr_sgt_ctx* c) { return ftrack::stream(c); }
+extern "C" void* gnsscorr_sgt_stream(gnsscorr_sgt_ctx* c) { return hostctx::stream(c); }
 
 extern "C" int gnsscorr_sgt_replay_dev(gnsscorr_sgt_ctx* c, int n_ch, gnsscorr_sgt_chan* d_chan,
                                        int n_epochs, const double* d_sums,

@@ -25,11 +25,13 @@
 // 1-ms chunk at 16.368 Msps; IF is read as 16-byte vector loads.
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#include <vector>
 #include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include "gnsscorr_internal.h"
+#include "hostctx.h"
 #include "if2.h"
 #include "osg_isr.h"
 
@@ -1853,8 +1855,7 @@ struct gnsscorr_track_ctx {
   gnsscorr_nco_cmd* d_cmds = nullptr;
   gnsscorr_track_result* d_res = nullptr;
   int32_t* d_dumps = nullptr;
-  int8_t* d_if = nullptr;
-  size_t if_cap = 0;
+  hostctx::DevBuf<int8_t> d_if;   // gnsscorr_track's staging, in bytes
   int max_dumps = 0;
   int64_t tic = 0, tic_ref = 0;
   int stage_if = 1;   // GNSSCORR_TRACK_STAGE_IF=0: lanes read their IF runs from global memory
@@ -1881,6 +1882,33 @@ static int set_dev(int dev) {
   return GNSSCORR_OK;
 }
 
+// the stream, the device buffers and the code tables on them
+static int init_device(gnsscorr_track_ctx* c) {
+  const int C = c->cfg.n_channels;
+  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  HIP_TRY(hipMalloc(&c->d_pk, sizeof(uint32_t) * GNSSCORR_OSG_PK_LEN));
+  HIP_TRY(hipMalloc(&c->d_pk8, GNSSCORR_OSG_PK_LEN + 64));   // +64: whole-dword row staging
+  HIP_TRY(hipMalloc(&c->d_state, sizeof(gnsscorr_chan_state) * C));
+  HIP_TRY(hipMalloc(&c->d_cmds, sizeof(gnsscorr_nco_cmd) * C));
+  HIP_TRY(hipMalloc(&c->d_res, sizeof(gnsscorr_track_result) * C));
+  HIP_TRY(hipMalloc(&c->d_dumps, sizeof(int32_t) * 6 * (size_t)C * c->max_dumps));
+  std::vector<uint32_t> pk(GNSSCORR_OSG_PK_LEN);
+  gnsscorr_osg_packed_table(pk.data());
+  HIP_TRY(hipMemcpy(c->d_pk, pk.data(), sizeof(uint32_t) * GNSSCORR_OSG_PK_LEN,
+                    hipMemcpyHostToDevice));
+  // pack8: each int8 bit (-1 / 0 / +1) of {late, prompt, early} as a 2-bit field
+  std::vector<uint8_t> pk8(GNSSCORR_OSG_PK_LEN);
+  for (int i = 0; i < GNSSCORR_OSG_PK_LEN; i++) {
+    uint32_t b = 0;
+    for (int k = 0; k < 3; k++) b |= ((uint32_t)(int8_t)(pk[i] >> (8 * k)) & 3u) << (2 * k);
+    pk8[i] = (uint8_t)b;
+  }
+  HIP_TRY(hipMemset(c->d_pk8, 0, GNSSCORR_OSG_PK_LEN + 64));
+  HIP_TRY(hipMemcpy(c->d_pk8, pk8.data(), GNSSCORR_OSG_PK_LEN, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(c->d_state, 0, sizeof(gnsscorr_chan_state) * C));
+  return GNSSCORR_OK;
+}
+
 extern "C" int gnsscorr_track_create(gnsscorr_track_ctx** out, const gnsscorr_track_cfg* cfg) {
   if (!out || !cfg || cfg->n_channels < 1 || cfg->max_nsamp < 1 || cfg->max_nsamp > kMaxNsamp ||
       (cfg->iq & ~(GNSSCORR_IF_IQ | GNSSCORR_IF_PACKED2))) {
@@ -1889,16 +1917,7 @@ extern "C" int gnsscorr_track_create(gnsscorr_track_ctx** out, const gnsscorr_tr
     return GNSSCORR_EINVAL;
   }
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    gnsscorr_set_error("gnsscorr_track_create: no HIP device");
-    return GNSSCORR_ENODEV;
-  }
-  if (cfg->device < 0 || cfg->device >= ndev) {
-    gnsscorr_set_error("gnsscorr_track_create: device %d out of range", cfg->device);
-    return GNSSCORR_EINVAL;
-  }
-  int rc = set_dev(cfg->device);
+  int rc = hostctx::open_device(__func__, cfg->device);
   if (rc) return rc;
   auto* c = new gnsscorr_track_ctx();
   c->cfg = *cfg;
@@ -1915,38 +1934,10 @@ extern "C" int gnsscorr_track_create(gnsscorr_track_ctx** out, const gnsscorr_tr
   if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, cfg->device) !=
           hipSuccess || c->n_cu < 1)
     c->n_cu = 256;
-
-  const int C = cfg->n_channels;
-  auto fail = [&](int code) {
+  rc = init_device(c);
+  if (rc) {
     gnsscorr_track_destroy(c);
-    return code;
-  };
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc(&c->d_pk, sizeof(uint32_t) * GNSSCORR_OSG_PK_LEN) != hipSuccess ||
-      hipMalloc(&c->d_pk8, GNSSCORR_OSG_PK_LEN + 64) != hipSuccess ||   // +64: whole-dword row staging
-      hipMalloc(&c->d_state, sizeof(gnsscorr_chan_state) * C) != hipSuccess ||
-      hipMalloc(&c->d_cmds, sizeof(gnsscorr_nco_cmd) * C) != hipSuccess ||
-      hipMalloc(&c->d_res, sizeof(gnsscorr_track_result) * C) != hipSuccess ||
-      hipMalloc(&c->d_dumps, sizeof(int32_t) * 6 * (size_t)C * c->max_dumps) != hipSuccess) {
-    gnsscorr_set_error("gnsscorr_track_create: device allocation failed");
-    return fail(GNSSCORR_ENOMEM);
-  }
-  uint32_t* pk = (uint32_t*)malloc(sizeof(uint32_t) * GNSSCORR_OSG_PK_LEN);
-  if (!pk) return fail(GNSSCORR_ENOMEM);
-  gnsscorr_osg_packed_table(pk);
-  hipError_t e = hipMemcpy(c->d_pk, pk, sizeof(uint32_t) * GNSSCORR_OSG_PK_LEN, hipMemcpyHostToDevice);
-  // pack8: each int8 bit (-1 / 0 / +1) of {late, prompt, early} as a 2-bit field
-  for (int i = 0; i < GNSSCORR_OSG_PK_LEN; i++) {
-    uint32_t b = 0;
-    for (int k = 0; k < 3; k++) b |= ((uint32_t)(int8_t)(pk[i] >> (8 * k)) & 3u) << (2 * k);
-    reinterpret_cast<uint8_t*>(pk)[i] = (uint8_t)b;
-  }
-  if (e == hipSuccess) e = hipMemset(c->d_pk8, 0, GNSSCORR_OSG_PK_LEN + 64);
-  if (e == hipSuccess) e = hipMemcpy(c->d_pk8, pk, GNSSCORR_OSG_PK_LEN, hipMemcpyHostToDevice);
-  free(pk);
-  if (e != hipSuccess || hipMemset(c->d_state, 0, sizeof(gnsscorr_chan_state) * C) != hipSuccess) {
-    gnsscorr_set_error("gnsscorr_track_create: upload failed: %s", hipGetErrorString(e));
-    return fail(GNSSCORR_EDEVICE);
+    return rc;
   }
   *out = c;
   return GNSSCORR_OK;
@@ -1965,15 +1956,9 @@ extern "C" int gnsscorr_track_set_layout(gnsscorr_track_ctx* c, int one_stream_p
 }
 
 extern "C" int gnsscorr_track_destroy(gnsscorr_track_ctx* c) {
-  if (!c) return GNSSCORR_OK;
-  (void)hipSetDevice(c->cfg.device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  void* bufs[] = {c->d_pk, c->d_pk8, c->d_state, c->d_cmds, c->d_res, c->d_dumps, c->d_if};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-  return GNSSCORR_OK;
+  return hostctx::destroy(c, [&] {
+    hostctx::release(c->d_pk, c->d_pk8, c->d_state, c->d_cmds, c->d_res, c->d_dumps, c->d_if);
+  });
 }
 
 extern "C" int gnsscorr_track_max_dumps(const gnsscorr_track_ctx* c) { return c ? c->max_dumps : 0; }
@@ -2172,24 +2157,18 @@ extern "C" int gnsscorr_track(gnsscorr_track_ctx* c, const int8_t* h_if, int64_t
   const int64_t al = pk ? 32 : 16;
   const int64_t dstride = n_streams > 1 ? ((stride * bps + al - 1) & ~(al - 1)) / bps : 0;
   const size_t need = (size_t)if_bytes((n_streams - 1) * dstride * bps + ((nsamp * bps + al - 1) & ~(al - 1)), pk);
-  if (need > c->if_cap) {
-    if (c->d_if) (void)hipFree(c->d_if);
-    c->d_if = nullptr;
-    c->if_cap = 0;
-    HIP_TRY(hipMalloc(&c->d_if, need));
-    c->if_cap = need;
-  }
+  if ((rc = hostctx::grow(c->d_if, need))) return rc;
   if (n_streams == 1 || dstride == stride) {
-    HIP_TRY(hipMemcpyAsync(c->d_if, h_if, (size_t)if_bytes(((n_streams - 1) * stride + nsamp) * bps, pk),
+    HIP_TRY(hipMemcpyAsync(c->d_if.p, h_if, (size_t)if_bytes(((n_streams - 1) * stride + nsamp) * bps, pk),
                            hipMemcpyHostToDevice, c->stream));
   } else {
-    HIP_TRY(hipMemcpy2DAsync(c->d_if, if_bytes(dstride * bps, pk), h_if, if_bytes(stride * bps, pk),
+    HIP_TRY(hipMemcpy2DAsync(c->d_if.p, if_bytes(dstride * bps, pk), h_if, if_bytes(stride * bps, pk),
                              if_bytes(nsamp * bps, pk), n_streams, hipMemcpyHostToDevice, c->stream));
   }
   HIP_TRY(hipMemcpyAsync(c->d_cmds, h_cmds, sizeof(gnsscorr_nco_cmd) * C, hipMemcpyHostToDevice,
                          c->stream));
   const int64_t tic = gnsscorr_track_next_tic(c, nsamp);
-  rc = launch(c, c->d_if, dstride, nsamp, c->d_cmds, c->d_res, h_all_dumps ? c->d_dumps : nullptr,
+  rc = launch(c, c->d_if.p, dstride, nsamp, c->d_cmds, c->d_res, h_all_dumps ? c->d_dumps : nullptr,
               tic);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(h_res, c->d_res, sizeof(gnsscorr_track_result) * C,
@@ -2283,13 +2262,9 @@ extern "C" int gnsscorr_track_set_state(gnsscorr_track_ctx* c, const gnsscorr_ch
   return GNSSCORR_OK;
 }
 
-extern "C" int gnsscorr_track_sync(gnsscorr_track_ctx* c) {
-  if (!c) return GNSSCORR_EINVAL;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GNSSCORR_OK;
-}
+extern "C" int gnsscorr_track_sync(gnsscorr_track_ctx* c) { return hostctx::sync(c); }
 
-extern "C" void* gnsscorr_track_stream(gnsscorr_track_ctx* c) { return c ? (void*)c->stream : nullptr; }
+extern "C" void* gnsscorr_track_stream(gnsscorr_track_ctx* c) { return hostctx::stream(c); }
 
 extern "C" int gnsscorr_device_lds_bytes(int device) {
   int blk = 0, cu = 0;
