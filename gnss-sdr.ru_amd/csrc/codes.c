@@ -8,6 +8,7 @@
  *                            row over-read (correlator.c:172-174, 247-251) is
  *                            reproduced (see DESIGN.md "over-read").
  *  gnsscorr_ca_code          SoftGNSS generateCAcode.sci:42-87 (ICD G2 delays)
+ *  gnsscorr_b1i_code         SoftGNSS COMPASS/B1 generateCAcode.sci:38-146
  *  gnsscorr_st_code          SoftGNSS GLONASS generateSTcode.sci:35-42
  *  gnsscorr_sample_code      makeCaTable.sci:64-72 / makeStTable.sci:60-67
  *  gnsscorr_sample_boc_code  GALILEO/E1/include/makeE1BCodesTable.sci:56-78
@@ -100,6 +101,32 @@ int gnsscorr_ca_code(int prn, int8_t *out)
   for (int i = 0; i < 1023; i++) {
     int j = (i - d + 1023) % 1023;                  /* g2 = [g2(end-d+1:end) g2(1:end-d)] */
     out[i] = (int8_t)(-(g1[i] * g2[j]));
+  }
+  return GNSSCORR_OK;
+}
+
+/* COMPASS/B1/include/generateCAcode.sci:38-146 in bit form: a register entry of
+ * -1 is a set bit (a product of entries is the xor of their bits), stage k of the
+ * file's reg(1:11) is bit k - 1.  Both registers start as -1*[-1 1 -1 ... -1], i.e.
+ * the even stages set; the chip is -(g1 * g2): +1 where the two output bits differ. */
+int gnsscorr_b1i_code(int prn, int8_t *out)
+{
+  /* the two G2 stages whose product is the G2 output, per PRN (:63-136) */
+  static const uint8_t tap[37][2] = {
+      {1, 3}, {1, 4}, {1, 5}, {1, 6}, {1, 8}, {1, 9}, {1, 10}, {1, 11}, {2, 7}, {3, 4},
+      {3, 5}, {3, 6}, {3, 8}, {3, 9}, {3, 10}, {3, 11}, {4, 5}, {4, 6}, {4, 8}, {4, 9},
+      {4, 10}, {4, 11}, {5, 6}, {5, 8}, {5, 9}, {5, 10}, {5, 11}, {6, 8}, {6, 9}, {6, 10},
+      {6, 11}, {8, 9}, {8, 10}, {8, 11}, {9, 10}, {9, 11}, {10, 11}};
+  if (prn < 1 || prn > 37 || !out) return GNSSCORR_EINVAL;
+  const unsigned fb1 = 0x7C1u;   /* G1 stages 1, 7, 8, 9, 10, 11 (:48) */
+  const unsigned fb2 = 0x59Fu;   /* G2 stages 1, 2, 3, 4, 5, 8, 9, 11 (:140) */
+  const unsigned sel = (1u << (tap[prn - 1][0] - 1)) | (1u << (tap[prn - 1][1] - 1));
+  unsigned r1 = 0x2AAu, r2 = 0x2AAu;
+  for (int i = 0; i < 2046; i++) {
+    const unsigned b = ((r1 >> 10) & 1u) ^ (unsigned)__builtin_parity(r2 & sel);
+    out[i] = (int8_t)(b ? 1 : -1);
+    r1 = ((r1 << 1) & 0x7FFu) | (unsigned)__builtin_parity(r1 & fb1);
+    r2 = ((r2 << 1) & 0x7FFu) | (unsigned)__builtin_parity(r2 & fb2);
   }
   return GNSSCORR_OK;
 }

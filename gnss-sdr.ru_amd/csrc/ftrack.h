@@ -121,13 +121,19 @@ __device__ __forceinline__ void carry_carrier(Chan& c, double A, int blk, double
   c.rem_carr = last - trunc(last / twopi) * twopi;
 }
 
-// FLL-assisted PLL on the prompt sums: sets carr_freq, returns the PLL discriminator
-template <class Chan>
+// FLL-assisted PLL on the prompt sums: sets carr_freq, returns the PLL discriminator.
+// kSignFlip: the previous prompt pair is negated when sign(I_P) changed
+// (COMPASS/B1/tracking.sci:295-298; Scilab's sign() is -1, 0 or 1).
+template <bool kSignFlip = false, class Chan>
 __device__ __forceinline__ double fll_pll_step(Chan& c, double k1, double k2, double k3,
                                                double I_P, double Q_P) {
 #pragma clang fp contract(off)
-  const double I2 = c.i1, Q2 = c.q1;
+  double I2 = c.i1, Q2 = c.q1;
   c.i1 = I_P; c.q1 = Q_P;
+  if (kSignFlip) {
+    const int s2 = (I2 > 0.0) - (I2 < 0.0), s1 = (I_P > 0.0) - (I_P < 0.0);
+    if (s2 != s1) { I2 = -I2; Q2 = -Q2; }
+  }
   const double cross = c.i1 * Q2 - I2 * c.q1;
   const double dot = fabs(c.i1 * I2 + c.q1 * Q2);
   const double freq_err = atan2(cross, dot) / M_PI;

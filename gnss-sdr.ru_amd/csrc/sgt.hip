@@ -1,7 +1,8 @@
 // sgt.hip -- SoftGNSS float tracking loop ("sgt") on gfx950.
 //
 // The Scilab receivers track one channel at a time over a recorded file
-// (GLONASS/L1/tracking.sci:150-400, GPS/L1/tracking.sci:124-360).  Here the
+// (GLONASS/L1/tracking.sci:150-400, GPS/L1/tracking.sci:124-360, and as system 2
+// BeiDou B1I, COMPASS/B1/tracking.sci:123-357, in kernels of its own).  Here the
 // whole record lives in HBM and one workgroup runs one channel's loop for
 // many epochs without leaving the GPU:
 //
@@ -40,6 +41,11 @@ using namespace ftrack;
 
 constexpr int kMaxCode = 1023;
 constexpr int kPadLen = kMaxCode + 2;
+// BeiDou B1I (system 2): 2046 chips, rows of 2048 words, PRN 1..37
+constexpr int kMaxCodeB1 = 2046;
+constexpr int kPadLenB1 = kMaxCodeB1 + 2;
+constexpr int kMaxPrnB1 = 37;
+__host__ __device__ constexpr int sgt_row_pitch(bool b1) { return b1 ? kPadLenB1 : kPadLen; }
 constexpr int kMaxWaves = 16;
 // wave mode asks for 3 waves per SIMD (<= 168 VGPRs): measured 3 % faster than 2
 constexpr int kWaveOcc = 3;
@@ -70,7 +76,9 @@ struct SgtParams {
 // (:377-398).  One definition for the tracking kernel and the sums-replay
 // kernel, so the replay against the reference's recorded run
 // (tests/test_sgt_trackres_gpu.py) checks the code the tracker runs.
-template <bool CLOSED>
+// B1: the BeiDou B1I loop (COMPASS/B1/tracking.sci:291-344): the previous prompt
+// pair negated when I_P changed sign (:295-298) and carrier aiding by /763 (:336).
+template <bool CLOSED, bool B1 = false>
 __device__ __forceinline__ gnsscorr_sgt_epoch sgt_epoch_end(const SgtParams& p,
                                                             gnsscorr_sgt_chan& c, int blk,
                                                             double step, const double (&S)[6]) {
@@ -85,12 +93,14 @@ __device__ __forceinline__ gnsscorr_sgt_epoch sgt_epoch_end(const SgtParams& p,
   c.pos += blk;
   double code_err = 0, carr_err = 0;
   if (CLOSED) {
-    carr_err = fll_pll_step(c, p.k1, p.k2, p.k3, I_P, Q_P);   // tracking.sci:329-353
+    carr_err = fll_pll_step<B1>(c, p.k1, p.k2, p.k3, I_P, Q_P);   // tracking.sci:329-353
     code_err = early_late_step(I_E, Q_E, I_L, Q_L, p.tau1, p.tau2, p.pdi_code, c.old_code_nco,
                                c.old_code_error);             // DLL, tracking.sci:355-374
     const double code_nco = c.old_code_nco;
     if (p.code_nco_variant == 1) {
       c.code_freq = p.code_basis - code_nco;               // :366, no carrier aiding
+    } else if (B1) {
+      c.code_freq = p.code_basis - code_nco + ((c.carr_freq - p.if_freq) / 763);
     } else if (p.system == 1) {
       const double fch = (double)c.code_id;                // :367-370
       c.code_freq = p.code_basis - code_nco +
@@ -130,7 +140,10 @@ __device__ __forceinline__ int xcd_channel(int b, int G) {
 // a 4-16-wave workgroup.
 // MAXT: the launch bound (64 = WAVE; 256 for the default small-receiver shape,
 // which then keeps its registers instead of fitting the 1024-thread budget).
-template <int FT, bool CLOSED, int MAXT>
+// B1: the BeiDou B1I instantiation (system 2): 2048-word code rows, the B1I epoch end,
+// the select form on 8-sample chunks in the wave kernel and the per-sample loop in the
+// others.  Its own kernels, so the GPS / GLONASS ones keep their code.
+template <int FT, bool CLOSED, int MAXT, bool B1 = false>
 __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_kernel(
     SgtParams p, const int8_t* __restrict__ ifbuf, int64_t stride, int64_t n_samples,
     const uint32_t* __restrict__ codes, gnsscorr_sgt_chan* __restrict__ chans, int n_epochs,
@@ -143,7 +156,9 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
   __shared__ double2 s_w[40];   // chunked paths: exp(i*A*n/fs), n < kC
   const int ch = xcd_channel(blockIdx.x, gridDim.x);
   constexpr bool WAVE = MAXT == 64;
-  constexpr bool kPrefix = sgt_prefix(MAXT);
+  // (B1I has no prefix form: no prefix columns in its LDS)
+  constexpr bool kPrefix = sgt_prefix(MAXT) && !B1;
+  constexpr int kPitch = sgt_row_pitch(B1);
   const int T = WAVE ? 64 : blockDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // this lane's prefix column (kPrefix): entry m at s_pf[m * 64]
   double2* s_pf = reinterpret_cast<double2*>(reinterpret_cast<uint8_t*>(s_sgn) +
@@ -152,13 +167,14 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
   const int nw = T >> 6;
   gnsscorr_sgt_chan c = chans[ch];
   const int L = p.code_length;
-  const int row = p.system == 1 ? 0 : c.code_id;
+  // (B1I: a PRN outside 1..37 lands on a row of the table, not outside it)
+  const int row = B1 ? clampu(c.code_id, kMaxPrnB1) : (p.system == 1 ? 0 : c.code_id);
   for (int i = tid; i < L + 2; i += T) {
-    s_sgn[i] = codes[row * kPadLen + i] ? -1.0 : 1.0;   // sign-bit masks of the table
+    s_sgn[i] = codes[row * kPitch + i] ? -1.0 : 1.0;   // sign-bit masks of the table
   }
   // one guard entry past the padded table (a copy of entry L+1): the unclamped
   // in_table path relies on a rounding argument to stay within [0, L+1]
-  if (tid == 0) s_sgn[L + 2] = codes[row * kPadLen + L + 1] ? -1.0 : 1.0;
+  if (tid == 0) s_sgn[L + 2] = codes[row * kPitch + L + 1] ? -1.0 : 1.0;
   __syncthreads();
 
   const int8_t* base = ifbuf + (int64_t)c.stream * stride;
@@ -685,6 +701,27 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
     const bool chunked = p.chunked && in_table && 15.0 * step < 0.999 &&
                          ((uintptr_t)src & (kBps - 1)) == 0;
     const double invs = 1.0 / step, sps = floor(p.spc * invs);   // samples per chip, spc in samples
+    if constexpr (B1) {
+      // The wave kernel takes the select form on chunks of 8 IQ samples (one 16-byte
+      // word, (8 - 1) * step < 0.999): the one chunk form that beat the per-sample loop,
+      // and only in this shape ("BeiDou B1I").  Chip-aligned chunks of one
+      // 8-sample chip (run_chips, kC = 8 / 9), of two chips (kC = 16 / 17, five capture
+      // windows) and 16-sample chunks with two crossings per arm were slower in every
+      // shape; a byte code table was no faster than the doubles; real samples (fileType
+      // 1) have no 8-byte chunk grid.  Everything else is the per-sample loop.
+      bool selected = false;
+      if constexpr (MAXT == 64 && FT == 2) {
+        // chunks of 8 samples, about one chip at 16 Msps: one crossing per arm at most
+        if (p.chunked && in_table && 7.0 * step < 0.999 && ((uintptr_t)src & (kBps - 1)) == 0) {
+          run_chunks(std::integral_constant<int, 8>{});
+          selected = true;
+        }
+      }
+      if (!selected) {
+        if (in_table) run(std::false_type{});
+        else run(std::true_type{});
+      }
+    } else {
     // the longest chunk is floor(samples per chip) + 1 samples: kC = 16 / 17 (GPS
     // at 16 / 16.368 Msps), 32 / 33 (GLONASS); the loop masks its last 3 samples
     const int ipc = (MAXT <= 256 && chunked && sps <= 3.0 && invs < 33.0) ? (int)invs : 0;
@@ -703,6 +740,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
       run(std::false_type{});
     else
       run(std::true_type{});
+    }
     ie = wave_sum(ie); ip = wave_sum(ip); il = wave_sum(il);
     qe = wave_sum(qe); qp = wave_sum(qp); ql = wave_sum(ql);
     double S[6] = {ie, ip, il, qe, qp, ql};
@@ -719,7 +757,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
 #pragma unroll
         for (int j = 0; j < 6; j++) S[j] += s_part[par][w][j];
     }
-    const gnsscorr_sgt_epoch r = sgt_epoch_end<CLOSED>(p, c, blk, step, S);
+    const gnsscorr_sgt_epoch r = sgt_epoch_end<CLOSED, B1>(p, c, blk, step, S);
     if (tid == 0) *rec = r;
   }
   if (tid == 0) chans[ch] = c;
@@ -729,6 +767,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
 // (sums[(ch*n_epochs + e)*6 + j]) instead of correlations of a record.  No
 // record bounds (there is no record); a NaN / negative / >= 2^31 blksize stops
 // the channel as in the tracking kernel.
+template <bool B1>
 __global__ void sgt_replay_kernel(SgtParams p, gnsscorr_sgt_chan* __restrict__ chans, int n_ch,
                                   int n_epochs, const double* __restrict__ sums,
                                   gnsscorr_sgt_epoch* __restrict__ out) {
@@ -756,7 +795,7 @@ __global__ void sgt_replay_kernel(SgtParams p, gnsscorr_sgt_chan* __restrict__ c
     }
     const double* sp = sums + ((int64_t)ch * n_epochs + e) * 6;
     const double S[6] = {sp[0], sp[1], sp[2], sp[3], sp[4], sp[5]};
-    *rec = sgt_epoch_end<true>(p, c, (int)blk_d, step, S);
+    *rec = sgt_epoch_end<true, B1>(p, c, (int)blk_d, step, S);
   }
   chans[ch] = c;
 }
@@ -782,17 +821,32 @@ extern "C" void gnsscorr_sgt_loop_coefs(const gnsscorr_sgt_cfg* cfg, double* tau
 }
 
 static int check_cfg(const gnsscorr_sgt_cfg* cfg) {
-  if (!cfg || (cfg->system != 0 && cfg->system != 1) ||
-      (cfg->file_type != 1 && cfg->file_type != 2) || cfg->samp_rate <= 0 ||
+  if (cfg && (cfg->system < 0 || cfg->system > 2)) {
+    gnsscorr_set_error("sgt: bad config (system %d: 0 = GPS L1 C/A, 1 = GLONASS L1OF, "
+                       "2 = BeiDou B1I)", cfg->system);
+    return GNSSCORR_EINVAL;
+  }
+  const int len = !cfg ? 0 : cfg->system == 2 ? kMaxCodeB1 : cfg->system == 1 ? 511 : 1023;
+  if (!cfg || (cfg->file_type != 1 && cfg->file_type != 2) || cfg->samp_rate <= 0 ||
       cfg->code_freq_basis <= 0 || cfg->dll_spacing < 0 || cfg->dll_spacing >= 1 ||
-      cfg->code_length != (cfg->system == 1 ? 511 : 1023) ||
+      cfg->code_length != len ||
       (cfg->code_nco_variant != 0 && cfg->code_nco_variant != 1) ||
       (cfg->abs_sample_variant != 0 && cfg->abs_sample_variant != 1)) {
-    gnsscorr_set_error("sgt: bad config (system 0/1, file_type 1/2, code_length 1023/511, "
-                       "0<=dll_spacing<1, variants 0/1)");
+    if (cfg && cfg->system == 2)
+      gnsscorr_set_error("sgt: bad config (system 2: file_type 1/2, code_length 2046, "
+                         "0<=dll_spacing<1, variants 0/1)");
+    else
+      gnsscorr_set_error("sgt: bad config (system 0/1, file_type 1/2, code_length 1023/511, "
+                         "0<=dll_spacing<1, variants 0/1)");
     return GNSSCORR_EINVAL;
   }
   return GNSSCORR_OK;
+}
+
+// the channel's code id for its system: GPS PRN, GLONASS frequency channel, B1I PRN
+static bool code_id_ok(int system, int id) {
+  if (system == 2) return id >= 1 && id <= kMaxPrnB1;
+  return system == 0 ? (id >= 1 && id <= 32) : (id >= -7 && id <= 6);
 }
 
 extern "C" int gnsscorr_sgt_init_chan(const gnsscorr_sgt_cfg* cfg, int code_id, int stream,
@@ -801,10 +855,12 @@ extern "C" int gnsscorr_sgt_init_chan(const gnsscorr_sgt_cfg* cfg, int code_id, 
   int rc = check_cfg(cfg);
   if (rc) return rc;
   if (!o || code_phase_1b < 1 || stream < 0 || skip < 0 ||
-      (cfg->system == 0 && (code_id < 1 || code_id > 32)) ||
-      (cfg->system == 1 && (code_id < -7 || code_id > 6))) {
-    gnsscorr_set_error("gnsscorr_sgt_init_chan: bad channel (PRN 1..32 / FCH -7..6, "
-                       "code_phase >= 1)");
+      !code_id_ok(cfg->system, code_id)) {
+    if (cfg->system == 2)
+      gnsscorr_set_error("gnsscorr_sgt_init_chan: bad channel (B1I PRN 1..37, code_phase >= 1)");
+    else
+      gnsscorr_set_error("gnsscorr_sgt_init_chan: bad channel (PRN 1..32 / FCH -7..6, "
+                         "code_phase >= 1)");
     return GNSSCORR_EINVAL;
   }
   memset(o, 0, sizeof *o);
@@ -855,21 +911,24 @@ extern "C" int gnsscorr_sgt_create(gnsscorr_sgt_ctx** out, const gnsscorr_sgt_cf
   p.pdi_code = 0.001;
   gnsscorr_sgt_loop_coefs(cfg, &p.tau1, &p.tau2, &p.k1, &p.k2, &p.k3);
   // padded code rows [c(end) c c(1)] as fp64 sign masks (tracking.sci:171-174)
-  const int rows = cfg->system == 1 ? 1 : 33;
-  uint32_t* h = (uint32_t*)calloc((size_t)rows * kPadLen, sizeof(uint32_t));
-  int8_t chips[kMaxCode];
+  // (row pitch: 1025 words for GPS / GLONASS, 2048 for the 38 rows of B1I)
+  const int rows = cfg->system == 1 ? 1 : (cfg->system == 2 ? kMaxPrnB1 + 1 : 33);
+  const int pitch = sgt_row_pitch(cfg->system == 2);
+  uint32_t* h = (uint32_t*)calloc((size_t)rows * pitch, sizeof(uint32_t));
+  int8_t chips[kMaxCodeB1];
   const int L = cfg->code_length;
   for (int r = 0; r < rows; r++) {
     if (cfg->system == 1) gnsscorr_st_code(chips);
     else if (r == 0) continue;
+    else if (cfg->system == 2) gnsscorr_b1i_code(r, chips);
     else gnsscorr_ca_code(r, chips);
-    uint32_t* row = h + (size_t)r * kPadLen;
+    uint32_t* row = h + (size_t)r * pitch;
     auto m = [](int8_t v) { return v < 0 ? 0x80000000u : 0u; };
     row[0] = m(chips[L - 1]);
     for (int i = 0; i < L; i++) row[1 + i] = m(chips[i]);
     row[L + 1] = m(chips[0]);
   }
-  rc = init_device(c, h, sizeof(uint32_t) * rows * kPadLen);
+  rc = init_device(c, h, sizeof(uint32_t) * rows * pitch);
   free(h);
   if (rc) {
     gnsscorr_sgt_destroy(c);
@@ -899,27 +958,37 @@ extern "C" int gnsscorr_sgt_track_dev(gnsscorr_sgt_ctx* c, const int8_t* d_if, i
   dim3 grid(n_ch), block(T);
   const size_t tab = sgt_tab_bytes(c->p.code_length);
   // + the prefix columns of run_chunks (the 128- and 256-thread shapes; not wave mode)
-  const size_t tab_pf = tab + (sgt_prefix(T) ? (size_t)(T / 64) * kPfWaveBytes : 0);
-#define SGT_LAUNCH(FT, CL)                                                                     \
+  // (the B1I kernels have no prefix columns)
+  const bool b1 = c->cfg.system == 2;
+  const size_t tab_pf = tab + (sgt_prefix(T) && !b1 ? (size_t)(T / 64) * kPfWaveBytes : 0);
+#define SGT_LAUNCH(FT, CL, B1)                                                                 \
   do {                                                                                         \
     if (T == 64)                                                                               \
-      hipLaunchKernelGGL((sgt_track_kernel<FT, CL, 64>), grid, block, tab_pf, c->stream, c->p,\
+      hipLaunchKernelGGL((sgt_track_kernel<FT, CL, 64, B1>), grid, block, tab_pf, c->stream,  \
+                         c->p,                                                                 \
                          d_if, stride, n_samples, c->d_codes, d_chan, n_epochs, d_ep);         \
     else if (T <= 256)                                                                         \
-      hipLaunchKernelGGL((sgt_track_kernel<FT, CL, 256>), grid, block, tab_pf, c->stream,     \
+      hipLaunchKernelGGL((sgt_track_kernel<FT, CL, 256, B1>), grid, block, tab_pf, c->stream, \
                          c->p,                                                                 \
                          d_if, stride, n_samples, c->d_codes, d_chan, n_epochs, d_ep);         \
     else                                                                                       \
-      hipLaunchKernelGGL((sgt_track_kernel<FT, CL, 1024>), grid, block, tab, c->stream, c->p, \
+      hipLaunchKernelGGL((sgt_track_kernel<FT, CL, 1024, B1>), grid, block, tab, c->stream,   \
+                         c->p,                                                                 \
                          d_if, stride, n_samples, c->d_codes, d_chan, n_epochs, d_ep);         \
   } while (0)
+#define SGT_LAUNCH_SYS(FT, CL)                                                                 \
+  do {                                                                                         \
+    if (b1) SGT_LAUNCH(FT, CL, true);                                                          \
+    else SGT_LAUNCH(FT, CL, false);                                                            \
+  } while (0)
   if (c->cfg.file_type == 2) {
-    if (closed_loop) SGT_LAUNCH(2, true);
-    else SGT_LAUNCH(2, false);
+    if (closed_loop) SGT_LAUNCH_SYS(2, true);
+    else SGT_LAUNCH_SYS(2, false);
   } else {
-    if (closed_loop) SGT_LAUNCH(1, true);
-    else SGT_LAUNCH(1, false);
+    if (closed_loop) SGT_LAUNCH_SYS(1, true);
+    else SGT_LAUNCH_SYS(1, false);
   }
+#undef SGT_LAUNCH_SYS
 #undef SGT_LAUNCH
   HIP_TRY(hipGetLastError());
   return GNSSCORR_OK;
@@ -931,7 +1000,7 @@ extern "C" int gnsscorr_sgt_track(gnsscorr_sgt_ctx* c, const int8_t* d_if, int64
   if (!c || !h_chan || !h_ep || n_ch < 1 || n_epochs < 1) return bad_arguments(__func__);
   for (int i = 0; i < n_ch; i++) {
     const int id = h_chan[i].code_id;
-    if (c->cfg.system == 0 ? (id < 1 || id > 32) : (id < -7 || id > 6)) {
+    if (!code_id_ok(c->cfg.system, id)) {
       gnsscorr_set_error("gnsscorr_sgt_track: channel %d: bad PRN/FCH %d", i, id);
       return GNSSCORR_EINVAL;
     }
@@ -950,7 +1019,11 @@ extern "C" void* gnsscorr_sgt_stream(gnsscorr_sgt_ctx* c) { return hostctx::stre
 extern "C" int gnsscorr_sgt_replay_dev(gnsscorr_sgt_ctx* c, int n_ch, gnsscorr_sgt_chan* d_chan,
                                        int n_epochs, const double* d_sums,
                                        gnsscorr_sgt_epoch* d_ep) {
-  return ftrack::replay_dev(__func__, c, sgt_replay_kernel, n_ch, d_chan, n_epochs, d_sums, d_ep);
+  if (c && c->cfg.system == 2)
+    return ftrack::replay_dev(__func__, c, sgt_replay_kernel<true>, n_ch, d_chan, n_epochs,
+                              d_sums, d_ep);
+  return ftrack::replay_dev(__func__, c, sgt_replay_kernel<false>, n_ch, d_chan, n_epochs, d_sums,
+                            d_ep);
 }
 
 extern "C" int gnsscorr_sgt_replay(gnsscorr_sgt_ctx* c, int n_ch, gnsscorr_sgt_chan* h_chan,

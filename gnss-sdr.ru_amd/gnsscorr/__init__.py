@@ -227,8 +227,8 @@ EXPORTED_FUNCTIONS = [
     "gnsscorr_dev_synchronize", "gnsscorr_event_create", "gnsscorr_event_record",
     "gnsscorr_stream_wait_event",
     "gnsscorr_event_elapsed_ms", "gnsscorr_event_destroy", "gnsscorr_dev_fill_if2",
-    "gnsscorr_ifgen", "gnsscorr_ca_code", "gnsscorr_st_code", "gnsscorr_sample_code",
-    "gnsscorr_sample_boc_code",
+    "gnsscorr_ifgen", "gnsscorr_ca_code", "gnsscorr_b1i_code", "gnsscorr_st_code",
+    "gnsscorr_sample_code", "gnsscorr_sample_boc_code",
     "correlator_init", "Sim_GP2021_int", "gnsscorr_osg_configure", "gnsscorr_osg_get_state",
 ]
 EXPORTED_DATA = ["REG_read", "REG_write", "Carrier_DCO_Delta", "Code_DCO_Delta",
@@ -359,6 +359,7 @@ def lib() -> C.CDLL:
         "gnsscorr_dev_fill_if2": (I, [I, P, C.c_size_t, U64]),
         "gnsscorr_ifgen": (I, [P, I64, I, D, D, D, I, P, U64]),
         "gnsscorr_ca_code": (I, [I, P]),
+        "gnsscorr_b1i_code": (I, [I, P]),
         "gnsscorr_st_code": (I, [P]),
         "gnsscorr_sample_code": (I, [P, I, D, D, I, P]),
         "gnsscorr_sample_boc_code": (I, [P, I, D, D, I, P]),
@@ -519,6 +520,14 @@ class Event:
 def ca_code(prn: int) -> np.ndarray:
     out = np.empty(1023, np.int8)
     _check(lib().gnsscorr_ca_code(prn, _ptr(out)), "gnsscorr_ca_code")
+    return out
+
+
+def b1i_code(prn: int) -> np.ndarray:
+    """BeiDou B1I ranging code of prn 1..37 as +-1 chips
+    (COMPASS/B1/include/generateCAcode.sci:38-146)."""
+    out = np.empty(2046, np.int8)
+    _check(lib().gnsscorr_b1i_code(prn, _ptr(out)), "gnsscorr_b1i_code")
     return out
 
 
@@ -778,8 +787,9 @@ class AcqCtx:
 
 # ---------------------------------------------------------------- SoftGNSS float tracking
 def sgt_cfg(system: int, device: int = 0, **kw) -> SgtCfg:
-    """initSettings.sci defaults (GLONASS/L1:41-107, GPS/L1:41-95); keyword overrides
-    use the Scilab names (samplingFreq, IF, dllCorrelatorSpacing, fileType, ...)."""
+    """initSettings.sci defaults (GLONASS/L1:41-107, GPS/L1:41-95, system 2:
+    COMPASS/B1:64-101); keyword overrides use the Scilab names (samplingFreq, IF,
+    dllCorrelatorSpacing, fileType, ...)."""
     glo = system == 1
     d = dict(samplingFreq=16e6, codeFreqBasis=0.511e6 if glo else 1.023e6,
              codeLength=511 if glo else 1023, IF=1e6 if glo else 2.42e6,
@@ -787,6 +797,9 @@ def sgt_cfg(system: int, device: int = 0, **kw) -> SgtCfg:
              dllCorrelatorSpacing=0.05 if glo else 0.2, dllNoiseBandwidth=0.5 if glo else 0.1,
              dllDampingRatio=0.7, pllNoiseBandwidth=25.0, fllNoiseBandwidth=250.0, fileType=2,
              switchIQ=0, codeNcoVariant=0, absSampleVariant=0)
+    if system == 2:
+        d.update(codeFreqBasis=2.046e6, codeLength=2046, IF=0.098e6, dllCorrelatorSpacing=0.1,
+                 dllNoiseBandwidth=0.5)
     unknown = set(kw) - set(d) - {"system"}
     if unknown:
         raise ValueError(f"unknown settings {sorted(unknown)}")

@@ -417,6 +417,10 @@ void *gnsscorr_acq_stream(gnsscorr_acq_ctx *ctx);
  * SoftGNSS float tracking ("sgt"): the Scilab receivers' per-channel loop
  *   GLONASS POSTPROCESSING_SCILAB_RECEIVERS/GLONASS/L1/tracking.sci:150-400
  *   GPS     POSTPROCESSING_SCILAB_RECEIVERS/GPS/L1/tracking.sci:124-360
+ *   BeiDou  POSTPROCESSING_SCILAB_RECEIVERS/COMPASS/B1/tracking.sci:123-357
+ *           (the GPS loop on the 2046-chip B1I code at 2.046 Mcps, 37 PRNs,
+ *           carrier aiding (carrFreq - IF)/763, and the previous prompt pair
+ *           negated when I_P changed sign, :295-298)
  * One epoch = one code period: blksize = ceil((L - remCode)/step) samples,
  * E/P/L replica indices ceil(remCode -/+ spc + k*step) (fp64, bit-exact),
  * carrier exp(i*(2*pi*f*t + remCarr)) (fp64), six fp64 sums
@@ -428,10 +432,11 @@ void *gnsscorr_acq_stream(gnsscorr_acq_ctx *ctx);
 typedef struct gnsscorr_sgt_ctx gnsscorr_sgt_ctx;
 
 typedef struct {          /* initSettings.sci fields used by tracking.sci     */
-  int32_t system;         /* 0 = GPS L1 C/A (C/A code per PRN), 1 = GLONASS L1OF (ST) */
+  int32_t system;         /* 0 = GPS L1 C/A (C/A code per PRN), 1 = GLONASS L1OF (ST),
+                             2 = BeiDou B1I (ranging code per PRN)              */
   int32_t file_type;      /* settings.fileType: 1 = int8 real, 2 = int8 interleaved I,Q */
   int32_t switch_iq;      /* settings.switchIQ (GLONASS only, tracking.sci:263-267) */
-  int32_t code_length;    /* settings.codeLength: 1023 / 511                   */
+  int32_t code_length;    /* settings.codeLength: 1023 / 511 / 2046 (system 0 / 1 / 2) */
   int32_t device;
   int32_t max_channels;
   double  samp_rate;      /* settings.samplingFreq                             */
@@ -444,14 +449,18 @@ typedef struct {          /* initSettings.sci fields used by tracking.sci     */
   double  pll_noise_bw, fll_noise_bw;  /* calcFLLPLLLoopCoef(pll, fll, PDIcarr=0.001) */
   /* tracking.sci variants; 0 = the current file for both.  The reference's
    * recorded runs (GLONASS/L1,L2/trackingResults.dat) used 1 and 1. */
-  int32_t code_nco_variant;   /* 0: codeFreq with carrier aiding (:367-370, GPS :1540 form);
+  int32_t code_nco_variant;   /* 0: codeFreq with carrier aiding (:367-370, GPS /1540 form,
+                                 B1I /763 form, COMPASS/B1/tracking.sci:336);
                                  1: codeFreq = codeFreqBasis - codeNco (:366)          */
   int32_t abs_sample_variant; /* 0: currentSample - remCodePhase*(fs/1000)/L (:384);
                                  1: mtell(fid)/dataAdaptCoeff, whole samples (:379)    */
 } gnsscorr_sgt_cfg;
 
 typedef struct {          /* one tracking channel (tracking.sci:159-201 + loop state) */
-  int32_t code_id;        /* GPS PRN 1..32, or GLONASS FCH -7..6                */
+  int32_t code_id;        /* GPS PRN 1..32, GLONASS FCH -7..6, or B1I PRN 1..37.
+                             gnsscorr_sgt_track checks it; gnsscorr_sgt_track_dev does
+                             not: a B1I id outside 1..37 is then clamped to row 0 (all
+                             +1) or row 37 of the code table, silently            */
   int32_t stream;         /* which IF record (stride given per call)           */
   int32_t status;         /* 0 tracking, 1 out of data (tracking.sci:273-277)  */
   int32_t n_epochs;       /* epochs processed so far                           */
@@ -925,6 +934,9 @@ int gnsscorr_ifgen(int8_t *h_out, int64_t nsamp, int iq, double fs, double if_gp
 
 /* GPS C/A code as +-1 chips (generateCAcode.sci:42-87 form), prn 1..32. */
 int gnsscorr_ca_code(int prn, int8_t *h_chips1023);
+/* BeiDou B1I ranging code as +-1 chips (COMPASS/B1/include/generateCAcode.sci:38-146),
+ * prn 1..37. */
+int gnsscorr_b1i_code(int prn, int8_t *h_chips2046);
 /* GLONASS ST code as +-1 chips (generateSTcode.sci:35-42). */
 int gnsscorr_st_code(int8_t *h_chips511);
 /* Sample a +-1 chip sequence with the makeCaTable.sci:64-72 rule:
