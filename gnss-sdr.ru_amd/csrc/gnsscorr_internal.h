@@ -27,8 +27,10 @@ int gnsscorr_track_iq(const gnsscorr_track_ctx *ctx);
  * channel's wave correlates call k, runs its gpsisr step and goes on to call
  * k+1 with the new command words; d_res / d_loop_hist receive every call.
  * GNSSCORR_TRACK_NOT_FUSED when that kernel does not serve the context (I-only
- * streams, A/B switches, shapes) or n_loops differs from the context's channel
- * count; the caller then runs the calls as correlator + osg_isr_kernel launches. */
+ * streams), when the later calls of n_calls > 1 would start misaligned (nsamp
+ * not a whole number of 16-byte int8 / 8-byte packed words), or when n_loops
+ * differs from the context's channel count; the caller then runs the calls as
+ * correlator + osg_isr_kernel launches. */
 #define GNSSCORR_TRACK_NOT_FUSED 1
 int gnsscorr_track_dev_isr(gnsscorr_track_ctx *ctx, const int8_t *d_if, int64_t stream_stride,
                            int64_t nsamp, int n_calls, gnsscorr_nco_cmd *d_cmds,

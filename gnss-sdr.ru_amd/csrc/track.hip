@@ -21,8 +21,9 @@
 //    wavefront reduces them with cross-lane shuffles and one lane per wave
 //    adds into an LDS slot per epoch.
 //
-// One workgroup = one channel x one call.  256 threads x 64 samples covers a
-// 1-ms chunk at 16.368 Msps; IF is read as 16-byte vector loads.
+// Two kernels: osg_stream_kernel (one wavefront per channel, every interleaved
+// I,Q stream) and osg_track_kernel (thread groups of 64-sample runs, real-sample
+// streams).
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <vector>
@@ -34,13 +35,6 @@
 #include "hostctx.h"
 #include "if2.h"
 #include "osg_isr.h"
-
-// Diagnostic hook (tools/trk_stamps.hip defines it; a no-op in the library)
-#ifndef TRACK_PSTAMP
-#define TRACK_PSTAMP(i) \
-  do {                  \
-  } while (0)
-#endif
 
 // Diagnostic hook of osg_stream_kernel (tools/trk_stream_stamps.hip; a no-op here)
 #ifndef STREAM_PSTAMP
@@ -55,8 +49,6 @@ constexpr int kRun = 64;              // samples per thread
 constexpr int kMaxThreads = 1024;
 constexpr int kMaxNsamp = kRun * kMaxThreads;
 constexpr uint64_t kNever = ~0ull;
-constexpr int kPitch = 9;             // 16-byte chunks per staged lane run (8 + 1 pad)
-constexpr int kStageMaxBytes = 48 * 1024;
 constexpr int kPk8Stage = 3088;       // LDS bytes of the E/P/L row (D <= 3071: slew <= 1025) + 3 of misalignment
 constexpr int kMaxCpw = 4;            // channels per workgroup (32 waves/CU: two 1024-thread WGs)
 
@@ -127,22 +119,17 @@ struct Acc {
   uint32_t a[6];
 };
 
-template <bool IQ>
-__device__ __forceinline__ void corr_sample(int I, int Q, uint32_t& phase, uint32_t& kph,
-                                            const Chan& c, uint32_t& hc, int& lb, int& pb,
-                                            int& eb, Acc& cur, Acc& first, bool& switched,
+// one real sample of the reference recurrence (correlator.c:200-283) on a
+// thread's (first, cur) epoch sums
+__device__ __forceinline__ void corr_sample(int I, uint32_t& phase, uint32_t& kph, const Chan& c,
+                                            uint32_t& hc, int& lb, int& pb, int& eb, Acc& cur,
+                                            Acc& first, bool& switched,
                                             const uint32_t* __restrict__ pk) {
   const uint32_t off = (phase >> 27) & 0x1Cu;
   const int il = __builtin_amdgcn_sbfe((int)kLutI, off, 4);
   const int ql = __builtin_amdgcn_sbfe((int)kLutQ, off, 4);
-  int ival, qval;
-  if (IQ) {
-    ival = il * I + ql * Q;   // correlator.c:215
-    qval = ql * I - il * Q;   // correlator.c:214
-  } else {
-    ival = I * il;            // correlator.c:222-223
-    qval = I * ql;
-  }
+  const int ival = I * il;    // correlator.c:222-223
+  const int qval = I * ql;
   cur.a[0] += (uint32_t)(lb * ival);
   cur.a[1] += (uint32_t)(lb * qval);
   cur.a[2] += (uint32_t)(pb * ival);
@@ -169,7 +156,7 @@ __device__ __forceinline__ void corr_sample(int I, int Q, uint32_t& phase, uint3
   }
 }
 
-// ---- IQ fast path: segment sums with v_dot4 ---------------------------------
+// ---- IQ streams (osg_stream_kernel): segment sums with v_dot4 ---------------
 // Between two code-NCO carries (one half-chip, ~8 samples) the E/P/L bits are
 // constant, so acc_X += bit_X * ival(n) over the segment equals bit_X times the
 // segment sum S = sum ival(n) (int32 wrap keeps it exact).  ival/qval of a
@@ -208,80 +195,6 @@ __device__ __forceinline__ void unpack8(uint32_t w, int& lb, int& pb, int& eb) {
   lb = __builtin_amdgcn_sbfe((int)w, 0, 2);
   pb = __builtin_amdgcn_sbfe((int)w, 2, 2);
   eb = __builtin_amdgcn_sbfe((int)w, 4, 2);
-}
-
-// the carry branch of correlator.c:243-283 (half-chip step, dump, bit reload);
-// tb: the channel's packed E/P/L row (LDS-staged, or the global table + base)
-template <typename TB>
-__device__ __forceinline__ void code_carry(const Chan& c, uint32_t& hc, int& lb, int& pb, int& eb,
-                                           Acc& cur, Acc& first, bool& switched, TB tb) {
-  hc = (hc + 1u) & 0xFFFFu;
-  const uint32_t ld = hc;
-  if (hc >= c.D) {
-#pragma unroll
-    for (int k = 0; k < 6; k++) { first.a[k] = cur.a[k]; cur.a[k] = 0; }
-    switched = true;
-    hc = 0;
-  }
-  unpack8(tb[ld], lb, pb, eb);
-}
-
-// one sample (the odd last sample of a tail run): x = {I, Q, 0, 0}
-template <typename TB>
-__device__ __forceinline__ void corr_single(uint32_t x, uint32_t& p0, uint32_t& kph, const Chan& c,
-                                            uint32_t& hc, int& lb, int& pb, int& eb, int& si,
-                                            int& sq, Acc& cur, Acc& first, bool& switched,
-                                            const uint2* __restrict__ lo2, TB tb) {
-  const uint2 lo = lo2[p0 >> 29];
-  p0 += c.cinc;
-  si = dot4(x, lo.x & 0xFFFFu, si);
-  sq = dot4(x, lo.y & 0xFFFFu, sq);
-  const uint32_t k0 = kph + c.kinc2;
-  const bool c0 = k0 < kph;
-  kph = k0;
-  if (c0) {
-    seg_flush(si, sq, lb, pb, eb, cur);
-    code_carry(c, hc, lb, pb, eb, cur, first, switched, tb);
-    si = 0;
-    sq = 0;
-  }
-}
-
-// samples n0, n0+1 (IF word x), carrier phases p0 / p0 + cinc
-template <typename TB>
-__device__ __forceinline__ void corr_pair(uint32_t x, uint32_t& p0, uint32_t& kph, const Chan& c,
-                                          uint32_t& hc, int& lb, int& pb, int& eb, int& si,
-                                          int& sq, Acc& cur, Acc& first, bool& switched,
-                                          const uint2* __restrict__ lo2, TB tb) {
-  const uint32_t p1 = p0 + c.cinc;
-  const uint2 lo = lo2[(p0 >> 29) | ((p1 >> 26) & 0x38u)];
-  p0 = p1 + c.cinc;
-  const uint32_t k0 = kph + c.kinc2;
-  const uint32_t k1 = k0 + c.kinc2;
-  const bool c0 = k0 < kph, c1 = k1 < k0;
-  kph = k1;
-  if (!(c0 | c1)) {   // no code carry in the pair (3 of 4 pairs at 8 samples/half-chip)
-    si = dot4(x, lo.x, si);
-    sq = dot4(x, lo.y, sq);
-    return;
-  }
-  if (!c0) {
-    si = dot4(x, lo.x, si);
-    sq = dot4(x, lo.y, sq);
-  } else {   // carry after the first sample of the pair
-    si = dot4(x, lo.x & 0xFFFFu, si);
-    sq = dot4(x, lo.y & 0xFFFFu, sq);
-    seg_flush(si, sq, lb, pb, eb, cur);
-    code_carry(c, hc, lb, pb, eb, cur, first, switched, tb);
-    si = dot4(x, lo.x & 0xFFFF0000u, 0);
-    sq = dot4(x, lo.y & 0xFFFF0000u, 0);
-  }
-  if (c1) {
-    seg_flush(si, sq, lb, pb, eb, cur);
-    code_carry(c, hc, lb, pb, eb, cur, first, switched, tb);
-    si = 0;
-    sq = 0;
-  }
 }
 
 // Per-channel epilogue of a call (one thread): dumps, ms/bit counters, TIC latch,
@@ -403,13 +316,11 @@ __device__ __forceinline__ void finish_call(const Chan& c, const gnsscorr_nco_cm
     }
   }
   __syncthreads();
-  TRACK_PSTAMP(4);
 
   // ---- per-channel epilogue (one thread per channel) ------------------------
   if (tid != 0 || !have) return;
   channel_epilogue(c, cmd, st, chn, active, ndump, Rtot, nsamp, tic_count,
                    [&](int i) { return (uint32_t)s_sum[i]; }, res, state, all_dumps, max_dumps);
-  TRACK_PSTAMP(5);
 }
 
 __device__ __forceinline__ int xcd_channel(int b, int G) {
@@ -417,41 +328,158 @@ __device__ __forceinline__ int xcd_channel(int b, int G) {
   return x * q + (x < r ? x : r) + slot;
 }
 
+// channel state and NCO words of one call (correlator.c:177-189)
+__device__ __forceinline__ bool chan_setup(const gnsscorr_nco_cmd& cmd, gnsscorr_chan_state& st,
+                                           Chan& c) {
+  if (cmd.epoch_load >= 0) {  // epoch set, correlator.c:177-182
+    const int v = cmd.epoch_load & 0xFFFF;
+    st.msbit_reg = v;
+    st.ms_counter = v & 0xff;
+    st.bit_counter = v >> 8;
+  }
+  const bool active = cmd.prn > 0 && cmd.prn <= 32;   // correlator.c:185
+  c.P0 = st.carrier_phase;
+  c.K0 = st.code_phase;
+  c.cinc = cmd.carrier_incr;
+  c.kinc2 = cmd.code_incr << 1;
+  c.hc0 = st.half_chip & 0xFFFFu;
+  c.D = (cmd.slew & 0xFFFFu) + 2046u;
+  const uint32_t h1 = (c.hc0 + 1u) & 0xFFFFu;
+  if (h1 >= c.D) c.j1 = 1;
+  else if (c.D <= 0xFFFFu) c.j1 = 1ull + (c.D - h1);
+  else c.j1 = kNever;  // uint16 half-chip can never reach D
+  c.base = (active ? cmd.prn : 0) * GNSSCORR_OSG_ROW;
+  return active;
+}
+
 // ============================================================================
-// osg_track2_kernel: branch-free segment sums for interleaved I,Q streams
-// (int8 or 2-bit packed).
+// osg_track_kernel: real-sample (I-only) streams, int8 or 2-bit packed (PK:
+// GNSSCORR_IF_PACKED2, if2.h).  Interleaved I,Q streams run on
+// osg_stream_kernel below.
 //
-// Why: in osg_track_kernel every lane walks its own 64-sample run and takes a
-// code-carry branch about once per 8 samples, at a different sample in every
-// lane, so a wave executes the carry path (segment flush, bit reload, epoch
-// switch) at nearly every sample pair: ~18 VALU + ~12 SALU instructions per
-// sample (PMC, round 2).  Here a lane's samples are cut into intervals of
-// three pairs (6 samples).  When a half-chip lasts at least 6 samples (kinc2 <=
-// 2^32 / 6, any fs >= 12.3 Msps) an interval holds at most one code carry, so
-// every pair is split branch-free into the part before the carry ("pre", LO
-// word masked by the carry position) and the whole pair ("tot"); at the end of
-// each interval -- the same instruction for every lane -- the pre sums are
-// flushed with the current E/P/L bits (correlator.c:213-241), the remainder
-// carries over into the next segment and the bits are reloaded once
-// (correlator.c:243-251).  The rare dump (epoch switch, correlator.c:251-281)
-// is the only branch.
+// One workgroup = cpw channels (cpw = 1024 / threads-per-channel, at most
+// kMaxCpw) x one call; thread group q = threadIdx.x / T runs channel
+// grp * cpw + q.  Every thread walks its own run of kRun samples with the
+// reference recurrence (corr_sample): 256 threads x 64 samples cover a 1-ms
+// chunk at 16.368 Msps.  Full int8 runs are read as 16-byte vector loads, tail
+// runs and packed runs element by element.
+// ============================================================================
+template <bool PK>
+__global__ __launch_bounds__(kMaxThreads, 8) void osg_track_kernel(
+    const int8_t* __restrict__ ifbuf, int64_t stream_stride, int nsamp, int n_channels, int cpw,
+    const gnsscorr_nco_cmd* __restrict__ cmds, gnsscorr_chan_state* __restrict__ state,
+    gnsscorr_track_result* __restrict__ res, int32_t* __restrict__ all_dumps, int max_dumps,
+    const uint32_t* __restrict__ pk, int64_t tic_count) {
+  // dynamic LDS: [cpw][ep_cap][6] epoch sums
+  extern __shared__ uint4 s_dyn[];
+  const int ep_cap = nsamp / GNSSCORR_OSG_ROW + 2;   // >= epochs of one call
+  const int T = (int)blockDim.x / cpw;
+  // wave-uniform (T is a multiple of 64): keeps the channel's command, state
+  // and NCO constants in scalar registers
+  const int q = __builtin_amdgcn_readfirstlane((int)threadIdx.x / T);
+  const int tid = (int)threadIdx.x - q * T;
+  int32_t* s_sum = reinterpret_cast<int32_t*>(s_dyn) + q * ep_cap * 6;
+  // XCD-aware order: workgroup b runs on XCD b % 8, so give every XCD a
+  // contiguous channel range -- the channels of one receiver (consecutive
+  // channels sharing an IF stream) then hit the same 4 MiB L2 and the stream
+  // is fetched from HBM once instead of once per XCD.
+  const int chn = xcd_channel(blockIdx.x, gridDim.x) * cpw + q;
+  const bool have = chn < n_channels;
+  gnsscorr_nco_cmd cmd = {};
+  gnsscorr_chan_state st = {};
+  if (have) {
+    cmd = cmds[chn];
+    st = state[chn];
+  }
+  Chan c;
+  const bool active = chan_setup(cmd, st, c) && have;
+  const uint64_t Rtot = ((uint64_t)c.K0 + (uint64_t)nsamp * c.kinc2) >> 32;
+  const uint32_t ndump = n_dumps_after(c, Rtot);
+  const int n_epochs = (int)ndump + 1;
+  if (active)
+    for (int i = tid; i < n_epochs * 6; i += T) s_sum[i] = 0;
+  __syncthreads();
+
+  // ---- per-thread run of kRun samples --------------------------------------
+  Acc cur, first;
+#pragma unroll
+  for (int k = 0; k < 6; k++) { cur.a[k] = 0; first.a[k] = 0; }
+  bool switched = false;
+  int e0 = 0;
+  const int n0 = tid * kRun;
+  const bool runs = active && n0 < nsamp;
+  if (runs) {
+    const uint64_t X = (uint64_t)c.K0 + (uint64_t)n0 * c.kinc2;
+    uint32_t kph = (uint32_t)X;
+    uint32_t phase = c.P0 + (uint32_t)n0 * c.cinc;
+    uint32_t hc, ld, ep;
+    hc_after(c, X >> 32, hc, ld, ep);
+    e0 = (int)ep;
+    const uint32_t w = pk[c.base + (int)ld];
+    int lb = (int)(int8_t)(w & 0xFFu);
+    int pb = (int)(int8_t)((w >> 8) & 0xFFu);
+    int eb = (int)(int8_t)((w >> 16) & 0xFFu);
+    // element offset of the run (a multiple of 64: n0 and the stream base are);
+    // src is its first byte in either format
+    const int64_t e_run = (int64_t)cmd.stream * stream_stride + n0;
+    const int8_t* src = PK ? ifbuf + (e_run >> 2) : ifbuf + e_run;
+    if (!PK && n0 + kRun <= nsamp) {
+      const int4* v = reinterpret_cast<const int4*>(src);
+#pragma unroll
+      for (int j = 0; j < kRun / 16; j++) {
+        const int4 u = v[j];
+        const int words[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+        for (int wd = 0; wd < 4; wd++)
+#pragma unroll
+          for (int b = 0; b < 4; b++)
+            corr_sample(sbyte(words[wd], b), phase, kph, c, hc, lb, pb, eb, cur, first, switched, pk);
+      }
+    } else {   // per sample (tail runs; every packed run)
+      const int L = min(kRun, nsamp - n0);
+      for (int k = 0; k < L; k++)
+        corr_sample(if_elem(src, k, PK), phase, kph, c, hc, lb, pb, eb, cur, first, switched, pk);
+    }
+  }
+  finish_call(c, cmd, st, chn, have, active, tid, runs, e0, switched, first, cur, s_sum, ndump, Rtot,
+              nsamp, tic_count, res, state, all_dumps, max_dumps);
+}
+
+// ============================================================================
+// Branch-free segment sums for interleaved I,Q streams (int8 or 2-bit packed):
+// the piece and interval form that osg_stream_kernel runs.
 //
-// Sample -> lane map: wave w of a channel covers samples [4096 w, 4096 w + 4096)
-// as two pieces of 2048; lane l takes samples [2048 p + 32 l, +32) of piece p.
-// A piece is 64 lanes x 32 samples of CONTIGUOUS IF, so each wave load reads
-// 1 KiB of consecutive bytes: int8 pieces (4 KiB) are staged through a
-// wave-private LDS slot (no workgroup barrier), packed pieces (16 B per lane)
-// are loaded straight into registers and expanded with v_perm.  No IF is
-// shared between channels, so the receiver layout (12 channels per stream)
-// and one stream per channel run the same code with the same LDS footprint.
+// Why: a lane that walks its samples one by one takes a code-carry branch
+// about once per 8 samples, at a different sample in every lane, so a wave
+// executes the carry path (segment flush, bit reload, epoch switch) at nearly
+// every sample pair: ~18 VALU + ~12 SALU instructions per sample (PMC, round
+// 2).  Here a lane's samples are cut into intervals of three pairs (6 samples;
+// four pairs where a half-chip lasts >= 8 samples, kIv4Kinc2).  When a
+// half-chip lasts at least 6 samples (kinc2 <= 2^32 / 6, any fs >= 12.3 Msps)
+// an interval holds at most one code carry, so every pair is split branch-free
+// into the part before the carry ("pre", LO word masked by the carry position)
+// and the whole pair ("tot"); at the end of each interval -- the same
+// instruction for every lane -- the pre sums are flushed with the current
+// E/P/L bits (correlator.c:213-241), the remainder carries over into the next
+// segment and the bits are reloaded once (correlator.c:243-251).  The rare dump
+// (epoch switch, correlator.c:251-281) is the only branch.
 //
-// Channels outside the fast path's conditions (kinc2 > 2^32/6, a half-chip
+// Sample -> lane map: a channel's wave walks the call in pieces of 2048
+// samples; lane l takes samples [2048 p + 32 l, +32) of piece p.  A piece is
+// 64 lanes x 32 samples of CONTIGUOUS IF, so each wave load reads 1 KiB of
+// consecutive bytes: int8 pieces (4 KiB) land by LDS-DMA in a wave-private,
+// swizzled LDS slot (slot_entry; no workgroup barrier), packed pieces (16 B per
+// lane) are loaded straight into registers and expanded through a 256-word LDS
+// table.  No IF is shared between channels in LDS, so the receiver layout (12
+// channels per stream) and one stream per channel run the same code with the
+// same LDS footprint.
+//
+// Channels outside the fast form's conditions (kinc2 > 2^32/6, a half-chip
 // range beyond the staged E/P/L row, no dump possible) run the per-sample
-// reference recurrence (corr_sample) on the same staged words, wave-uniformly.
+// reference recurrence (corr_sample_s) on the same words, wave-uniformly.
 // ============================================================================
 constexpr int kPieceLen = 32;                    // samples per lane per piece
 constexpr int kPieceSpan = 64 * kPieceLen;       // samples per wave per piece
-constexpr int kWaveSpan = 2 * kPieceSpan;        // samples per wave
 constexpr int kStage2Bytes = kPieceSpan * 2;     // int8 IQ bytes of one staged piece (4 KiB)
 constexpr uint32_t kFastKinc2 = 0xFFFFFFFFu / 6u;   // >= 6 samples per half-chip
 
@@ -479,42 +507,18 @@ __device__ __forceinline__ void hc_after_fast(const Chan& c, uint64_t r, float i
 // Lane state through its pieces.
 struct Seg {
   uint32_t p0, kph, hc, ld;
-  uint32_t cb, nb;             // TRACK_PF: row byte of the current bits / of index hc + 1
+  uint32_t cb, nb;             // kPF: row byte of the current bits / of index hc + 1
   int lb, pb, eb;
   int ti, tq, pi, pq;          // interval sums: whole pairs / part before the carry
   bool carried;               // a code carry in the current interval
 };
 
 // one pair of samples (IF word x) in the branch-free interval form; ONE: the
-// word holds a single (last) sample, so no carry after a second one
-template <bool ONE>
-__device__ __forceinline__ void pair2(uint32_t x, const Chan& c, Seg& g, const uint2* __restrict__ lo2) {
-  const uint32_t p1 = g.p0 + c.cinc;
-  const uint2 lo = lo2[(g.p0 >> 29) | ((p1 >> 26) & 0x38u)];
-  g.p0 = p1 + c.cinc;
-  const uint32_t k0 = g.kph + c.kinc2;
-  const bool c0 = k0 < g.kph;
-  uint32_t k1 = k0;
-  bool c1 = false;
-  if (!ONE) {
-    k1 = k0 + c.kinc2;
-    c1 = k1 < k0;
-  }
-  g.kph = k1;
-  uint32_t m = c0 ? 0xFFFFu : 0xFFFFFFFFu;   // carry after sample a: only a is "pre"
-  m = g.carried ? 0u : m;                    // after this interval's carry: nothing is
-  g.carried = g.carried | c0 | c1;
-  const uint32_t xm = x & m;
-  g.ti = dot4(x, lo.x, g.ti);
-  g.tq = dot4(x, lo.y, g.tq);
-  g.pi = dot4(xm, lo.x, g.pi);
-  g.pq = dot4(xm, lo.y, g.pq);
-}
-
-// pair2 with the LO word pairs as two 256-byte tables (ival words, qval words):
-// a ds_read_b32 of 64 lanes then touches each bank at most once per distinct
-// entry (64 entries x 4 B = the 64 banks), where the 512-byte uint2 table put
-// entries e and e + 32 on the same banks
+// word holds a single (last) sample, so no carry after a second one.  The LO
+// word pairs are two 256-byte tables (ival words, qval words): a ds_read_b32 of
+// 64 lanes then touches each bank at most once per distinct entry (64 entries
+// x 4 B = the 64 banks), where one 512-byte uint2 table would put entries e and
+// e + 32 on the same banks
 template <bool ONE>
 __device__ __forceinline__ void pair2s(uint32_t x, const Chan& c, Seg& g,
                                        const uint32_t* __restrict__ lox,
@@ -542,530 +546,6 @@ __device__ __forceinline__ void pair2s(uint32_t x, const Chan& c, Seg& g,
   g.pq = dot4(xm, lo_y, g.pq);
 }
 
-// end of an interval: flush the part before the carry with the current bits,
-// carry the rest into the next segment, step the half-chip (correlator.c:243-283)
-__device__ __forceinline__ void interval_end(const Chan& c, Seg& g, Acc& cur, Acc& first,
-                                             bool& switched, const uint8_t* __restrict__ row) {
-  seg_flush(g.pi, g.pq, g.lb, g.pb, g.eb, cur);
-  const int ri = g.ti - g.pi, rq = g.tq - g.pq;
-  g.ti = g.pi = ri;
-  g.tq = g.pq = rq;
-  const bool cy = g.carried;               // branch-free: one carry at most
-  g.hc += cy ? 1u : 0u;
-  g.ld = cy ? g.hc : g.ld;
-  g.carried = false;
-  // (a half-chip count already >= D -- slew lowered between calls -- dumps at
-  // the next carry, not before: the reference tests only after a step)
-  if (cy && g.hc >= c.D) {   // dump (correlator.c:251-281): rare, one lane per channel
-    // snapshot of the epoch's sums; cur keeps running over both epochs and the
-    // lane's share of the next epoch is cur - first (osg_track2_kernel's end)
-#pragma unroll
-    for (int k = 0; k < 6; k++) first.a[k] = cur.a[k];
-    switched = true;
-    g.hc = 0;          // the bits of half-chip 0 come from the pre-reset index ld
-  }
-  unpack8(row[g.ld], g.lb, g.pb, g.eb);
-}
-
-// The per-wave piece path (see the osg_track2 notes above): every lane's two
-// 32-sample pieces in the branch-free interval form (fast) or by the per-sample
-// recurrence; sums as (old epoch, new epoch) in (first, cur) when switched.
-// s_wave: this wave's 4 KiB LDS slot (int8 streams).
-template <bool PK>
-__device__ __forceinline__ void run_pieces(const int8_t* __restrict__ ifbuf, int64_t stream_stride,
-                                           int nsamp, int tid, const Chan& c, int stream,
-                                           bool active, bool fast, const uint8_t* s_pk8,
-                                           const uint2* s_lo, uint4* s_wave,
-                                           const uint32_t* __restrict__ pk, Acc& cur, Acc& first,
-                                           bool& switched, int& e0, bool& runs) {
-  const float invD = 1.0f / (float)c.D;
-  const int lane = (int)threadIdx.x & 63;
-  const int wbase = (tid >> 6) * kWaveSpan;               // first sample of this wave
-  runs = active && wbase + lane * kPieceLen < nsamp;
-  // element offset of the channel's stream
-  const int64_t e_stream = (int64_t)stream * stream_stride * 2;
-  Seg g;
-
-#pragma unroll
-  for (int p = 0; p < 2; p++) {
-    const int n_piece = wbase + p * kPieceSpan;            // first sample of the wave's piece
-    if (!active || n_piece >= nsamp) break;                // wave-uniform
-    const int n0 = n_piece + lane * kPieceLen;             // this lane's first sample
-    const int L = max(0, min(kPieceLen, nsamp - n0));      // this lane's valid samples
-    // ---- IF of the lane's piece: 16 sample-pair words in 4 chunks of 4
-    uint32_t pw[4] = {0u, 0u, 0u, 0u};   // packed: one 32-bit word (4 pairs) per chunk
-    if constexpr (PK) {
-      // 16 B per lane (8-byte aligned streams): two 8-byte loads of whole bytes
-      const uint8_t* b = reinterpret_cast<const uint8_t*>(ifbuf) + ((e_stream + 2 * (int64_t)n0) >> 2);
-      if (L == kPieceLen) {
-        const uint2 u0 = reinterpret_cast<const uint2*>(b)[0];
-        const uint2 u1 = reinterpret_cast<const uint2*>(b)[1];
-        pw[0] = u0.x; pw[1] = u0.y; pw[2] = u1.x; pw[3] = u1.y;
-      } else {
-        for (int k = 0; 2 * k < L; k++) pw[k >> 2] |= (uint32_t)b[k] << (8 * (k & 3));
-      }
-    } else {
-      // int8: the wave's 4 KiB piece through its LDS slot.  Chunk i (16 B) of the
-      // piece belongs to lane i >> 2; it is stored at lane * 64 + 16 * ((i ^ (lane >> 2)) & 3)
-      // so that the 16-byte reads of 16 consecutive lanes hit 64 distinct banks.
-      const int8_t* g8 = ifbuf + e_stream + 2 * (int64_t)n_piece;
-      const int valid = max(0, min(kPieceSpan, nsamp - n_piece));   // samples of the piece in the call
-      const int full_chunks = valid / 8;
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int i = r * 64 + lane;
-        const int ow = i >> 2, sub = i & 3;
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (i < full_chunks) {
-          v = reinterpret_cast<const uint4*>(g8)[i];
-        } else if (i * 8 < valid) {   // the partial chunk: whole words, then the odd sample
-          const int rem = valid - i * 8;   // 1..7 samples
-          const uint32_t* g32 = reinterpret_cast<const uint32_t*>(g8) + 4 * i;
-          uint32_t t[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-          for (int k = 0; k < 3; k++)
-            if (k < rem / 2) t[k] = g32[k];
-          const uint32_t odd = (rem & 1) ? (uint32_t)reinterpret_cast<const uint16_t*>(g32)[rem - 1] : 0u;
-#pragma unroll
-          for (int k = 0; k < 4; k++)
-            if (k == rem / 2) t[k] = odd;
-          v = make_uint4(t[0], t[1], t[2], t[3]);
-        }
-        s_wave[ow * 4 + ((sub ^ (ow >> 2)) & 3)] = v;
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-    // chunk j of the lane's piece as four pair words
-    auto chunk = [&](int j) -> uint4 {
-      if constexpr (PK) return if2_expand_word(pw[j]);
-      else return s_wave[lane * 4 + ((j ^ (lane >> 2)) & 3)];
-    };
-    if (L > 0) {
-      // ---- lane state at its first sample
-      const uint64_t X = (uint64_t)c.K0 + (uint64_t)n0 * c.kinc2;
-      const uint64_t r0 = X >> 32;
-      g.kph = (uint32_t)X;
-      if (fast) {
-        // closed form at the piece start; a dump between the lane's two pieces
-        // shows as a later epoch (at most one dump per lane: D >= 2046 half-chips)
-        uint32_t ep;
-        hc_after_fast(c, r0, invD, g.hc, g.ld, ep);
-        if (p == 0) {
-          e0 = (int)ep;
-        } else if ((int)ep > e0 + (switched ? 1 : 0)) {
-#pragma unroll
-          for (int k = 0; k < 6; k++) first.a[k] = cur.a[k];   // snapshot (see interval_end)
-          switched = true;
-        }
-        unpack8(s_pk8[g.ld], g.lb, g.pb, g.eb);
-        g.ti = g.tq = g.pi = g.pq = 0;
-        g.carried = false;
-        // one code path per wave: a wave with one partial lane (the call's last
-        // samples) runs the guarded loop for all its lanes instead of both loops
-        if (__all(L == kPieceLen)) {   // every wave but the last of a channel
-#pragma unroll
-          for (int j = 0; j < 4; j++) {
-            const uint4 u = chunk(j);
-            const uint32_t words[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-              const int k = 4 * j + i;
-              pair2<false>(words[i], c, g, s_lo);
-              if (k % 3 == 2 || k == kPieceLen / 2 - 1) interval_end(c, g, cur, first, switched, s_pk8);
-            }
-          }
-        } else {
-          const int np = L >> 1;
-#pragma unroll
-          for (int j = 0; j < 4; j++) {
-            const uint4 u = chunk(j);
-            const uint32_t words[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-              const int k = 4 * j + i;
-              if (k < np) pair2<false>(words[i], c, g, s_lo);
-              else if (k == np && (L & 1)) pair2<true>(words[i] & 0xFFFFu, c, g, s_lo);
-              if (k % 3 == 2 || k == kPieceLen / 2 - 1) interval_end(c, g, cur, first, switched, s_pk8);
-            }
-          }
-        }
-        // the samples after the piece's last carry: the open segment, with the
-        // bits in force after it
-        seg_flush(g.ti, g.tq, g.lb, g.pb, g.eb, cur);
-      } else {
-        // per-sample reference recurrence (correlator.c:200-283), table from global memory
-        uint32_t hc, ld, ep;
-        hc_after(c, r0, hc, ld, ep);
-        if (p == 0) {
-          e0 = (int)ep;
-        } else if ((int)ep > e0 + (switched ? 1 : 0)) {
-#pragma unroll
-          for (int k = 0; k < 6; k++) first.a[k] = cur.a[k];   // snapshot
-          switched = true;
-        }
-        const uint32_t tw = pk[c.base + (int)ld];
-        int lb = (int)(int8_t)(tw & 0xFFu), pb = (int)(int8_t)((tw >> 8) & 0xFFu),
-            eb = (int)(int8_t)((tw >> 16) & 0xFFu);
-        // corr_sample keeps (first, cur) as (old epoch, new epoch); the kernel
-        // keeps (snapshot, running total): convert around the call
-        if (switched)
-#pragma unroll
-          for (int k = 0; k < 6; k++) cur.a[k] -= first.a[k];
-        uint32_t phase = g.p0, kph = g.kph;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          const uint4 u = chunk(j);
-          const uint32_t words[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-          for (int i = 0; i < 4; i++) {
-            const int k = 4 * j + i;
-#pragma unroll
-            for (int h = 0; h < 2; h++)
-              if (2 * k + h < L)
-                corr_sample<true>(sbyte((int)words[i], 2 * h), sbyte((int)words[i], 2 * h + 1), phase,
-                                  kph, c, hc, lb, pb, eb, cur, first, switched, pk);
-          }
-        }
-        if (switched)
-#pragma unroll
-          for (int k = 0; k < 6; k++) cur.a[k] += first.a[k];
-      }
-    }
-    if constexpr (!PK) __builtin_amdgcn_wave_barrier();   // the slot is refilled by the next piece
-  }
-  if (switched)   // (snapshot, running total) -> (old epoch, new epoch) for finish_call
-#pragma unroll
-    for (int k = 0; k < 6; k++) cur.a[k] -= first.a[k];
-}
-
-
-// One workgroup = cpw channels (cpw = 1024 / threads-per-channel, at most
-// kMaxCpw) x one call; thread group q = threadIdx.x / T runs channel
-// grp*cpw + q.  When every active channel of the workgroup reads the same IF
-// stream (the channels of one receiver), the stream's 64-sample runs are
-// staged once in LDS with coalesced 16-byte loads and shared by the cpw
-// channels: each lane's run would otherwise be 8 loads that put every lane on
-// its own cache line (8x the L2 -> CU bytes, once per channel).
-// PK: the IF streams are GNSSCORR_IF_PACKED2 (if2.h): staged runs are expanded
-// to int8 in LDS; unstaged runs expand per 16-element word in registers.
-template <bool IQ, bool PK>
-__global__ __launch_bounds__(kMaxThreads, 8) void osg_track_kernel(
-    const int8_t* __restrict__ ifbuf, int64_t stream_stride, int nsamp, int n_channels, int cpw,
-    const gnsscorr_nco_cmd* __restrict__ cmds, gnsscorr_chan_state* __restrict__ state,
-    gnsscorr_track_result* __restrict__ res, int32_t* __restrict__ all_dumps, int max_dumps,
-    const uint32_t* __restrict__ pk, const uint8_t* __restrict__ pk8, int64_t tic_count,
-    int stage_ok) {
-  __shared__ uint2 s_lo[64];
-  __shared__ int s_stream[kMaxCpw];
-  __shared__ int s_short[kMaxCpw];
-  // dynamic LDS: [cpw][ep_cap][6] epoch sums | [cpw][kPk8Stage] E/P/L row bytes |
-  // staged IF runs (lane runs of 128 B at a 144 B pitch)
-  extern __shared__ uint4 s_dyn[];
-  const int ep_cap = nsamp / GNSSCORR_OSG_ROW + 2;   // >= epochs of one call
-  const int sum_words = ((cpw * ep_cap * 6) + 3) & ~3;
-  const int T = (int)blockDim.x / cpw;
-  // wave-uniform (T is a multiple of 64): keeps the channel's command, state
-  // and NCO constants in scalar registers
-  const int q = __builtin_amdgcn_readfirstlane((int)threadIdx.x / T);
-  const int tid = (int)threadIdx.x - q * T;
-  int32_t* s_sum = reinterpret_cast<int32_t*>(s_dyn) + q * ep_cap * 6;
-  uint8_t* s_pk8 = reinterpret_cast<uint8_t*>(s_dyn) + sum_words * 4 + q * kPk8Stage;
-  uint4* s_if = s_dyn + sum_words / 4 + cpw * (kPk8Stage / 16);
-  // XCD-aware order: workgroup b runs on XCD b % 8, so give every XCD a
-  // contiguous channel range -- the channels of one receiver (consecutive
-  // channels sharing an IF stream) then hit the same 4 MiB L2 and the stream
-  // is fetched from HBM once instead of once per XCD.
-  TRACK_PSTAMP(0);
-  const int chn = xcd_channel(blockIdx.x, gridDim.x) * cpw + q;
-  const bool have = chn < n_channels;
-  gnsscorr_nco_cmd cmd = {};
-  gnsscorr_chan_state st = {};
-  if (have) {
-    cmd = cmds[chn];
-    st = state[chn];
-  }
-  if (cmd.epoch_load >= 0) {  // epoch set, correlator.c:177-182
-    const int v = cmd.epoch_load & 0xFFFF;
-    st.msbit_reg = v;
-    st.ms_counter = v & 0xff;
-    st.bit_counter = v >> 8;
-  }
-  const bool active = have && cmd.prn > 0 && cmd.prn <= 32;   // correlator.c:185
-  if (tid == 0) s_stream[q] = active ? cmd.stream : -1;
-
-  Chan c;
-  c.P0 = st.carrier_phase;
-  c.K0 = st.code_phase;
-  c.cinc = cmd.carrier_incr;
-  c.kinc2 = cmd.code_incr << 1;
-  c.hc0 = st.half_chip & 0xFFFFu;
-  c.D = (cmd.slew & 0xFFFFu) + 2046u;
-  {
-    const uint32_t h1 = (c.hc0 + 1u) & 0xFFFFu;
-    if (h1 >= c.D) c.j1 = 1;
-    else if (c.D <= 0xFFFFu) c.j1 = 1ull + (c.D - h1);
-    else c.j1 = kNever;  // uint16 half-chip can never reach D
-  }
-  c.base = (active ? cmd.prn : 0) * GNSSCORR_OSG_ROW;
-  // A lane of the piece path covers kPieceSpan + kPieceLen samples (two pieces)
-  // and holds at most one dump.  Two consecutive dumps are D code carries
-  // apart, at least D * 2^32 / kinc2 - 1 samples: a channel whose epoch can be
-  // that short (about 2.05-2.08 Msps, one half-chip per sample) sends its
-  // workgroup to the per-thread 64-sample runs, which hold one dump at most.
-  if (tid == 0)
-    s_short[q] = active && ((uint64_t)c.D << 32) <= (uint64_t)(kPieceSpan + kPieceLen + 1) * c.kinc2;
-  TRACK_PSTAMP(1);
-  const uint64_t Rtot = ((uint64_t)c.K0 + (uint64_t)nsamp * c.kinc2) >> 32;
-  const uint32_t ndump = n_dumps_after(c, Rtot);
-  const int n_epochs = (int)ndump + 1;
-
-  if (active)
-    for (int i = tid; i < n_epochs * 6; i += T) s_sum[i] = 0;
-  if (IQ && threadIdx.x < 64) {   // LO words of the sample pair (a, b) = (t & 7, t >> 3)
-    const int a = threadIdx.x & 7, b = threadIdx.x >> 3;
-    const uint32_t ia = (uint32_t)__builtin_amdgcn_sbfe((int)kLutI, 4 * a, 4) & 0xFFu;
-    const uint32_t qa = (uint32_t)__builtin_amdgcn_sbfe((int)kLutQ, 4 * a, 4) & 0xFFu;
-    const uint32_t ib = (uint32_t)__builtin_amdgcn_sbfe((int)kLutI, 4 * b, 4) & 0xFFu;
-    const uint32_t qb = (uint32_t)__builtin_amdgcn_sbfe((int)kLutQ, 4 * b, 4) & 0xFFu;
-    s_lo[threadIdx.x] = make_uint2(ia | qa << 8 | ib << 16 | qb << 24,
-                                   qa | ((0u - ia) & 0xFFu) << 8 | qb << 16 | ((0u - ib) & 0xFFu) << 24);
-  }
-  // The half-chip table indices of this call lie in [0, max(D, hc0, hc0+1)]
-  // (correlator.c:243-251; the dump reloads from the pre-reset index D):
-  // stage that part of the channel's row in LDS so the reload at every code
-  // carry is an LDS read, not a dependent global-memory round trip.
-  const uint32_t pk_hi = max(max(c.D, c.hc0), (c.hc0 + 1u) & 0xFFFFu);
-  const bool pk_lds = IQ && active && c.j1 != kNever && pk_hi < 3072u;
-  if (pk_lds) {
-    // whole dwords of the row (the packed table is padded by 64 bytes): byte i of
-    // the staged row is s_pk8[i] with s_pk8 offset by the row's misalignment
-    const uint32_t* g32 = reinterpret_cast<const uint32_t*>(pk8) + (c.base >> 2);
-    uint32_t* l32 = reinterpret_cast<uint32_t*>(s_pk8);
-    const int n32 = (int)((pk_hi + (uint32_t)(c.base & 3)) >> 2) + 1;
-    for (int i = tid; i < n32; i += T) l32[i] = g32[i];
-  }
-  s_pk8 += c.base & 3;
-  __syncthreads();
-  int sst = -1;
-  bool uni = true, any_short = false;
-  for (int k = 0; k < cpw; k++) {
-    const int v = s_stream[k];
-    any_short |= s_short[k] != 0;
-    if (v >= 0) {
-      if (sst < 0) sst = v;
-      else if (v != sst) uni = false;
-    }
-  }
-  // stage_ok: 0 no staging (lanes read their runs from global memory); 1 a
-  // stream shared by the whole workgroup is staged once in LDS and read by its
-  // cpw channels; channels of a workgroup on different streams (one stream
-  // per channel, receivers split over workgroups) take the per-wave piece
-  // path (run_pieces: coalesced 1 KiB wave loads, no workgroup barrier)
-  // (stage_ok 4: A/B, the piece path for every workgroup)
-  const bool shared_stage = IQ && stage_ok && stage_ok != 4 && uni && sst >= 0;
-  const bool pieces = IQ && (stage_ok == 1 || stage_ok == 4) && !shared_stage && !any_short;
-  const bool stage = shared_stage;
-  uint4* s_ifq = s_if;
-  if (stage) {
-    const int n_full = nsamp / kRun;
-    const int st_id = sst;
-    const int lt = (int)threadIdx.x;       // staging lane and width
-    const int nt = (int)blockDim.x;
-    uint32_t* t32 = reinterpret_cast<uint32_t*>(s_ifq + n_full * kPitch);
-    if constexpr (!PK) {
-      // full 64-sample runs only; consecutive threads load consecutive 16-byte chunks
-      const int4* g = reinterpret_cast<const int4*>(ifbuf + (int64_t)st_id * stream_stride * 2);
-      const int n_chunks = n_full * (kRun * 2 / 16);
-      for (int ch = lt; ch < n_chunks; ch += nt) {
-        const int4 v = g[ch];
-        s_ifq[(ch >> 3) * kPitch + (ch & 7)] = make_uint4(v.x, v.y, v.z, v.w);
-      }
-      // the whole sample pairs of the tail run go to the next slot (an odd last
-      // sample is read from global memory by its lane)
-      const uint32_t* g32 = reinterpret_cast<const uint32_t*>(g) + n_full * (kRun / 2);
-      for (int wi = lt; wi < (nsamp - n_full * kRun) / 2; wi += nt) t32[wi] = g32[wi];
-    } else {
-      // packed: one byte per sample pair; an 8-byte chunk (packed data is
-      // only 8-byte aligned: 1 ms at 16.368 Msps is 8184 bytes) is a quarter
-      // run and expands to two 16-byte int8 chunks (once per workgroup,
-      // shared by its cpw channels)
-      const uint8_t* gb = reinterpret_cast<const uint8_t*>(ifbuf) + (int64_t)st_id * stream_stride / 2;
-      const uint2* g = reinterpret_cast<const uint2*>(gb);
-      const int n_chunks = n_full * 4;
-      for (int ch = lt; ch < n_chunks; ch += nt) {
-        const uint2 v = g[ch];
-        uint4* d = &s_ifq[(ch >> 2) * kPitch + (ch & 3) * 2];
-        d[0] = if2_expand_word(v.x);
-        d[1] = if2_expand_word(v.y);
-      }
-      for (int wi = lt; wi < (nsamp - n_full * kRun) / 2; wi += nt)
-        t32[wi] = if2_expand_byte(gb[n_full * (kRun / 2) + wi]);
-    }
-    __syncthreads();
-  }
-  TRACK_PSTAMP(2);
-
-  Acc cur, first;
-#pragma unroll
-  for (int k = 0; k < 6; k++) { cur.a[k] = 0; first.a[k] = 0; }
-  bool switched = false;
-  int e0 = 0;
-  bool runs = false;
-  if (pieces) {
-    // the fast (branch-free) form needs the row in LDS and >= 6 samples per half-chip
-    const bool fast = pk_lds && c.kinc2 <= kFastKinc2;
-    const int wave = (int)threadIdx.x >> 6;
-    run_pieces<PK>(ifbuf, stream_stride, nsamp, tid, c, cmd.stream, active, fast, s_pk8, s_lo,
-                   s_if + wave * (kStage2Bytes / 16), pk, cur, first, switched, e0, runs);
-  } else {
-  // ---- per-thread run of kRun samples --------------------------------------
-  const int n0 = tid * kRun;
-  runs = active && n0 < nsamp;
-  if (runs) {
-    const uint64_t X = (uint64_t)c.K0 + (uint64_t)n0 * c.kinc2;
-    uint32_t kph = (uint32_t)X;
-    uint32_t phase = c.P0 + (uint32_t)n0 * c.cinc;
-    uint32_t hc, ld, ep;
-    hc_after(c, X >> 32, hc, ld, ep);
-    e0 = (int)ep;
-    int lb, pb, eb;
-    if (pk_lds) {
-      unpack8(s_pk8[ld], lb, pb, eb);
-    } else {
-      const uint32_t w = pk[c.base + (int)ld];
-      lb = (int)(int8_t)(w & 0xFFu);
-      pb = (int)(int8_t)((w >> 8) & 0xFFu);
-      eb = (int)(int8_t)((w >> 16) & 0xFFu);
-    }
-    constexpr int kBps = IQ ? 2 : 1;
-    // element offset of the run (a multiple of 64: n0 and the stream base are);
-    // src is its first byte in either format
-    const int64_t e_run = ((int64_t)cmd.stream * stream_stride + n0) * kBps;
-    const int8_t* src = PK ? ifbuf + (e_run >> 2) : ifbuf + e_run;
-    const uint8_t* srcb = reinterpret_cast<const uint8_t*>(src);
-    // {I, Q} word of sample k of the run (odd last sample of a tail run)
-    auto single_word = [&](int k) -> uint32_t {
-      if constexpr (PK)
-        return (if2_expand_byte(srcb[k >> 1]) >> (16 * (k & 1))) & 0xFFFFu;
-      else
-        return (uint32_t)srcb[2 * k] | (uint32_t)srcb[2 * k + 1] << 8;
-    };
-    if (IQ && pk_lds) {   // (a channel whose half-chip range exceeds the staged row takes
-                          //  the per-sample path below, reading the table from global memory)
-      constexpr int kVec = kRun * 2 / 16;
-      const int L = min(kRun, nsamp - n0);
-      auto body = [&](auto tb) {
-        int si = 0, sq = 0;
-        const int np = L >> 1;
-        // one 16-byte int8 chunk = 4 sample pairs (chunk j of the run)
-        auto chunk = [&](const uint4 u, int j) {
-          const uint32_t words[4] = {u.x, u.y, u.z, u.w};
-          if (4 * j + 4 <= np) {
-#pragma unroll
-            for (int wd = 0; wd < 4; wd++)
-              corr_pair(words[wd], phase, kph, c, hc, lb, pb, eb, si, sq, cur, first, switched,
-                        s_lo, tb);
-          } else {
-            for (int wd = 0; wd < 4; wd++)
-              if (4 * j + wd < np)
-                corr_pair(words[wd], phase, kph, c, hc, lb, pb, eb, si, sq, cur, first, switched,
-                          s_lo, tb);
-          }
-        };
-        if (stage || (!PK && L == kRun)) {
-          // one 16-byte chunk (4 pairs) per iteration with the next one in
-          // flight: a rolled loop keeps the register footprint small enough
-          // for two 1024-thread workgroups per CU.  The tail run (staged in
-          // LDS) goes through the same loop with its missing pairs masked, so
-          // it does not serialise behind the full runs of its wave.
-          {
-          // one loop per source, typed by address space: a pointer selected
-          // between the LDS stage and global memory is a generic pointer, and
-          // its loads became flat loads, which count in both vmcnt and lgkmcnt -- every wait for a
-          // LO-word or E/P/L-row read then also waited for the prefetch
-          typedef unsigned int V4U __attribute__((ext_vector_type(4)));
-          auto run_loop = [&](auto run) {
-            V4U nx = run[0];
-#pragma unroll 1
-            for (int j = 0; j < kVec; j++) {
-              const uint4 u = make_uint4(nx.x, nx.y, nx.z, nx.w);
-              if (j + 1 < kVec) nx = run[j + 1];
-              chunk(u, j);
-            }
-          };
-          typedef const __attribute__((address_space(3))) V4U* LdsU4;
-          typedef const __attribute__((address_space(1))) V4U* GlbU4;
-          if (stage)
-            run_loop((LdsU4)(&s_ifq[tid * kPitch]));
-          else
-            run_loop((GlbU4)(src));
-          }
-        } else if (PK && L == kRun) {
-          // packed, unstaged (channels of a workgroup on different streams):
-          // the run is 32 bytes (8-byte aligned), each 4-byte word expands
-          // to one int8 chunk
-          const uint2* prun = reinterpret_cast<const uint2*>(src);
-          uint2 nx = prun[0];
-#pragma unroll 1
-          for (int h = 0; h < 4; h++) {
-            const uint2 p = nx;
-            if (h + 1 < 4) nx = prun[h + 1];
-            chunk(if2_expand_word(p.x), 2 * h);
-            chunk(if2_expand_word(p.y), 2 * h + 1);
-          }
-        } else {   // tail run without staging (one lane): same arithmetic, word loads
-          const uint32_t* w32 = reinterpret_cast<const uint32_t*>(src);
-          for (int k = 0; k < np; k++)
-            corr_pair(PK ? if2_expand_byte(srcb[k]) : w32[k], phase, kph, c, hc, lb, pb, eb, si,
-                      sq, cur, first, switched, s_lo, tb);
-        }
-        if (L & 1)
-          corr_single(single_word(L - 1), phase, kph, c, hc, lb, pb, eb, si, sq, cur, first,
-                      switched, s_lo, tb);
-        seg_flush(si, sq, lb, pb, eb, cur);
-      };
-      body(s_pk8);
-    } else if (!PK && n0 + kRun <= nsamp) {
-      const int4* v = reinterpret_cast<const int4*>(src);
-      constexpr int kVec = kRun * kBps / 16;
-#pragma unroll
-      for (int j = 0; j < kVec; j++) {
-        const int4 q = v[j];
-        const int words[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int wd = 0; wd < 4; wd++) {
-          const int x = words[wd];
-          if (IQ) {
-            corr_sample<IQ>(sbyte(x, 0), sbyte(x, 1), phase, kph, c, hc, lb, pb, eb, cur, first,
-                            switched, pk);
-            corr_sample<IQ>(sbyte(x, 2), sbyte(x, 3), phase, kph, c, hc, lb, pb, eb, cur, first,
-                            switched, pk);
-          } else {
-#pragma unroll
-            for (int b = 0; b < 4; b++)
-              corr_sample<IQ>(sbyte(x, b), 0, phase, kph, c, hc, lb, pb, eb, cur, first,
-                              switched, pk);
-          }
-        }
-      }
-    } else {   // per sample (tail runs; every packed run off the fast path)
-      const int L = min(kRun, nsamp - n0);
-      for (int k = 0; k < L; k++) {
-        const int I = if_elem(src, (int64_t)k * kBps, PK);
-        const int Q = IQ ? if_elem(src, (int64_t)k * kBps + 1, PK) : 0;
-        corr_sample<IQ>(I, Q, phase, kph, c, hc, lb, pb, eb, cur, first, switched, pk);
-      }
-    }
-  }
-
-  }   // per-thread runs
-  TRACK_PSTAMP(3);
-  finish_call(c, cmd, st, chn, have, active, tid, runs, e0, switched, first, cur, s_sum, ndump, Rtot,
-              nsamp, tic_count, res, state, all_dumps, max_dumps);
-}
-
-
-
 // ============================================================================
 // osg_stream_kernel: ONE WAVEFRONT PER CHANNEL AND CALL (interleaved I,Q
 // streams, int8 or 2-bit packed; round 4).
@@ -1078,8 +558,8 @@ __global__ __launch_bounds__(kMaxThreads, 8) void osg_track_kernel(
 //     landed the lanes copy their 64 bytes to registers and the DMA of the
 //     next piece is issued into the same slot;
 //   * packed: the lane's 16 bytes straight into registers, one piece ahead.
-// Each piece runs the branch-free interval form of run_pieces (pair2 /
-// interval_end: at most one code carry per 6 samples) when a half-chip lasts
+// Each piece runs the branch-free interval form above (pair2s / pair2r,
+// interval_end_s: at most one code carry per 6 samples) when a half-chip lasts
 // >= 6 samples and the channel's E/P/L row fits the LDS stage, else the
 // per-sample reference recurrence.  A lane carries ONE set of six running sums
 // (its current epoch) across all its pieces; at an epoch change -- a dump
@@ -1089,34 +569,17 @@ __global__ __launch_bounds__(kMaxThreads, 8) void osg_track_kernel(
 // reduction and no workgroup barrier: the epoch sums are complete when the
 // wave is, and lane 0 runs the channel's epilogue (correlator.c:243-316).
 //
-// Against the per-call workgroup kernel (4 waves of 64-sample lanes per
-// channel): the per-wave fixed work (reduction, epilogue, state setup) is
+// Against a per-call workgroup of 64-sample lanes (4 waves per channel,
+// osg_track_kernel's shape, which served these streams until round 4): the
+// per-wave fixed work (reduction, epilogue, state setup) is
 // paid once per channel-call instead of four times, the IF of the next piece
 // streams in while the current one computes, and a lane holds at most one
 // dump per piece (32 samples << D >= 2046 half-chips) at every sample rate.
 // Channels sharing a stream (receivers) read it through L2, which the
 // XCD-aware channel order keeps on one XCD.
 // ============================================================================
-#ifndef TRACK_STREAM_CH
-#define TRACK_STREAM_CH 4
-#endif
-constexpr int kStreamCh = TRACK_STREAM_CH;   // channels (wavefronts) per workgroup
-#ifndef TRACK_PF
-#define TRACK_PF 1                // LO words and row bytes read ahead (pair2r, interval_end_s)
-#endif
-#ifndef TRACK_NODUMP_COPY
-#define TRACK_NODUMP_COPY 1       // pieces without a dump run a copy without the dump test
-#endif
-#ifndef TRACK_IV4
-#define TRACK_IV4 1               // 4-pair intervals when a half-chip lasts >= 8 samples
-#endif
-#ifndef TRACK_ALIGNED
-#define TRACK_ALIGNED 1           // pieces whose code carries repeat every 8 samples: fixed masks
-#endif
-#ifndef TRACK_X2LUT
-#define TRACK_X2LUT 1             // packed bytes expanded through a 256-word LDS table
-#endif
-constexpr uint32_t kIv4Kinc2 = 0x20000000u;   // 8 kinc2 <= 2^32
+constexpr int kStreamCh = 4;   // channels (wavefronts) per workgroup (1 / 2 / 4 / 8 measured alike)
+constexpr uint32_t kIv4Kinc2 = 0x20000000u;   // 8 kinc2 <= 2^32: 4-pair intervals
 
 // The int8 piece slot (4 KiB: 256 chunks of 16 B = 8 IQ samples; lane l's 32
 // samples are chunks 4 l .. 4 l + 3) is swizzled: chunk g sits at entry
@@ -1213,9 +676,10 @@ struct StreamArgs {
   gnsscorr_osg_loop* hist;     // call k: hist + k*n_channels (optional)
 };
 
-// interval end (see interval_end): flush the part before the carry, carry the
-// rest, step the half-chip; a dump adds the epoch's sums to the LDS and
-// starts the next epoch
+// end of an interval: flush the part before the carry with the current bits,
+// carry the rest into the next segment, step the half-chip (correlator.c:243-283);
+// a dump adds the epoch's sums to the LDS and starts the next epoch.  PF: the
+// row bytes are read one interval ahead
 template <bool PF, bool DUMPS = true>
 __device__ __forceinline__ void interval_end_s(const Chan& c, Seg& g, Acc& acc, int& e,
                                                int32_t* s_sum, const uint8_t* __restrict__ row) {
@@ -1250,7 +714,7 @@ __device__ __forceinline__ void interval_end_s(const Chan& c, Seg& g, Acc& acc, 
   }
 }
 
-// pair2s with the pair's LO words already in registers (TRACK_PF: a piece's 16
+// pair2s with the pair's LO words already in registers (kPF: a piece's 16
 // LO word pairs are read from LDS before its first interval)
 template <bool ONE>
 __device__ __forceinline__ void pair2r(uint32_t x, uint32_t lo_x, uint32_t lo_y, const Chan& c,
@@ -1315,44 +779,17 @@ __device__ __forceinline__ void corr_sample_s(int I, int Q, uint32_t& phase, uin
   }
 }
 
-// channel state and NCO words of one call (correlator.c:177-189)
-__device__ __forceinline__ bool chan_setup(const gnsscorr_nco_cmd& cmd, gnsscorr_chan_state& st,
-                                           Chan& c) {
-  if (cmd.epoch_load >= 0) {  // epoch set, correlator.c:177-182
-    const int v = cmd.epoch_load & 0xFFFF;
-    st.msbit_reg = v;
-    st.ms_counter = v & 0xff;
-    st.bit_counter = v >> 8;
-  }
-  const bool active = cmd.prn > 0 && cmd.prn <= 32;   // correlator.c:185
-  c.P0 = st.carrier_phase;
-  c.K0 = st.code_phase;
-  c.cinc = cmd.carrier_incr;
-  c.kinc2 = cmd.code_incr << 1;
-  c.hc0 = st.half_chip & 0xFFFFu;
-  c.D = (cmd.slew & 0xFFFFu) + 2046u;
-  const uint32_t h1 = (c.hc0 + 1u) & 0xFFFFu;
-  if (h1 >= c.D) c.j1 = 1;
-  else if (c.D <= 0xFFFFu) c.j1 = 1ull + (c.D - h1);
-  else c.j1 = kNever;
-  c.base = (active ? cmd.prn : 0) * GNSSCORR_OSG_ROW;
-  return active;
-}
-
 // Open loop: at least 4 waves per SIMD (<= 128 VGPRs; the build takes 117, no
 // spills): 3072 channels put 3 waves on a SIMD, 12288 put 4; same-box A/B
 // 3 % faster than the unbounded build at 3072 channels.  The closed loop (gpsisr
 // inlined, ~150 VGPRs) keeps the default bound.
-#ifndef TRACK_STREAM_WAVES
-#define TRACK_STREAM_WAVES 4
-#endif
 template <bool PK, bool CLOSED>
-__global__ __launch_bounds__(64 * kStreamCh, CLOSED ? 1 : TRACK_STREAM_WAVES) void osg_stream_kernel(
+__global__ __launch_bounds__(64 * kStreamCh, CLOSED ? 1 : 4) void osg_stream_kernel(
     StreamArgs A) {
-  // the LO words read ahead (TRACK_PF) in the open loop only: in the closed loop
+  // the LO words and row bytes read ahead in the open loop only: in the closed loop
   // their 32 registers pushed the kernel from 151 to 183 VGPRs (2 waves per SIMD:
   // 32.6 -> 42.7 us per 3072-channel call, same box)
-  constexpr bool kPF = TRACK_PF && !CLOSED;
+  constexpr bool kPF = !CLOSED;
   extern __shared__ uint4 s_dyn[];
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int lane = (int)threadIdx.x & 63;
@@ -1365,7 +802,7 @@ __global__ __launch_bounds__(64 * kStreamCh, CLOSED ? 1 : TRACK_STREAM_WAVES) vo
   __shared__ uint32_t s_lot[128];
   // packed: byte b -> its four int8 levels (one LDS read instead of the spread
   // and v_perm of if2_expand_byte per output word)
-  constexpr bool kX2 = PK && TRACK_X2LUT;
+  constexpr bool kX2 = PK;
   __shared__ uint32_t s_x2[kX2 ? 256 : 1];
   if constexpr (kX2) {
     for (int i = threadIdx.x; i < 256; i += blockDim.x) s_x2[i] = if2_expand_byte((uint32_t)i);
@@ -1562,21 +999,14 @@ __global__ __launch_bounds__(64 * kStreamCh, CLOSED ? 1 : TRACK_STREAM_WAVES) vo
       // ---- this lane's 32 samples as 16 pair words (4 chunks of 4)
       uint4 ch4[4];
       if constexpr (PK) {
-        if constexpr (kX2) {
-          auto x2 = [&](uint32_t w) {
-            return make_uint4(s_x2[w & 0xFFu], s_x2[(w >> 8) & 0xFFu], s_x2[(w >> 16) & 0xFFu],
-                              s_x2[w >> 24]);
-          };
-          ch4[0] = x2(pq0.x);
-          ch4[1] = x2(pq0.y);
-          ch4[2] = x2(pq1.x);
-          ch4[3] = x2(pq1.y);
-        } else {
-          ch4[0] = if2_expand_word(pq0.x);
-          ch4[1] = if2_expand_word(pq0.y);
-          ch4[2] = if2_expand_word(pq1.x);
-          ch4[3] = if2_expand_word(pq1.y);
-        }
+        auto x2 = [&](uint32_t w) {
+          return make_uint4(s_x2[w & 0xFFu], s_x2[(w >> 8) & 0xFFu], s_x2[(w >> 16) & 0xFFu],
+                            s_x2[w >> 24]);
+        };
+        ch4[0] = x2(pq0.x);
+        ch4[1] = x2(pq0.y);
+        ch4[2] = x2(pq1.x);
+        ch4[3] = x2(pq1.y);
       } else {
         if (p * kPieceSpan + kPieceSpan > nsamp && (nsamp & 7)) {
           // the call's partial last chunk (nsamp not a multiple of 8; single
@@ -1706,7 +1136,7 @@ __global__ __launch_bounds__(64 * kStreamCh, CLOSED ? 1 : TRACK_STREAM_WAVES) vo
           using I3 = std::integral_constant<int, 3>;
           using I4 = std::integral_constant<int, 4>;
           bool aligned = false;
-          if (TRACK_ALIGNED && TRACK_NODUMP_COPY && !anyd) {
+          if (!anyd) {
             // j: samples before the lane's first carry (sample n has half-chip
             // hc + h(n), h(n) = (kph + n kinc2) >> 32), estimated in fp32 and
             // checked exactly.  h(j - 1) = 0, h(j) = 1, h(j + 23) = 3, h(j + 24) = 4
@@ -1734,8 +1164,8 @@ __global__ __launch_bounds__(64 * kStreamCh, CLOSED ? 1 : TRACK_STREAM_WAVES) vo
             }
           }
           if (aligned) {
-          } else if (TRACK_NODUMP_COPY && !anyd) {
-            if (TRACK_IV4 && c.kinc2 <= kIv4Kinc2) full_piece(std::false_type{}, I4{});
+          } else if (!anyd) {
+            if (c.kinc2 <= kIv4Kinc2) full_piece(std::false_type{}, I4{});
             else full_piece(std::false_type{}, I3{});
           } else {
             full_piece(std::true_type{}, I3{});
@@ -1858,12 +1288,7 @@ struct gnsscorr_track_ctx {
   hostctx::DevBuf<int8_t> d_if;   // gnsscorr_track's staging, in bytes
   int max_dumps = 0;
   int64_t tic = 0, tic_ref = 0;
-  int stage_if = 1;   // GNSSCORR_TRACK_STAGE_IF=0: lanes read their IF runs from global memory
-  int cpw_override = 0;   // GNSSCORR_TRACK_CPW: channels per workgroup
-  int pieces_all = 0;     // GNSSCORR_TRACK_PIECES=1: the piece path for receivers too (A/B)
-  int stream_kernel = 1;  // GNSSCORR_TRACK_STREAM=0: IQ calls on the per-call workgroup
-                          // kernel instead of osg_stream_kernel (A/B)
-  int balance = 1;         // GNSSCORR_TRACK_BALANCE=0: no LDS padding for an even spread (A/B)
+  int balance = 1;        // GNSSCORR_TRACK_BALANCE=0: no LDS padding for an even spread (A/B)
   int xcall_prefetch = 1;  // GNSSCORR_TRACK_XPF=0: no cross-call piece prefetch (A/B)
   int n_cu = 256;
   size_t lds_max = 0;     // LDS bytes a workgroup may allocate (gnsscorr_device_lds_bytes)
@@ -1925,10 +1350,6 @@ extern "C" int gnsscorr_track_create(gnsscorr_track_ctx** out, const gnsscorr_tr
   c->max_dumps = cfg->max_nsamp / GNSSCORR_OSG_ROW + 2;
   c->tic_ref = (int64_t)(cfg->samp_rate * cfg->tic_period);
   c->tic = c->tic_ref;
-  if (const char* e = getenv("GNSSCORR_TRACK_STAGE_IF")) c->stage_if = atoi(e) != 0;
-  if (const char* e = getenv("GNSSCORR_TRACK_CPW")) c->cpw_override = atoi(e);
-  if (const char* e = getenv("GNSSCORR_TRACK_PIECES")) c->pieces_all = atoi(e) != 0;
-  if (const char* e = getenv("GNSSCORR_TRACK_STREAM")) c->stream_kernel = atoi(e) != 0;
   if (const char* e = getenv("GNSSCORR_TRACK_BALANCE")) c->balance = atoi(e) != 0;
   if (const char* e = getenv("GNSSCORR_TRACK_XPF")) c->xcall_prefetch = atoi(e) != 0;
   if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, cfg->device) !=
@@ -1944,9 +1365,9 @@ extern "C" int gnsscorr_track_create(gnsscorr_track_ctx** out, const gnsscorr_tr
 }
 
 // Layout hint (round 2: per-channel LDS staging for one stream per channel).
-// Since round 3 every workgroup picks its IF path itself -- the shared LDS
-// stage when its channels read one stream, the per-wave piece path otherwise --
-// so the hint is accepted and has no effect.
+// Neither kernel needs it: osg_stream_kernel gives every channel its own
+// wavefront and IF pieces whatever the layout, and osg_track_kernel's threads
+// read their runs from global memory.  The hint is validated and has no effect.
 extern "C" int gnsscorr_track_set_layout(gnsscorr_track_ctx* c, int one_stream_per_channel) {
   if (!c || one_stream_per_channel < 0 || one_stream_per_channel > 1) {
     gnsscorr_set_error("gnsscorr_track_set_layout: bad arguments");
@@ -1980,14 +1401,15 @@ extern "C" int64_t gnsscorr_track_next_tic(gnsscorr_track_ctx* c, int64_t nsamp)
 // first call's TIC sample (tic_explicit) or the TIC counter to step per call.
 // lcfg/d_loops: the closed loop, every channel's gpsisr step after each call.
 // Returns GNSSCORR_TRACK_NOT_FUSED when the kernel does not serve the context
-// or the shape (I-only streams, LDS, alignment of later calls).
+// (I-only streams) or the shape (alignment of the later calls of n_calls > 1);
+// a single call of an IQ context is always served.
 static int launch_stream(gnsscorr_track_ctx* c, const int8_t* d_if, int64_t stride, int64_t nsamp,
                          int n_calls, gnsscorr_nco_cmd* d_cmds, int cmd_step,
                          gnsscorr_track_result* d_res, int32_t* d_dumps, int64_t tic,
                          int tic_explicit, const gnsscorr_osg_loop_cfg* lcfg,
                          gnsscorr_osg_loop* d_loops, gnsscorr_osg_loop* d_hist) {
   const bool pk = packed(c), iq = bps_of(c) == 2;
-  if (!iq || !c->stream_kernel) return GNSSCORR_TRACK_NOT_FUSED;
+  if (!iq) return GNSSCORR_TRACK_NOT_FUSED;
   if (nsamp < 1 || nsamp > c->cfg.max_nsamp) {
     gnsscorr_set_error("nsamp %lld outside [1, max_nsamp=%d]", (long long)nsamp, c->cfg.max_nsamp);
     return GNSSCORR_EINVAL;
@@ -2002,7 +1424,13 @@ static int launch_stream(gnsscorr_track_ctx* c, const int8_t* d_if, int64_t stri
   const int C = c->cfg.n_channels;
   size_t dyn = (size_t)stream_wave_lds(pk, (int)nsamp) * kStreamCh;
   constexpr size_t kStatic = 2048;   // s_lot, s_x2 (packed), with margin
-  if (dyn + kStatic > c->lds_max) return GNSSCORR_TRACK_NOT_FUSED;
+  // every permitted nsamp fits the 64 KiB any workgroup may allocate
+  static_assert(stream_wave_lds(false, kMaxNsamp) * kStreamCh + kStatic <= 64 * 1024, "stream LDS");
+  if (dyn + kStatic > c->lds_max) {
+    gnsscorr_set_error("gnsscorr_track: nsamp %lld needs %zu B of LDS per workgroup, the device "
+                       "allows %zu", (long long)nsamp, dyn + kStatic, c->lds_max);
+    return GNSSCORR_EINVAL;
+  }
   // A launch takes as long as its busiest CU.  The dispatcher fills a CU with
   // as many workgroups as its resources allow, so at 768 workgroups on 256 CUs
   // some CUs got 4-5 while others got 2 (wave stamps: pieces p10 16.6 / p90
@@ -2065,61 +1493,23 @@ static int launch(gnsscorr_track_ctx* c, const int8_t* d_if, int64_t stride, int
     gnsscorr_set_error("IF base and stream stride must be %d-byte aligned", pk ? 8 : 16);
     return GNSSCORR_EINVAL;
   }
+  if (iq)   // (one call of an IQ context is never GNSSCORR_TRACK_NOT_FUSED)
+    return launch_stream(c, d_if, stride, nsamp, 1, const_cast<gnsscorr_nco_cmd*>(d_cmds), 0, d_res,
+                         d_dumps, tic_count, 1, nullptr, nullptr, nullptr);
+  // I-only: osg_track_kernel, one thread per 64-sample run, as many channels
+  // per workgroup as fit 1024 threads
   const int C = c->cfg.n_channels;
-  if (iq && c->stream_kernel) {
-    const int rs = launch_stream(c, d_if, stride, nsamp, 1, const_cast<gnsscorr_nco_cmd*>(d_cmds),
-                                 0, d_res, d_dumps, tic_count, 1, nullptr, nullptr, nullptr);
-    if (rs != GNSSCORR_TRACK_NOT_FUSED) return rs;
-  }
-  int threads = (int)((nsamp + kRun - 1) / kRun);
-  threads = (threads + 63) & ~63;
-  const size_t stage_bytes = (size_t)((nsamp + kRun - 1) / kRun) * kPitch * 16;
-  int stage = iq && c->stage_if && stage_bytes <= (size_t)kStageMaxBytes;
-  if (stage && c->pieces_all) stage = 4;
-  // dynamic LDS: epoch sums, E/P/L row bytes, then one region that holds either
-  // the workgroup's shared IF stage or the waves' 4 KiB piece slots
-  auto lds_bytes = [&](int cpw) {
-    const size_t sum_bytes = (size_t)((cpw * ((int)nsamp / GNSSCORR_OSG_ROW + 2) * 6 + 3) & ~3) * 4;
-    const size_t slots = (size_t)(threads / 64) * cpw * kStage2Bytes;
-    return sum_bytes + (iq ? (size_t)cpw * kPk8Stage +
-                                 (stage ? (stage_bytes > slots ? stage_bytes : slots) : 0) : 0);
-  };
-  // Channels per workgroup: as many as fit 1024 threads (they share one staged
-  // IF copy).  The 1.5-round tail at 3072 channels (768 workgroups, 512
-  // resident) is cheaper than smaller workgroups (MI355X, 3072 x 1 ms:
-  // cpw 4 33.4 us, 3 35.2, 2 34.1, 1 46.4); GNSSCORR_TRACK_CPW overrides.
-  int cpw = 1;
-  auto pick_cpw = [&]() {
-    cpw = min(kMaxCpw, kMaxThreads / threads);
-    if (c->cpw_override > 0) cpw = min(cpw, c->cpw_override);
-    // the LDS must fit beside the static LDS (s_lo, s_stream, s_short: < 1 KiB)
-    while (cpw > 1 && lds_bytes(cpw) + 1024 > c->lds_max) cpw--;
-  };
-  pick_cpw();
-  if (stage && lds_bytes(cpw) + 1024 > c->lds_max) {   // no room for the IF stage or
-    stage = 0;                                          // the piece slots: lane reads
-    pick_cpw();
-  }
-  if (lds_bytes(cpw) + 1024 > c->lds_max) {
-    gnsscorr_set_error("gnsscorr_track: nsamp %lld needs %zu B of LDS per workgroup, the device "
-                       "allows %zu", (long long)nsamp, lds_bytes(cpw) + 1024, c->lds_max);
-    return GNSSCORR_EINVAL;
-  }
+  const int threads = ((int)((nsamp + kRun - 1) / kRun) + 63) & ~63;
+  const int cpw = min(kMaxCpw, kMaxThreads / threads);
+  // dynamic LDS: the channels' epoch sums (under 1 KiB at every permitted nsamp)
+  const size_t dyn = (size_t)cpw * ((int)nsamp / GNSSCORR_OSG_ROW + 2) * 6 * sizeof(int32_t);
   dim3 grid((C + cpw - 1) / cpw), block(threads * cpw);
-  const size_t dyn = lds_bytes(cpw);
-#define TRACK_LAUNCH(IQ, PK, ST)                                                               \
-  hipLaunchKernelGGL((osg_track_kernel<IQ, PK>), grid, block, dyn, c->stream, d_if, stride,    \
-                     (int)nsamp, C, cpw, d_cmds, c->d_state, d_res, d_dumps, c->max_dumps,     \
-                     c->d_pk, c->d_pk8, tic_count, ST)
-  if (iq && pk)
-    TRACK_LAUNCH(true, true, stage);
-  else if (iq)
-    TRACK_LAUNCH(true, false, stage);
-  else if (pk)
-    TRACK_LAUNCH(false, true, 0);
+  if (pk)
+    hipLaunchKernelGGL((osg_track_kernel<true>), grid, block, dyn, c->stream, d_if, stride, (int)nsamp,
+                       C, cpw, d_cmds, c->d_state, d_res, d_dumps, c->max_dumps, c->d_pk, tic_count);
   else
-    TRACK_LAUNCH(false, false, 0);
-#undef TRACK_LAUNCH
+    hipLaunchKernelGGL((osg_track_kernel<false>), grid, block, dyn, c->stream, d_if, stride, (int)nsamp,
+                       C, cpw, d_cmds, c->d_state, d_res, d_dumps, c->max_dumps, c->d_pk, tic_count);
   HIP_TRY(hipGetLastError());
   return GNSSCORR_OK;
 }

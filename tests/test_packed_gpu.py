@@ -5,11 +5,13 @@ A packed stream is the int8 stream of the same levels in a quarter of the
 bytes, so every result must be IDENTICAL to the int8 path on the unpacked
 samples (which the other GPU tests pin to the reference): tracking results,
 dumps and channel state bit-exact; acquisition rows and decisions bit-exact
-(same fp64 / fp32 arithmetic on the same values).  Covered paths of
-osg_track_kernel: staged shared streams (the channels of one receiver),
-unstaged one-stream-per-channel runs (C_s = 1), tail runs (nsamp not a multiple
-of 64, odd nsamp), the per-sample path (slews beyond the LDS-staged E/P/L row)
-and I-only streams; plus a few channels against the scalar oracle directly.
+(same fp64 / fp32 arithmetic on the same values).  The IQ cases run
+osg_stream_kernel<PK>: streams shared by the channels of one receiver and
+one-stream-per-channel runs (C_s = 1; the same code either way, every channel
+its own wavefront), partial last pieces (nsamp not a multiple of 8, odd nsamp),
+its per-sample recurrence (slews beyond the LDS-staged E/P/L row) and multi-call
+replay.  The I-only cases run osg_track_kernel<PK>, whose packed runs are read
+element by element.  Plus a few channels against the scalar oracle directly.
 """
 import numpy as np
 import pytest
@@ -52,10 +54,10 @@ def test_track_packed_equals_int8(gpu, layout, nsamp):
     """Host API, several calls, all dumps: packed == int8 bit-exact."""
     rng = np.random.default_rng(nsamp + len(layout))
     n_calls = 3
-    if layout == "receivers":          # 12 channels per stream: staged, shared in LDS
+    if layout == "receivers":          # 12 channels per stream, shared through L2
         C, n_streams = 96, 8
         stream_of = np.arange(C) // 12
-    else:                              # C_s = 1: unstaged packed runs
+    else:                              # C_s = 1: every channel-wave its own stream
         C, n_streams = 64, 64
         stream_of = np.arange(C)
     streams = [S.synth_if(nsamp * n_calls, 300 + i, [(i % 32 + 1, 37 * i, 0, 3)])
@@ -105,7 +107,8 @@ def test_track_packed_vs_oracle(gpu, oracle):
 
 
 def test_track_packed_big_slew_and_real(gpu):
-    """Per-sample paths: slews beyond the LDS-staged row (IQ) and I-only streams."""
+    """Per-sample paths: slews beyond the LDS-staged row (IQ, osg_stream_kernel's
+    corr_sample_s) and I-only streams (osg_track_kernel)."""
     rng = np.random.default_rng(5)
     C, nsamp, n_calls = 48, 16368, 3
     for iq in (True, False):

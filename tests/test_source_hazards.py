@@ -8,6 +8,11 @@ DESIGN.md section 3).  Every inline asm in the device sources must be volatile.
 The repro form (TRACK_ASM_MAD) and the other measured-out tracking switches
 (TRACK_SLOTS > 1 with its inline-asm slot read, TRACK_DMA_AUX, GNSSCORR_TRACK_V1,
 TRACK_LOAD4) were removed in round 6; git history keeps them.
+So does it keep the IQ half of osg_track_kernel, which osg_stream_kernel had replaced
+on every product path, with its four environment switches, and the stream kernel's
+seven compile-time switches that sat at their measured values and are constants now
+(the names: `gone` below; none is part of a surviving identifier --
+GNSSCORR_TRACK_XPF and GNSSCORR_TRACK_BALANCE stay).
 """
 import os
 import re
@@ -36,7 +41,13 @@ def test_measured_out_switches_are_gone():
     gone = ("TRACK_ASM_MAD", "TRACK_SLOTS", "TRACK_DMA_AUX", "GNSSCORR_TRACK_V1", "TRACK_LOAD4",
             # sgt.hip's compile-time switches, each measured and lost
             "SGT_KC32", "SGT_WPE", "SGT_PREFIX", "SGT_KSUB", "SGT_CHIPS", "SGT_CHIP_GROUP",
-            "SGT_CHIP_FMA", "SGT_CHIP_PF", "SGT_SCHED")
+            "SGT_CHIP_FMA", "SGT_CHIP_PF", "SGT_SCHED",
+            # the IQ half of osg_track_kernel: its environment switches ...
+            "GNSSCORR_TRACK_STAGE_IF", "GNSSCORR_TRACK_PIECES", "GNSSCORR_TRACK_STREAM",
+            "GNSSCORR_TRACK_CPW",
+            # ... and osg_stream_kernel's settled compile-time switches
+            "TRACK_NODUMP_COPY", "TRACK_IV4", "TRACK_ALIGNED", "TRACK_X2LUT", "TRACK_STREAM_CH",
+            "TRACK_STREAM_WAVES", "TRACK_PF")
     for f, lines in _sources():
         text = "\n".join(lines)
         for g in gone:

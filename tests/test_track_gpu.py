@@ -107,8 +107,9 @@ def test_batched_many_channels_vs_oracle(gpu, oracle, nsamp):
 
 @pytest.mark.parametrize("per_channel_layout", [False, True])
 def test_one_stream_per_channel_vs_oracle(gpu, oracle, per_channel_layout):
-    """C_s = 1 (every channel its own int8 stream), with and without the
-    gnsscorr_track_set_layout hint (per-channel LDS staging): bit-exact either way."""
+    """C_s = 1 (every channel its own int8 stream) on osg_stream_kernel, with and
+    without the gnsscorr_track_set_layout hint (a validated no-op since every channel
+    has its own wavefront and IF pieces): bit-exact either way."""
     rng = np.random.default_rng(31)
     C, nsamp, n_calls = 48, 16368, 2
     streams = [S.synth_if(nsamp * n_calls, 300 + i, [(i % 32 + 1, 37 * i, 0, 3)]) for i in range(C)]
@@ -135,10 +136,11 @@ def test_one_stream_per_channel_vs_oracle(gpu, oracle, per_channel_layout):
 
 
 # code NCO words for low sample rates: at fs = 4.092 Msps a half-chip is 2
-# samples (kinc2 = 2^31), at 2.048 Msps about one (kinc2 ~ 0.999 * 2^32).  There
-# an epoch of D >= 2046 half-chips can be as short as a piece-path lane's span
-# of 2080 samples (two 32-sample pieces 2048 apart), so those channels must
-# not take the per-wave piece path (track.hip: s_short).
+# samples (kinc2 = 2^31), at 2.048 Msps about one (kinc2 ~ 0.999 * 2^32).  These
+# IQ calls run on osg_stream_kernel: a half-chip shorter than 6 samples takes its
+# per-sample recurrence (track.hip: kFastKinc2), and an epoch of D >= 2046
+# half-chips is then as short as one or two 2048-sample pieces, so a lane meets
+# a later epoch at nearly every piece start and several dumps fall into one call.
 LOW_RATES = {"4.092": 1 << 30, "2.048": int(round((1 << 31) * 2.046 / 2.048))}
 
 
@@ -204,8 +206,8 @@ def test_low_rate_one_stream_per_channel_all_dumps_vs_oracle(gpu, oracle, rate, 
 @pytest.mark.parametrize("packed", [False, True])
 @pytest.mark.parametrize("rate", sorted(LOW_RATES))
 def test_low_rate_one_stream_per_channel_slews_vs_oracle(gpu, oracle, rate, packed):
-    """Same rates with slews around the piece path's limit (D = 2046 + slew
-    against a 2080-sample lane span) and beyond the staged E/P/L row: last dump,
+    """Same rates with slews that put the epoch (D = 2046 + slew half-chips) around
+    the 2048-sample piece of osg_stream_kernel and beyond its staged E/P/L row: last dump,
     dump flags and channel state bit-exact over 3 calls of 16368 samples."""
     rng = np.random.default_rng(23 + 5 * packed)
     C, nsamp, n_calls = 42, 16368, 3
@@ -227,6 +229,58 @@ def test_low_rate_one_stream_per_channel_slews_vs_oracle(gpu, oracle, rate, pack
     for c in range(C):
         for key in ("carrier_phase", "carrier_cycle", "code_phase", "half_chip", "acc"):
             np.testing.assert_array_equal(st[key][c], ref_state[c][key][0], err_msg=f"{key} ch{c}")
+
+
+_LARGEST = {}
+
+
+def _largest_nsamp_case(oracle, nsamp):
+    """Streams, commands and the oracle's dumps and states of one call of `nsamp`
+    samples on 4 channels (computed once per nsamp, shared by int8 and packed)."""
+    if nsamp not in _LARGEST:
+        C = 4
+        streams = [S.synth_if(nsamp, 900 + i, [(i + 1, 53 * i, 0, 3)]) for i in range(C)]
+        cmds = _random_cmds(np.random.default_rng(65536), 1, C, C)[0]
+        cmds["prn"] = np.arange(1, C + 1)
+        cmds["stream"] = np.arange(C)
+        cmds["slew"] = [0, 7, 0, 0]
+        want, state = [], []
+        for c in range(C):
+            o = oracle.OracleOSG(1, True, 16.368e6, 0.0)
+            rw = o.REG_write
+            rw[7] = -1
+            cm = cmds[c]
+            rw[0] = cm["prn"]
+            rw[3], rw[4] = int(cm["carrier_incr"]) >> 16, int(cm["carrier_incr"]) & 0xFFFF
+            rw[5], rw[6] = int(cm["code_incr"]) >> 16, int(cm["code_incr"]) & 0xFFFF
+            rw[0x84] = cm["slew"]
+            want.append(o.sim_dumps(streams[c], nsamp)[:, 1:])
+            state.append(o.chan_state())
+        _LARGEST[nsamp] = (streams, cmds, want, state)
+    return _LARGEST[nsamp]
+
+
+@pytest.mark.parametrize("packed", [False, True], ids=["int8", "packed2"])
+@pytest.mark.parametrize("nsamp", [65536, 65535])
+def test_iq_largest_nsamp_vs_oracle(gpu, oracle, nsamp, packed):
+    """The upper end of nsamp (kMaxNsamp = 65536, and the odd size below it) on
+    osg_stream_kernel: one workgroup of 4 channels on their own streams, one call,
+    a slew on one channel.  Its LDS per workgroup grows with nsamp only (the
+    epoch sums), and a call that did not fit is an error, so this size must launch:
+    EVERY dump and the channel state equal the oracle's."""
+    streams, cmds, want, state = _largest_nsamp_case(oracle, nsamp)
+    C = len(streams)
+    buf, stride = _layout_streams(streams, nsamp, 1)
+    ctx = gpu.TrackCtx(C, iq=True, max_nsamp=nsamp, packed=packed)
+    res, _, d = ctx.track(gpu.pack2(buf) if packed else buf, nsamp, cmds, n_streams=C,
+                          stream_stride=stride, all_dumps=True)
+    st = ctx.get_state()
+    for c in range(C):
+        assert len(want[c]) >= 3, (c, len(want[c]))       # a 4-ms call: several dumps each
+        assert res["n_dumps"][c] == len(want[c]), (c, res["n_dumps"][c], len(want[c]))
+        np.testing.assert_array_equal(d[c, :len(want[c])], want[c], err_msg=f"ch{c}")
+        for key in ("carrier_phase", "carrier_cycle", "code_phase", "half_chip", "acc"):
+            np.testing.assert_array_equal(st[key][c], state[c][key][0], err_msg=f"{key} ch{c}")
 
 
 def test_chunking_invariance_full_size(gpu):
@@ -447,6 +501,6 @@ def test_track_rejects_bad_prn(gpu):
 
 
 def test_device_lds_bytes(gpu):
-    """The LDS a workgroup may allocate, as the per-channel staging fit check reads it
+    """The LDS a workgroup may allocate, as osg_stream_kernel's launch check reads it
     (gnsscorr_device_lds_bytes): 160 KiB on gfx950."""
     assert gpu.device_lds_bytes(0) >= 160 * 1024

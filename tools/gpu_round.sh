@@ -85,19 +85,6 @@ for S in sgt sdr; do
   rm -rf $O/pmc_$S/FETCH_SIZE/ $O/pmc_$S/WRITE_SIZE/
   echo "pmc section $S ok"
 done
-echo "== tracking A/B (same box): stream kernel, TRACK_LO_SPLIT=0 build, per-call workgroup kernel"
-for L in cs1_int8 cs1_packed2 rx12_int8 rx12_packed2; do
-  for V in new lo0 wg; do
-    case $V in
-      new) unset GNSSCORR_LIB; S=1;;
-      lo0) export GNSSCORR_LIB=$PWD/gnss-sdr.ru_amd/ab/libgnsscorr_lo0.so; S=1;;
-      wg) unset GNSSCORR_LIB; S=0;;
-    esac
-    [ $V = lo0 ] && [ ! -f gnss-sdr.ru_amd/ab/libgnsscorr_lo0.so ] && continue
-    echo "$L $V: $(GNSSCORR_TRACK_STREAM=$S timeout -k 10 120 python3 tools/trk_layout.py $L 40)" | tee -a $O/trk_ab.log
-  done
-done
-unset GNSSCORR_LIB
 for F in 1 0; do
   GNSSCORR_OSG_FUSED=$F timeout -k 10 200 python -u tools/bench_part.py track 40 > $O/track_fused$F.log 2>&1
   echo "closed loop fused=$F $(tail -1 $O/track_fused$F.log | cut -c1-200)" | tee -a $O/trk_ab.log
