@@ -33,22 +33,8 @@
 #include "acq_ctx.h"
 #include "if2.h"
 
-// Diagnostic hook: tools/acq_stamps.hip defines ACQ_STAMP(i) to record
-// s_memtime at phase boundaries; in the library it compiles to nothing.
-// tools/acq_ablate.hip sets ACQ_SKIP to time the kernel with phases removed
-// (1: no 3x11 pass, 2: no radix-31 pass, 4: no row statistics); 0 in the library.
-#ifndef ACQ_SKIP
-#define ACQ_SKIP 0
-#endif
-#ifndef ACQ_LOAD_AUX
-#define ACQ_LOAD_AUX 0   // cache-policy bits of the X / F row loads
-#endif
-#ifndef ACQ_STAMP
-#define ACQ_STAMP(i)
-#endif
-#ifndef ACQ_LDGROUP         // pipelined kernel: planes per group of row loads
-#define ACQ_LDGROUP 16
-#endif
+// Diagnostic hook: tools/acq_pstamps.hip defines it to record s_memtime at the
+// pipelined kernel's phase boundaries; in the library it compiles to nothing.
 #ifndef ACQ_PSTAMP          // pipelined kernel: (unit iteration, stamp id), tools/acq_pstamps.hip
 #define ACQ_PSTAMP(it, i)
 #endif
@@ -62,10 +48,7 @@ constexpr int E16 = 15345, E3 = 10912, E11 = 5952, E31 = 528;
 constexpr int kThreads = 512;           // 8 wavefronts -> up to 256 VGPRs each
 // Spectra rows in HBM are padded to 16 planes x 1024 complex (128 KiB) so the
 // radix-16 loads are 16-byte aligned: LDS position a*1023+g <-> a*1024+g.
-#ifndef ACQ_PLANE
-#define ACQ_PLANE 1024
-#endif
-constexpr int kPlane = ACQ_PLANE;
+constexpr int kPlane = 1024;
 constexpr int NPAD = 16 * kPlane;
 constexpr int kGroups31 = N / 31;       // 528 radix-31 groups
 constexpr int kLeft = kGroups31 - kThreads;  // 16 groups done as direct dot products
@@ -216,8 +199,8 @@ __device__ __forceinline__ void load_mul_pass16(const float2* __restrict__ Xb,
   if (sh.a == 0 && sh.b == 0 && sh.c == 0 && sh.d == 0) {   // uniform branch
 #pragma unroll
     for (int a = 0; a < 16; a++) {
-      const f4v u = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rx, voff, a * kPlane * 8, ACQ_LOAD_AUX));
-      const f4v f = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rf, voff, a * kPlane * 8, ACQ_LOAD_AUX));
+      const f4v u = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rx, voff, a * kPlane * 8, 0));
+      const f4v f = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rf, voff, a * kPlane * 8, 0));
       // conj(u) * f = u.re * f + u.im * (f.im, -f.re)
       const v2f f0 = (v2f){f.x, f.y}, f1 = (v2f){f.z, f.w};
       x0[a] = bc(u.x) * f0 + bc(u.y) * mul_mi(f0);
@@ -229,9 +212,9 @@ __device__ __forceinline__ void load_mul_pass16(const float2* __restrict__ Xb,
 #pragma unroll
     for (int a = 0; a < 16; a++) {
       const int pa = ((a - sh.a) & 15) * kPlane * 8;
-      const f2v u0 = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(rx, v0, pa, ACQ_LOAD_AUX));
-      const f2v u1 = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(rx, v1, pa, ACQ_LOAD_AUX));
-      const f4v f = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rf, voff, a * kPlane * 8, ACQ_LOAD_AUX));
+      const f2v u0 = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(rx, v0, pa, 0));
+      const f2v u1 = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(rx, v1, pa, 0));
+      const f4v f = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rf, voff, a * kPlane * 8, 0));
       const v2f f0 = (v2f){f.x, f.y}, f1 = (v2f){f.z, f.w};
       x0[a] = bc(u0.x) * f0 + bc(u0.y) * mul_mi(f0);
       x1[a] = bc(u1.x) * f1 + bc(u1.y) * mul_mi(f1);
@@ -604,7 +587,10 @@ __device__ __forceinline__ float block_max0(float v, float* scratch) {
   return v;
 }
 
-// ---- the hot kernel ------------------------------------------------------------
+// ---- the one-unit correlation kernel --------------------------------------------
+// Serves the non-coherent searches (<NONCOHERENT, false>) and the power-row dump
+// of gnsscorr_acq_power_row (<BEST_OF_BLOCKS, true>); every best-of-blocks search
+// runs acq_corr_pipe_kernel below.
 // One workgroup = one work unit: BEST_OF_BLOCKS -> unit = (row, block), the
 // statistics of that block go to stats[unit]; NONCOHERENT -> unit = row, |.|^2
 // summed over the blocks in registers, stats to stats[row * n_blocks].
@@ -622,7 +608,6 @@ __global__ __launch_bounds__(kThreads) void acq_corr_kernel(
   __shared__ PeakSlot s_pk[kThreads / 64];
   __shared__ float s_mx[kThreads / 64];
   constexpr bool kNonCoh = MODE == GNSSCORR_ACQ_NONCOHERENT;
-  ACQ_STAMP(12);
   const int unit = order[blockIdx.x];
   const int rowid = kNonCoh ? unit : unit / n_blocks;
   const int blk0 = kNonCoh ? 0 : unit % n_blocks;
@@ -651,29 +636,20 @@ __global__ __launch_bounds__(kThreads) void acq_corr_kernel(
   for (int i = 0; i < nblk; i++) {
     const int blk = blk0 + i;
     const float2* Xb = X + ((long)fm.x * n_blocks + blk) * NPAD;
-    ACQ_STAMP(i * 6 + 0);
     // D = conj(X) * F  (= conj(X * conj(F)), acquisition.sci:116), then radix-16
     load_mul_pass16(Xb, Fc, lds, t, sh);
     __syncthreads();
-    ACQ_STAMP(i * 6 + 1);
-    if (!(ACQ_SKIP & 1)) pass33(lds, t);
+    pass33(lds, t);
     __syncthreads();
-    ACQ_STAMP(i * 6 + 2);
     float pw[32];  // pw[31] = this thread's leftover output (or -1)
-    if (ACQ_SKIP & 2) {
+    const float2 y = extra ? dft31_single(lds, tw, t) : make_float2(0.f, 0.f);
+    pw[31] = extra ? (y.x * y.x + y.y * y.y) * inv_n2 : -1.f;
+    v2f x[31];
 #pragma unroll
-      for (int d = 0; d < 32; d++) pw[d] = lds[(t * 31 + d) % N].x;
-    } else {
-      const float2 y = extra ? dft31_single(lds, tw, t) : make_float2(0.f, 0.f);
-      pw[31] = extra ? (y.x * y.x + y.y * y.y) * inv_n2 : -1.f;
-      v2f x[31];
+    for (int d = 0; d < 31; d++) x[d] = ld2(lds[t * 31 + d]);
+    dftp<31>(x);
 #pragma unroll
-      for (int d = 0; d < 31; d++) x[d] = ld2(lds[t * 31 + d]);
-      dftp<31>(x);
-#pragma unroll
-      for (int d = 0; d < 31; d++) pw[d] = (x[d].x * x[d].x + x[d].y * x[d].y) * inv_n2;
-    }
-    ACQ_STAMP(i * 6 + 3);
+    for (int d = 0; d < 31; d++) pw[d] = (x[d].x * x[d].x + x[d].y * x[d].y) * inv_n2;
     if (DUMP && blk == dump_block) {
       int k = kb;
 #pragma unroll
@@ -699,10 +675,6 @@ __global__ __launch_bounds__(kThreads) void acq_corr_kernel(
     // the +-spc window without a second pass.  The leftover output (kx) is
     // handled on its own.  Within-thread exact ties keep the first slot
     // (slot order, not natural order).
-    if (ACQ_SKIP & 4) {   // diagnostic only: no statistics
-      best_pk = pw[0] + pw[30];
-      continue;
-    }
     float m1 = -1.f, m2 = -1.f;
     int d1 = 0;
 #pragma unroll
@@ -718,7 +690,6 @@ __global__ __launch_bounds__(kThreads) void acq_corr_kernel(
     int kk = k1;
     if (extra && better(pw[31], kx, v, kk)) { v = pw[31]; kk = kx; }
     block_argmax(v, kk, s_pk);
-    ACQ_STAMP(i * 6 + 4);
     // second peak outside the open window (argmax - spc, argmax + spc), circular
     auto in_win = [&](int k) {
       int dist = k - kk;
@@ -728,7 +699,6 @@ __global__ __launch_bounds__(kThreads) void acq_corr_kernel(
     float sv = in_win(k1) ? m2 : m1;
     if (extra && !in_win(kx)) sv = fmaxf(sv, pw[31]);
     sv = block_max0(sv, s_mx);
-    ACQ_STAMP(i * 6 + 5);
     best_pk = v;
     best_k = kk;
     best_sec = sv;
@@ -741,10 +711,11 @@ __global__ __launch_bounds__(kThreads) void acq_corr_kernel(
     r.block = kNonCoh ? -1 : blk0;
     stats[(long)rowid * n_blocks + blk0] = r;
   }
-  ACQ_STAMP(13);
 }
 
 // ---- the pipelined (persistent, two-role) correlation kernel -------------------
+// Serves every best-of-blocks search (no dump, no non-coherent sum: those stay with
+// acq_corr_kernel above).
 // One workgroup per CU (the 128 KiB row fills the LDS), 1024 threads:
 //   waves 0-7  ("compute"): the in-LDS passes of unit u -- 3x11, radix-31 --
 //              and the row statistics;
@@ -812,7 +783,8 @@ __device__ __forceinline__ void load_mul_r(const float2* __restrict__ Xb,
   // of its products (sched_group_barrier pins the VMEM reads first), so a
   // unit costs 16 / kLdGroup L2 round trips instead of one per plane.
   // Column ga takes plane a with F[a]; column gb takes plane -a with conj(F[a]).
-  constexpr int kLdGroup = ACQ_LDGROUP;
+  // One group of all 48 loads measured 115.5 us against 118.8.
+  constexpr int kLdGroup = 16;
   int x0off = foff, x1off = gb * 8;
   int pa_shift = 0;
   if (!(sh.a == 0 && sh.b == 0 && sh.c == 0 && sh.d == 0)) {   // uniform branch
@@ -1431,7 +1403,6 @@ extern "C" int gnsscorr_acq_create(gnsscorr_acq_ctx** out, const gnsscorr_acq_cf
   if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, cfg->device) !=
           hipSuccess || c->n_cu < 1)
     c->n_cu = 256;
-  if (const char* e = getenv("GNSSCORR_ACQ_PIPE")) c->pipe = atoi(e) != 0;
   rc = init_shared(c);
   if (!rc) rc = c->prec == GNSSCORR_ACQ_F64 ? acq64_init(c) : init_f32(c);
   if (!rc && c->prec == GNSSCORR_ACQ_F64) rc = acq64_preload(c);
@@ -1780,12 +1751,10 @@ static int correlate_launch(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_g
     ACQ_CORR_LAUNCH(GNSSCORR_ACQ_BEST_OF_BLOCKS, true);
   else if (mode == GNSSCORR_ACQ_NONCOHERENT)
     ACQ_CORR_LAUNCH(GNSSCORR_ACQ_NONCOHERENT, false);
-  else if (c->pipe) {
+  else
     hipLaunchKernelGGL(acq_corr_pipe_kernel, dim3(n_units < c->n_cu ? n_units : c->n_cu),
                        dim3(kPipeThreads), 0, c->stream, c->d_X, c->d_F, n_blocks, d_gcode,
                        d_gfreq, n_bins, spc, c->d_stats.p, c->d_order.p, c->d_fmap, n_units);
-  } else
-    ACQ_CORR_LAUNCH(GNSSCORR_ACQ_BEST_OF_BLOCKS, false);
 #undef ACQ_CORR_LAUNCH
   HIP_TRY(hipGetLastError());
   }

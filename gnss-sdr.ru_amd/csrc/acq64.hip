@@ -1586,6 +1586,21 @@ __global__ __launch_bounds__(kStatsThreads) void g_stats1_kernel(
   }
 }
 
+// the row statistics of a chunk's nu power rows (units u0 ...) on stream st: the one
+// pass where it is exact, else the two passes
+int g_stats_launch(gnsscorr_acq_ctx* c, hipStream_t st, const double* pw, int NK, int nu, int u0,
+                   int n_blocks, bool nc, int spc, double* d_dump, int dump_block) {
+  if (stats1_exact(NK, spc))
+    hipLaunchKernelGGL(g_stats1_kernel, dim3(nu), dim3(kStatsThreads), 0, st, pw, NK, u0,
+                       n_blocks, (int)nc, spc, c->d_stats.p, d_dump, dump_block,
+                       c->cfg.n_samples);
+  else
+    hipLaunchKernelGGL(g_stats_kernel, dim3(nu), dim3(kGThreads), 0, st, pw, NK, u0, n_blocks,
+                       (int)nc, spc, c->d_stats.p, d_dump, dump_block, c->cfg.n_samples);
+  HIP_TRY(hipGetLastError());
+  return GNSSCORR_OK;
+}
+
 // wipe-off rows in natural order (acq64_wipe_kernel with a runtime N)
 __global__ __launch_bounds__(256) void g_wipe_kernel(const int8_t* __restrict__ src, int iq,
                                                      int n_blocks, int coh,
@@ -1687,11 +1702,9 @@ int chunk_cap(const gnsscorr_acq_ctx* c, int rows) {
 
 int g_init(gnsscorr_acq_ctx* c) {
   const long N = c->cfg.n_samples;
-  int M = 16, P = 0;   // P: passes (radix 16, the last possibly 2 / 4 / 8)
+  int M = 16;
   while (M < 2 * N - 1) M *= 2;
-  for (int m = 1; m < M; m *= 16) P++;
   c->gM = M;
-  c->gP = P;
   // chunk: ~64 MiB per work buffer
   c->g_chunk = chunk_cap(c, (int)((64L << 20) / ((long)M * 16)));
   HIP_TRY(hipMalloc(&c->d_chirp, sizeof(double2) * N));
@@ -1811,15 +1824,9 @@ int g_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int n
                          dim3(kGThreads), 0, c->stream, D, N, M, b > 0, c->d_gpw, NK);
       HIP_TRY(hipGetLastError());
     }
-    if (stats1_exact(NK, spc))
-      hipLaunchKernelGGL(g_stats1_kernel, dim3(nu), dim3(kStatsThreads), 0, c->stream,
-                         (const double*)c->d_gpw, NK, u0, n_blocks, (int)nc, spc, c->d_stats.p,
-                         d_dump, dump_block, N);
-    else
-      hipLaunchKernelGGL(g_stats_kernel, dim3(nu), dim3(kGThreads), 0, c->stream,
-                         (const double*)c->d_gpw, NK, u0, n_blocks, (int)nc, spc, c->d_stats.p,
-                         d_dump, dump_block, N);
-    HIP_TRY(hipGetLastError());
+    const int rc = g_stats_launch(c, c->stream, c->d_gpw, NK, nu, u0, n_blocks, nc, spc, d_dump,
+                                  dump_block);
+    if (rc) return rc;
   }
   return GNSSCORR_OK;
 }
@@ -1838,9 +1845,6 @@ int g_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int n
 // non-coherent search), so no pre / post passes run (acquisition.sci:107-132).
 // ---------------------------------------------------------------------------------
 constexpr int kMixThreads = 128;
-#ifndef MX_WAVES
-#define MX_WAVES 3
-#endif
 
 struct MixCorr {
   const v2d* X;
@@ -1886,7 +1890,7 @@ __device__ __forceinline__ void mix_unit_rows(const MixCorr& cp, int unit, const
 // first pass otherwise keeps all 2R complex loads in flight: 244 VGPRs, 2 waves;
 // at 4 waves radix 16 spills)
 template <int R>
-constexpr int mx_waves() { return R <= 16 ? MX_WAVES : 2; }
+constexpr int mx_waves() { return R <= 16 ? 3 : 2; }
 template <int R, int MODE>
 __global__ __launch_bounds__(kMixThreads, mx_waves<R>()) void mx_pass(const v2d* __restrict__ in, int in_rs,
                                                        v2d* __restrict__ out, int out_rs, int N,
@@ -2047,27 +2051,9 @@ int mx_launch(gnsscorr_acq_ctx* c, int R, const v2d* in, int in_rs, v2d* out, in
 // N = 38 192 = 112 x 341; the correlation product is formed in the first, |.|^2 /
 // N^2 in the second (acquisition.sci:107-132), as in mx_pass.
 // ---------------------------------------------------------------------------------
-#ifndef M4_CT
-#define M4_CT 128   // m4_cols2 threads
-#endif
-#ifndef M4_T2
-#define M4_T2 16    // m4_cols2: columns n2 per workgroup
-#endif
-#ifndef M4_RT
-#define M4_RT 64    // m4_rows2 threads
-#endif
-#ifndef M4_COLS2_PLANE
-#define M4_COLS2_PLANE 1   // m4_cols2: exchange through one fp64 plane at a time (0: complex)
-#endif
-#ifndef M4_COLS2_WPE
-#define M4_COLS2_WPE 4     // m4_cols2: waves per SIMD the allocator is held to (0: free)
-#endif
-#if M4_COLS2_WPE
-#define M4_COLS2_ATTR __attribute__((amdgpu_waves_per_eu(M4_COLS2_WPE)))
-#else
-#define M4_COLS2_ATTR
-#endif
-constexpr int kM4ColThreads = M4_CT, kM4T2 = M4_T2, kM4RowThreads = M4_RT;
+constexpr int kM4ColThreads = 128;   // m4_cols2 threads
+constexpr int kM4T2 = 16;            // m4_cols2: columns n2 per workgroup
+constexpr int kM4RowThreads = 64;    // m4_rows2 threads
 // The intermediate rows Y[k1][n2] are stored at a pitch of N2 rounded up to whole
 // m4_cols2 tiles (kM4T2 columns = 256 B): every tile writes whole, aligned 128-byte
 // lines that no other workgroup touches (at the natural pitch N2 = 341 a tile's
@@ -2157,13 +2143,13 @@ struct M4StatsJob {
 // columns, whole 256-byte runs -- and the B-point stage writes its outputs, times
 // W_N^(n2 k1), straight to Y.  The LDS holds only the exchange between the stages, one
 // fp64 plane at a time (real parts, then imaginary parts: 15.2 KB per tile, 126 VGPRs,
-// 16 waves per CU; complex, 30.5 KB held it to 10).
+// 16 waves per CU; the complex exchange, 30.5 KB, held it to 10 and lost: DESIGN.md
+// section 3).  The register allocator is held to those 4 waves per SIMD.
 template <int A, int B, int MODE>
-__global__ __launch_bounds__(kM4ColThreads) M4_COLS2_ATTR void m4_cols2(const v2d* __restrict__ in, int in_rs,
-                                                        v2d* __restrict__ out, int N,
-                                                        const v2d* __restrict__ tw,
-                                                        const v2d* __restrict__ tws, MixCorr cp,
-                                                        M4StatsJob sj) {
+__global__ __launch_bounds__(kM4ColThreads) __attribute__((amdgpu_waves_per_eu(4)))
+void m4_cols2(const v2d* __restrict__ in, int in_rs, v2d* __restrict__ out, int N,
+              const v2d* __restrict__ tw, const v2d* __restrict__ tws, MixCorr cp,
+              M4StatsJob sj) {
   constexpr int N1 = A * B;
   static_assert(kM4ColThreads % kM4T2 == 0, "m4_cols2: a lane keeps one column");
   if ((int)blockIdx.y >= sj.main_rows) {   // the previous chunk's statistics (whole workgroups)
@@ -2172,11 +2158,7 @@ __global__ __launch_bounds__(kM4ColThreads) M4_COLS2_ATTR void m4_cols2(const v2
     if (r < sj.n) m4_stats_row(sj.top, r, sj.N1, N, sj.u0, sj.n_blocks, sj.nc, sj.spc, sj.stats);
     return;
   }
-#if M4_COLS2_PLANE
   __shared__ double sp[N1][kM4T2 + 1];   // one fp64 plane: real parts, then imaginary
-#else
-  __shared__ v2d s[N1][kM4T2 + 1];
-#endif
   const int N2 = N / N1;
   const int n2_0 = blockIdx.x * kM4T2;
   const long row = blockIdx.y;
@@ -2189,9 +2171,7 @@ __global__ __launch_bounds__(kM4ColThreads) M4_COLS2_ATTR void m4_cols2(const v2
   // x[B p + q], times W_N1^(q u), into LDS slot B u + q
   constexpr int kLanesQ = kM4ColThreads / kM4T2;   // values of q per pass
   constexpr int kItA = (B + kLanesQ - 1) / kLanesQ;
-#if M4_COLS2_PLANE
   double ai[kItA][A];
-#endif
 #pragma unroll
   for (int it = 0; it < kItA; it++) {
     const int q = threadIdx.x / kM4T2 + kLanesQ * it;
@@ -2212,22 +2192,16 @@ __global__ __launch_bounds__(kM4ColThreads) M4_COLS2_ATTR void m4_cols2(const v2
     dft<A>(v);
 #pragma unroll
     for (int u = 1; u < A; u++) v[u] = cmul(v[u], tws[q * u]);   // W_N1^(q u), q u < N1
-#if M4_COLS2_PLANE
 #pragma unroll
     for (int u = 0; u < A; u++) {
       sp[B * u + q][t] = v[u].x;
       ai[it][u] = v[u].y;
     }
-#else
-#pragma unroll
-    for (int u = 0; u < A; u++) s[B * u + q][t] = v[u];
-#endif
   }
   __syncthreads();
   // ---- stage B: task (u, t), u = threadIdx.x / kM4T2 < A: the B-point DFT over q;
   // output w is k1 = u + A w, times W_N^(n2 k1) = W_N^(n2 u) (W_N^(A n2))^w
   constexpr int kItB = (A + kLanesQ - 1) / kLanesQ;
-#if M4_COLS2_PLANE
   static_assert(kItB == 1, "m4_cols2: one B-point pass (the plane exchange)");
   v2d vb[B];
   {
@@ -2250,18 +2224,11 @@ __global__ __launch_bounds__(kM4ColThreads) M4_COLS2_ATTR void m4_cols2(const v2
 #pragma unroll
     for (int q = 0; q < B; q++) vb[q].y = u < A ? sp[B * u + q][t] : 0.0;
   }
-#endif
 #pragma unroll
   for (int it = 0; it < kItB; it++) {
     const int u = threadIdx.x / kM4T2 + kLanesQ * it;
     if (u >= A) continue;
-#if M4_COLS2_PLANE
     v2d (&v)[B] = vb;
-#else
-    v2d v[B];
-#pragma unroll
-    for (int q = 0; q < B; q++) v[q] = s[B * u + q][t];
-#endif
     dft<B>(v);
     if (col) {
       v2d wc = tw[n2 * u], ws = tw[A * n2];   // n2 u < N, A n2 < N
@@ -2287,16 +2254,13 @@ __global__ __launch_bounds__(kM4ColThreads) M4_COLS2_ATTR void m4_cols2(const v2
 // round trip).  164 VGPRs: 12 waves per CU.  The arithmetic is m4_rows' except the
 // stage-A twiddles (a recurrence, <= C roundings of drift).  38.192 Msps search
 // 1.14-1.15 -> 1.09-1.11 ms (profiles/r6/acq_generic_rows2_ab_r7b.log).
-#ifndef M4_ROWS2_WPE
-#define M4_ROWS2_WPE 3   // waves per SIMD of m4_rows2 (164 VGPRs)
-#endif
-#ifndef M4_ROWS2_ROWS
-#define M4_ROWS2_ROWS 4   // rows k1 per m4_rows2 workgroup (2: 150 VGPRs, 12 waves per CU, but
-                          // 22 of 64 lanes in the 31-point stage: 1.21 against 1.10 ms)
-#endif
-constexpr int kR2 = M4_ROWS2_ROWS;
+// Rows k1 per m4_rows2 workgroup (2: 150 VGPRs, 12 waves per CU, but 22 of 64 lanes in
+// the 31-point stage: 1.21 against 1.10 ms; 5: 0.995-1.006 against 0.948-0.957 ms,
+// DESIGN.md section 3)
+constexpr int kR2 = 4;
+// 3 waves per SIMD (164 VGPRs; 2: 1.09-1.11 against 1.05-1.07 ms)
 template <int C, int D, int MODE, bool ACC>
-__global__ __launch_bounds__(kM4RowThreads) __attribute__((amdgpu_waves_per_eu(M4_ROWS2_WPE)))
+__global__ __launch_bounds__(kM4RowThreads) __attribute__((amdgpu_waves_per_eu(3)))
 void m4_rows2(const v2d* __restrict__ Y, v2d* __restrict__ out, int out_rs, int N,
               const v2d* __restrict__ tws, double* __restrict__ pw, int acc,
               M4Top* __restrict__ top) {
@@ -2421,12 +2385,18 @@ int m4_plan(int N) {
   return 0;
 }
 
-// rows [src] -> DFT rows or the correlation's power rows, one chunk of `rows`
+// Chunk lane i of the four-step plan.  Lane 0 is the context's stream with the work and
+// power rows that the Bluestein and mixed-radix passes share; lane 1 has its own.
+acq_chunk_lane chunk_lane(const gnsscorr_acq_ctx* c, int i) {
+  if (i) return c->lane1;
+  return {c->stream, c->d_gA, c->d_gpw, c->d_m4top};
+}
+
+// rows [src] -> DFT rows or the correlation's power rows, one chunk of `rows` on lane ln
 template <int MODE_IN, int MODE_OUT>
-int m4_launch(gnsscorr_acq_ctx* c, const v2d* in, int in_rs, v2d* out, int out_rs, int rows,
-              const MixCorr& cp, double* pw, int acc,
-              const M4StatsJob* stats_job = nullptr, int lane = 0,
-              hipEvent_t after_cols = nullptr) {
+int m4_launch(gnsscorr_acq_ctx* c, const acq_chunk_lane& ln, const v2d* in, int in_rs, v2d* out,
+              int out_rs, int rows, const MixCorr& cp, double* pw, int acc,
+              const M4StatsJob* stats_job = nullptr, hipEvent_t after_cols = nullptr) {
   const int N = c->cfg.n_samples;
   M4StatsJob sj = stats_job ? *stats_job : M4StatsJob{};
   sj.main_rows = rows;
@@ -2435,9 +2405,9 @@ int m4_launch(gnsscorr_acq_ctx* c, const v2d* in, int in_rs, v2d* out, int out_r
   const int ey = sj.n > 0 ? (sj.n + per_y - 1) / per_y : 0;
   const v2d* tw = (const v2d*)c->d_twN;
   const v2d* tws1 = (const v2d*)c->d_twm4;   // W_N1^j, then W_N2^j from + N1
-  v2d* Y = (v2d*)(lane ? c->d_gA2 : c->d_gA);
-  M4Top* top = (M4Top*)(lane ? c->d_m4top2 : c->d_m4top);
-  hipStream_t st = lane ? c->m4_s2 : c->stream;
+  v2d* Y = (v2d*)ln.Y;
+  M4Top* top = (M4Top*)ln.top;
+  hipStream_t st = ln.stream;
   switch (c->m4) {
 #define M4_CASE(I, A, B, C, D)                                                                 \
   case I:                                                                                      \
@@ -2474,8 +2444,8 @@ int mx_dft_rows(gnsscorr_acq_ctx* c, const v2d* a, int src_rs, int rows, v2d* ou
   for (int r0 = 0; r0 < rows; r0 += c->g_chunk) {
     const int nr = rows - r0 < c->g_chunk ? rows - r0 : c->g_chunk;
     if (c->m4) {
-      const int rc = m4_launch<0, 0>(c, a + (long)r0 * src_rs, src_rs, out + (long)r0 * rs, rs, nr,
-                                     none, nullptr, 0);
+      const int rc = m4_launch<0, 0>(c, chunk_lane(c, 0), a + (long)r0 * src_rs, src_rs,
+                                     out + (long)r0 * rs, rs, nr, none, nullptr, 0);
       if (rc) return rc;
       continue;
     }
@@ -2534,11 +2504,10 @@ int mx_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int 
   for (int u0 = 0; u0 < n_units; u0 += step, ci++) {
     const int nu = n_units - u0 < step ? n_units - u0 : step;
     const int nb = nc ? n_blocks : 1;
-    const int lane = lanes == 2 ? ci % 2 : 0;
-    M4StatsJob& pend = pends[lane];
-    double* const pw = lane ? c->d_gpw2 : c->d_gpw;
-    hipStream_t const st = lane ? c->m4_s2 : c->stream;
-    if (lanes == 2 && ci == 1) HIP_TRY(hipStreamWaitEvent(c->m4_s2, c->m4_ev[0], 0));
+    const int li = lanes == 2 ? ci % 2 : 0;
+    const acq_chunk_lane ln = chunk_lane(c, li);
+    M4StatsJob& pend = pends[li];
+    if (lanes == 2 && ci == 1) HIP_TRY(hipStreamWaitEvent(ln.stream, c->m4_ev[0], 0));
     for (int b = 0; b < nb; b++) {
       MixCorr cp{(const v2d*)c->d_X64.p, (const v2d*)c->d_F64, c->rs64, n_blocks, nc ? b : -1,
                  n_bins, u0, d_gcode, d_gfreq, (const int2*)c->d_fmap64, n_groups,
@@ -2548,8 +2517,8 @@ int mx_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int 
         hipEvent_t const fork = lanes == 2 && ci == 0 && b == 0 ? c->m4_ev[0] : nullptr;
         const int rc =
             fused && b == nb - 1
-                ? m4_launch<1, 3>(c, nullptr, 0, nullptr, 0, nu, cp, pw, b > 0, sj, lane, fork)
-                : m4_launch<1, 2>(c, nullptr, 0, nullptr, 0, nu, cp, pw, b > 0, sj, lane, fork);
+                ? m4_launch<1, 3>(c, ln, nullptr, 0, nullptr, 0, nu, cp, ln.pw, b > 0, sj, fork)
+                : m4_launch<1, 2>(c, ln, nullptr, 0, nullptr, 0, nu, cp, ln.pw, b > 0, sj, fork);
         if (rc) return rc;
         if (sj) pend.n = 0;
         continue;
@@ -2573,7 +2542,7 @@ int mx_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int 
       }
     }
     if (fused) {   // carried by the lane's next column pass, or launched below
-      pend.top = (const M4Top*)(lane ? c->d_m4top2 : c->d_m4top);
+      pend.top = (const M4Top*)ln.top;
       pend.stats = c->d_stats.p;
       pend.n = nu;
       pend.u0 = u0;
@@ -2581,25 +2550,20 @@ int mx_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int 
       pend.n_blocks = n_blocks;
       pend.nc = (int)nc;
       pend.spc = spc;
-    } else if (stats1_exact(NK, spc))
-      hipLaunchKernelGGL(g_stats1_kernel, dim3(nu), dim3(kStatsThreads), 0, st,
-                         (const double*)pw, NK, u0, n_blocks, (int)nc, spc, c->d_stats.p,
-                         d_dump, dump_block, N);
-    else
-      hipLaunchKernelGGL(g_stats_kernel, dim3(nu), dim3(kGThreads), 0, st,
-                         (const double*)pw, NK, u0, n_blocks, (int)nc, spc, c->d_stats.p,
-                         d_dump, dump_block, N);
-    HIP_TRY(hipGetLastError());
+    } else {
+      const int rc = g_stats_launch(c, ln.stream, ln.pw, NK, nu, u0, n_blocks, nc, spc, d_dump,
+                                    dump_block);
+      if (rc) return rc;
+    }
   }
   for (int l = 0; l < 2; l++)
     if (pends[l].n > 0) {   // each lane's last chunk's statistics
-      hipLaunchKernelGGL(m4_stats_kernel, dim3(pends[l].n), dim3(64), 0,
-                         l ? c->m4_s2 : c->stream, pends[l].top, N1, N, pends[l].u0, n_blocks,
-                         (int)nc, spc, c->d_stats.p);
+      hipLaunchKernelGGL(m4_stats_kernel, dim3(pends[l].n), dim3(64), 0, chunk_lane(c, l).stream,
+                         pends[l].top, N1, N, pends[l].u0, n_blocks, (int)nc, spc, c->d_stats.p);
       HIP_TRY(hipGetLastError());
     }
-  if (lanes == 2) {
-    HIP_TRY(hipEventRecord(c->m4_ev[1], c->m4_s2));
+  if (lanes == 2) {   // join lane 1 back to the context stream
+    HIP_TRY(hipEventRecord(c->m4_ev[1], c->lane1.stream));
     HIP_TRY(hipStreamWaitEvent(c->stream, c->m4_ev[1], 0));
   }
   return GNSSCORR_OK;
@@ -2643,10 +2607,10 @@ int mx_init(gnsscorr_acq_ctx* c) {
                            c->g_chunk;
   if (c->m4 && !(fs && fs[0] == '0')) HIP_TRY(hipMalloc(&c->d_m4top, top_bytes));
   if (c->m4_lanes == 2) {
-    HIP_TRY(hipMalloc(&c->d_gA2, sizeof(double2) * (size_t)ya * c->g_chunk));
-    HIP_TRY(hipMalloc(&c->d_gpw2, sizeof(double) * (size_t)N * c->g_chunk));
-    if (c->d_m4top) HIP_TRY(hipMalloc(&c->d_m4top2, top_bytes));
-    HIP_TRY(hipStreamCreateWithFlags(&c->m4_s2, hipStreamNonBlocking));
+    HIP_TRY(hipMalloc(&c->lane1.Y, sizeof(double2) * (size_t)ya * c->g_chunk));
+    HIP_TRY(hipMalloc(&c->lane1.pw, sizeof(double) * (size_t)N * c->g_chunk));
+    if (c->d_m4top) HIP_TRY(hipMalloc(&c->lane1.top, top_bytes));
+    HIP_TRY(hipStreamCreateWithFlags(&c->lane1.stream, hipStreamNonBlocking));
     for (hipEvent_t& ev : c->m4_ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   }
   double2* h = (double2*)malloc(sizeof(double2) * N);
@@ -2733,15 +2697,15 @@ int acq64_init(gnsscorr_acq_ctx* c) {
 
 void acq64_free(gnsscorr_acq_ctx* c) {
   hostctx::release(c->d_F64, c->d_X64, c->d_in64, c->d_twN, c->d_fmap64, c->d_lead64, c->d_chirp,
-                   c->d_vf, c->d_twM, c->d_gA, c->d_gB, c->d_gpw, c->d_m4top, c->d_twm4, c->d_gA2,
-                   c->d_gpw2, c->d_m4top2);
+                   c->d_vf, c->d_twM, c->d_gA, c->d_gB, c->d_gpw, c->d_m4top, c->d_twm4,
+                   c->lane1.Y, c->lane1.pw, c->lane1.top);
   for (hipEvent_t& ev : c->m4_ev)
     if (ev) {
       (void)hipEventDestroy(ev);
       ev = nullptr;
     }
-  if (c->m4_s2) (void)hipStreamDestroy(c->m4_s2);
-  c->m4_s2 = nullptr;
+  if (c->lane1.stream) (void)hipStreamDestroy(c->lane1.stream);
+  c->lane1.stream = nullptr;
 }
 
 namespace {

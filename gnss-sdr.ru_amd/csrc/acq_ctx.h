@@ -8,6 +8,14 @@
 #include "gnsscorr_internal.h"
 #include "hostctx.h"
 
+// where one chunk of the generic engine's four-step correlation runs and what it writes
+struct acq_chunk_lane {
+  hipStream_t stream = nullptr;
+  double2* Y = nullptr;                 // chunk x N1 x pitch intermediate rows
+  double* pw = nullptr;                 // chunk x N power rows
+  void* top = nullptr;                  // chunk x N1 per-column top-2 (null: statistics pass)
+};
+
 struct gnsscorr_acq_ctx {
   gnsscorr_acq_cfg cfg;
   hipStream_t stream = nullptr;
@@ -18,7 +26,6 @@ struct gnsscorr_acq_ctx {
   float2* d_X = nullptr;     // IF spectra, permuted, [max_freqs*max_blocks][N]
   int4* d_fmap = nullptr;               // per frequency: spectrum class + PFA shift coordinates
   hostctx::DevBuf<float2> d_stage;      // forward-FFT staging rows
-  int pipe = 1;                         // GNSSCORR_ACQ_PIPE=0: one-unit-per-workgroup kernel
   // ---- fp64 path (prec == GNSSCORR_ACQ_F64)
   int plan64 = 0;                       // acq64 plan id (acq64_plan_for)
   double2* d_F64 = nullptr;             // code spectra, storage order of the plan, [max_codes][rs64]
@@ -29,8 +36,8 @@ struct gnsscorr_acq_ctx {
   int* d_lead64 = nullptr;              // classify scratch: per frequency, its class leader
   int rs64 = 0;                         // fp64 row stride (complex elements)
   // generic-N fp64 plan (plan64 == 3, any other N): Bluestein with radix-16
-  // Stockham FFTs of length M = 16^P >= 2N - 1 (acq64.hip)
-  int gM = 0, gP = 0;
+  // Stockham FFTs of length M, a power of two >= 2N - 1 (acq64.hip)
+  int gM = 0;
   double2* d_chirp = nullptr;           // c_n = exp(-i pi n^2 / N), n < N
   double2* d_vf = nullptr;              // FFT_M of the conjugate chirp (two-sided)
   double2* d_twM = nullptr;             // W_M^t, t < M
@@ -55,14 +62,11 @@ struct gnsscorr_acq_ctx {
   double2* d_twm4 = nullptr;            // four-step: W_N1^j (j < N1) then W_N2^j (j < N2)
   // four-step plan, two chunk lanes: odd chunks run on a second stream with their own
   // Y, power rows and column top-2 (m4_lanes == 2), so one chunk's column pass overlaps
-  // the other's row pass
+  // the other's row pass.  Lane 0 is the context's stream with d_gA, d_gpw and d_m4top
+  // (acq64.hip: chunk_lane); lane1 is what the second lane owns.
   int m4_lanes = 1;
-  hipStream_t m4_s2 = nullptr;
-  hipEvent_t m4_ev[3] = {nullptr, nullptr, nullptr};   // fork (after lane 0's first column
-                                                       // pass), join, spare
-  double2* d_gA2 = nullptr;
-  double* d_gpw2 = nullptr;
-  void* d_m4top2 = nullptr;
+  acq_chunk_lane lane1;
+  hipEvent_t m4_ev[2] = {nullptr, nullptr};   // fork (after lane 0's first column pass), join
   // ---- shared
   int n_codes = 0;
   int spec_blocks = 0, spec_freqs = 0;  // shape of the resident IF spectra

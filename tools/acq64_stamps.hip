@@ -62,7 +62,8 @@ int main() {
     (void)hipEventRecord(e0, 0);
     hipLaunchKernelGGL((acq64_corr_kernel<PlanA, 0, false>), dim3(units), dim3(PlanA::TB), 0, 0,
                        (const v2d*)dX, (const v2d*)dF, RS, NB, dgc, dgf, B, 16, dst,
-                       (double*)nullptr, -1, dord, dfm, (const v2d*)nullptr);
+                       (double*)nullptr, -1, dord, dfm, (const v2d*)nullptr,
+                       G, NB, (const int*)nullptr);   // one record: G groups, NB resident blocks
     (void)hipEventRecord(e1, 0);
     (void)hipEventSynchronize(e1);
   }
