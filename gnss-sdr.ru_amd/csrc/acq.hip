@@ -588,16 +588,18 @@ __device__ __forceinline__ float block_max0(float v, float* scratch) {
 }
 
 // ---- the one-unit correlation kernel --------------------------------------------
-// Serves the non-coherent searches (<NONCOHERENT, false>) and the power-row dump
-// of gnsscorr_acq_power_row (<BEST_OF_BLOCKS, true>); every best-of-blocks search
-// runs acq_corr_pipe_kernel below.
+// Serves the non-coherent searches (<NONCOHERENT, false>), the power-row dump
+// of gnsscorr_acq_power_row (<BEST_OF_BLOCKS, true>) and every search whose
+// second-peak window can hold two outputs of one thread (WIDE: 2 spc - 1 > 528,
+// see the row statistics below); every other best-of-blocks search runs
+// acq_corr_pipe_kernel below.
 // One workgroup = one work unit: BEST_OF_BLOCKS -> unit = (row, block), the
 // statistics of that block go to stats[unit]; NONCOHERENT -> unit = row, |.|^2
 // summed over the blocks in registers, stats to stats[row * n_blocks].
 // (Row-sized units would leave the last of ~5 rounds of workgroups 1/8 full.)
 // Every thread owns radix-31 group t (positions t*31 .. t*31+30) and threads
 // t < 496 also own one output of the 16 leftover groups (position 512*31 + t).
-template <int MODE, bool DUMP>
+template <int MODE, bool DUMP, bool WIDE>
 __global__ __launch_bounds__(kThreads) void acq_corr_kernel(
     const float2* __restrict__ X, const float2* __restrict__ F, int n_blocks,
     const int* __restrict__ group_code, const int* __restrict__ group_freq, int n_bins,
@@ -670,11 +672,14 @@ __global__ __launch_bounds__(kThreads) void acq_corr_kernel(
       pw[31] = extra ? pacc[31 % kAcc] : -1.f;
     }
     // Row statistics.  Thread t's 31 strided outputs sit at natural indices
-    // kb + 528 d (mod N), so ANY window of < 528 samples holds at most one of
-    // them: a per-thread top-2 (max + fmed3) gives the largest value outside
-    // the +-spc window without a second pass.  The leftover output (kx) is
-    // handled on its own.  Within-thread exact ties keep the first slot
-    // (slot order, not natural order).
+    // kb + 528 d (mod N), so a window of at most 528 samples (2 spc - 1 <= 528,
+    // spc <= 264) holds at most one of them: a per-thread top-2 (max + fmed3)
+    // gives the largest value outside the +-spc window without a second pass.
+    // A wider window can hold a thread's two largest outputs, and its runner-up
+    // would then be an in-window value: WIDE takes an exact second pass over the
+    // registers instead.  The leftover output (kx) is handled on its own.
+    // Within-thread exact ties keep the first slot (slot order, not natural
+    // order).
     float m1 = -1.f, m2 = -1.f;
     int d1 = 0;
 #pragma unroll
@@ -697,6 +702,16 @@ __global__ __launch_bounds__(kThreads) void acq_corr_kernel(
       return dist < spc || dist > N - spc;
     };
     float sv = in_win(k1) ? m2 : m1;
+    if (WIDE) {
+      sv = -1.f;
+      int k = kb;
+#pragma unroll
+      for (int d = 0; d < 31; d++) {
+        if (!in_win(k)) sv = fmaxf(sv, pw[d]);
+        k += E31;
+        if (k >= N) k -= N;
+      }
+    }
     if (extra && !in_win(kx)) sv = fmaxf(sv, pw[31]);
     sv = block_max0(sv, s_mx);
     best_pk = v;
@@ -714,7 +729,8 @@ __global__ __launch_bounds__(kThreads) void acq_corr_kernel(
 }
 
 // ---- the pipelined (persistent, two-role) correlation kernel -------------------
-// Serves every best-of-blocks search (no dump, no non-coherent sum: those stay with
+// Serves every best-of-blocks search with 2 spc - 1 <= 528 (no dump, no non-coherent
+// sum, no window wider than its top-2 statistics allow: those stay with
 // acq_corr_kernel above).
 // One workgroup per CU (the 128 KiB row fills the LDS), 1024 threads:
 //   waves 0-7  ("compute"): the in-LDS passes of unit u -- 3x11, radix-31 --
@@ -1077,7 +1093,9 @@ __device__ __forceinline__ PeakSlot read_argmax(const PeakSlot* slots) {
 }
 
 // second-peak candidate of this thread given the row argmax kk (open circular
-// window); each candidate set has at most one slot inside any window of < 528
+// window).  The slots of a candidate set lie 528 samples apart, so at most one of
+// them is inside a window of at most 528 samples: exact for 2 spc - 1 <= 528 only
+// (correlate_launch sends wider windows to acq_corr_kernel<.., WIDE>)
 __device__ __forceinline__ float second_cand(const RowCand& c, int kk, int spc) {
   auto in_win = [&](int k) {
     int dist = k - kk;
@@ -1743,14 +1761,22 @@ static int correlate_launch(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_g
                          dump_block);
     if (rc) return rc;
   } else {
-#define ACQ_CORR_LAUNCH(M, D)                                                                \
-  hipLaunchKernelGGL((acq_corr_kernel<M, D>), dim3(n_units), dim3(kThreads), 0, c->stream,    \
+#define ACQ_CORR_LAUNCH(M, D, W)                                                             \
+  hipLaunchKernelGGL((acq_corr_kernel<M, D, W>), dim3(n_units), dim3(kThreads), 0, c->stream, \
                      c->d_X, c->d_F, n_blocks, d_gcode, d_gfreq, n_bins, spc, c->d_stats.p,    \
                      d_dump, dump_block, c->d_order.p, c->d_fmap)
+  // the per-thread top-2 of the statistics is exact while the window (2 spc - 1
+  // samples) holds at most one of a thread's outputs, 528 apart; wider windows take
+  // the one-unit kernel's exact pass (the power-row dump searches at spc 16)
+  const bool wide = 2 * spc - 1 > E31;
   if (d_dump)
-    ACQ_CORR_LAUNCH(GNSSCORR_ACQ_BEST_OF_BLOCKS, true);
+    ACQ_CORR_LAUNCH(GNSSCORR_ACQ_BEST_OF_BLOCKS, true, false);
+  else if (mode == GNSSCORR_ACQ_NONCOHERENT && wide)
+    ACQ_CORR_LAUNCH(GNSSCORR_ACQ_NONCOHERENT, false, true);
   else if (mode == GNSSCORR_ACQ_NONCOHERENT)
-    ACQ_CORR_LAUNCH(GNSSCORR_ACQ_NONCOHERENT, false);
+    ACQ_CORR_LAUNCH(GNSSCORR_ACQ_NONCOHERENT, false, false);
+  else if (wide)
+    ACQ_CORR_LAUNCH(GNSSCORR_ACQ_BEST_OF_BLOCKS, false, true);
   else
     hipLaunchKernelGGL(acq_corr_pipe_kernel, dim3(n_units < c->n_cu ? n_units : c->n_cu),
                        dim3(kPipeThreads), 0, c->stream, c->d_X, c->d_F, n_blocks, d_gcode,

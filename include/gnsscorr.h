@@ -315,7 +315,9 @@ int gnsscorr_acq_set_prn_codes(gnsscorr_acq_ctx *ctx, int n_codes, const int32_t
  * frequencies [Hz] (wipe-off exp(i*2*pi*f*t), t = n/fs).  Groups: n_groups
  * searches, each of n_bins rows: group g uses code group_code[g] and
  * frequency index group_freq[g*n_bins + b] for bin b.
- * spc = samplesPerCodeChip (exclusion half-width for the second peak).
+ * spc = samplesPerCodeChip (exclusion half-width for the second peak),
+ * 1 <= spc <= n_samples / 2; the second peak is exact for every such spc in
+ * both precisions (windows too wide for the one-pass statistics take an exact pass).
  * Outputs: h_rows (n_groups*n_bins, may be NULL), h_res (n_groups). */
 int gnsscorr_acq_search(gnsscorr_acq_ctx *ctx, const int8_t *h_if, int iq, int n_blocks,
                         int mode, int n_freqs, const double *h_freqs, int n_groups,
