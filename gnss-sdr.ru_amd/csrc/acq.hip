@@ -21,9 +21,8 @@
 //    code replica are written to HBM already permuted into the correlation
 //    kernel's LDS order (sigma = n^-1 o k), so the hot kernel streams both
 //    operands with fully coalesced 8-byte loads and needs no gathers.
-//  * The hot kernel fuses: conj(X)*F, 3 FFT passes, |.|^2, the per-row
-//    max/argmax (first occurrence in natural order), the second peak outside
-//    the +-spc window, and the best-of-blocks or non-coherent combine over
+//  * The hot kernel fuses: conj(X)*F, 3 FFT passes, |.|^2, the row statistics
+//    (acq_peak.h), and the best-of-blocks or non-coherent combine over
 //    blocks -- the 16368-point power row never leaves registers.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -31,6 +30,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "acq_ctx.h"
+#include "acq_peak.h"
 #include "if2.h"
 
 // Diagnostic hook: tools/acq_pstamps.hip defines it to record s_memtime at the
@@ -293,11 +293,6 @@ __device__ __forceinline__ int out_base(int t) {
 //         and its inverse is the same N-periodic power row (GLONASS
 //         acquisition.sci:52-72, 113-135: "The rest are copies of the first 1msec")
 // mode 1: code row c; x[n] = code[c][n]
-__device__ __forceinline__ double grid_residue(double f, double delta) {
-  double r = fmod(f, delta);
-  return r < 0 ? r + delta : r;
-}
-
 constexpr int kFuseClass = 64;   // frequency tables this short are classified inside fwd16
 constexpr int kFwd1Threads = 256;
 constexpr int kFwd1G = kFwd1Threads / 16;   // radix-16 columns g per workgroup
@@ -549,10 +544,6 @@ struct PeakSlot {
   int k;
 };
 
-__device__ __forceinline__ bool better(float v1, int k1, float v0, int k0) {
-  return v1 > v0 || (v1 == v0 && k1 < k0);
-}
-
 // max value, smallest natural index among equals; result broadcast to all
 // threads.  One barrier: the scratch slots are next written after at least
 // one more barrier (the next block / unit), so no trailing barrier is needed.
@@ -590,7 +581,7 @@ __device__ __forceinline__ float block_max0(float v, float* scratch) {
 // ---- the one-unit correlation kernel --------------------------------------------
 // Serves the non-coherent searches (<NONCOHERENT, false>), the power-row dump
 // of gnsscorr_acq_power_row (<BEST_OF_BLOCKS, true>) and every search whose
-// second-peak window can hold two outputs of one thread (WIDE: 2 spc - 1 > 528,
+// second-peak window can hold two outputs of one thread (WIDE: !top2_exact(528, spc),
 // see the row statistics below); every other best-of-blocks search runs
 // acq_corr_pipe_kernel below.
 // One workgroup = one work unit: BEST_OF_BLOCKS -> unit = (row, block), the
@@ -611,8 +602,7 @@ __global__ __launch_bounds__(kThreads) void acq_corr_kernel(
   __shared__ float s_mx[kThreads / 64];
   constexpr bool kNonCoh = MODE == GNSSCORR_ACQ_NONCOHERENT;
   const int unit = order[blockIdx.x];
-  const int rowid = kNonCoh ? unit : unit / n_blocks;
-  const int blk0 = kNonCoh ? 0 : unit % n_blocks;
+  const auto [rowid, blk0] = unit_row(unit, n_blocks, kNonCoh);
   const int nblk = kNonCoh ? n_blocks : 1;
   const int g = rowid / n_bins, bin = rowid % n_bins;
   const int code = group_code[g];
@@ -671,65 +661,41 @@ __global__ __launch_bounds__(kThreads) void acq_corr_kernel(
       for (int d = 0; d < 31; d++) pw[d] = pacc[d % kAcc];
       pw[31] = extra ? pacc[31 % kAcc] : -1.f;
     }
-    // Row statistics.  Thread t's 31 strided outputs sit at natural indices
-    // kb + 528 d (mod N), so a window of at most 528 samples (2 spc - 1 <= 528,
-    // spc <= 264) holds at most one of them: a per-thread top-2 (max + fmed3)
-    // gives the largest value outside the +-spc window without a second pass.
-    // A wider window can hold a thread's two largest outputs, and its runner-up
-    // would then be an in-window value: WIDE takes an exact second pass over the
+    // Row statistics (acq_peak.h).  Thread t's 31 strided outputs sit at natural
+    // indices kb + 528 d (mod N): stride E31 = 528 for top2_exact, and the per-thread
+    // top-2 (slot order) answers in one pass.  WIDE: an exact second pass over the
     // registers instead.  The leftover output (kx) is handled on its own.
-    // Within-thread exact ties keep the first slot (slot order, not natural
-    // order).
-    float m1 = -1.f, m2 = -1.f;
-    int d1 = 0;
+    Top2<float> own{-1.f, -1.f, 0};   // (ak: the slot until the loop ends)
 #pragma unroll
-    for (int d = 0; d < 31; d++) {
-      const float v = pw[d];
-      d1 = v > m1 ? d : d1;
-      m2 = __builtin_amdgcn_fmed3f(m2, m1, v);
-      m1 = fmaxf(m1, v);
-    }
-    int k1 = kb + d1 * E31;
-    if (k1 >= N) k1 -= N;
-    float v = m1;
-    int kk = k1;
+    for (int d = 0; d < 31; d++) push_slot_order(pw[d], d, own.a1, own.a2, own.ak);
+    own.ak = kb + own.ak * E31;
+    if (own.ak >= N) own.ak -= N;
+    float v = own.a1;
+    int kk = own.ak;
     if (extra && better(pw[31], kx, v, kk)) { v = pw[31]; kk = kx; }
     block_argmax(v, kk, s_pk);
-    // second peak outside the open window (argmax - spc, argmax + spc), circular
-    auto in_win = [&](int k) {
-      int dist = k - kk;
-      if (dist < 0) dist += N;
-      return dist < spc || dist > N - spc;
-    };
-    float sv = in_win(k1) ? m2 : m1;
+    float sv = own.second(kk, spc, N);
     if (WIDE) {
       sv = -1.f;
       int k = kb;
 #pragma unroll
       for (int d = 0; d < 31; d++) {
-        if (!in_win(k)) sv = fmaxf(sv, pw[d]);
+        if (outside_window(k, kk, spc, N)) sv = fmaxf(sv, pw[d]);
         k += E31;
         if (k >= N) k -= N;
       }
     }
-    if (extra && !in_win(kx)) sv = fmaxf(sv, pw[31]);
+    if (extra && outside_window(kx, kk, spc, N)) sv = fmaxf(sv, pw[31]);
     sv = block_max0(sv, s_mx);
     best_pk = v;
     best_k = kk;
     best_sec = sv;
   }
-  if (t == 0) {
-    gnsscorr_acq_row r;
-    r.peak = best_pk;
-    r.argmax = best_k;
-    r.second = best_sec;
-    r.block = kNonCoh ? -1 : blk0;
-    stats[(long)rowid * n_blocks + blk0] = r;
-  }
+  if (t == 0) store_row(stats, rowid, blk0, n_blocks, kNonCoh, best_pk, best_k, best_sec);
 }
 
 // ---- the pipelined (persistent, two-role) correlation kernel -------------------
-// Serves every best-of-blocks search with 2 spc - 1 <= 528 (no dump, no non-coherent
+// Serves every best-of-blocks search with top2_exact(528, spc) (no dump, no non-coherent
 // sum, no window wider than its top-2 statistics allow: those stay with
 // acq_corr_kernel above).
 // One workgroup per CU (the 128 KiB row fills the LDS), 1024 threads:
@@ -881,13 +847,7 @@ __device__ __forceinline__ void pass33_r(float2* lds, int t, v2f (&r)[33]) {
 // pair is squared and folded into (m1, d1, m2) as soon as it exists, so no
 // outputs are held (VGPR budget of the 1024-thread kernel).  Slots are visited
 // in the order 0, 1, 30, 2, 29, ..., 15, 16; an exact tie keeps the earlier
-// visited slot.
-__device__ __forceinline__ void top2_push(float p, int d, float& m1, float& m2, int& d1) {
-  d1 = p > m1 ? d : d1;
-  m2 = __builtin_amdgcn_fmed3f(m2, m1, p);
-  m1 = fmaxf(m1, p);
-}
-
+// visited slot (push_slot_order).
 __device__ __forceinline__ void dft31_top2(v2f (&r)[33], float scale, float& m1, float& m2,
                                            int& d1) {
   constexpr int P = 31, H = 15;
@@ -917,8 +877,8 @@ __device__ __forceinline__ void dft31_top2(v2f (&r)[33], float scale, float& m1,
     const v2f re = __builtin_elementwise_fma(bc(B.y), (v2f){1.f, -1.f}, bc(A.x));
     const v2f im = __builtin_elementwise_fma(bc(B.x), (v2f){-1.f, 1.f}, bc(A.y));
     const v2f pw = __builtin_elementwise_fma(im, im, re * re) * bc(scale);
-    top2_push(pw.x, m, m1, m2, d1);
-    top2_push(pw.y, P - m, m1, m2, d1);
+    push_slot_order(pw.x, m, m1, m2, d1);
+    push_slot_order(pw.y, P - m, m1, m2, d1);
   }
 }
 
@@ -1046,8 +1006,7 @@ __device__ __forceinline__ UnitInfo unit_info(int u, const int* __restrict__ ord
 // Per-unit statistics of the pipelined kernel, carried across the next
 // unit's barriers by the compute role.
 struct RowCand {
-  float m1, m2, l1, l2;   // own group top-2, leftover pair top-2
-  int k1, kl;             // natural indices of m1 / l1
+  Top2<float> own, left;   // own group top-2, leftover pair top-2
 };
 
 // DPP lane exchanges (quad_perm 1032 / 2301, row_half_mirror, row_mirror):
@@ -1092,17 +1051,18 @@ __device__ __forceinline__ PeakSlot read_argmax(const PeakSlot* slots) {
   return PeakSlot{sv[0], sk[0]};
 }
 
-// second-peak candidate of this thread given the row argmax kk (open circular
-// window).  The slots of a candidate set lie 528 samples apart, so at most one of
-// them is inside a window of at most 528 samples: exact for 2 spc - 1 <= 528 only
+// second-peak candidate of this thread given the row argmax kk.  The slots of either
+// set lie E31 = 528 samples apart: exact where top2_exact(E31, spc) only
 // (correlate_launch sends wider windows to acq_corr_kernel<.., WIDE>)
+// Top2::second spelled locally as !outside_window: through the header's wrap the
+// compiler gives this kernel another instruction sequence, which measured slower.
 __device__ __forceinline__ float second_cand(const RowCand& c, int kk, int spc) {
   auto in_win = [&](int k) {
     int dist = k - kk;
     if (dist < 0) dist += N;
     return dist < spc || dist > N - spc;
   };
-  return fmaxf(in_win(c.k1) ? c.m2 : c.m1, in_win(c.kl) ? c.l2 : c.l1);
+  return fmaxf(in_win(c.own.ak) ? c.own.a2 : c.own.a1, in_win(c.left.ak) ? c.left.a2 : c.left.a1);
 }
 
 __device__ __forceinline__ void wave_max_slot(float v, float* slots) {
@@ -1128,12 +1088,7 @@ __device__ __forceinline__ float read_max(const float* slots) {
 
 __device__ __forceinline__ void write_stats(gnsscorr_acq_row* stats, const UnitInfo& uc,
                                             int n_blocks, float peak, int argmax, float second) {
-  gnsscorr_acq_row o;
-  o.peak = peak;
-  o.argmax = argmax;
-  o.second = second;
-  o.block = uc.blk;
-  stats[(long)uc.rowid * n_blocks + uc.blk] = o;
+  store_row(stats, uc.rowid, uc.blk, n_blocks, false, peak, argmax, second);
 }
 
 __device__ __forceinline__ gnsscorr_acq_row combine_blocks(const gnsscorr_acq_row* st,
@@ -1245,7 +1200,7 @@ __global__ __launch_bounds__(kPipeThreads) void acq_corr_pipe_kernel(
   }
   __syncthreads();
 
-  RowCand prev{-1.f, -1.f, -1.f, -1.f, 0, 0};
+  RowCand prev{{-1.f, -1.f, 0}, {-1.f, -1.f, 0}};
   PeakSlot pk{-1.f, 0};
   int it = 0;
   for (; u < n_units; u += G, it++) {
@@ -1285,15 +1240,16 @@ __global__ __launch_bounds__(kPipeThreads) void acq_corr_pipe_kernel(
     // P3: compute role -- radix-31 group tl, then (tl < 256) one output pair of
     // the 16 leftover groups from the side copy; stream role -- the row write
     if (!stream) {
-      RowCand c{-1.f, -1.f, -1.f, -1.f, 0, 0};
+      RowCand c{{-1.f, -1.f, 0}, {-1.f, -1.f, 0}};
       int d1;
-      dft31_top2(r, inv_n2, c.m1, c.m2, d1);
-      c.k1 = kb + d1 * E31;
-      if (c.k1 >= N) c.k1 -= N;
-      if (tl < kLeft * 16) leftover_pair(side, tw16, tl, inv_n2, c.l1, c.l2, c.kl);
-      float v = c.m1;
-      int k = c.k1;
-      pick(v, k, c.l1, c.kl);
+      dft31_top2(r, inv_n2, c.own.a1, c.own.a2, d1);
+      c.own.ak = kb + d1 * E31;
+      if (c.own.ak >= N) c.own.ak -= N;
+      if (tl < kLeft * 16)
+        leftover_pair(side, tw16, tl, inv_n2, c.left.a1, c.left.a2, c.left.ak);
+      float v = c.own.a1;
+      int k = c.own.ak;
+      pick(v, k, c.left.a1, c.left.ak);
       wave_argmax_slot(v, k, s_pk);
       prev = c;
     } else if (nxt) {
@@ -1765,10 +1721,9 @@ static int correlate_launch(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_g
   hipLaunchKernelGGL((acq_corr_kernel<M, D, W>), dim3(n_units), dim3(kThreads), 0, c->stream, \
                      c->d_X, c->d_F, n_blocks, d_gcode, d_gfreq, n_bins, spc, c->d_stats.p,    \
                      d_dump, dump_block, c->d_order.p, c->d_fmap)
-  // the per-thread top-2 of the statistics is exact while the window (2 spc - 1
-  // samples) holds at most one of a thread's outputs, 528 apart; wider windows take
-  // the one-unit kernel's exact pass (the power-row dump searches at spc 16)
-  const bool wide = 2 * spc - 1 > E31;
+  // a thread's outputs lie E31 = 528 apart; windows too wide for its top-2 take the
+  // one-unit kernel's exact pass (the power-row dump searches at spc 16)
+  const bool wide = !top2_exact(E31, spc);
   if (d_dump)
     ACQ_CORR_LAUNCH(GNSSCORR_ACQ_BEST_OF_BLOCKS, true, false);
   else if (mode == GNSSCORR_ACQ_NONCOHERENT && wide)

@@ -35,9 +35,8 @@
 //  * The inverse FFT is a forward FFT of conj(Y): |ifft(Y)|^2 = |fft(conj Y)|^2 / N^2.
 //  * The correlation kernel fuses conj(X)*F (with the bin's circular shift on
 //    the fs/N grid folded into the X load), the three stages, |.|^2, the
-//    non-coherent sum over blocks, and exact row statistics (argmax = first
-//    natural index of the maximum; second peak = max outside the open circular
-//    window (argmax - spc, argmax + spc)) in two register passes.
+//    non-coherent sum over blocks, and exact row statistics (acq_peak.h) in two
+//    register passes.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -45,6 +44,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "acq_ctx.h"
+#include "acq_peak.h"
 #include "if2.h"
 
 // Diagnostic hook: tools/acq64_stamps.hip defines ACQ64_STAMP(i) to record
@@ -677,9 +677,6 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l),
                           __builtin_amdgcn_readlane(__double2loint(v), l));
 }
-__device__ __forceinline__ bool better(double v1, int k1, double v0, int k0) {
-  return v1 > v0 || (v1 == v0 && k1 < k0);
-}
 template <int CTRL>
 __device__ __forceinline__ void argmax_step(double& v, int& k) {
   const double v2 = dpp_f64<CTRL>(-1.0, v);
@@ -746,10 +743,6 @@ __device__ __forceinline__ double block_max0(double v, double* sm, int tid = thr
 // fuse_n > 0 (short frequency tables) every workgroup first classifies the
 // table itself (acq64_classify_kernel's job) and workgroup 0 publishes it.
 constexpr int kFuseClass = 64;
-__device__ __forceinline__ double grid_residue(double f, double delta) {
-  double r = fmod(f, delta);
-  return r < 0 ? r + delta : r;
-}
 template <class P>
 __global__ __launch_bounds__(256) void acq64_wipe_kernel(
     const int8_t* __restrict__ src, int iq, int n_blocks, int coh, const double* __restrict__ cfreq_in,
@@ -993,8 +986,7 @@ __global__ __launch_bounds__(P::TB) void acq64_corr_kernel(
   const bool act = t < T;
   ACQ64_STAMP(0);
   const int unit = order[blockIdx.x];
-  const int rowid = kNC ? unit : unit / n_blocks;
-  const int blk0 = kNC ? 0 : unit % n_blocks;
+  const auto [rowid, blk0] = unit_row(unit, n_blocks, kNC);
   const int nblk = kNC ? n_blocks : 1;
   // records (gnsscorr_acq_set_records): virtual group gv = rec * gpr + g reads
   // blocks rec * n_blocks .. of the nbT resident blocks per class
@@ -1209,16 +1201,15 @@ __global__ __launch_bounds__(P::TB) void acq64_corr_kernel(
     for (int j = 0; j < 2; j++)
       pwl[j] = P::lvalid(t, j) ? s_extra[kE * T + j * P::LT + t] : -1.0;
   }
-  // ---- row statistics.  Per stage-3 group, the thread's outputs lie
-  // SPACING = N/R3 samples apart, so an exclusion window narrower than that
-  // holds at most one of them: a per-group top-2 (max with the first natural
-  // index of an exact tie, and the runner-up) gives the largest value outside
-  // the window in one pass.  Wider windows (spc > SPACING/2) take an exact
-  // second pass over the registers.
+  // ---- row statistics (acq_peak.h).  The thread's outputs lie at least
+  // SPACING = N/R3 samples apart: the stride of top2_exact for its top-2.  Wider
+  // windows take an exact second pass over the registers.
   auto wrap_add = [](int k, int d) {   // (k + d) mod N for k, d in [0, N)
     const unsigned u = (unsigned)(k + d);
     return (int)min(u, u - (unsigned)N);
   };
+  // (Top2::push and store_row written out here: called, they reorder this kernel's
+  // instructions)
   double a1 = -1.0, a2 = -1.0;
   int ak = INT_MAX;
 #pragma unroll
@@ -1229,7 +1220,7 @@ __global__ __launch_bounds__(P::TB) void acq64_corr_kernel(
 #pragma unroll
     for (int k3 = 0; k3 < R3; k3++) {
       const double v = pw[j][k3];
-      const bool take = v > a1 || (v == a1 && k < ak);
+      const bool take = better(v, k, a1, ak);
       a2 = fmax(a2, fmin(a1, v));
       ak = take ? k : ak;
       a1 = fmax(a1, v);
@@ -1252,15 +1243,9 @@ __global__ __launch_bounds__(P::TB) void acq64_corr_kernel(
   }
   block_argmax<P::NW>(bv, bk, s_v, s_k, t);
   ACQ64_STAMP(9);
-  // second peak: max outside the open circular window (bk - spc, bk + spc)
-  auto outside = [&](int k) {
-    int d = k - bk;
-    d += d < 0 ? N : 0;
-    return d >= spc && d <= N - spc;
-  };
   double sv = -1.0;
-  if (2 * spc - 1 <= P::SPACING) {
-    sv = outside(ak) ? a1 : a2;
+  if (top2_exact(P::SPACING, spc)) {
+    sv = outside_window(ak, bk, spc, N) ? a1 : a2;
   } else if (act) {
 #pragma unroll
     for (int j = 0; j < K3; j++) {
@@ -1269,7 +1254,7 @@ __global__ __launch_bounds__(P::TB) void acq64_corr_kernel(
       int k = base;
 #pragma unroll
       for (int k3 = 0; k3 < R3; k3++) {
-        if (outside(k)) sv = fmax(sv, pw[j][k3]);
+        if (outside_window(k, bk, spc, N)) sv = fmax(sv, pw[j][k3]);
         k = wrap_add(k, step);
       }
     }
@@ -1277,7 +1262,7 @@ __global__ __launch_bounds__(P::TB) void acq64_corr_kernel(
   if constexpr (L > 0) {
 #pragma unroll
     for (int j = 0; j < 2; j++)
-      if (P::lvalid(t, j) && outside(kl[j])) sv = fmax(sv, pwl[j]);
+      if (P::lvalid(t, j) && outside_window(kl[j], bk, spc, N)) sv = fmax(sv, pwl[j]);
   }
   sv = block_max0<P::NW>(sv, s_m, t);
   ACQ64_STAMP(10);
@@ -1494,10 +1479,22 @@ __global__ __launch_bounds__(kGThreads) void g_power_kernel(const v2d* __restric
   *o = acc ? *o + p : p;
 }
 
-// row statistics of a power row (acq64_corr_kernel's: first natural index of
-// the maximum, max outside the open circular window (argmax - spc, argmax + spc)).
+// Row statistics of a power row (acq_peak.h), two kernels that differ in their scan.
 // N: the lags searched, circular in N (the row length, or the kept lags of a
-// zero-padded search: E1/acquisition.sci:121-145); rs: the stride of the rows of pw
+// zero-padded search: E1/acquisition.sci:121-145); rs: the stride of the rows of pw.
+// Their common end: the power-row dump, the row record.
+template <int NT>
+__device__ __forceinline__ void g_stats_finish(const double* __restrict__ row, int N, int unit,
+                                               int n_blocks, int nc, double bv, int bk, double sv,
+                                               gnsscorr_acq_row* __restrict__ stats,
+                                               double* __restrict__ dump, int dump_block) {
+  const auto [rowid, blk0] = unit_row(unit, n_blocks, nc);
+  if (dump && !nc && blk0 == dump_block)
+    for (int k = threadIdx.x; k < N; k += NT) dump[(long)rowid * N + k] = row[k];
+  if (threadIdx.x == 0) store_row(stats, rowid, blk0, n_blocks, nc, bv, bk, sv);
+}
+
+// two passes, exact for every window: the argmax, then the maximum outside the window
 __global__ __launch_bounds__(kGThreads) void g_stats_kernel(const double* __restrict__ pw, int N,
                                                             int u0, int n_blocks, int nc, int spc,
                                                             gnsscorr_acq_row* __restrict__ stats,
@@ -1505,85 +1502,46 @@ __global__ __launch_bounds__(kGThreads) void g_stats_kernel(const double* __rest
                                                             int dump_block, int rs) {
   __shared__ double s_v[kGThreads / 64], s_m[kGThreads / 64];
   __shared__ int s_k[kGThreads / 64];
-  const int unit = u0 + blockIdx.x;
   const double* row = pw + (long)blockIdx.x * rs;
-  const int rowid = nc ? unit : unit / n_blocks;
-  const int blk0 = nc ? 0 : unit % n_blocks;
   double bv = -1.0;
   int bk = INT_MAX;
   for (int k = threadIdx.x; k < N; k += kGThreads)
     if (row[k] > bv) { bv = row[k]; bk = k; }     // first index within the thread's stride
   block_argmax<kGThreads / 64>(bv, bk, s_v, s_k);
   double sv = -1.0;
-  for (int k = threadIdx.x; k < N; k += kGThreads) {
-    int d = k - bk;
-    d += d < 0 ? N : 0;
-    if (d >= spc && d <= N - spc) sv = fmax(sv, row[k]);
-  }
+  for (int k = threadIdx.x; k < N; k += kGThreads)
+    if (outside_window(k, bk, spc, N)) sv = fmax(sv, row[k]);
   sv = block_max0<kGThreads / 64>(sv, s_m);
-  if (dump && !nc && blk0 == dump_block)
-    for (int k = threadIdx.x; k < N; k += kGThreads) dump[(long)rowid * N + k] = row[k];
-  if (threadIdx.x == 0) {
-    gnsscorr_acq_row r;
-    r.peak = bv;
-    r.second = sv;
-    r.argmax = bk;
-    r.block = nc ? -1 : blk0;
-    stats[(long)rowid * n_blocks + blk0] = r;
-  }
+  g_stats_finish<kGThreads>(row, N, u0 + blockIdx.x, n_blocks, nc, bv, bk, sv, stats, dump,
+                            dump_block);
 }
 
-// One-pass row statistics (the generic path's default): 1024 threads, thread t
-// scans k = t, t + 1024, ...  Its elements lie 1024 samples apart (fewer across the
-// wrap, stats1_exact), so the open window (argmax - spc, argmax + spc) holds at most
-// one of them when stats1_exact: the thread's runner-up stands in for its maximum when
-// that maximum is
-// inside the window (acq64_corr_kernel's per-thread top-2).  Same results as
-// g_stats_kernel's two passes; one read of the row.
+// One pass (the generic path's default): 1024 threads, thread t keeps the top-2 of
+// k = t, t + 1024, ...  Same results as g_stats_kernel where stats1_exact holds; one
+// read of the row.
 constexpr int kStatsThreads = 1024;
-// g_stats1_kernel is exact when no thread holds two samples inside one open window
-// of 2 spc - 1 positions.  A thread's samples are kStatsThreads apart, except across
-// the wrap: thread t's last sample t + kStatsThreads q and its first lie N - kStatsThreads q
-// apart, smallest (r = N - kStatsThreads floor((N - 1) / kStatsThreads)) for the
-// threads with the most samples (304 at N = 38192, 16 at N = 16400).
+// The stride of a thread's samples for top2_exact: kStatsThreads, except across the
+// wrap, where thread t's last sample t + kStatsThreads q and its first lie
+// N - kStatsThreads q apart, smallest (r = N - kStatsThreads floor((N - 1) / kStatsThreads))
+// for the threads with the most samples (304 at N = 38192, 16 at N = 16400).
 static inline bool stats1_exact(int N, int spc) {
   const int r = N <= kStatsThreads ? kStatsThreads : N - kStatsThreads * ((N - 1) / kStatsThreads);
-  return 2 * spc - 1 <= (r < kStatsThreads ? r : kStatsThreads);
+  return top2_exact(r < kStatsThreads ? r : kStatsThreads, spc);
 }
 __global__ __launch_bounds__(kStatsThreads) void g_stats1_kernel(
     const double* __restrict__ pw, int N, int u0, int n_blocks, int nc, int spc,
     gnsscorr_acq_row* __restrict__ stats, double* __restrict__ dump, int dump_block, int rs) {
   __shared__ double s_v[kStatsThreads / 64], s_m[kStatsThreads / 64];
   __shared__ int s_k[kStatsThreads / 64];
-  const int unit = u0 + blockIdx.x;
-  const double* row = pw + (long)blockIdx.x * rs;   // N, rs as in g_stats_kernel
-  const int rowid = nc ? unit : unit / n_blocks;
-  const int blk0 = nc ? 0 : unit % n_blocks;
-  double a1 = -1.0, a2 = -1.0;
-  int ak = INT_MAX;
-  for (int k = threadIdx.x; k < N; k += kStatsThreads) {
-    const double v = row[k];
-    a2 = v > a1 ? a1 : fmax(a2, v);
-    ak = v > a1 ? k : ak;       // strict: the first index of the thread's maximum
-    a1 = fmax(a1, v);
-  }
-  double bv = a1;
-  int bk = ak;
+  const double* row = pw + (long)blockIdx.x * rs;
+  Top2<double> own;
+  for (int k = threadIdx.x; k < N; k += kStatsThreads) own.push(row[k], k);
+  double bv = own.a1;
+  int bk = own.ak;
   block_argmax<kStatsThreads / 64>(bv, bk, s_v, s_k);
-  int d = ak == INT_MAX ? 0 : ak - bk;
-  d += d < 0 ? N : 0;
-  double sv = (ak != INT_MAX && d >= spc && d <= N - spc) ? a1 : a2;
-  sv = block_max0<kStatsThreads / 64>(sv, s_m);
-  if (dump && !nc && blk0 == dump_block)
-    for (int k = threadIdx.x; k < N; k += kStatsThreads) dump[(long)rowid * N + k] = row[k];
-  if (threadIdx.x == 0) {
-    gnsscorr_acq_row r;
-    r.peak = bv;
-    r.second = sv;
-    r.argmax = bk;
-    r.block = nc ? -1 : blk0;
-    stats[(long)rowid * n_blocks + blk0] = r;
-  }
+  const double sv = block_max0<kStatsThreads / 64>(own.second(bk, spc, N), s_m);
+  g_stats_finish<kStatsThreads>(row, N, u0 + blockIdx.x, n_blocks, nc, bv, bk, sv, stats, dump,
+                                dump_block);
 }
 
 // the row statistics of a chunk's nu power rows (units u0 ...) on stream st: the one
@@ -2063,60 +2021,32 @@ __host__ __device__ constexpr int m4_pitch(int n2) { return (n2 + kM4T2 - 1) / k
 
 
 // Per-column top-2 of a power row (MODE 3 of m4_rows2): the column k1 holds the
-// samples k1 + N1 k2, N1 apart, so when 2 spc - 1 <= N1 the open window around the
-// row's argmax holds at most one of them and {a1, first index, runner-up} per column
-// give the second peak exactly (g_stats1_kernel's argument with columns for threads).
+// samples k1 + N1 k2, so N1 is the stride of top2_exact for a column's top-2
+// (g_stats1_kernel's argument with columns for threads).
 struct M4Top {
   double a1, a2;
   int ak, pad;
 };
-// merge the top-2 of a disjoint set into (a1, ak, a2): ties keep the first index
-__device__ __forceinline__ void top2_merge(double& a1, int& ak, double& a2, double b1, int bk,
-                                           double b2) {
-  const bool take = better(b1, bk, a1, ak);
-  a2 = take ? fmax(a1, b2) : fmax(a2, b1);
-  ak = take ? bk : ak;
-  a1 = take ? b1 : a1;
-}
 
-// push one sample into (a1, ak, a2): top2_merge with b2 = -1, in 5 VALU operations
-// (a2 = max(a2, min(v, a1)) holds whether or not v takes the lead)
-__device__ __forceinline__ void top1_push(double& a1, int& ak, double& a2, double v, int k) {
-  const bool take = v > a1 || (v == a1 && k < ak);
-  a2 = fmax(a2, fmin(v, a1));
-  ak = take ? k : ak;
-  a1 = fmax(a1, v);
-}
-
-// one wave: the statistics of unit u0 + r from its per-column top-2 rows
+// one wave: the statistics of unit u0 + r from its per-column top-2 rows (the argmax
+// over the columns, then the largest of the columns' candidates for `second`).  Same
+// results as g_stats1_kernel on the power rows.
 __device__ __forceinline__ void m4_stats_row(const M4Top* __restrict__ top, int r, int N1, int N,
                                              int u0, int n_blocks, int nc, int spc,
                                              gnsscorr_acq_row* __restrict__ stats) {
   const int lane = threadIdx.x % 64;
-  const int unit = u0 + r;
   const M4Top* t = top + (long)r * N1;
-  const int rowid = nc ? unit : unit / n_blocks;
-  const int blk0 = nc ? 0 : unit % n_blocks;
+  const auto [rowid, blk0] = unit_row(u0 + r, n_blocks, nc);
   double bv = -1.0;
   int bk = INT_MAX;
   for (int c = lane; c < N1; c += 64)
     if (better(t[c].a1, t[c].ak, bv, bk)) { bv = t[c].a1; bk = t[c].ak; }
   wave_argmax(bv, bk);
   double sv = -1.0;
-  for (int c = lane; c < N1; c += 64) {
-    int d = t[c].ak - bk;
-    d += d < 0 ? N : 0;
-    sv = fmax(sv, (d >= spc && d <= N - spc) ? t[c].a1 : t[c].a2);
-  }
+  for (int c = lane; c < N1; c += 64)
+    sv = fmax(sv, Top2<double>{t[c].a1, t[c].a2, t[c].ak}.second(bk, spc, N));
   sv = wave_max(sv);
-  if (lane == 0) {
-    gnsscorr_acq_row o;
-    o.peak = bv;
-    o.second = sv;
-    o.argmax = bk;
-    o.block = nc ? -1 : blk0;
-    stats[(long)rowid * n_blocks + blk0] = o;
-  }
+  if (lane == 0) store_row(stats, rowid, blk0, n_blocks, nc, bv, bk, sv);
 }
 
 __global__ __launch_bounds__(64) void m4_stats_kernel(const M4Top* __restrict__ top, int N1,
@@ -2342,8 +2272,7 @@ void m4_rows2(const v2d* __restrict__ Y, v2d* __restrict__ out, int out_rs, int 
   // ---- stage B: the D-point DFT; output w is element k2 = ub + C w of column k1
   const int k1 = k1_0 + rb;
   const double sc = 1.0 / ((double)N * (double)N);
-  double a1 = -1.0, a2 = -1.0;
-  int ak = INT_MAX;
+  Top2<double> col;
   auto emit = [&](int w, v2d v) {
     if (!actB) return;
     const int d = k1 + N1 * (ub + C * w);   // < N
@@ -2352,7 +2281,7 @@ void m4_rows2(const v2d* __restrict__ Y, v2d* __restrict__ out, int out_rs, int 
       double* o = pw + row * N + d;
       const double val = ACC ? *o + q : q;   // (ACC: the running sums of earlier blocks)
       if constexpr (MODE == 2) *o = val;
-      else top1_push(a1, ak, a2, val, d);    // (the row's power is not stored)
+      else col.push(val, d);                 // (the row's power is not stored)
     } else {
       out[row * out_rs + d] = v;
     }
@@ -2363,18 +2292,13 @@ void m4_rows2(const v2d* __restrict__ Y, v2d* __restrict__ out, int out_rs, int 
     // the disjoint lane ranges [u, u + s) and [u + s, u + 2 s) within the column)
 #pragma unroll
     for (int st = 1; st < C; st <<= 1) {
-      const double b1 = __shfl_down(a1, kR2 * st, 64), b2 = __shfl_down(a2, kR2 * st, 64);
-      const int bk = __shfl_down(ak, kR2 * st, 64);
-      if (ub + st < C) top2_merge(a1, ak, a2, b1, bk, b2);
+      const Top2<double> o{__shfl_down(col.a1, kR2 * st, 64), __shfl_down(col.a2, kR2 * st, 64),
+                           __shfl_down(col.ak, kR2 * st, 64)};
+      if (ub + st < C) col.merge(o);
     }
-    if (t < kR2 && k1_0 + t < N1) top[row * N1 + k1_0 + t] = M4Top{a1, a2, ak, 0};
+    if (t < kR2 && k1_0 + t < N1) top[row * N1 + k1_0 + t] = M4Top{col.a1, col.a2, col.ak, 0};
   }
 }
-
-// Row statistics from the per-column top-2 (one wave per row): the argmax over the
-// columns, then the second peak as the maximum of each column's a1 when its argmax lies
-// outside the open circular window (argmax - spc, argmax + spc), else its runner-up.
-// Same results as g_stats1_kernel on the power rows.
 
 // the compiled four-step plans: {A, B, C, D}
 constexpr int kM4Plans[][4] = {{0, 0, 0, 0}, {7, 16, 11, 31}, {3, 16, 11, 31}};
@@ -2485,10 +2409,10 @@ int mx_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int 
   const int nrec = c->spec_recs;
   const int n_units = nrec * n_groups * n_bins * (nc ? 1 : n_blocks);
   // four-step plans: the row statistics ride on the last block's m4_rows2 (per-column
-  // top-2; its power rows are then not stored) unless the window can hold two samples
-  // of a column or the power rows are dumped
+  // top-2 of samples N1 apart; its power rows are then not stored) unless the window is
+  // too wide for that top-2 or the power rows are dumped
   const int N1 = m4 ? kM4Plans[m4][0] * kM4Plans[m4][1] : 0;
-  const bool fused = m4 && c->d_m4top && 2 * spc - 1 <= N1 && !d_dump;
+  const bool fused = m4 && c->d_m4top && top2_exact(N1, spc) && !d_dump;
   // equal chunks (7 x 375 rows rather than 6 x 385 + 314 at the bench's 2 624); with
   // two lanes an even count, chunk i on lane i % 2 (stream, Y, power rows, top-2 of
   // its own), forked from and joined back to the context stream

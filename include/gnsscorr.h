@@ -269,7 +269,8 @@ typedef struct {
   int    precision;       /* GNSSCORR_ACQ_F64 (default, 0) or GNSSCORR_ACQ_F32      */
 } gnsscorr_acq_cfg;
 
-/* Statistics of one correlation row (code x carrier frequency [x block]). */
+/* Statistics of one correlation row (code x carrier frequency [x block]).  The
+ * window's edge convention and the tie rules: csrc/acq_peak.h. */
 typedef struct {
   double  peak;           /* max |ifft|^2 of the row                               */
   double  second;         /* max outside the open +-spc window around argmax       */

@@ -48,12 +48,19 @@ SEED = 0x5EED0A00
 #   generic, N = 5000         stats1_exact: 1024 threads, 5000 - 4 * 1024 = 904 across
 #                             the wrap -> one pass up to spc = 452
 #   generic, N = 4111         4111 - 4 * 1024 = 15 across the wrap -> up to spc = 8
+#   generic forced at 16368   the {3, 16, 11, 31} four-step plan, N1 = 48: a column's
+#                             samples lie 48 apart, its fused top-2 serves up to
+#                             spc = 24; above that the rows go to the generic
+#                             statistics, 16368 - 15 * 1024 = 1008 across the wrap ->
+#                             one pass up to spc = 504, two passes above
 ENGINES = {
     "f64-16368": dict(fs=16.368e6, n=16368, ds=(264, 16)),
     "f64-16000": dict(fs=16.0e6, n=16000, ds=(200, 16)),
     "f32-16368": dict(fs=16.368e6, n=16368, ds=(264, 16)),
     "mixed-5000": dict(fs=5.0e6, n=5000, ds=(452, 16)),
     "bluestein-4111": dict(fs=4.111e6, n=4111, ds=(8, 16)),
+    "m4-16368": dict(fs=16.368e6, n=16368, ds=(24, 504, 16),
+                     env={"GNSSCORR_ACQ_GENERIC": "1"}, n1=48),
 }
 STATS_THREADS = 1024     # kStatsThreads of the generic engine's one-pass statistics
 

@@ -14,7 +14,8 @@ import pytest
 
 import acq_window_scenes as W
 
-# fp32 and fp64 at 16368 search the same scenes: one oracle run serves both
+# fp32 and fp64 at 16368 search the same scenes: one oracle run serves both (the
+# four-step engine shares their d = 16 references and adds its own distances)
 ENGINES = [e for e in W.ENGINES if e != "f32-16368"]
 
 
@@ -54,6 +55,13 @@ def test_edge_distances_straddle_the_engines_thresholds():
     for engine in ("mixed-5000", "bluestein-4111"):
         e = W.ENGINES[engine]
         assert W.stats1_exact(e["n"], e["ds"][0]) and not W.stats1_exact(e["n"], e["ds"][0] + 1)
+    # the four-step plan: the fused column top-2 up to 2 spc - 1 <= N1, then the generic
+    # statistics' one pass up to its own threshold, then their two passes
+    m4 = W.ENGINES["m4-16368"]
+    fused_d, one_pass_d = m4["ds"][:2]
+    assert 2 * fused_d - 1 <= m4["n1"] < 2 * (fused_d + 1) - 1
+    assert W.stats1_exact(m4["n"], fused_d + 1)
+    assert W.stats1_exact(m4["n"], one_pass_d) and not W.stats1_exact(m4["n"], one_pass_d + 1)
     for e in W.ENGINES.values():
         assert 16 in e["ds"] and max(e["ds"]) + 1 <= e["n"] // 2
 

@@ -34,8 +34,11 @@ MODES = ["best", "noncoherent"]
 def _make_ctx(gpu, engine, max_blocks=W.N_BLOCKS):
     e = W.ENGINES[engine]
     prec = gpu.ACQ_F32 if engine.startswith("f32") else gpu.ACQ_F64
-    ctx = gpu.AcqCtx(e["fs"], e["n"], max_freqs=4, max_blocks=max_blocks, max_codes=1,
-                     precision=prec)
+    with pytest.MonkeyPatch.context() as mp:     # the engine choice is read at create
+        for k, v in e.get("env", {}).items():
+            mp.setenv(k, v)
+        ctx = gpu.AcqCtx(e["fs"], e["n"], max_freqs=4, max_blocks=max_blocks, max_codes=1,
+                         precision=prec)
     ctx.set_codes(W.code_row(e["n"]))
     return ctx
 
@@ -108,6 +111,14 @@ def test_window_generic_mixed_radix_5000(gpu, ctxs, mode, case):
 @pytest.mark.parametrize("case", _window_params("bluestein-4111"))
 def test_window_generic_bluestein_4111(gpu, ctxs, mode, case):
     _window_case(gpu, ctxs("bluestein-4111"), "bluestein-4111", mode, case)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("case", _window_params("m4-16368"))
+def test_window_generic_four_step_16368(gpu, ctxs, mode, case):
+    """The generic engine forced at 16368 (the {3, 16, 11, 31} four-step plan): the fused
+    column top-2 (spc <= 24), the generic statistics' one pass (<= 504), their two."""
+    _window_case(gpu, ctxs("m4-16368"), "m4-16368", mode, case)
 
 
 def test_f32_power_row_beside_a_wide_window(gpu, ctxs):
