@@ -1692,10 +1692,12 @@ static int correlate_launch(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_g
   if (rc) return rc;
   if (n_groups < 1 || n_bins < 1 || spc < 1 ||
       spc > (c->keep ? c->keep : c->cfg.n_samples) / 2 ||
+      (c->keep && c->peak_period && 2 * spc >= c->peak_period) ||
       n_blocks != c->spec_blocks ||
       (c->prec == GNSSCORR_ACQ_F64 && c->spec_recs != c->recs)) {
     gnsscorr_set_error("gnsscorr_acq_correlate: bad arguments (groups %d, bins %d, spc %d, "
-                       "blocks %d vs spectra %d)", n_groups, n_bins, spc, n_blocks, c->spec_blocks);
+                       "blocks %d vs spectra %d, peak period %d needs 2 spc < period)", n_groups,
+                       n_bins, spc, n_blocks, c->spec_blocks, c->keep ? c->peak_period : 0);
     return GNSSCORR_EINVAL;
   }
   const int upr = mode == GNSSCORR_ACQ_NONCOHERENT ? 1 : n_blocks;  // work units per row
@@ -1992,6 +1994,12 @@ extern "C" int gnsscorr_acq_set_zero_padded(gnsscorr_acq_ctx* c, int keep) {
     gnsscorr_set_error("gnsscorr_acq_set_zero_padded: need 0 <= keep <= n_samples");
     return GNSSCORR_EINVAL;
   }
+  if (keep > 0 && keep < c->peak_period) {
+    gnsscorr_set_error("gnsscorr_acq_set_zero_padded: keep %d is below the peak period %d in "
+                       "force (set_peak_period(0) or set_zero_padded(0) first)", keep,
+                       c->peak_period);
+    return GNSSCORR_EINVAL;
+  }
   if (keep > 0) {
     const char* why = c->prec != GNSSCORR_ACQ_F64 ? "the fp64 precision"
                       : c->plan64 != 3 ? "the generic engine (not the compiled plans of "
@@ -2009,7 +2017,37 @@ extern "C" int gnsscorr_acq_set_zero_padded(gnsscorr_acq_ctx* c, int keep) {
     if (rc) return rc;
   }
   c->keep = keep;
+  if (!keep) c->peak_period = 0;   // the period rule lives inside the mode
   return GNSSCORR_OK;
+}
+
+extern "C" int gnsscorr_acq_set_peak_period(gnsscorr_acq_ctx* c, int period) {
+  if (!c || period < 0) {
+    gnsscorr_set_error("gnsscorr_acq_set_peak_period: need period >= 0");
+    return GNSSCORR_EINVAL;
+  }
+  if (period > 0 && !c->keep) {
+    gnsscorr_set_error("gnsscorr_acq_set_peak_period: needs a zero-padded search "
+                       "(set_zero_padded first)");
+    return GNSSCORR_EINVAL;
+  }
+  if (period > c->keep) {
+    gnsscorr_set_error("gnsscorr_acq_set_peak_period: need period <= keep (%d > %d)", period,
+                       c->keep);
+    return GNSSCORR_EINVAL;
+  }
+  c->peak_period = period;
+  return GNSSCORR_OK;
+}
+
+// the statistics kernels' own predicates (acq_peak.h), on the host
+extern "C" int gnsscorr_acq_second_peak_candidate(int k, int argmax, int spc, int n, int period) {
+  if (n < 1 || k < 0 || k >= n || argmax < 0 || argmax >= n || spc < 1 || period < 0 ||
+      (period ? period > n || 2 * spc >= period : 2 * spc > n)) {
+    gnsscorr_set_error("gnsscorr_acq_second_peak_candidate: bad arguments");
+    return GNSSCORR_EINVAL;
+  }
+  return period ? in_period_range(k, argmax, spc, period) : outside_window(k, argmax, spc, n);
 }
 
 extern "C" int gnsscorr_acq_sync(gnsscorr_acq_ctx* c) {

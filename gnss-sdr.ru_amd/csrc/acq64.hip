@@ -1495,11 +1495,13 @@ __device__ __forceinline__ void g_stats_finish(const double* __restrict__ row, i
 }
 
 // two passes, exact for every window: the argmax, then the maximum outside the window
+// (period = 0), or over the candidate range of GLONASS/L3/acquisition.sci:134-153 written
+// on `period` samples (set_peak_period; acq_peak.h: in_period_range)
 __global__ __launch_bounds__(kGThreads) void g_stats_kernel(const double* __restrict__ pw, int N,
                                                             int u0, int n_blocks, int nc, int spc,
                                                             gnsscorr_acq_row* __restrict__ stats,
                                                             double* __restrict__ dump,
-                                                            int dump_block, int rs) {
+                                                            int dump_block, int rs, int period) {
   __shared__ double s_v[kGThreads / 64], s_m[kGThreads / 64];
   __shared__ int s_k[kGThreads / 64];
   const double* row = pw + (long)blockIdx.x * rs;
@@ -1510,7 +1512,8 @@ __global__ __launch_bounds__(kGThreads) void g_stats_kernel(const double* __rest
   block_argmax<kGThreads / 64>(bv, bk, s_v, s_k);
   double sv = -1.0;
   for (int k = threadIdx.x; k < N; k += kGThreads)
-    if (outside_window(k, bk, spc, N)) sv = fmax(sv, row[k]);
+    if (period ? in_period_range(k, bk, spc, period) : outside_window(k, bk, spc, N))
+      sv = fmax(sv, row[k]);
   sv = block_max0<kGThreads / 64>(sv, s_m);
   g_stats_finish<kGThreads>(row, N, u0 + blockIdx.x, n_blocks, nc, bv, bk, sv, stats, dump,
                             dump_block);
@@ -1545,16 +1548,18 @@ __global__ __launch_bounds__(kStatsThreads) void g_stats1_kernel(
 }
 
 // the row statistics of a chunk's nu power rows (units u0 ...) on stream st: the one
-// pass where it is exact, else the two passes
+// pass where it is exact, else the two passes; always the two passes for the period
+// rule of a zero-padded search (set_peak_period), which no thread's top-2 answers
 int g_stats_launch(gnsscorr_acq_ctx* c, hipStream_t st, const double* pw, int NK, int nu, int u0,
                    int n_blocks, bool nc, int spc, double* d_dump, int dump_block) {
-  if (stats1_exact(NK, spc))
+  const int period = c->keep ? c->peak_period : 0;
+  if (!period && stats1_exact(NK, spc))
     hipLaunchKernelGGL(g_stats1_kernel, dim3(nu), dim3(kStatsThreads), 0, st, pw, NK, u0,
                        n_blocks, (int)nc, spc, c->d_stats.p, d_dump, dump_block,
                        c->cfg.n_samples);
   else
     hipLaunchKernelGGL(g_stats_kernel, dim3(nu), dim3(kGThreads), 0, st, pw, NK, u0, n_blocks,
-                       (int)nc, spc, c->d_stats.p, d_dump, dump_block, c->cfg.n_samples);
+                       (int)nc, spc, c->d_stats.p, d_dump, dump_block, c->cfg.n_samples, period);
   HIP_TRY(hipGetLastError());
   return GNSSCORR_OK;
 }

@@ -79,6 +79,8 @@ struct gnsscorr_acq_ctx {
   int coh = 1;                          // code periods per coherent block (set_coherent)
   int recs = 1;                         // records per search (set_records, fp64 plans)
   int keep = 0;                         // zero-padded search: lags kept (set_zero_padded; 0: off)
+  int peak_period = 0;                  // zero-padded search: the period the second-peak range is
+                                        // written on (set_peak_period; 0: circular in keep)
   const int32_t* d_group_rec = nullptr; // per group: its IF record (set_group_records; NULL: every
                                         // group on every record)
   int spec_recs = 1;                    // records of the resident IF spectra

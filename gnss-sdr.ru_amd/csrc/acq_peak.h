@@ -37,6 +37,22 @@ __host__ __device__ __forceinline__ bool outside_window(int k, int argmax, int s
   return d >= spc && d <= N - spc;
 }
 
+// The second-peak candidates of GLONASS/L3/acquisition.sci:134-153 (set_peak_period): the
+// range is written on a period S = samplesPerCode while the row holds several periods
+// (5 S there), so it is not a window circular in the row.  0-based, a = argmax in
+// [0, row length), s = spc, 2 s < S:
+//   a <= s            a + s <= k <= S + a - s      (index S itself is reachable: a = s)
+//   else a >= S - s   a + s - S <= k <= a - s      (linear, not wrapped, for every such a)
+//   else              k <= a - s  or  a + s <= k <= S - 1
+// The caller scans k over the row only, so an index at or past the row's end (S + a - s
+// with S = row length, on which Scilab would abort) is no candidate.  One thread's
+// top-2 does not answer this set: rows with a period take the exact pass.
+__host__ __device__ __forceinline__ bool in_period_range(int k, int a, int s, int S) {
+  if (a <= s) return k >= a + s && k <= S + a - s;
+  if (a >= S - s) return k >= a + s - S && k <= a - s;
+  return k <= a - s || (k >= a + s && k <= S - 1);
+}
+
 // A set of samples at least `stride` apart (circularly) has at most one member among
 // the window's 2 spc - 1 samples when this holds; then the set's {maximum, its index,
 // runner-up} answer `second` in one pass: the maximum if it is outside the window,

@@ -9,6 +9,7 @@
  *                            reproduced (see DESIGN.md "over-read").
  *  gnsscorr_ca_code          SoftGNSS generateCAcode.sci:42-87 (ICD G2 delays)
  *  gnsscorr_b1i_code         SoftGNSS COMPASS/B1 generateCAcode.sci:38-146
+ *  gnsscorr_l3_code          SoftGNSS GLONASS/L3 generateCAcode.sci:40-139
  *  gnsscorr_st_code          SoftGNSS GLONASS generateSTcode.sci:35-42
  *  gnsscorr_sample_code      makeCaTable.sci:64-72 / makeStTable.sci:60-67
  *  gnsscorr_sample_boc_code  GALILEO/E1/include/makeE1BCodesTable.sci:56-78
@@ -127,6 +128,40 @@ int gnsscorr_b1i_code(int prn, int8_t *out)
     out[i] = (int8_t)(b ? 1 : -1);
     r1 = ((r1 << 1) & 0x7FFu) | (unsigned)__builtin_parity(r1 & fb1);
     r2 = ((r2 << 1) & 0x7FFu) | (unsigned)__builtin_parity(r2 & fb2);
+  }
+  return GNSSCORR_OK;
+}
+
+/* GLONASS/L3/include/generateCAcode.sci:40-139 in bit form (a register entry of -1 is
+ * a set bit, stage k of the file's reg(1:14) / reg2(1:7) is bit k - 1).
+ *  G1 (:112-120): 14 stages from -1*[-1 -1 1 1 -1 1 -1 -1 1 1 1 -1 -1 -1], i.e. stages
+ *     3, 4, 6, 9, 10, 11 set; feedback stages 4, 8, 13, 14; output stage 14.
+ *  G2 (:127-136): 7 stages, feedback stages 6, 7, output stage 7; the initial state of
+ *     table row n (:40-105) is -1 * the 7-bit binary of n, MSB in stage 1, a one bit as
+ *     +1: stage j is set where bit 7 - j of n is.
+ *  chip (:139) = -(g1 * g2): +1 where the two output bits differ.
+ * The table as the file has it, not as the ICD does:
+ *  - the line commented #32 (:72) assigns row 31 again: id 31 starts from 32's state;
+ *  - row 32 is never assigned, Scilab zero-fills it, g2 and the code are all zero;
+ *  - row 64 (:105) repeats row 63. */
+int gnsscorr_l3_code(int id, int8_t *out)
+{
+  if (id < 1 || id > 64 || !out) return GNSSCORR_EINVAL;
+  if (id == 32) {
+    memset(out, 0, 10230);
+    return GNSSCORR_OK;
+  }
+  const unsigned n = id == 31 ? 32u : id == 64 ? 63u : (unsigned)id;
+  unsigned r2 = 0;
+  for (int j = 1; j <= 7; j++) r2 |= ((n >> (7 - j)) & 1u) << (j - 1);
+  unsigned r1 = 0x72Cu;
+  const unsigned fb1 = 0x3088u;   /* G1 stages 4, 8, 13, 14 (:117) */
+  const unsigned fb2 = 0x60u;     /* G2 stages 6, 7 (:133) */
+  for (int i = 0; i < 10230; i++) {
+    const unsigned b = ((r1 >> 13) ^ (r2 >> 6)) & 1u;
+    out[i] = (int8_t)(b ? 1 : -1);
+    r1 = ((r1 << 1) & 0x3FFFu) | (unsigned)__builtin_parity(r1 & fb1);
+    r2 = ((r2 << 1) & 0x7Fu) | (unsigned)__builtin_parity(r2 & fb2);
   }
   return GNSSCORR_OK;
 }

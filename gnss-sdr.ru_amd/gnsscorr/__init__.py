@@ -88,6 +88,19 @@ E1T_EPOCH = np.dtype([(f, "<f8") for f in E1T_SUMS] +
                       ("pllDiscrFilt", "<f8"), ("blksize", "<i4"), ("status", "<i4"),
                       ("segment", "<i4"), ("pad", "<i4")])
 assert E1T_CHAN.itemsize == 160 and E1T_EPOCH.itemsize == 176
+L3T_SUMS = ("I_E", "I_P", "I_L", "Q_E", "Q_P", "Q_L",          # pilot channel
+            "I_E2", "I_P2", "I_L2", "Q_E2", "Q_P2", "Q_L2")    # data channel
+L3T_CHAN = np.dtype([("code_id", "<i4"), ("stream", "<i4"), ("status", "<i4"),
+                     ("n_epochs", "<i4"), ("pos", "<i8"), ("pad", "<i8"),
+                     ("rem_code", "<f8"), ("rem_carr", "<f8"), ("code_freq", "<f8"),
+                     ("carr_freq", "<f8"), ("carr_freq_basis", "<f8"), ("old_code_nco", "<f8"),
+                     ("old_code_error", "<f8"), ("old_carr_nco", "<f8"),
+                     ("old_carr_error", "<f8"), ("i1", "<f8"), ("q1", "<f8"), ("pad2", "<f8")])
+L3T_EPOCH = np.dtype([(f, "<f8") for f in L3T_SUMS] +
+                     [("carrFreq", "<f8"), ("codeFreq", "<f8"), ("absoluteSample", "<f8"),
+                      ("dllDiscr", "<f8"), ("dllDiscrFilt", "<f8"), ("pllDiscr", "<f8"),
+                      ("pllDiscrFilt", "<f8"), ("blksize", "<i4"), ("status", "<i4")])
+assert L3T_CHAN.itemsize == 128 and L3T_EPOCH.itemsize == 160
 SDR_CHAN = np.dtype([("code_phase", "<f8"), ("carrier_phase", "<f8"),
                      ("carrier_phase_prev", "<f8"), ("code_phase_mod", "<f8"),
                      ("carrier_phase_mod", "<f8"), ("code_nco", "<f8"), ("carrier_nco", "<f8"),
@@ -179,6 +192,16 @@ class E1tCfg(C.Structure):
                 ("fll_noise_bw", C.c_double)]
 
 
+class L3tCfg(C.Structure):
+    _fields_ = [("file_type", C.c_int32), ("switch_iq", C.c_int32), ("code_length", C.c_int32),
+                ("device", C.c_int32), ("max_channels", C.c_int32), ("pad", C.c_int32),
+                ("samp_rate", C.c_double), ("code_freq_basis", C.c_double),
+                ("if_freq", C.c_double), ("nominal_freq", C.c_double),
+                ("dll_spacing", C.c_double), ("dll_noise_bw", C.c_double),
+                ("dll_damping", C.c_double), ("pll_noise_bw", C.c_double),
+                ("fll_noise_bw", C.c_double)]
+
+
 class SdrCorrCfg(C.Structure):
     _fields_ = [("device", C.c_int32), ("saturate", C.c_int32)]
 
@@ -210,6 +233,11 @@ EXPORTED_FUNCTIONS = [
     "gnsscorr_e1t_destroy", "gnsscorr_e1t_set_codes", "gnsscorr_e1t_track_dev",
     "gnsscorr_e1t_track", "gnsscorr_e1t_replay_dev", "gnsscorr_e1t_replay", "gnsscorr_e1t_sync",
     "gnsscorr_e1t_stream",
+    "gnsscorr_acq_set_peak_period", "gnsscorr_acq_second_peak_candidate", "gnsscorr_l3_code",
+    "gnsscorr_l3t_loop_coefs", "gnsscorr_l3t_init_chan", "gnsscorr_l3t_create",
+    "gnsscorr_l3t_destroy", "gnsscorr_l3t_track_dev", "gnsscorr_l3t_track",
+    "gnsscorr_l3t_replay_dev", "gnsscorr_l3t_replay", "gnsscorr_l3t_sync",
+    "gnsscorr_l3t_stream",
     "gnsscorr_sdr_prn_codes", "gnsscorr_sdr_sine_gen", "gnsscorr_sdr_acq_create",
     "gnsscorr_sdr_acq_destroy", "gnsscorr_sdr_acq_strong", "gnsscorr_sdr_acq_strong_dev",
     "gnsscorr_sdr_channel_start", "gnsscorr_sdr_channel_accum_dev", "gnsscorr_sdr_track_dev",
@@ -310,6 +338,19 @@ def lib() -> C.CDLL:
         "gnsscorr_e1t_replay_dev": (I, [P, I, P, I, P, P]),
         "gnsscorr_e1t_sync": (I, [P]),
         "gnsscorr_e1t_stream": (P, [P]),
+        "gnsscorr_acq_set_peak_period": (I, [P, I]),
+        "gnsscorr_acq_second_peak_candidate": (I, [I, I, I, I, I]),
+        "gnsscorr_l3_code": (I, [I, P]),
+        "gnsscorr_l3t_loop_coefs": (None, [C.POINTER(L3tCfg)] + [C.POINTER(D)] * 5),
+        "gnsscorr_l3t_init_chan": (I, [C.POINTER(L3tCfg), I, I, I64, I64, D, P]),
+        "gnsscorr_l3t_create": (I, [C.POINTER(P), C.POINTER(L3tCfg)]),
+        "gnsscorr_l3t_destroy": (I, [P]),
+        "gnsscorr_l3t_track_dev": (I, [P, P, I64, I64, I, P, I, I, P]),
+        "gnsscorr_l3t_track": (I, [P, P, I64, I64, I, P, I, I, P]),
+        "gnsscorr_l3t_replay": (I, [P, I, P, I, P, P]),
+        "gnsscorr_l3t_replay_dev": (I, [P, I, P, I, P, P]),
+        "gnsscorr_l3t_sync": (I, [P]),
+        "gnsscorr_l3t_stream": (P, [P]),
         "gnsscorr_sdr_prn_codes": (I, [P]),
         "gnsscorr_sdr_sine_gen": (None, [P, D, D, I]),
         "gnsscorr_sdr_acq_create": (I, [C.POINTER(P), C.POINTER(SdrAcqCfg)]),
@@ -531,6 +572,15 @@ def b1i_code(prn: int) -> np.ndarray:
     return out
 
 
+def l3_code(code_id: int) -> np.ndarray:
+    """GLONASS L3OC code of table row 1..64 as 10230 chips (GLONASS/L3/include/
+    generateCAcode.sci:40-139, its table as it stands: id 31 has 32's G2 state, id 32 is
+    all zero, id 64 equals 63).  Ids 1..31: pilot codes; 33..63: data codes of PRN id - 32."""
+    out = np.empty(10230, np.int8)
+    _check(lib().gnsscorr_l3_code(code_id, _ptr(out)), "gnsscorr_l3_code")
+    return out
+
+
 def st_code() -> np.ndarray:
     out = np.empty(511, np.int8)
     _check(lib().gnsscorr_st_code(_ptr(out)), "gnsscorr_st_code")
@@ -561,6 +611,14 @@ def e1b_bins(if_freq: float, band_khz: float, ms_code_len: int) -> np.ndarray:
     nb = int(round(band_khz * 2 * ms_code_len)) + 1
     k = np.arange(1, nb + 1)
     return if_freq - (band_khz / 2) * 1000 + (1000 / (2 * ms_code_len)) * (k - 1)
+
+
+def l3_bins(if_freq: float, band_khz: float) -> np.ndarray:
+    """The frequency grid of GLONASS/L3/acquisition.sci:66, 103-105: round(band * 2 * 5) + 1
+    bins from IF - band/2 kHz in steps of 1000 / (2 * 5) Hz."""
+    nb = int(round(band_khz * 2 * 5)) + 1
+    k = np.arange(1, nb + 1)
+    return if_freq - (band_khz / 2) * 1000 + (1000 / (2 * 5)) * (k - 1)
 
 
 def make_sigs(sigs) -> np.ndarray:
@@ -702,6 +760,13 @@ class AcqCtx:
         the second-peak window circular in keep (E1/acquisition.sci:112-145); 0: off."""
         _check(lib().gnsscorr_acq_set_zero_padded(self.h, int(keep)),
                "gnsscorr_acq_set_zero_padded")
+
+    def set_peak_period(self, period: int):
+        """gnsscorr_acq_set_peak_period: the second-peak range of GLONASS/L3/
+        acquisition.sci:134-153, written on `period` samples inside a zero-padded search's
+        keep lags (2 spc < period <= keep); 0: off, the window circular in keep."""
+        _check(lib().gnsscorr_acq_set_peak_period(self.h, int(period)),
+               "gnsscorr_acq_set_peak_period")
 
     def set_prn_codes(self, code_ids):
         """gnsscorr_acq_set_prn_codes: replicas generated on the device from code ids
@@ -984,6 +1049,105 @@ class E1tCtx:
     @property
     def stream(self) -> int:
         return lib().gnsscorr_e1t_stream(self.h)
+
+
+# ---------------------------------------------------------------- GLONASS L3OC float tracking
+def l3t_cfg(device: int = 0, **kw) -> L3tCfg:
+    """GLONASS/L3/initSettings.sci:64-96 defaults; keyword overrides use the Scilab names
+    (samplingFreq, IF, GLONASS_nominal_freq, dllCorrelatorSpacing, switchIQ, ...)."""
+    d = dict(fileType=2, switchIQ=0, samplingFreq=24e6, codeFreqBasis=10.23e6, codeLength=10230,
+             IF=-2.025e6, GLONASS_nominal_freq=1202.025e6, dllDampingRatio=0.7,
+             dllNoiseBandwidth=1.0, dllCorrelatorSpacing=0.4, pllNoiseBandwidth=25.0,
+             fllNoiseBandwidth=250.0)
+    unknown = set(kw) - set(d)
+    if unknown:
+        raise ValueError(f"unknown settings {sorted(unknown)}")
+    d.update(kw)
+    return L3tCfg(d["fileType"], d["switchIQ"], d["codeLength"], device, 0, 0, d["samplingFreq"],
+                  d["codeFreqBasis"], d["IF"], d["GLONASS_nominal_freq"],
+                  d["dllCorrelatorSpacing"], d["dllNoiseBandwidth"], d["dllDampingRatio"],
+                  d["pllNoiseBandwidth"], d["fllNoiseBandwidth"])
+
+
+def l3t_loop_coefs(cfg: L3tCfg):
+    """(tau1code, tau2code, k1, k2, k3) of a configuration (host only)."""
+    v = [C.c_double() for _ in range(5)]
+    lib().gnsscorr_l3t_loop_coefs(C.byref(cfg), *[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def l3t_init_chan(cfg: L3tCfg, prn, code_phase_1b, acq_freq, stream=0, skip=0) -> np.ndarray:
+    """One L3T_CHAN (shape (1,)) from an acquisition result (host only); PRN 1..31."""
+    out = np.zeros(1, L3T_CHAN)
+    _check(lib().gnsscorr_l3t_init_chan(C.byref(cfg), int(prn), int(stream), int(skip),
+                                        int(code_phase_1b), float(acq_freq), out.ctypes.data),
+           "gnsscorr_l3t_init_chan")
+    return out
+
+
+class L3tCtx:
+    """GLONASS L3OC float tracking (GLONASS/L3/tracking.sci) for many channels over
+    HBM-resident IQ records: pilot and data code on one code NCO, twelve sums, FLL and DLL
+    on the data channel, PLL on the pilot."""
+
+    def __init__(self, device: int = 0, **settings):
+        self.cfg = l3t_cfg(device, **settings)
+        h = C.c_void_p()
+        _check(lib().gnsscorr_l3t_create(C.byref(h), C.byref(self.cfg)), "gnsscorr_l3t_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().gnsscorr_l3t_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def loop_coefs(self):
+        return l3t_loop_coefs(self.cfg)
+
+    def init_chan(self, prn, code_phase_1b, acq_freq, stream=0, skip=0):
+        return l3t_init_chan(self.cfg, prn, code_phase_1b, acq_freq, stream, skip)
+
+    def init_chans(self, prns, code_phases_1b, acq_freqs, streams=None, skip=0):
+        n = len(prns)
+        streams = np.zeros(n, np.int64) if streams is None else np.asarray(streams)
+        return np.concatenate([self.init_chan(prns[i], code_phases_1b[i], acq_freqs[i],
+                                              streams[i], skip) for i in range(n)])
+
+    def track(self, d_if, stride, n_samples, chans, n_epochs, closed_loop=True):
+        """Host channel array in/out; returns epochs [n_ch, n_epochs]."""
+        assert chans.dtype == L3T_CHAN and chans.flags.c_contiguous
+        ep = np.zeros((len(chans), n_epochs), L3T_EPOCH)
+        _check(lib().gnsscorr_l3t_track(self.h, d_if, stride, n_samples, len(chans),
+                                        _ptr(chans), n_epochs, int(closed_loop), _ptr(ep)),
+               "gnsscorr_l3t_track")
+        return ep
+
+    def track_dev(self, d_if, stride, n_samples, n_ch, d_chan, n_epochs, d_epochs,
+                  closed_loop=True):
+        _check(lib().gnsscorr_l3t_track_dev(self.h, d_if, stride, n_samples, n_ch, d_chan,
+                                            n_epochs, int(closed_loop), d_epochs),
+               "gnsscorr_l3t_track_dev")
+
+    def replay(self, chans, sums):
+        """The loop half on given sums [n_ch, n_epochs, 12] (L3T_SUMS order); host
+        channel array in/out; returns epochs [n_ch, n_epochs]."""
+        assert chans.dtype == L3T_CHAN and chans.flags.c_contiguous
+        sums = np.ascontiguousarray(sums, dtype=np.float64)
+        n_ch, n_ep = sums.shape[0], sums.shape[1]
+        assert sums.shape == (len(chans), n_ep, 12)
+        ep = np.zeros((n_ch, n_ep), L3T_EPOCH)
+        _check(lib().gnsscorr_l3t_replay(self.h, n_ch, _ptr(chans), n_ep, _ptr(sums), _ptr(ep)),
+               "gnsscorr_l3t_replay")
+        return ep
+
+    def sync(self):
+        _check(lib().gnsscorr_l3t_sync(self.h), "gnsscorr_l3t_sync")
+
+    @property
+    def stream(self) -> int:
+        return lib().gnsscorr_l3t_stream(self.h)
 
 
 # ---------------------------------------------------------------- GPS-SDR integer acquisition

@@ -401,6 +401,33 @@ int gnsscorr_acq_set_group_records(gnsscorr_acq_ctx *ctx, const int32_t *d_group
  * returns the full row of n_samples powers.  (No reference counterpart for n_blocks
  * > 1: acquisition.sci searches one 2 x samplesPerCode block.) */
 int gnsscorr_acq_set_zero_padded(gnsscorr_acq_ctx *ctx, int keep);
+/* The second-peak rule of GLONASS/L3/acquisition.sci:134-153 for a zero-padded search
+ * whose kept lags span several code periods (L3: keep = 5 x samplesPerCode, the replica
+ * five periods signed by the overlay, :94-97, :121): the candidate range is written on
+ * `period` = samplesPerCode samples although the row is keep wide.  With period > 0,
+ * peak and argmax still run over lags 0 .. keep-1, and `second` is the maximum over
+ * the lags k < keep of this 0-based set, a = argmax, S = period, s = spc:
+ *   a <= s            a + s <= k <= S + a - s    (index S itself is reachable: the
+ *                                                 reference's own range, :143-144)
+ *   else a >= S - s   a + s - S <= k <= a - s    (:146-147; linear, not wrapped, for
+ *                                                 every a up to keep - 1)
+ *   else              k <= a - s  or  a + s <= k <= S - 1          (:149-150)
+ * in both search modes and on both generic engines; such rows take the exact two-pass
+ * statistics.  period = 0 (the default) is the window circular in keep described
+ * above.  Valid only while the zero-padded mode is on and for period <= keep
+ * (GNSSCORR_EINVAL otherwise); a search with 2 * spc >= period is GNSSCORR_EINVAL;
+ * gnsscorr_acq_set_zero_padded(ctx, 0) clears it.  The L3 replica takes no entry point
+ * of its own: gnsscorr_acq_set_codes_padded with code_len = 5 x samplesPerCode. */
+int gnsscorr_acq_set_peak_period(gnsscorr_acq_ctx *ctx, int period);
+/* While a period is in force, gnsscorr_acq_set_zero_padded(ctx, keep) with
+ * 0 < keep < period is GNSSCORR_EINVAL (the period would exceed the kept lags).
+ *
+ * Host only: 1 if lag k of a row of n searched lags is a candidate for `second` given
+ * the row's argmax, else 0 -- the predicate the statistics kernels themselves evaluate.
+ * period = 0: k is outside the open circular window (argmax - spc, argmax + spc) of n
+ * lags; period > 0: the range above.  GNSSCORR_EINVAL for k or argmax outside [0, n),
+ * spc < 1, period > n, 2 spc >= period, or (period 0) 2 spc > n. */
+int gnsscorr_acq_second_peak_candidate(int k, int argmax, int spc, int n, int period);
 /* gnsscorr_acq_set_codes for codes shorter than the transform: n_codes x code_len
  * int8 chips of +-1 (code_len <= n_samples), zero-extended to n_samples on the
  * device; their spectra are computed there and kept resident.  Like
@@ -622,6 +649,106 @@ int gnsscorr_e1t_replay(gnsscorr_e1t_ctx *ctx, int n_ch, gnsscorr_e1t_chan *h_ch
                         int n_epochs, const double *h_sums, gnsscorr_e1t_epoch *h_epochs);
 int gnsscorr_e1t_sync(gnsscorr_e1t_ctx *ctx);
 void *gnsscorr_e1t_stream(gnsscorr_e1t_ctx *ctx);
+
+/* ======================================================================
+ * GLONASS L3OC float tracking ("l3t"): the Scilab receiver's per-channel loop
+ *   POSTPROCESSING_SCILAB_RECEIVERS/GLONASS/L3/tracking.sci:123-423
+ *   settings: GLONASS/L3/initSettings.sci:64-96
+ * One epoch = 1 ms = one period of the 10230-chip code at 10.23 Mcps:
+ * blksize = ceil((10230 - remCode)/step) samples (:265-267).  One code NCO; its
+ * early / prompt / late indices ceil((remCode -/+ spc) + k*step) + 1 into
+ * [c(L) c c(1)] (:296-317) read two codes, the pilot generateCAcode(PRN) and the
+ * data channel generateCAcode(PRN + 32) (:172-179): twelve fp64 sums.  Closed
+ * loop (:353-392): the FLL discriminator atan2(cross, |dot|)/pi on the data
+ * prompt pair (no sign flip; I1..Q2 start at 0.001), the PLL discriminator
+ * atan(Q_P/I_P)/2pi on the pilot prompt, carrNco = old + k1 e - k2 e_old + k3 f
+ * (the FLL term added, unlike the other families), the envelope DLL on the data
+ * early / late sums, codeFreq = basis - codeNco + (carrFreq - IF)/(nominal/basis)
+ * (the ratio is 117.5).  blksize, the indices and the remCodePhase / remCarrPhase
+ * carries are fp64 without contraction: bit-exact.  The records stay resident in
+ * HBM as for the sgt family above.
+ * ==================================================================== */
+typedef struct gnsscorr_l3t_ctx gnsscorr_l3t_ctx;
+
+typedef struct {          /* initSettings.sci fields used by tracking.sci     */
+  int32_t file_type;      /* settings.fileType: 2 = int8 interleaved I,Q only; 1 (real
+                             samples) is refused with GNSSCORR_EINVAL          */
+  int32_t switch_iq;      /* settings.switchIQ (:278-282)                      */
+  int32_t code_length;    /* settings.codeLength: 10230 only                   */
+  int32_t device;
+  int32_t max_channels;
+  int32_t pad;
+  double  samp_rate;      /* settings.samplingFreq                             */
+  double  code_freq_basis;/* settings.codeFreqBasis                            */
+  double  if_freq;        /* settings.IF                                       */
+  double  nominal_freq;   /* settings.GLONASS_nominal_freq                     */
+  double  dll_spacing;    /* settings.dllCorrelatorSpacing [chips]             */
+  double  dll_noise_bw, dll_damping;   /* calcLoopCoef(dll.., dll.., 1)        */
+  double  pll_noise_bw, fll_noise_bw;  /* calcFLLPLLLoopCoef(pll, fll, PDIcarr=0.001) */
+} gnsscorr_l3t_cfg;
+
+typedef struct {          /* one tracking channel (tracking.sci:157-208 + loop state) */
+  int32_t code_id;        /* PRN 1..31: pilot code id PRN, data code id PRN + 32.
+                             gnsscorr_l3t_init_chan and gnsscorr_l3t_track refuse
+                             anything else (PRN 32 too: its pilot code is all zero in
+                             the reference, whose loop then divides 0/0);
+                             gnsscorr_l3t_track_dev does not check: a value outside
+                             1..31 is clamped to 0..31 (negative to 31), silently, and
+                             0 reads all +1 rows                                   */
+  int32_t stream;         /* which IF record (stride given per call)           */
+  int32_t status;         /* 0 tracking, 1 out of data (:286-292)              */
+  int32_t n_epochs;       /* epochs processed so far                           */
+  int64_t pos;            /* next complex sample of the record                 */
+  int64_t pad;
+  double  rem_code, rem_carr, code_freq, carr_freq, carr_freq_basis;
+  double  old_code_nco, old_code_error, old_carr_nco, old_carr_error;
+  double  i1, q1;         /* the previous data-channel prompt pair (:354-355)  */
+  double  pad2;
+} gnsscorr_l3t_chan;      /* 128 bytes */
+
+typedef struct {          /* trackResults(ch).* for one epoch (tracking.sci:401-422) */
+  double  i_e, i_p, i_l, q_e, q_p, q_l;         /* pilot channel               */
+  double  i_e2, i_p2, i_l2, q_e2, q_p2, q_l2;   /* data channel                */
+  double  carr_freq, code_freq, absolute_sample;
+  double  dll_discr, dll_discr_filt, pll_discr, pll_discr_filt;
+  int32_t blksize;        /* samples of the epoch; on a stop record the blksize that did
+                             not fit, or -1 if it is not a representable count    */
+  int32_t status;         /* 0 ok; 1 = this epoch was not processed (out of data) */
+} gnsscorr_l3t_epoch;     /* 160 bytes */
+
+/* calcLoopCoef.sci:39-43 (k = 1.0) and calcFLLPLLLoopCoef.sci:36-38. */
+void gnsscorr_l3t_loop_coefs(const gnsscorr_l3t_cfg *cfg, double *tau1code, double *tau2code,
+                             double *k1, double *k2, double *k3);
+/* Channel initialisation from an acquisition result (tracking.sci:164-208):
+ * pos = skip_samples + code_phase_1b - 1, codeFreq = basis alone (the aiding term of
+ * :184-186 is multiplied by 0), carrFreq = carrFreqBasis = acquired_freq,
+ * I1 = Q1 = 0.001.  prn 1..31. */
+int gnsscorr_l3t_init_chan(const gnsscorr_l3t_cfg *cfg, int prn, int stream,
+                           int64_t skip_samples, int64_t code_phase_1b, double acquired_freq,
+                           gnsscorr_l3t_chan *out);
+/* The padded code rows of every id are built here, once, and stay resident. */
+int gnsscorr_l3t_create(gnsscorr_l3t_ctx **out, const gnsscorr_l3t_cfg *cfg);
+int gnsscorr_l3t_destroy(gnsscorr_l3t_ctx *ctx);
+/* Run n_epochs epochs of n_ch channels (state in d_chan, updated in place);
+ * arguments as gnsscorr_sgt_track_dev.  closed_loop=0 holds both frequencies. */
+int gnsscorr_l3t_track_dev(gnsscorr_l3t_ctx *ctx, const int8_t *d_if, int64_t stream_stride,
+                           int64_t n_samples, int n_ch, gnsscorr_l3t_chan *d_chan,
+                           int n_epochs, int closed_loop, gnsscorr_l3t_epoch *d_epochs);
+/* Same with host channel state / results (synchronous); a PRN outside 1..31 is
+ * GNSSCORR_EINVAL. */
+int gnsscorr_l3t_track(gnsscorr_l3t_ctx *ctx, const int8_t *d_if, int64_t stream_stride,
+                       int64_t n_samples, int n_ch, gnsscorr_l3t_chan *h_chan, int n_epochs,
+                       int closed_loop, gnsscorr_l3t_epoch *h_epochs);
+/* The loop half alone, driven by given sums[(ch*n_epochs + e)*12 + j], j in the
+ * record's order (pilot I_E I_P I_L Q_E Q_P Q_L, then the data channel's): the same
+ * device code as the closed-loop tracker's epoch end.  No record, so no status 1
+ * from the record's end. */
+int gnsscorr_l3t_replay_dev(gnsscorr_l3t_ctx *ctx, int n_ch, gnsscorr_l3t_chan *d_chan,
+                            int n_epochs, const double *d_sums, gnsscorr_l3t_epoch *d_epochs);
+int gnsscorr_l3t_replay(gnsscorr_l3t_ctx *ctx, int n_ch, gnsscorr_l3t_chan *h_chan,
+                        int n_epochs, const double *h_sums, gnsscorr_l3t_epoch *h_epochs);
+int gnsscorr_l3t_sync(gnsscorr_l3t_ctx *ctx);
+void *gnsscorr_l3t_stream(gnsscorr_l3t_ctx *ctx);
 
 /* ======================================================================
  * GPS-SDR integer strong acquisition ("sdr"), bit-exact with the real-time
@@ -940,6 +1067,12 @@ int gnsscorr_ca_code(int prn, int8_t *h_chips1023);
 /* BeiDou B1I ranging code as +-1 chips (COMPASS/B1/include/generateCAcode.sci:38-146),
  * prn 1..37. */
 int gnsscorr_b1i_code(int prn, int8_t *h_chips2046);
+/* GLONASS L3OC ranging code of table row id 1..64 (GLONASS/L3/include/
+ * generateCAcode.sci:40-139: ids 1..31 the pilot codes, 33..63 the data-channel codes
+ * of PRN id - 32) as 10230 chips.  The file's table is reproduced as it stands: id 31
+ * starts G2 from the state of 32 (:72 assigns row 31 again), id 32 is never assigned
+ * and comes out as 10230 zeros, id 64 equals id 63 (:105). */
+int gnsscorr_l3_code(int id, int8_t *h_chips10230);
 /* GLONASS ST code as +-1 chips (generateSTcode.sci:35-42). */
 int gnsscorr_st_code(int8_t *h_chips511);
 /* Sample a +-1 chip sequence with the makeCaTable.sci:64-72 rule:
