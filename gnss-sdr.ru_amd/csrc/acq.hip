@@ -1638,9 +1638,17 @@ static int check_search(gnsscorr_acq_ctx* c, int n_blocks, int n_freqs, int mode
                        "code period per block, one record and no group-record table");
     return GNSSCORR_EINVAL;
   }
+  if (mode == GNSSCORR_ACQ_CONCAT &&
+      (!c->keep || c->bstride != c->keep || (long)n_blocks * c->keep > 0x7fffffffL)) {
+    gnsscorr_set_error("gnsscorr_acq: GNSSCORR_ACQ_CONCAT needs a zero-padded search "
+                       "(set_zero_padded) and block stride == keep (stride %d, keep %d)",
+                       c->bstride, c->keep);
+    return GNSSCORR_EINVAL;
+  }
   if (n_blocks < 1 || n_blocks * c->coh * c->recs > c->cfg.max_blocks || n_freqs < 1 ||
       n_freqs > c->cfg.max_freqs || c->n_codes < 1 ||
-      (mode != GNSSCORR_ACQ_BEST_OF_BLOCKS && mode != GNSSCORR_ACQ_NONCOHERENT)) {
+      (mode != GNSSCORR_ACQ_BEST_OF_BLOCKS && mode != GNSSCORR_ACQ_NONCOHERENT &&
+       mode != GNSSCORR_ACQ_CONCAT)) {
     gnsscorr_set_error("gnsscorr_acq: bad arguments (blocks %d x coherent %d x records %d / "
                        "max_blocks %d, freqs %d/%d, codes %d)", n_blocks, c->coh, c->recs,
                        c->cfg.max_blocks, n_freqs, c->cfg.max_freqs, c->n_codes);
@@ -1744,7 +1752,8 @@ static int correlate_launch(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_g
   c->stat_groups = n_groups;
   c->stat_recs = nrec;
   c->stat_bins = n_bins;
-  c->stat_blocks = n_blocks;
+  // a concatenated search leaves one record per (group, bin): nothing to combine
+  c->stat_blocks = mode == GNSSCORR_ACQ_CONCAT ? 1 : n_blocks;
   c->stat_mode = mode;
   if (d_rows || d_res) {
     if (!d_rows || (d_res && !d_freqs)) {
@@ -1752,7 +1761,8 @@ static int correlate_launch(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_g
       return GNSSCORR_EINVAL;
     }
     hipLaunchKernelGGL(acq_select_kernel, dim3(gall), dim3(64), 0, c->stream, c->d_stats.p,
-                       gall, n_bins, n_blocks, mode, d_gfreq, d_freqs, d_rows, d_res, n_groups);
+                       gall, n_bins, c->stat_blocks, mode, d_gfreq, d_freqs, d_rows, d_res,
+                       n_groups);
     HIP_TRY(hipGetLastError());
   }
   return GNSSCORR_OK;
@@ -1763,7 +1773,9 @@ static int search_launch(gnsscorr_acq_ctx* c, const int8_t* d_if, int iq, int n_
                          const int32_t* d_gcode, const int32_t* d_gfreq, int spc,
                          gnsscorr_acq_row* d_rows, gnsscorr_acq_result* d_res, double* d_dump,
                          int dump_block) {
-  int rc = spectra_launch(c, d_if, iq, n_blocks, n_freqs, d_freqs);
+  // a concatenated search that cannot run is refused before its spectra are made
+  int rc = mode == GNSSCORR_ACQ_CONCAT ? check_search(c, n_blocks, n_freqs, mode) : GNSSCORR_OK;
+  if (!rc) rc = spectra_launch(c, d_if, iq, n_blocks, n_freqs, d_freqs);
   if (rc) return rc;
   return correlate_launch(c, n_blocks, mode, n_groups, n_bins, d_freqs, d_gcode, d_gfreq, spc,
                           d_rows, d_res, d_dump, dump_block);
@@ -1854,9 +1866,12 @@ static int stage_host(gnsscorr_acq_ctx* c, const int8_t* h_if, int iq, int n_blo
   if (!rc) rc = hostctx::grow(c->d_gcode, n_groups);
   if (!rc) rc = hostctx::grow(c->d_gfreq, R);
   if (rc) return rc;
+  // samples of the record: blocks end to end, or with a block stride the last block's
+  // end (one record and one code period per block then: set_zero_padded)
+  const int64_t n_if = c->bstride ? (int64_t)(n_blocks - 1) * c->bstride + c->cfg.n_samples
+                                  : (int64_t)c->recs * n_blocks * c->coh * c->cfg.n_samples;
   HIP_TRY(hipMemcpyAsync(c->d_if, h_if,
-                         (size_t)if_bytes((int64_t)c->recs * n_blocks * c->coh * c->cfg.n_samples *
-                                              ((iq & GNSSCORR_IF_IQ) ? 2 : 1),
+                         (size_t)if_bytes(n_if * ((iq & GNSSCORR_IF_IQ) ? 2 : 1),
                                           iq & GNSSCORR_IF_PACKED2),
                          hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->d_freqs, h_freqs, sizeof(double) * n_freqs, hipMemcpyHostToDevice,
@@ -2018,6 +2033,25 @@ extern "C" int gnsscorr_acq_set_zero_padded(gnsscorr_acq_ctx* c, int keep) {
   }
   c->keep = keep;
   if (!keep) c->peak_period = 0;   // the period rule lives inside the mode
+  if (!keep && c->bstride) {       // and so does the block stride
+    c->bstride = 0;
+    c->spec_blocks = 0;   // resident spectra were made with the previous setting
+  }
+  return GNSSCORR_OK;
+}
+
+extern "C" int gnsscorr_acq_set_block_stride(gnsscorr_acq_ctx* c, int stride) {
+  if (!c || stride < 0 || stride > c->cfg.n_samples) {
+    gnsscorr_set_error("gnsscorr_acq_set_block_stride: need 0 <= stride <= n_samples");
+    return GNSSCORR_EINVAL;
+  }
+  if (stride > 0 && !c->keep) {
+    gnsscorr_set_error("gnsscorr_acq_set_block_stride: needs a zero-padded search "
+                       "(set_zero_padded first)");
+    return GNSSCORR_EINVAL;
+  }
+  if (stride != c->bstride) c->spec_blocks = 0;   // resident spectra: the previous setting
+  c->bstride = stride;
   return GNSSCORR_OK;
 }
 

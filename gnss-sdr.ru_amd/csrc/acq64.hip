@@ -1564,9 +1564,81 @@ int g_stats_launch(gnsscorr_acq_ctx* c, hipStream_t st, const double* pw, int NK
   return GNSSCORR_OK;
 }
 
+// Row statistics of a concatenated search (GNSSCORR_ACQ_CONCAT): the row of one (group,
+// bin) is the kept lags of its n_blocks blocks laid end to end
+// (COMPASS/B1/acquisition_7x3ms.sci:139-145), index q at lag q % keep of power row
+// q / keep; the blocks' power rows are consecutive, rs apart.  One workgroup per
+// (group, bin): the argmax over the n_blocks * keep lags (first index among equals, so
+// the first of exactly equal blocks, :154-157), then the maximum over the candidates
+// with n = n_blocks * keep -- outside the window circular in n, or with a period the
+// range of :159-176 (acq_peak.h: in_period_range), scanned over its span only
+// (period_span: at most period + 1 lags of the row, which may cross a block boundary).
+__global__ __launch_bounds__(kGThreads) void g_stats_concat_kernel(
+    const double* __restrict__ pw, int keep, int n_blocks, int r0, int spc,
+    gnsscorr_acq_row* __restrict__ stats, int rs, int period) {
+  __shared__ double s_v[kGThreads / 64], s_m[kGThreads / 64];
+  __shared__ int s_k[kGThreads / 64];
+  const double* rows = pw + (long)blockIdx.x * n_blocks * rs;
+  const int n = n_blocks * keep;
+  double bv = -1.0;
+  int bk = INT_MAX;
+  for (int b = 0; b < n_blocks; b++) {
+    const double* row = rows + (long)b * rs;
+    for (int k = threadIdx.x; k < keep; k += kGThreads)
+      if (better(row[k], b * keep + k, bv, bk)) { bv = row[k]; bk = b * keep + k; }
+  }
+  block_argmax<kGThreads / 64>(bv, bk, s_v, s_k);
+  double sv = -1.0;
+  if (period) {
+    const PeriodSpan sp = period_span(bk, spc, period);
+    const int hi = sp.hi < n ? sp.hi : n - 1;
+    for (int q = sp.lo + threadIdx.x; q <= hi; q += kGThreads)
+      if (in_period_range(q, bk, spc, period))
+        sv = fmax(sv, rows[(long)(q / keep) * rs + q % keep]);
+  } else {
+    for (int b = 0; b < n_blocks; b++) {
+      const double* row = rows + (long)b * rs;
+      for (int k = threadIdx.x; k < keep; k += kGThreads)
+        if (outside_window(b * keep + k, bk, spc, n)) sv = fmax(sv, row[k]);
+    }
+  }
+  sv = block_max0<kGThreads / 64>(sv, s_m);
+  if (threadIdx.x == 0) {
+    gnsscorr_acq_row r;
+    r.peak = bv;
+    r.second = sv;
+    r.argmax = bk;
+    r.block = bk / keep;
+    stats[r0 + blockIdx.x] = r;   // one record per (group, bin): acq_select with one block
+  }
+}
+
+// the statistics of a concatenated search's chunk: units u0 .. u0 + nu - 1 are whole
+// rows (both a multiple of n_blocks), their power rows consecutive in pw
+int g_stats_concat_launch(gnsscorr_acq_ctx* c, hipStream_t st, const double* pw, int nu, int u0,
+                          int n_blocks, int spc) {
+  hipLaunchKernelGGL(g_stats_concat_kernel, dim3(nu / n_blocks), dim3(kGThreads), 0, st, pw,
+                     c->keep, n_blocks, u0 / n_blocks, spc, c->d_stats.p, c->cfg.n_samples,
+                     c->peak_period);
+  HIP_TRY(hipGetLastError());
+  return GNSSCORR_OK;
+}
+
+// rows per chunk of a search: for a concatenated search whole rows of n_blocks units
+int concat_chunk(const gnsscorr_acq_ctx* c, int n_blocks, int* chunk) {
+  *chunk = c->g_chunk - c->g_chunk % n_blocks;
+  if (*chunk < n_blocks) {
+    gnsscorr_set_error("gnsscorr_acq: GNSSCORR_ACQ_CONCAT needs a chunk of at least n_blocks "
+                       "rows (%d < %d: max_codes x max_freqs x max_blocks too small)",
+                       c->g_chunk, n_blocks);
+    return GNSSCORR_EINVAL;
+  }
+  return GNSSCORR_OK;
+}
+
 // wipe-off rows in natural order (acq64_wipe_kernel with a runtime N)
 __global__ __launch_bounds__(256) void g_wipe_kernel(const int8_t* __restrict__ src, int iq,
-                                                     int n_blocks, int coh,
+                                                     int n_blocks, int coh, long bstride,
                                                      const double* __restrict__ cfreq,
                                                      const int* __restrict__ n_cls_dev, double ts,
                                                      int N, v2d* __restrict__ out) {
@@ -1578,7 +1650,9 @@ __global__ __launch_bounds__(256) void g_wipe_kernel(const int8_t* __restrict__ 
     const double f = cfreq[cls];
     const bool cplx = iq & GNSSCORR_IF_IQ, pk = iq & GNSSCORR_IF_PACKED2;
     const int ne = cplx ? 2 : 1;
-    const long e0 = (long)blk * coh * N * ne;
+    // the block's first element: bstride samples after the previous block's (coh * N end
+    // to end, or the block stride of set_block_stride: acquisition_7x3ms.sci:52-58)
+    const long e0 = (long)blk * bstride * ne;
     double re = 0.0, im = 0.0;
     for (int p = 0; p < coh; p++) {
       const long m = n + (long)p * N;
@@ -1745,7 +1819,8 @@ int g_spectra(gnsscorr_acq_ctx* c, const int8_t* d_if, int iq, int n_blocks, int
   const long work = (long)rows * N;
   const int grid = (int)((work + 255) / 256 < 2048 ? (work + 255) / 256 : 2048);
   hipLaunchKernelGGL(g_wipe_kernel, dim3(grid), dim3(256), 0, c->stream, d_if, iq, n_blocks,
-                     c->coh, (const double*)c->d_cfreq, (const int*)c->d_nclass,
+                     c->coh, c->bstride ? (long)c->bstride : (long)c->coh * N,
+                     (const double*)c->d_cfreq, (const int*)c->d_nclass,
                      1.0 / c->cfg.samp_rate, N, (v2d*)c->d_in64.p);
   HIP_TRY(hipGetLastError());
   // transform only the class rows (the count is on the device: one small read
@@ -1766,8 +1841,15 @@ int g_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int n
   const int NK = c->keep ? c->keep : N;   // lags searched (zero-padded search: the kept ones)
   const bool nc = mode == GNSSCORR_ACQ_NONCOHERENT;
   const int n_units = n_groups * n_bins * (nc ? 1 : n_blocks);
-  for (int u0 = 0; u0 < n_units; u0 += c->g_chunk) {
-    const int nu = n_units - u0 < c->g_chunk ? n_units - u0 : c->g_chunk;
+  // a concatenated search's units are per block, every chunk whole rows of n_blocks
+  const bool concat = mode == GNSSCORR_ACQ_CONCAT;
+  int chunk = c->g_chunk;
+  if (concat) {
+    const int rc = concat_chunk(c, n_blocks, &chunk);
+    if (rc) return rc;
+  }
+  for (int u0 = 0; u0 < n_units; u0 += chunk) {
+    const int nu = n_units - u0 < chunk ? n_units - u0 : chunk;
     for (int b = 0; b < (nc ? n_blocks : 1); b++) {
       v2d *A = (v2d*)c->d_gA, *B = (v2d*)c->d_gB, *D;
       hipLaunchKernelGGL(g_corr_pre_kernel, dim3((M + kGThreads - 1) / kGThreads, nu),
@@ -1787,8 +1869,9 @@ int g_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int n
                          dim3(kGThreads), 0, c->stream, D, N, M, b > 0, c->d_gpw, NK);
       HIP_TRY(hipGetLastError());
     }
-    const int rc = g_stats_launch(c, c->stream, c->d_gpw, NK, nu, u0, n_blocks, nc, spc, d_dump,
-                                  dump_block);
+    const int rc = concat ? g_stats_concat_launch(c, c->stream, c->d_gpw, nu, u0, n_blocks, spc)
+                          : g_stats_launch(c, c->stream, c->d_gpw, NK, nu, u0, n_blocks, nc, spc,
+                                           d_dump, dump_block);
     if (rc) return rc;
   }
   return GNSSCORR_OK;
@@ -2422,9 +2505,18 @@ int mx_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int 
   // two lanes an even count, chunk i on lane i % 2 (stream, Y, power rows, top-2 of
   // its own), forked from and joined back to the context stream
   const int lanes = m4 ? c->m4_lanes : 1;
-  int n_ch = (n_units + c->g_chunk - 1) / c->g_chunk;
+  // a concatenated search's units are per block, every chunk whole rows of n_blocks (the
+  // equal step rounded up to one: still within the chunk, itself a multiple of n_blocks)
+  const bool concat = mode == GNSSCORR_ACQ_CONCAT;
+  int chunk = c->g_chunk;
+  if (concat) {
+    const int rc = concat_chunk(c, n_blocks, &chunk);
+    if (rc) return rc;
+  }
+  int n_ch = (n_units + chunk - 1) / chunk;
   if (lanes == 2 && n_ch > 1 && n_ch % 2) n_ch++;
-  const int step = n_ch > 0 ? (n_units + n_ch - 1) / n_ch : c->g_chunk;
+  int step = n_ch > 0 ? (n_units + n_ch - 1) / n_ch : chunk;
+  if (concat) step = (step + n_blocks - 1) / n_blocks * n_blocks;
   // lane 1 starts after lane 0's first column pass, so from then on one lane's column
   // pass (memory-bound) runs beside the other's row pass (fp64-issue-bound); started
   // together, the lanes ran the same pass at the same time
@@ -2480,8 +2572,9 @@ int mx_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int 
       pend.nc = (int)nc;
       pend.spc = spc;
     } else {
-      const int rc = g_stats_launch(c, ln.stream, ln.pw, NK, nu, u0, n_blocks, nc, spc, d_dump,
-                                    dump_block);
+      const int rc = concat ? g_stats_concat_launch(c, ln.stream, ln.pw, nu, u0, n_blocks, spc)
+                            : g_stats_launch(c, ln.stream, ln.pw, NK, nu, u0, n_blocks, nc, spc,
+                                             d_dump, dump_block);
       if (rc) return rc;
     }
   }

@@ -81,6 +81,8 @@ struct gnsscorr_acq_ctx {
   int keep = 0;                         // zero-padded search: lags kept (set_zero_padded; 0: off)
   int peak_period = 0;                  // zero-padded search: the period the second-peak range is
                                         // written on (set_peak_period; 0: circular in keep)
+  int bstride = 0;                      // zero-padded search: block b starts at sample b * bstride
+                                        // (set_block_stride; 0: blocks end to end)
   const int32_t* d_group_rec = nullptr; // per group: its IF record (set_group_records; NULL: every
                                         // group on every record)
   int spec_recs = 1;                    // records of the resident IF spectra

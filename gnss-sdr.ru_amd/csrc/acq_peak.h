@@ -53,6 +53,19 @@ __host__ __device__ __forceinline__ bool in_period_range(int k, int a, int s, in
   return k <= a - s || (k >= a + s && k <= S - 1);
 }
 
+// Bounds of that set: every k in_period_range(k, a, s, S) admits lies in [lo, hi], and
+// hi - lo <= S, so a scan of lo .. hi under the predicate visits at most S + 1 indices
+// whatever the row's length (the concatenated rows of COMPASS/B1/acquisition_7x3ms.sci:
+// 21 periods).  Not the rule: the predicate above still decides every index.
+struct PeriodSpan {
+  int lo, hi;
+};
+__host__ __device__ __forceinline__ PeriodSpan period_span(int a, int s, int S) {
+  if (a <= s) return PeriodSpan{a + s, S + a - s};
+  if (a >= S - s) return PeriodSpan{a + s - S, a - s};
+  return PeriodSpan{0, S - 1};
+}
+
 // A set of samples at least `stride` apart (circularly) has at most one member among
 // the window's 2 spc - 1 samples when this holds; then the set's {maximum, its index,
 // runner-up} answer `second` in one pass: the maximum if it is outside the window,

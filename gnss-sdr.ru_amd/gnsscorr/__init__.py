@@ -153,6 +153,7 @@ IF_IQ = 1        # GNSSCORR_IF_IQ: interleaved I,Q
 IF_PACKED2 = 2   # GNSSCORR_IF_PACKED2: 2-bit codes, 4 elements per byte (GN3S LUT {-3,-1,1,3})
 ACQ_BEST_OF_BLOCKS = 0
 ACQ_NONCOHERENT = 1
+ACQ_CONCAT = 2   # GNSSCORR_ACQ_CONCAT: the blocks' kept lags end to end (set_block_stride)
 ACQ_F64 = 0      # reference precision (acquisition.sci evaluates in doubles)
 ACQ_F32 = 1      # single-precision fast path (n_samples 16368 only)
 CODE_GLO_ST = 0  # GNSSCORR_CODE_GLO_ST: the GLONASS ST code id of set_prn_codes
@@ -234,6 +235,7 @@ EXPORTED_FUNCTIONS = [
     "gnsscorr_e1t_track", "gnsscorr_e1t_replay_dev", "gnsscorr_e1t_replay", "gnsscorr_e1t_sync",
     "gnsscorr_e1t_stream",
     "gnsscorr_acq_set_peak_period", "gnsscorr_acq_second_peak_candidate", "gnsscorr_l3_code",
+    "gnsscorr_acq_set_block_stride",
     "gnsscorr_l3t_loop_coefs", "gnsscorr_l3t_init_chan", "gnsscorr_l3t_create",
     "gnsscorr_l3t_destroy", "gnsscorr_l3t_track_dev", "gnsscorr_l3t_track",
     "gnsscorr_l3t_replay_dev", "gnsscorr_l3t_replay", "gnsscorr_l3t_sync",
@@ -340,6 +342,7 @@ def lib() -> C.CDLL:
         "gnsscorr_e1t_stream": (P, [P]),
         "gnsscorr_acq_set_peak_period": (I, [P, I]),
         "gnsscorr_acq_second_peak_candidate": (I, [I, I, I, I, I]),
+        "gnsscorr_acq_set_block_stride": (I, [P, I]),
         "gnsscorr_l3_code": (I, [I, P]),
         "gnsscorr_l3t_loop_coefs": (None, [C.POINTER(L3tCfg)] + [C.POINTER(D)] * 5),
         "gnsscorr_l3t_init_chan": (I, [C.POINTER(L3tCfg), I, I, I64, I64, D, P]),
@@ -621,6 +624,15 @@ def l3_bins(if_freq: float, band_khz: float) -> np.ndarray:
     return if_freq - (band_khz / 2) * 1000 + (1000 / (2 * 5)) * (k - 1)
 
 
+def b1_coh_bins(if_freq: float, band_khz: float, coh: int) -> np.ndarray:
+    """The frequency grid of COMPASS/B1/acquisition_7x3ms.sci:67, 103-105 (coh = 3) and
+    acquisition_4x5ms.sci (coh = 5): round(band * 2 * coh) + 1 bins from IF - band/2 kHz in
+    steps of 1000 / (2 * coh) Hz."""
+    nb = int(round(band_khz * 2 * coh)) + 1
+    k = np.arange(1, nb + 1)
+    return if_freq - (band_khz / 2) * 1000 + (1000 / (2 * coh)) * (k - 1)
+
+
 def make_sigs(sigs) -> np.ndarray:
     """sigs: list of dicts with keys of SIG (missing keys default to 0)."""
     a = np.zeros(len(sigs), SIG)
@@ -760,6 +772,17 @@ class AcqCtx:
         the second-peak window circular in keep (E1/acquisition.sci:112-145); 0: off."""
         _check(lib().gnsscorr_acq_set_zero_padded(self.h, int(keep)),
                "gnsscorr_acq_set_zero_padded")
+        if not int(keep):
+            self.block_stride = 0   # the library clears it with the mode
+
+    def set_block_stride(self, stride: int):
+        """gnsscorr_acq_set_block_stride: block b of a zero-padded search starts at sample
+        b * stride of the record (COMPASS/B1/acquisition_7x3ms.sci:52-58: overlapping
+        segments), which then holds (n_blocks - 1) * stride + n_samples samples; 0: blocks
+        end to end.  mode=ACQ_CONCAT needs stride == keep."""
+        _check(lib().gnsscorr_acq_set_block_stride(self.h, int(stride)),
+               "gnsscorr_acq_set_block_stride")
+        self.block_stride = int(stride)
 
     def set_peak_period(self, period: int):
         """gnsscorr_acq_set_peak_period: the second-peak range of GLONASS/L3/
@@ -783,6 +806,14 @@ class AcqCtx:
         group_code = np.ascontiguousarray(group_code, np.int32)
         group_freq = np.ascontiguousarray(group_freq, np.int32).reshape(len(group_code), -1)
         G, B = group_freq.shape
+        stride = getattr(self, "block_stride", 0)
+        if stride and n_blocks >= 1:
+            # the library copies the strided record's length: refuse a shorter host array
+            n_el = ((n_blocks - 1) * stride + self.n) * (2 if int(iq) & IF_IQ else 1)
+            need = (n_el + 3) // 4 if int(iq) & IF_PACKED2 else n_el
+            if if_samples.size < need:
+                raise GnssCorrError(f"gnsscorr_acq_search: {n_blocks} blocks at stride {stride} "
+                                    f"need {need} bytes of IF, got {if_samples.size}")
         R = 1 if getattr(self, "_group_rec", None) is not None else self.records
         rows = np.zeros(R * G * B, ACQ_ROW)
         res = np.zeros(R * G, ACQ_RESULT)

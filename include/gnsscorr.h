@@ -292,6 +292,9 @@ typedef struct {
 
 #define GNSSCORR_ACQ_BEST_OF_BLOCKS 0  /* SoftGNSS: keep the block with larger max */
 #define GNSSCORR_ACQ_NONCOHERENT    1  /* sum |.|^2 over blocks before the search  */
+#define GNSSCORR_ACQ_CONCAT         2  /* the blocks' kept lags laid end to end: one row
+                                        * of n_blocks * keep lags per (group, bin); see
+                                        * gnsscorr_acq_set_block_stride                */
 
 int gnsscorr_acq_create(gnsscorr_acq_ctx **out, const gnsscorr_acq_cfg *cfg);
 int gnsscorr_acq_destroy(gnsscorr_acq_ctx *ctx);
@@ -426,8 +429,38 @@ int gnsscorr_acq_set_peak_period(gnsscorr_acq_ctx *ctx, int period);
  * the row's argmax, else 0 -- the predicate the statistics kernels themselves evaluate.
  * period = 0: k is outside the open circular window (argmax - spc, argmax + spc) of n
  * lags; period > 0: the range above.  GNSSCORR_EINVAL for k or argmax outside [0, n),
- * spc < 1, period > n, 2 spc >= period, or (period 0) 2 spc > n. */
+ * spc < 1, period > n, 2 spc >= period, or (period 0) 2 spc > n.  For a
+ * GNSSCORR_ACQ_CONCAT search n is the concatenated row's length, n_blocks * keep. */
 int gnsscorr_acq_second_peak_candidate(int k, int argmax, int spc, int n, int period);
+/* Overlapping blocks of a zero-padded search (COMPASS/B1/acquisition_7x3ms.sci:52-58,
+ * acquisition_4x5ms.sci:52-55: segment k is longSignal(k*M+1 : (k+2)*M), 2 M samples
+ * long, M after the previous one): block b of the following searches starts at sample
+ * b * stride of the IF record (IQ pairs counted as one sample) instead of
+ * b * n_samples, so the record holds (n_blocks - 1) * stride + n_samples samples --
+ * what gnsscorr_acq_search copies, int8 or 2-bit packed, IQ or real, and what a device
+ * record must hold.  The carrier restarts at phase 0 in every block as before (:64,
+ * :107).  stride = 0 (the default) is the end-to-end layout.  Applies to both
+ * per-block modes and to GNSSCORR_ACQ_CONCAT, and to gnsscorr_acq_power_row.  Valid only
+ * while the zero-padded mode is on, for 1 <= stride <= n_samples (GNSSCORR_EINVAL
+ * otherwise); gnsscorr_acq_set_zero_padded(ctx, 0) clears it.
+ *
+ * mode GNSSCORR_ACQ_CONCAT (:139-145): the row of (group, bin) is the kept lags of
+ * blocks 0 .. n_blocks-1 laid end to end, n_blocks * keep lags.  Valid only with the
+ * zero-padded mode on and block stride == keep (GNSSCORR_EINVAL otherwise): with a
+ * replica of keep samples followed by n_samples - keep >= keep zeros, index q of that
+ * row is then the linear correlation at lag q of the record.  One gnsscorr_acq_row per
+ * (group, bin): peak the row maximum, argmax its first 0-based index in the
+ * concatenated row (:154-157; among exactly equal blocks the first wins, as Scilab's
+ * max does), block = argmax / keep, and second by the rule in force with n =
+ * n_blocks * keep: the open window circular in n, or with gnsscorr_acq_set_peak_period
+ * the range written on the period (:159-176 are GLONASS/L3/acquisition.sci:134-153
+ * branch for branch; period <= keep as before, and for a peak in a later period the
+ * range a + s - S .. a - s is linear: it may reach back into the previous block).
+ * Per group: bin, the pad flag and carr_freq as in the other modes, code_phase = 1 +
+ * the concatenated index, not reduced (tracking.sci:137 seeks to codePhase - 1).  The
+ * Neumann-Hoffman-signed replica (:95-97) takes no entry point of its own:
+ * gnsscorr_acq_set_codes_padded with code_len = keep. */
+int gnsscorr_acq_set_block_stride(gnsscorr_acq_ctx *ctx, int stride);
 /* gnsscorr_acq_set_codes for codes shorter than the transform: n_codes x code_len
  * int8 chips of +-1 (code_len <= n_samples), zero-extended to n_samples on the
  * device; their spectra are computed there and kept resident.  Like
