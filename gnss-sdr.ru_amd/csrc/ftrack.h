@@ -177,10 +177,10 @@ inline void calc_loop_coef(double lbw, double z, double* tau1, double* tau2) {
   *tau2 = 2.0 * z / wn;
 }
 
-// calcFLLPLLLoopCoef.sci:36-38 (T = PDIcarr = 0.001)
+// calcFLLPLLLoopCoef.sci:36-38 (T = PDIcarr, 0.001 in every 1 ms loop)
 inline void calc_fll_pll_loop_coef(double pll_bw, double fll_bw, double* k1, double* k2,
-                                   double* k3) {
-  const double T = 0.001, b = pll_bw / 0.53;
+                                   double* k3, double T = 0.001) {
+  const double b = pll_bw / 0.53;
   *k1 = T * (b * b) + 1.414 * b;
   *k2 = 1.414 * b;
   *k3 = T * (fll_bw / 0.25);

@@ -190,7 +190,8 @@ class E1tCfg(C.Structure):
                 ("dll_noise_bw", C.c_double), ("dll_damping", C.c_double),
                 ("sll_spacing", C.c_double), ("sll_noise_bw", C.c_double),
                 ("sll_damping", C.c_double), ("pll_noise_bw", C.c_double),
-                ("fll_noise_bw", C.c_double)]
+                ("fll_noise_bw", C.c_double), ("epoch_ms", C.c_int32),
+                ("ambiguous", C.c_int32)]
 
 
 class L3tCfg(C.Structure):
@@ -978,12 +979,14 @@ class SgtCtx:
 # ---------------------------------------------------------------- Galileo E1B float tracking
 def e1t_cfg(device: int = 0, **kw) -> E1tCfg:
     """GALILEO/E1/initSettings.sci:65-107 defaults; keyword overrides use the Scilab
-    names (samplingFreq, IF, sllCorrelatorSpacing, fileType, ...) plus maxCodes."""
+    names (samplingFreq, IF, sllCorrelatorSpacing, fileType, ...) plus maxCodes and the
+    loop of GALILEO/E1/BOC_tracking_alternatives/ to run: epochMs 1 (tracking.sci) or 4
+    (tracking_4ms.sci), ambiguous 1 for the three-arm tracking_ambiguous_{1,4}ms.sci."""
     d = dict(fileType=2, samplingFreq=16e6, codeFreqBasis=1.023e6, meandrFreqBasis=2.046e6,
              IF=2.42e6, codeLength=4092, meandrLength=8184, dllDampingRatio=0.7,
              dllNoiseBandwidth=0.5, dllCorrelatorSpacing=0.25, sllDampingRatio=0.7,
              sllNoiseBandwidth=0.5, sllCorrelatorSpacing=0.1, pllNoiseBandwidth=25.0,
-             fllNoiseBandwidth=250.0, maxCodes=50)
+             fllNoiseBandwidth=250.0, maxCodes=50, epochMs=1, ambiguous=0)
     unknown = set(kw) - set(d)
     if unknown:
         raise ValueError(f"unknown settings {sorted(unknown)}")
@@ -992,7 +995,7 @@ def e1t_cfg(device: int = 0, **kw) -> E1tCfg:
                   d["samplingFreq"], d["codeFreqBasis"], d["meandrFreqBasis"], d["IF"],
                   d["dllCorrelatorSpacing"], d["dllNoiseBandwidth"], d["dllDampingRatio"],
                   d["sllCorrelatorSpacing"], d["sllNoiseBandwidth"], d["sllDampingRatio"],
-                  d["pllNoiseBandwidth"], d["fllNoiseBandwidth"])
+                  d["pllNoiseBandwidth"], d["fllNoiseBandwidth"], d["epochMs"], d["ambiguous"])
 
 
 def e1t_loop_coefs(cfg: E1tCfg):
@@ -1013,7 +1016,9 @@ def e1t_init_chan(cfg: E1tCfg, code_id, code_phase_1b, acq_freq, stream=0, skip=
 
 class E1tCtx:
     """Galileo E1B float tracking (GALILEO/E1/tracking.sci) for many channels over
-    HBM-resident records: code and subcarrier NCOs, five arms, PLL/FLL + DLL + SLL."""
+    HBM-resident records: code and subcarrier NCOs, five arms, PLL/FLL + DLL + SLL.
+    epochMs=4 and / or ambiguous=1 select the loops of BOC_tracking_alternatives/ (e1t_cfg);
+    in the ambiguous modes I_E .. Q_L are the I_P_E, I_P_P, I_P_L, Q_P_E, Q_P_P, Q_P_L fields."""
 
     def __init__(self, device: int = 0, **settings):
         self.cfg = e1t_cfg(device, **settings)

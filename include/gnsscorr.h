@@ -595,6 +595,48 @@ void *gnsscorr_sgt_stream(gnsscorr_sgt_ctx *ctx);
  * the FLL-assisted PLL (:371-389), the DLL on P-E / P-L (:394-407) and the SLL
  * on E-P / L-P (:412-425).  Indices are fp64 without contraction: bit-exact.
  * The records stay resident in HBM as for the sgt family above.
+ *
+ * The three loops of GALILEO/E1/BOC_tracking_alternatives/ are modes of the
+ * same context, chosen by cfg.epoch_ms and cfg.ambiguous (0, 0 = the loop above):
+ *   epoch_ms  ambiguous  file
+ *      1         0       tracking.sci (the default)
+ *      4         0       tracking_4ms.sci            ("4ms" below)
+ *      1         1       tracking_ambiguous_1ms.sci  ("amb_1ms")
+ *      4         1       tracking_ambiguous_4ms.sci  ("amb_4ms")
+ * 4ms: the same five arms and three loops over the whole 4092-chip code: one
+ *   padded 4094-entry row [c($) c c(1)] (4ms:159), no quarters (segment stays
+ *   0), blksize = ceil((4092 - remCode)/codeStep) (:261), carries - 4092.0 and
+ *   - 8184.0 (:305, :328), PDIcode = PDImeandr = PDIcarr = 0.004 (:107,115,123),
+ *   aiding /1540 and /770 (:403,424), absoluteSample over codeLength (:433-435).
+ *   Its subcarrier table [m($) m m(1)] (:163-165, 8186 entries) has a one-entry
+ *   front pad, so the value at ceil(t) + 1 is -1 iff ceil(t) is even, the
+ *   opposite of tracking.sci; status 2 is an index outside 1..8186.
+ * amb_1ms, amb_4ms: BOC(1,1) tracked as one sequence ca = kron(c, [1 1]) .*
+ *   [+1 -1 ...] of 8184 entries (amb_1ms:141-145) clocked at 2 * codeFreqBasis
+ *   (:157): three arms E / P / L, six sums, PLL/FLL and DLL, no subcarrier loop.
+ *   amb_1ms: four padded rows of 2048, row s = [ca(2046 s) ca(2046 s + 1 :
+ *   2046 s + 2046) ca(2046 s + 2047)], circular (:148-151); blksize =
+ *   ceil((8184/4 - remCode)/codeStep) (:232); carry - 2046.0, then the row
+ *   counter (:276-281); PDIcode = PDIcarr = 0.001 (:98,107).
+ *   amb_4ms: one row [ca($) ca ca(1)] of 8186 (:146); blksize = ceil((8184 -
+ *   remCode)/codeStep) (:224); carry - 8184.0 (:268); PDIcode 0.004 and PDIcarr
+ *   0.008, as the file says (:97,106).
+ *   Both: codeFreq = 2*codeFreqBasis - codeNco + (carrFreq - IF)/770 (amb_1ms:351,
+ *   amb_4ms:340); absoluteSample divides by 2*codeLength = 8184, still with
+ *   fs/1000 (amb_1ms:360-362).
+ *   Records and state in the ambiguous modes, structs and sizes unchanged:
+ *   I_E, I_P, I_L, Q_E, Q_P, Q_L land in i_p_e, i_p_p, i_p_l, q_p_e, q_p_p,
+ *   q_p_l; i_e_p, i_l_p, q_e_p, q_l_p, meandr_freq, sll_discr and
+ *   sll_discr_filt are written as 0.  The channel's rem_meandr, meandr_freq and
+ *   old_meandr_* are left as they came in (init_chan sets them to 0); code_freq
+ *   is the composite rate (init_chan: 2 * code_freq_basis, amb_1ms:157).
+ *   segment counts the composite quarter rows in amb_1ms (remCodePhase2_cnt - 1,
+ *   :278-281) and stays 0 in both 4 ms modes.  Status 2 cannot occur.
+ * In every mode gnsscorr_e1t_replay* takes ten sums per epoch in the record's
+ * order (the ambiguous modes ignore the four they do not use),
+ * gnsscorr_e1t_loop_coefs returns the mode's own coefficients (0 for the two
+ * SLL ones in the ambiguous modes) and gnsscorr_e1t_set_codes takes
+ * chips[n][4092] of +-1 and builds the mode's rows itself.
  * ==================================================================== */
 typedef struct gnsscorr_e1t_ctx gnsscorr_e1t_ctx;
 
@@ -613,7 +655,10 @@ typedef struct {          /* initSettings.sci fields used by tracking.sci     */
   double  dll_noise_bw, dll_damping;   /* calcLoopCoef(dll.., dll.., 1)        */
   double  sll_spacing;    /* settings.sllCorrelatorSpacing [subcarrier half-cycles] */
   double  sll_noise_bw, sll_damping;   /* calcLoopCoef(sll.., sll.., 1)        */
-  double  pll_noise_bw, fll_noise_bw;  /* calcFLLPLLLoopCoef(pll, fll, PDIcarr=0.001) */
+  double  pll_noise_bw, fll_noise_bw;  /* calcFLLPLLLoopCoef(pll, fll, PDIcarr of the mode) */
+  int32_t epoch_ms;       /* 0 or 1: the quarter-code 1 ms epoch; 4: the whole code  */
+  int32_t ambiguous;      /* 0: five arms, code x subcarrier; 1: three arms on the
+                             composite sequence.  Other values: GNSSCORR_EINVAL     */
 } gnsscorr_e1t_cfg;
 
 typedef struct {          /* one tracking channel (tracking.sci:150-205 + loop state) */
@@ -660,7 +705,8 @@ int gnsscorr_e1t_create(gnsscorr_e1t_ctx **out, const gnsscorr_e1t_cfg *cfg);
 int gnsscorr_e1t_destroy(gnsscorr_e1t_ctx *ctx);
 /* Upload n_codes primary codes, chips[n_codes][4092] of +-1 (anything else:
  * GNSSCORR_EINVAL, checked before any device call).  The four padded 1025-entry
- * rows of tracking.sci:157-160 are built here, once per code. */
+ * rows of tracking.sci:157-160, or the rows of the context's mode (above), are
+ * built here, once per code. */
 int gnsscorr_e1t_set_codes(gnsscorr_e1t_ctx *ctx, int n_codes, const int8_t *chips);
 /* Run n_epochs epochs of n_ch channels (state in d_chan, updated in place);
  * arguments as gnsscorr_sgt_track_dev.  closed_loop=0 holds the three
