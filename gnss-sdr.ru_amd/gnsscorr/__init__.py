@@ -212,85 +212,38 @@ class SdrAcqCfg(C.Structure):
     _fields_ = [("fif", C.c_double), ("device", C.c_int32), ("saturate", C.c_int32)]
 
 
-# every symbol include/gnsscorr.h + include/gnsscorr_osg.h declare
-EXPORTED_FUNCTIONS = [
-    "gnsscorr_last_error", "gnsscorr_version", "gnsscorr_device_count",
-    "gnsscorr_device_pci_bus_id", "gnsscorr_hip_runtime", "gnsscorr_device_lds_bytes",
-    "gnsscorr_track_create", "gnsscorr_track_destroy", "gnsscorr_track_max_dumps",
-    "gnsscorr_track_set_layout",
-    "gnsscorr_pack2", "gnsscorr_track_if_bytes",
-    "gnsscorr_track", "gnsscorr_track_dev", "gnsscorr_track_next_tic",
-    "gnsscorr_track_replay_dev", "gnsscorr_track_get_state", "gnsscorr_track_set_state",
-    "gnsscorr_track_sync", "gnsscorr_track_stream",
-    "gnsscorr_acq_create", "gnsscorr_acq_destroy", "gnsscorr_acq_set_codes",
-    "gnsscorr_acq_search", "gnsscorr_acq_search_dev", "gnsscorr_acq_power_row",
-    "gnsscorr_acq_spectra_dev", "gnsscorr_acq_correlate_dev", "gnsscorr_acq_select_dev",
-    "gnsscorr_acq_sync", "gnsscorr_acq_stream", "gnsscorr_acq_set_coherent",
-    "gnsscorr_acq_set_records", "gnsscorr_acq_set_group_records", "gnsscorr_acq_set_prn_codes",
-    "gnsscorr_acq_set_zero_padded", "gnsscorr_acq_set_codes_padded",
-    "gnsscorr_sgt_loop_coefs", "gnsscorr_sgt_init_chan", "gnsscorr_sgt_create",
-    "gnsscorr_sgt_destroy", "gnsscorr_sgt_track_dev", "gnsscorr_sgt_track", "gnsscorr_sgt_sync",
-    "gnsscorr_sgt_stream", "gnsscorr_sgt_replay", "gnsscorr_sgt_replay_dev",
-    "gnsscorr_e1t_loop_coefs", "gnsscorr_e1t_init_chan", "gnsscorr_e1t_create",
-    "gnsscorr_e1t_destroy", "gnsscorr_e1t_set_codes", "gnsscorr_e1t_track_dev",
-    "gnsscorr_e1t_track", "gnsscorr_e1t_replay_dev", "gnsscorr_e1t_replay", "gnsscorr_e1t_sync",
-    "gnsscorr_e1t_stream",
-    "gnsscorr_acq_set_peak_period", "gnsscorr_acq_second_peak_candidate", "gnsscorr_l3_code",
-    "gnsscorr_acq_set_block_stride",
-    "gnsscorr_l3t_loop_coefs", "gnsscorr_l3t_init_chan", "gnsscorr_l3t_create",
-    "gnsscorr_l3t_destroy", "gnsscorr_l3t_track_dev", "gnsscorr_l3t_track",
-    "gnsscorr_l3t_replay_dev", "gnsscorr_l3t_replay", "gnsscorr_l3t_sync",
-    "gnsscorr_l3t_stream",
-    "gnsscorr_sdr_prn_codes", "gnsscorr_sdr_sine_gen", "gnsscorr_sdr_acq_create",
-    "gnsscorr_sdr_acq_destroy", "gnsscorr_sdr_acq_strong", "gnsscorr_sdr_acq_strong_dev",
-    "gnsscorr_sdr_channel_start", "gnsscorr_sdr_channel_accum_dev", "gnsscorr_sdr_track_dev",
-    "gnsscorr_sdr_acq_sync", "gnsscorr_sdr_acq_stream", "gnsscorr_sdr_acq_prep_dev",
-    "gnsscorr_sdr_acq_search_dev", "gnsscorr_sdr_acq_acquire",
-    "gnsscorr_sdr_corr_create", "gnsscorr_sdr_corr_destroy", "gnsscorr_sdr_init_chan",
-    "gnsscorr_sdr_accum_dev", "gnsscorr_sdr_correlate", "gnsscorr_sdr_corr_sync",
-    "gnsscorr_sdr_corr_stream", "gnsscorr_sdr_corr_device",
-    "gnsscorr_sdr_gn3s_products", "gnsscorr_sdr_fe_create", "gnsscorr_sdr_fe_destroy",
-    "gnsscorr_sdr_gn3s_dev", "gnsscorr_sdr_gn3s", "gnsscorr_sdr_downsample_count",
-    "gnsscorr_sdr_downsample_dev", "gnsscorr_sdr_fe_sync", "gnsscorr_sdr_fe_stream",
-    "gnsscorr_osg_loop_cfg_init", "gnsscorr_osg_loop_reset", "gnsscorr_osg_isr_dev",
-    "gnsscorr_osg_closed_loop_dev",
-    "gnsscorr_dev_alloc", "gnsscorr_dev_free", "gnsscorr_memcpy_htod", "gnsscorr_memcpy_dtoh",
-    "gnsscorr_dev_synchronize", "gnsscorr_event_create", "gnsscorr_event_record",
-    "gnsscorr_stream_wait_event",
-    "gnsscorr_event_elapsed_ms", "gnsscorr_event_destroy", "gnsscorr_dev_fill_if2",
-    "gnsscorr_ifgen", "gnsscorr_ca_code", "gnsscorr_b1i_code", "gnsscorr_st_code",
-    "gnsscorr_sample_code", "gnsscorr_sample_boc_code",
-    "correlator_init", "Sim_GP2021_int", "gnsscorr_osg_configure", "gnsscorr_osg_get_state",
-]
-EXPORTED_DATA = ["REG_read", "REG_write", "Carrier_DCO_Delta", "Code_DCO_Delta",
-                 "gps_code_ref", "gps_carrier_ref", "glonass_code_ref",
-                 "glonass_carrier_ref", "d_freq"]
-
-_lib = None
+_P, _I, _I64, _D, _U64 = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_uint64
 
 
-class GnssCorrError(RuntimeError):
-    pass
+def _ctx_sig(prefix, *create_args):
+    """The rows every context family has: create, destroy, sync, stream."""
+    return {prefix + "_create": (_I, [C.POINTER(_P), *create_args]),
+            prefix + "_destroy": (_I, [_P]), prefix + "_sync": (_I, [_P]),
+            prefix + "_stream": (_P, [_P])}
 
 
-def lib() -> C.CDLL:
-    """Load libgnsscorr.so (raises if it has not been built)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise GnssCorrError(f"{LIB_PATH} not built (run `make -C gnss-sdr.ru_amd`)")
-    L = C.CDLL(LIB_PATH)  # RTLD_LOCAL: never interpose REG_read etc. into other libraries
-    P, I, I64, D, U64 = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_uint64
-    sig = {
+def _tracker_sig(prefix, Cfg, n_coefs):
+    """The rows of a float tracker family (csrc/ftrack.h), alike up to prefix and cfg."""
+    cfg = C.POINTER(Cfg)
+    run = (_I, [_P, _P, _I64, _I64, _I, _P, _I, _I, _P])
+    rep = (_I, [_P, _I, _P, _I, _P, _P])
+    return {prefix + "_loop_coefs": (None, [cfg] + [C.POINTER(_D)] * n_coefs),
+            prefix + "_init_chan": (_I, [cfg, _I, _I, _I64, _I64, _D, _P]),
+            **_ctx_sig(prefix, cfg),
+            prefix + "_track_dev": run, prefix + "_track": run,
+            prefix + "_replay": rep, prefix + "_replay_dev": rep}
+
+
+def _sig_table():
+    P, I, I64, D, U64 = _P, _I, _I64, _D, _U64
+    return {
         "gnsscorr_last_error": (C.c_char_p, []),
         "gnsscorr_version": (C.c_char_p, []),
         "gnsscorr_device_count": (I, []),
         "gnsscorr_device_pci_bus_id": (I, [I, P, I]),
         "gnsscorr_device_lds_bytes": (I, [I]),
         "gnsscorr_hip_runtime": (I, [P, I, P]),
-        "gnsscorr_track_create": (I, [C.POINTER(P), C.POINTER(TrackCfg)]),
-        "gnsscorr_track_destroy": (I, [P]),
+        **_ctx_sig("gnsscorr_track", C.POINTER(TrackCfg)),
         "gnsscorr_track_set_layout": (I, [P, I]),
         "gnsscorr_track_max_dumps": (I, [P]),
         "gnsscorr_track": (I, [P, P, I64, I, I64, P, P, P, C.POINTER(I)]),
@@ -301,10 +254,7 @@ def lib() -> C.CDLL:
         "gnsscorr_track_replay_dev": (I, [P, P, I64, I64, I, P, P]),
         "gnsscorr_track_get_state": (I, [P, P]),
         "gnsscorr_track_set_state": (I, [P, P]),
-        "gnsscorr_track_sync": (I, [P]),
-        "gnsscorr_track_stream": (P, [P]),
-        "gnsscorr_acq_create": (I, [C.POINTER(P), C.POINTER(AcqCfg)]),
-        "gnsscorr_acq_destroy": (I, [P]),
+        **_ctx_sig("gnsscorr_acq", C.POINTER(AcqCfg)),
         "gnsscorr_acq_set_codes": (I, [P, I, P]),
         "gnsscorr_acq_search": (I, [P, P, I, I, I, I, P, I, I, P, P, I, P, P]),
         "gnsscorr_acq_search_dev": (I, [P, P, I, I, I, I, P, I, I, P, P, I, P, P]),
@@ -312,70 +262,35 @@ def lib() -> C.CDLL:
         "gnsscorr_acq_spectra_dev": (I, [P, P, I, I, I, P]),
         "gnsscorr_acq_correlate_dev": (I, [P, I, I, P, I, I, P, P, I, P, P]),
         "gnsscorr_acq_select_dev": (I, [P, I, I, P, P, P, P]),
-        "gnsscorr_acq_sync": (I, [P]),
         "gnsscorr_acq_set_coherent": (I, [P, I]),
         "gnsscorr_acq_set_records": (I, [P, I]),
         "gnsscorr_acq_set_group_records": (I, [P, P]),
         "gnsscorr_acq_set_prn_codes": (I, [P, I, P]),
         "gnsscorr_acq_set_zero_padded": (I, [P, I]),
         "gnsscorr_acq_set_codes_padded": (I, [P, I, P, I]),
-        "gnsscorr_acq_stream": (P, [P]),
-        "gnsscorr_sgt_loop_coefs": (None, [C.POINTER(SgtCfg)] + [C.POINTER(D)] * 5),
-        "gnsscorr_sgt_init_chan": (I, [C.POINTER(SgtCfg), I, I, I64, I64, D, P]),
-        "gnsscorr_sgt_create": (I, [C.POINTER(P), C.POINTER(SgtCfg)]),
-        "gnsscorr_sgt_destroy": (I, [P]),
-        "gnsscorr_sgt_track_dev": (I, [P, P, I64, I64, I, P, I, I, P]),
-        "gnsscorr_sgt_track": (I, [P, P, I64, I64, I, P, I, I, P]),
-        "gnsscorr_sgt_replay": (I, [P, I, P, I, P, P]),
-        "gnsscorr_sgt_replay_dev": (I, [P, I, P, I, P, P]),
-        "gnsscorr_sgt_sync": (I, [P]),
-        "gnsscorr_sgt_stream": (P, [P]),
-        "gnsscorr_e1t_loop_coefs": (None, [C.POINTER(E1tCfg)] + [C.POINTER(D)] * 7),
-        "gnsscorr_e1t_init_chan": (I, [C.POINTER(E1tCfg), I, I, I64, I64, D, P]),
-        "gnsscorr_e1t_create": (I, [C.POINTER(P), C.POINTER(E1tCfg)]),
-        "gnsscorr_e1t_destroy": (I, [P]),
-        "gnsscorr_e1t_set_codes": (I, [P, I, P]),
-        "gnsscorr_e1t_track_dev": (I, [P, P, I64, I64, I, P, I, I, P]),
-        "gnsscorr_e1t_track": (I, [P, P, I64, I64, I, P, I, I, P]),
-        "gnsscorr_e1t_replay": (I, [P, I, P, I, P, P]),
-        "gnsscorr_e1t_replay_dev": (I, [P, I, P, I, P, P]),
-        "gnsscorr_e1t_sync": (I, [P]),
-        "gnsscorr_e1t_stream": (P, [P]),
         "gnsscorr_acq_set_peak_period": (I, [P, I]),
         "gnsscorr_acq_second_peak_candidate": (I, [I, I, I, I, I]),
         "gnsscorr_acq_set_block_stride": (I, [P, I]),
+        **_tracker_sig("gnsscorr_sgt", SgtCfg, 5),
+        **_tracker_sig("gnsscorr_e1t", E1tCfg, 7),
+        "gnsscorr_e1t_set_codes": (I, [P, I, P]),
         "gnsscorr_l3_code": (I, [I, P]),
-        "gnsscorr_l3t_loop_coefs": (None, [C.POINTER(L3tCfg)] + [C.POINTER(D)] * 5),
-        "gnsscorr_l3t_init_chan": (I, [C.POINTER(L3tCfg), I, I, I64, I64, D, P]),
-        "gnsscorr_l3t_create": (I, [C.POINTER(P), C.POINTER(L3tCfg)]),
-        "gnsscorr_l3t_destroy": (I, [P]),
-        "gnsscorr_l3t_track_dev": (I, [P, P, I64, I64, I, P, I, I, P]),
-        "gnsscorr_l3t_track": (I, [P, P, I64, I64, I, P, I, I, P]),
-        "gnsscorr_l3t_replay": (I, [P, I, P, I, P, P]),
-        "gnsscorr_l3t_replay_dev": (I, [P, I, P, I, P, P]),
-        "gnsscorr_l3t_sync": (I, [P]),
-        "gnsscorr_l3t_stream": (P, [P]),
+        **_tracker_sig("gnsscorr_l3t", L3tCfg, 5),
         "gnsscorr_sdr_prn_codes": (I, [P]),
         "gnsscorr_sdr_sine_gen": (None, [P, D, D, I]),
-        "gnsscorr_sdr_acq_create": (I, [C.POINTER(P), C.POINTER(SdrAcqCfg)]),
-        "gnsscorr_sdr_acq_destroy": (I, [P]),
+        **_ctx_sig("gnsscorr_sdr_acq", C.POINTER(SdrAcqCfg)),
         "gnsscorr_sdr_acq_strong": (I, [P, P, I, I, P, I, I, P]),
         "gnsscorr_sdr_acq_strong_dev": (I, [P, P, I, I, P, I, I, P]),
-        "gnsscorr_sdr_acq_sync": (I, [P]),
         "gnsscorr_sdr_acq_prep_dev": (I, [P, I, P, I]),
         "gnsscorr_sdr_channel_start": (I, [P, I, I, I, I]),
         "gnsscorr_sdr_channel_accum_dev": (I, [P, I, I, P, P, P, P, P, I, P]),
         "gnsscorr_sdr_track_dev": (I, [P, P, I, I, I, P, P, P, P, P, P, I, P, P, P, I, P]),
         "gnsscorr_sdr_acq_search_dev": (I, [P, I, I, I, P, I, I, P]),
         "gnsscorr_sdr_acq_acquire": (I, [P, I, P, I, I, P, I, I, P]),
-        "gnsscorr_sdr_acq_stream": (P, [P]),
-        "gnsscorr_sdr_corr_create": (I, [C.POINTER(P), C.POINTER(SdrCorrCfg)]),
-        "gnsscorr_sdr_corr_destroy": (I, [P]),
+        **_ctx_sig("gnsscorr_sdr_corr", C.POINTER(SdrCorrCfg)),
         "gnsscorr_sdr_init_chan": (I, [P, I, I, I, D]),
         "gnsscorr_sdr_accum_dev": (I, [P, P, I, P, P]),
         "gnsscorr_sdr_correlate": (I, [P, P, I, I, P, P, P, P, P]),
-        "gnsscorr_sdr_corr_sync": (I, [P]),
-        "gnsscorr_sdr_corr_stream": (P, [P]),
         "gnsscorr_sdr_corr_device": (I, [P]),
         "gnsscorr_sdr_gn3s_products": (None, [P]),
         "gnsscorr_osg_loop_cfg_init": (None, [P, D, D, D, I, I, D, C.c_long, C.c_long, C.c_long,
@@ -383,14 +298,11 @@ def lib() -> C.CDLL:
         "gnsscorr_osg_loop_reset": (None, [P, I, P, P, P]),
         "gnsscorr_osg_isr_dev": (I, [P, P, I, P, P, P]),
         "gnsscorr_osg_closed_loop_dev": (I, [P, P, P, I64, I64, I, I, P, P, P, P]),
-        "gnsscorr_sdr_fe_create": (I, [C.POINTER(P), I]),
-        "gnsscorr_sdr_fe_destroy": (I, [P]),
+        **_ctx_sig("gnsscorr_sdr_fe", I),
         "gnsscorr_sdr_gn3s_dev": (I, [P, P, I, I, C.POINTER(C.c_uint32), C.c_uint32, P]),
         "gnsscorr_sdr_gn3s": (I, [P, P, I, I, C.POINTER(C.c_uint32), C.c_uint32, P]),
         "gnsscorr_sdr_downsample_count": (I, [I, D, D, P]),
         "gnsscorr_sdr_downsample_dev": (I, [P, P, I, D, D, P, C.POINTER(C.c_int)]),
-        "gnsscorr_sdr_fe_sync": (I, [P]),
-        "gnsscorr_sdr_fe_stream": (P, [P]),
         "gnsscorr_dev_alloc": (I, [I, C.c_size_t, C.POINTER(P)]),
         "gnsscorr_dev_free": (I, [I, P]),
         "gnsscorr_memcpy_htod": (I, [I, P, P, C.c_size_t]),
@@ -413,7 +325,32 @@ def lib() -> C.CDLL:
         "gnsscorr_osg_configure": (I, [D, D, D, D, I, I, I, I, D, I]),
         "gnsscorr_osg_get_state": (I, [P]),
     }
-    for name, (res, args) in sig.items():
+
+
+# name -> (restype, argtypes) of every function include/gnsscorr.h and
+# include/gnsscorr_osg.h declare; lib() sets them on the loaded library
+_SIG = _sig_table()
+EXPORTED_FUNCTIONS = list(_SIG)
+EXPORTED_DATA = ["REG_read", "REG_write", "Carrier_DCO_Delta", "Code_DCO_Delta",
+                 "gps_code_ref", "gps_carrier_ref", "glonass_code_ref",
+                 "glonass_carrier_ref", "d_freq"]
+
+_lib = None
+
+
+class GnssCorrError(RuntimeError):
+    pass
+
+
+def lib() -> C.CDLL:
+    """Load libgnsscorr.so (raises if it has not been built)."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise GnssCorrError(f"{LIB_PATH} not built (run `make -C gnss-sdr.ru_amd`)")
+    L = C.CDLL(LIB_PATH)  # RTLD_LOCAL: never interpose REG_read etc. into other libraries
+    for name, (res, args) in _SIG.items():
         if not hasattr(L, name):
             continue  # reported by tests/test_abi.py
         f = getattr(L, name)
@@ -423,10 +360,43 @@ def lib() -> C.CDLL:
     return L
 
 
-def _check(rc: int, what: str) -> None:
+def _check(rc: int, what) -> None:
+    """what: the symbol's name, or its ctypes function (named only when the call failed)."""
     if rc != 0:
         msg = lib().gnsscorr_last_error().decode(errors="replace")
-        raise GnssCorrError(f"{what} failed ({rc}): {msg}")
+        raise GnssCorrError(f"{getattr(what, '__name__', what)} failed ({rc}): {msg}")
+
+
+class _Handle:
+    """What the context classes share: a handle `h` made by <prefix>_create and freed by
+    <prefix>_destroy, sync() and the stream property.  The family's ctypes functions are
+    looked up once, at creation: sync and stream sit inside timed loops."""
+
+    _prefix = None   # "gnsscorr_track", ...
+
+    def _create(self, *args, ops=()):
+        """<prefix>_create(&h, *args); binds <prefix>_<op> as self._<op> for `ops` too."""
+        L = lib()
+        for op in ("destroy", "sync", "stream") + ops:
+            setattr(self, "_" + op, getattr(L, f"{self._prefix}_{op}"))
+        h = C.c_void_p()
+        _check(getattr(L, self._prefix + "_create")(C.byref(h), *args),
+               self._prefix + "_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):   # also after a constructor that failed before h existed
+            self._destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def sync(self):
+        _check(self._sync(self.h), self._sync)
+
+    @property
+    def stream(self) -> int:
+        return self._stream(self.h)
 
 
 def _ptr(a: np.ndarray) -> int:
@@ -654,8 +624,10 @@ def ifgen(nsamp: int, sigs=(), fs=16.368e6, if_gps=2.42e6, if_glo=1.0e6, iq=True
 
 
 # ---------------------------------------------------------------- tracking
-class TrackCtx:
+class TrackCtx(_Handle):
     """Batched GP2021-semantics tracking correlator context (one per GPU)."""
+
+    _prefix = "gnsscorr_track"
 
     def __init__(self, n_channels: int, iq: bool = True, device: int = 0,
                  max_nsamp: int = 65536, samp_rate: float = 16.368e6,
@@ -665,22 +637,13 @@ class TrackCtx:
         self.packed = bool(packed or int(iq) & IF_PACKED2)
         cfg = TrackCfg(n_channels, iq_flags(self.iq, self.packed), device, max_nsamp, samp_rate,
                        tic_period)
-        h = C.c_void_p()
-        _check(lib().gnsscorr_track_create(C.byref(h), C.byref(cfg)), "gnsscorr_track_create")
-        self.h = h
-        self.max_dumps = lib().gnsscorr_track_max_dumps(h)
+        self._create(C.byref(cfg))
+        self.max_dumps = lib().gnsscorr_track_max_dumps(self.h)
 
     def set_layout(self, one_stream_per_channel: bool):
         """gnsscorr_track_set_layout: per-channel LDS staging of int8 C_s = 1 streams."""
         _check(lib().gnsscorr_track_set_layout(self.h, int(bool(one_stream_per_channel))),
                "gnsscorr_track_set_layout")
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().gnsscorr_track_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def track(self, if_samples: np.ndarray, nsamp: int, cmds: np.ndarray, n_streams: int = 1,
               stream_stride: int = 0, all_dumps: bool = False):
@@ -722,36 +685,22 @@ class TrackCtx:
         st = np.ascontiguousarray(st, CHAN_STATE)
         _check(lib().gnsscorr_track_set_state(self.h, _ptr(st)), "gnsscorr_track_set_state")
 
-    def sync(self):
-        _check(lib().gnsscorr_track_sync(self.h), "gnsscorr_track_sync")
-
-    @property
-    def stream(self) -> int:
-        return lib().gnsscorr_track_stream(self.h)
-
 
 # ---------------------------------------------------------------- acquisition
-class AcqCtx:
+class AcqCtx(_Handle):
     """Parallel code-phase acquisition context (SoftGNSS acquisition.sci semantics)."""
+
+    _prefix = "gnsscorr_acq"
 
     def __init__(self, samp_rate: float = 16.368e6, n_samples: int = 16368, device: int = 0,
                  max_freqs: int = 1024, max_blocks: int = 16, max_codes: int = 64,
                  precision: int = ACQ_F64):
         cfg = AcqCfg(samp_rate, n_samples, device, max_freqs, max_blocks, max_codes, precision)
         self.precision = precision
-        h = C.c_void_p()
-        _check(lib().gnsscorr_acq_create(C.byref(h), C.byref(cfg)), "gnsscorr_acq_create")
-        self.h = h
+        self._create(C.byref(cfg))
         self.n = n_samples
         self.fs = samp_rate
         self.records = 1
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().gnsscorr_acq_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def set_codes(self, codes: np.ndarray):
         codes = np.ascontiguousarray(codes, np.int8).reshape(-1, self.n)
@@ -874,12 +823,83 @@ class AcqCtx:
                                             freq, code, _ptr(out)), "gnsscorr_acq_power_row")
         return out
 
-    def sync(self):
-        _check(lib().gnsscorr_acq_sync(self.h), "gnsscorr_acq_sync")
 
-    @property
-    def stream(self) -> int:
-        return lib().gnsscorr_acq_stream(self.h)
+# ---------------------------------------------------------------- float trackers
+def _settings(defaults: dict, kw: dict, also=()) -> dict:
+    """The defaults overridden by kw; a key that is neither a default nor in `also` is refused."""
+    unknown = set(kw) - set(defaults) - set(also)
+    if unknown:
+        raise ValueError(f"unknown settings {sorted(unknown)}")
+    defaults.update(kw)
+    return defaults
+
+
+def _loop_coefs(prefix, cfg, n):
+    v = [C.c_double() for _ in range(n)]
+    getattr(lib(), prefix + "_loop_coefs")(C.byref(cfg), *[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def _init_chan(prefix, chan_dtype, cfg, code_id, code_phase_1b, acq_freq, stream, skip):
+    out = np.zeros(1, chan_dtype)
+    _check(getattr(lib(), prefix + "_init_chan")(C.byref(cfg), int(code_id), int(stream),
+                                                 int(skip), int(code_phase_1b), float(acq_freq),
+                                                 out.ctypes.data), prefix + "_init_chan")
+    return out
+
+
+class _FloatTracker(_Handle):
+    """What SgtCtx, E1tCtx and L3tCtx share (csrc/ftrack.h on the C side).  A subclass
+    states _prefix, _make_cfg (its *_cfg builder), its CHAN and EPOCH dtypes, the number of
+    sums per epoch and the number of loop coefficients."""
+
+    _make_cfg = _CHAN = _EPOCH = _n_sums = _n_coefs = None
+
+    def __init__(self, device: int = 0, **settings):
+        self._open(self._make_cfg(device, **settings))
+
+    def _open(self, cfg):
+        self.cfg = cfg
+        self._create(C.byref(cfg), ops=("track", "track_dev", "replay"))
+
+    def loop_coefs(self):
+        """sgt, l3t: (tau1code, tau2code, k1, k2, k3); e1t: *_loop_coefs' seven."""
+        return _loop_coefs(self._prefix, self.cfg, self._n_coefs)
+
+    def init_chans(self, code_ids, code_phases_1b, acq_freqs, streams=None, skip=0):
+        n = len(code_ids)
+        streams = np.zeros(n, np.int64) if streams is None else np.asarray(streams)
+        out = np.zeros(n, self._CHAN)
+        for i in range(n):
+            out[i] = _init_chan(self._prefix, self._CHAN, self.cfg, code_ids[i],
+                                code_phases_1b[i], acq_freqs[i], streams[i], skip)[0]
+        return out
+
+    def track(self, d_if, stride, n_samples, chans, n_epochs, closed_loop=True):
+        """Host channel array in/out; returns epochs [n_ch, n_epochs]."""
+        assert chans.dtype == self._CHAN and chans.flags.c_contiguous
+        ep = np.zeros((len(chans), n_epochs), self._EPOCH)
+        _check(self._track(self.h, d_if, stride, n_samples, len(chans), _ptr(chans), n_epochs,
+                           int(closed_loop), _ptr(ep)), self._track)
+        return ep
+
+    def track_dev(self, d_if, stride, n_samples, n_ch, d_chan, n_epochs, d_epochs,
+                  closed_loop=True):
+        _check(self._track_dev(self.h, d_if, stride, n_samples, n_ch, d_chan, n_epochs,
+                               int(closed_loop), d_epochs), self._track_dev)
+
+    def replay(self, chans, sums):
+        """The loop half on given sums [n_ch, n_epochs, n_sums] (sgt: I_E, I_P, I_L, Q_E,
+        Q_P, Q_L; e1t: E1T_SUMS order; l3t: L3T_SUMS order); host channel array in/out;
+        returns epochs [n_ch, n_epochs]."""
+        assert chans.dtype == self._CHAN and chans.flags.c_contiguous
+        sums = np.ascontiguousarray(sums, dtype=np.float64)
+        n_ch, n_ep = sums.shape[0], sums.shape[1]
+        assert sums.shape == (len(chans), n_ep, self._n_sums)
+        ep = np.zeros((n_ch, n_ep), self._EPOCH)
+        _check(self._replay(self.h, n_ch, _ptr(chans), n_ep, _ptr(sums), _ptr(ep)),
+               self._replay)
+        return ep
 
 
 # ---------------------------------------------------------------- SoftGNSS float tracking
@@ -897,10 +917,7 @@ def sgt_cfg(system: int, device: int = 0, **kw) -> SgtCfg:
     if system == 2:
         d.update(codeFreqBasis=2.046e6, codeLength=2046, IF=0.098e6, dllCorrelatorSpacing=0.1,
                  dllNoiseBandwidth=0.5)
-    unknown = set(kw) - set(d) - {"system"}
-    if unknown:
-        raise ValueError(f"unknown settings {sorted(unknown)}")
-    d.update(kw)
+    d = _settings(d, kw, also=("system",))
     return SgtCfg(system, d["fileType"], d["switchIQ"], d["codeLength"], device, 0,
                   d["samplingFreq"], d["codeFreqBasis"], d["IF"], d["L1_IF_step"],
                   d["GLONASS_zero_channel"], d["dllCorrelatorSpacing"], d["dllNoiseBandwidth"],
@@ -908,72 +925,13 @@ def sgt_cfg(system: int, device: int = 0, **kw) -> SgtCfg:
                   d["codeNcoVariant"], d["absSampleVariant"])
 
 
-class SgtCtx:
+class SgtCtx(_FloatTracker):
     """SoftGNSS float tracking (tracking.sci) for many channels over HBM-resident records."""
 
+    _prefix, _CHAN, _EPOCH, _n_sums, _n_coefs = "gnsscorr_sgt", SGT_CHAN, SGT_EPOCH, 6, 5
+
     def __init__(self, system: int, device: int = 0, **settings):
-        self.cfg = sgt_cfg(system, device, **settings)
-        h = C.c_void_p()
-        _check(lib().gnsscorr_sgt_create(C.byref(h), C.byref(self.cfg)), "gnsscorr_sgt_create")
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().gnsscorr_sgt_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    def loop_coefs(self):
-        v = [C.c_double() for _ in range(5)]
-        lib().gnsscorr_sgt_loop_coefs(C.byref(self.cfg), *[C.byref(x) for x in v])
-        return tuple(x.value for x in v)     # tau1code, tau2code, k1, k2, k3
-
-    def init_chans(self, code_ids, code_phases_1b, acq_freqs, streams=None, skip=0):
-        n = len(code_ids)
-        out = np.zeros(n, SGT_CHAN)
-        streams = np.zeros(n, np.int64) if streams is None else np.asarray(streams)
-        for i in range(n):
-            _check(lib().gnsscorr_sgt_init_chan(C.byref(self.cfg), int(code_ids[i]),
-                                                int(streams[i]), int(skip),
-                                                int(code_phases_1b[i]), float(acq_freqs[i]),
-                                                out[i:i + 1].ctypes.data),
-                   "gnsscorr_sgt_init_chan")
-        return out
-
-    def track(self, d_if, stride, n_samples, chans, n_epochs, closed_loop=True):
-        """Host channel array in/out; returns epochs [n_ch, n_epochs]."""
-        assert chans.dtype == SGT_CHAN and chans.flags.c_contiguous
-        ep = np.zeros((len(chans), n_epochs), SGT_EPOCH)
-        _check(lib().gnsscorr_sgt_track(self.h, d_if, stride, n_samples, len(chans),
-                                        _ptr(chans), n_epochs, int(closed_loop), _ptr(ep)),
-               "gnsscorr_sgt_track")
-        return ep
-
-    def track_dev(self, d_if, stride, n_samples, n_ch, d_chan, n_epochs, d_epochs,
-                  closed_loop=True):
-        _check(lib().gnsscorr_sgt_track_dev(self.h, d_if, stride, n_samples, n_ch, d_chan,
-                                            n_epochs, int(closed_loop), d_epochs),
-               "gnsscorr_sgt_track_dev")
-
-    def replay(self, chans, sums):
-        """The loop half on given sums [n_ch, n_epochs, 6] (I_E, I_P, I_L, Q_E, Q_P,
-        Q_L); host channel array in/out; returns epochs [n_ch, n_epochs]."""
-        assert chans.dtype == SGT_CHAN and chans.flags.c_contiguous
-        sums = np.ascontiguousarray(sums, dtype=np.float64)
-        n_ch, n_ep = sums.shape[0], sums.shape[1]
-        assert sums.shape == (len(chans), n_ep, 6)
-        ep = np.zeros((n_ch, n_ep), SGT_EPOCH)
-        _check(lib().gnsscorr_sgt_replay(self.h, n_ch, _ptr(chans), n_ep, _ptr(sums), _ptr(ep)),
-               "gnsscorr_sgt_replay")
-        return ep
-
-    def sync(self):
-        _check(lib().gnsscorr_sgt_sync(self.h), "gnsscorr_sgt_sync")
-
-    @property
-    def stream(self) -> int:
-        return lib().gnsscorr_sgt_stream(self.h)
+        self._open(sgt_cfg(system, device, **settings))
 
 
 # ---------------------------------------------------------------- Galileo E1B float tracking
@@ -982,15 +940,12 @@ def e1t_cfg(device: int = 0, **kw) -> E1tCfg:
     names (samplingFreq, IF, sllCorrelatorSpacing, fileType, ...) plus maxCodes and the
     loop of GALILEO/E1/BOC_tracking_alternatives/ to run: epochMs 1 (tracking.sci) or 4
     (tracking_4ms.sci), ambiguous 1 for the three-arm tracking_ambiguous_{1,4}ms.sci."""
-    d = dict(fileType=2, samplingFreq=16e6, codeFreqBasis=1.023e6, meandrFreqBasis=2.046e6,
-             IF=2.42e6, codeLength=4092, meandrLength=8184, dllDampingRatio=0.7,
-             dllNoiseBandwidth=0.5, dllCorrelatorSpacing=0.25, sllDampingRatio=0.7,
-             sllNoiseBandwidth=0.5, sllCorrelatorSpacing=0.1, pllNoiseBandwidth=25.0,
-             fllNoiseBandwidth=250.0, maxCodes=50, epochMs=1, ambiguous=0)
-    unknown = set(kw) - set(d)
-    if unknown:
-        raise ValueError(f"unknown settings {sorted(unknown)}")
-    d.update(kw)
+    d = _settings(dict(
+        fileType=2, samplingFreq=16e6, codeFreqBasis=1.023e6, meandrFreqBasis=2.046e6,
+        IF=2.42e6, codeLength=4092, meandrLength=8184, dllDampingRatio=0.7,
+        dllNoiseBandwidth=0.5, dllCorrelatorSpacing=0.25, sllDampingRatio=0.7,
+        sllNoiseBandwidth=0.5, sllCorrelatorSpacing=0.1, pllNoiseBandwidth=25.0,
+        fllNoiseBandwidth=250.0, maxCodes=50, epochMs=1, ambiguous=0), kw)
     return E1tCfg(d["fileType"], device, 0, d["maxCodes"], d["codeLength"], d["meandrLength"],
                   d["samplingFreq"], d["codeFreqBasis"], d["meandrFreqBasis"], d["IF"],
                   d["dllCorrelatorSpacing"], d["dllNoiseBandwidth"], d["dllDampingRatio"],
@@ -1000,41 +955,23 @@ def e1t_cfg(device: int = 0, **kw) -> E1tCfg:
 
 def e1t_loop_coefs(cfg: E1tCfg):
     """(tau1code, tau2code, tau1meandr, tau2meandr, k1, k2, k3) of a configuration (host only)."""
-    v = [C.c_double() for _ in range(7)]
-    lib().gnsscorr_e1t_loop_coefs(C.byref(cfg), *[C.byref(x) for x in v])
-    return tuple(x.value for x in v)
+    return _loop_coefs("gnsscorr_e1t", cfg, 7)
 
 
 def e1t_init_chan(cfg: E1tCfg, code_id, code_phase_1b, acq_freq, stream=0, skip=0) -> np.ndarray:
     """One E1T_CHAN (shape (1,)) from an acquisition result (host only)."""
-    out = np.zeros(1, E1T_CHAN)
-    _check(lib().gnsscorr_e1t_init_chan(C.byref(cfg), int(code_id), int(stream), int(skip),
-                                        int(code_phase_1b), float(acq_freq), out.ctypes.data),
-           "gnsscorr_e1t_init_chan")
-    return out
+    return _init_chan("gnsscorr_e1t", E1T_CHAN, cfg, code_id, code_phase_1b, acq_freq, stream,
+                      skip)
 
 
-class E1tCtx:
+class E1tCtx(_FloatTracker):
     """Galileo E1B float tracking (GALILEO/E1/tracking.sci) for many channels over
     HBM-resident records: code and subcarrier NCOs, five arms, PLL/FLL + DLL + SLL.
     epochMs=4 and / or ambiguous=1 select the loops of BOC_tracking_alternatives/ (e1t_cfg);
     in the ambiguous modes I_E .. Q_L are the I_P_E, I_P_P, I_P_L, Q_P_E, Q_P_P, Q_P_L fields."""
 
-    def __init__(self, device: int = 0, **settings):
-        self.cfg = e1t_cfg(device, **settings)
-        h = C.c_void_p()
-        _check(lib().gnsscorr_e1t_create(C.byref(h), C.byref(self.cfg)), "gnsscorr_e1t_create")
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().gnsscorr_e1t_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    def loop_coefs(self):
-        return e1t_loop_coefs(self.cfg)
+    _prefix, _CHAN, _EPOCH, _n_sums, _n_coefs = "gnsscorr_e1t", E1T_CHAN, E1T_EPOCH, 10, 7
+    _make_cfg = staticmethod(e1t_cfg)
 
     def set_codes(self, chips):
         """chips: (n_codes, 4092) of +-1; channel code_id is the row."""
@@ -1046,59 +983,16 @@ class E1tCtx:
     def init_chan(self, code_id, code_phase_1b, acq_freq, stream=0, skip=0):
         return e1t_init_chan(self.cfg, code_id, code_phase_1b, acq_freq, stream, skip)
 
-    def init_chans(self, code_ids, code_phases_1b, acq_freqs, streams=None, skip=0):
-        n = len(code_ids)
-        streams = np.zeros(n, np.int64) if streams is None else np.asarray(streams)
-        return np.concatenate([self.init_chan(code_ids[i], code_phases_1b[i], acq_freqs[i],
-                                              streams[i], skip) for i in range(n)])
-
-    def track(self, d_if, stride, n_samples, chans, n_epochs, closed_loop=True):
-        """Host channel array in/out; returns epochs [n_ch, n_epochs]."""
-        assert chans.dtype == E1T_CHAN and chans.flags.c_contiguous
-        ep = np.zeros((len(chans), n_epochs), E1T_EPOCH)
-        _check(lib().gnsscorr_e1t_track(self.h, d_if, stride, n_samples, len(chans),
-                                        _ptr(chans), n_epochs, int(closed_loop), _ptr(ep)),
-               "gnsscorr_e1t_track")
-        return ep
-
-    def track_dev(self, d_if, stride, n_samples, n_ch, d_chan, n_epochs, d_epochs,
-                  closed_loop=True):
-        _check(lib().gnsscorr_e1t_track_dev(self.h, d_if, stride, n_samples, n_ch, d_chan,
-                                            n_epochs, int(closed_loop), d_epochs),
-               "gnsscorr_e1t_track_dev")
-
-    def replay(self, chans, sums):
-        """The loop half on given sums [n_ch, n_epochs, 10] (E1T_SUMS order); host
-        channel array in/out; returns epochs [n_ch, n_epochs]."""
-        assert chans.dtype == E1T_CHAN and chans.flags.c_contiguous
-        sums = np.ascontiguousarray(sums, dtype=np.float64)
-        n_ch, n_ep = sums.shape[0], sums.shape[1]
-        assert sums.shape == (len(chans), n_ep, 10)
-        ep = np.zeros((n_ch, n_ep), E1T_EPOCH)
-        _check(lib().gnsscorr_e1t_replay(self.h, n_ch, _ptr(chans), n_ep, _ptr(sums), _ptr(ep)),
-               "gnsscorr_e1t_replay")
-        return ep
-
-    def sync(self):
-        _check(lib().gnsscorr_e1t_sync(self.h), "gnsscorr_e1t_sync")
-
-    @property
-    def stream(self) -> int:
-        return lib().gnsscorr_e1t_stream(self.h)
-
 
 # ---------------------------------------------------------------- GLONASS L3OC float tracking
 def l3t_cfg(device: int = 0, **kw) -> L3tCfg:
     """GLONASS/L3/initSettings.sci:64-96 defaults; keyword overrides use the Scilab names
     (samplingFreq, IF, GLONASS_nominal_freq, dllCorrelatorSpacing, switchIQ, ...)."""
-    d = dict(fileType=2, switchIQ=0, samplingFreq=24e6, codeFreqBasis=10.23e6, codeLength=10230,
-             IF=-2.025e6, GLONASS_nominal_freq=1202.025e6, dllDampingRatio=0.7,
-             dllNoiseBandwidth=1.0, dllCorrelatorSpacing=0.4, pllNoiseBandwidth=25.0,
-             fllNoiseBandwidth=250.0)
-    unknown = set(kw) - set(d)
-    if unknown:
-        raise ValueError(f"unknown settings {sorted(unknown)}")
-    d.update(kw)
+    d = _settings(dict(
+        fileType=2, switchIQ=0, samplingFreq=24e6, codeFreqBasis=10.23e6, codeLength=10230,
+        IF=-2.025e6, GLONASS_nominal_freq=1202.025e6, dllDampingRatio=0.7,
+        dllNoiseBandwidth=1.0, dllCorrelatorSpacing=0.4, pllNoiseBandwidth=25.0,
+        fllNoiseBandwidth=250.0), kw)
     return L3tCfg(d["fileType"], d["switchIQ"], d["codeLength"], device, 0, 0, d["samplingFreq"],
                   d["codeFreqBasis"], d["IF"], d["GLONASS_nominal_freq"],
                   d["dllCorrelatorSpacing"], d["dllNoiseBandwidth"], d["dllDampingRatio"],
@@ -1107,83 +1001,27 @@ def l3t_cfg(device: int = 0, **kw) -> L3tCfg:
 
 def l3t_loop_coefs(cfg: L3tCfg):
     """(tau1code, tau2code, k1, k2, k3) of a configuration (host only)."""
-    v = [C.c_double() for _ in range(5)]
-    lib().gnsscorr_l3t_loop_coefs(C.byref(cfg), *[C.byref(x) for x in v])
-    return tuple(x.value for x in v)
+    return _loop_coefs("gnsscorr_l3t", cfg, 5)
 
 
 def l3t_init_chan(cfg: L3tCfg, prn, code_phase_1b, acq_freq, stream=0, skip=0) -> np.ndarray:
     """One L3T_CHAN (shape (1,)) from an acquisition result (host only); PRN 1..31."""
-    out = np.zeros(1, L3T_CHAN)
-    _check(lib().gnsscorr_l3t_init_chan(C.byref(cfg), int(prn), int(stream), int(skip),
-                                        int(code_phase_1b), float(acq_freq), out.ctypes.data),
-           "gnsscorr_l3t_init_chan")
-    return out
+    return _init_chan("gnsscorr_l3t", L3T_CHAN, cfg, prn, code_phase_1b, acq_freq, stream, skip)
 
 
-class L3tCtx:
+class L3tCtx(_FloatTracker):
     """GLONASS L3OC float tracking (GLONASS/L3/tracking.sci) for many channels over
     HBM-resident IQ records: pilot and data code on one code NCO, twelve sums, FLL and DLL
     on the data channel, PLL on the pilot."""
 
-    def __init__(self, device: int = 0, **settings):
-        self.cfg = l3t_cfg(device, **settings)
-        h = C.c_void_p()
-        _check(lib().gnsscorr_l3t_create(C.byref(h), C.byref(self.cfg)), "gnsscorr_l3t_create")
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().gnsscorr_l3t_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    def loop_coefs(self):
-        return l3t_loop_coefs(self.cfg)
+    _prefix, _CHAN, _EPOCH, _n_sums, _n_coefs = "gnsscorr_l3t", L3T_CHAN, L3T_EPOCH, 12, 5
+    _make_cfg = staticmethod(l3t_cfg)
 
     def init_chan(self, prn, code_phase_1b, acq_freq, stream=0, skip=0):
         return l3t_init_chan(self.cfg, prn, code_phase_1b, acq_freq, stream, skip)
 
     def init_chans(self, prns, code_phases_1b, acq_freqs, streams=None, skip=0):
-        n = len(prns)
-        streams = np.zeros(n, np.int64) if streams is None else np.asarray(streams)
-        return np.concatenate([self.init_chan(prns[i], code_phases_1b[i], acq_freqs[i],
-                                              streams[i], skip) for i in range(n)])
-
-    def track(self, d_if, stride, n_samples, chans, n_epochs, closed_loop=True):
-        """Host channel array in/out; returns epochs [n_ch, n_epochs]."""
-        assert chans.dtype == L3T_CHAN and chans.flags.c_contiguous
-        ep = np.zeros((len(chans), n_epochs), L3T_EPOCH)
-        _check(lib().gnsscorr_l3t_track(self.h, d_if, stride, n_samples, len(chans),
-                                        _ptr(chans), n_epochs, int(closed_loop), _ptr(ep)),
-               "gnsscorr_l3t_track")
-        return ep
-
-    def track_dev(self, d_if, stride, n_samples, n_ch, d_chan, n_epochs, d_epochs,
-                  closed_loop=True):
-        _check(lib().gnsscorr_l3t_track_dev(self.h, d_if, stride, n_samples, n_ch, d_chan,
-                                            n_epochs, int(closed_loop), d_epochs),
-               "gnsscorr_l3t_track_dev")
-
-    def replay(self, chans, sums):
-        """The loop half on given sums [n_ch, n_epochs, 12] (L3T_SUMS order); host
-        channel array in/out; returns epochs [n_ch, n_epochs]."""
-        assert chans.dtype == L3T_CHAN and chans.flags.c_contiguous
-        sums = np.ascontiguousarray(sums, dtype=np.float64)
-        n_ch, n_ep = sums.shape[0], sums.shape[1]
-        assert sums.shape == (len(chans), n_ep, 12)
-        ep = np.zeros((n_ch, n_ep), L3T_EPOCH)
-        _check(lib().gnsscorr_l3t_replay(self.h, n_ch, _ptr(chans), n_ep, _ptr(sums), _ptr(ep)),
-               "gnsscorr_l3t_replay")
-        return ep
-
-    def sync(self):
-        _check(lib().gnsscorr_l3t_sync(self.h), "gnsscorr_l3t_sync")
-
-    @property
-    def stream(self) -> int:
-        return lib().gnsscorr_l3t_stream(self.h)
+        return super().init_chans(prns, code_phases_1b, acq_freqs, streams, skip)
 
 
 # ---------------------------------------------------------------- GPS-SDR integer acquisition
@@ -1200,22 +1038,13 @@ def sdr_sine_gen(f: float, n: int = 2048, fs: float = 2048000.0) -> np.ndarray:
     return out
 
 
-class SdrAcqCtx:
+class SdrAcqCtx(_Handle):
     """GPS-SDR strong (1 ms, int16 FFT) acquisition, bit-exact with the reference."""
 
+    _prefix = "gnsscorr_sdr_acq"
+
     def __init__(self, fif: float = 38400.0, device: int = 0, saturate: bool = False):
-        h = C.c_void_p()
-        _check(lib().gnsscorr_sdr_acq_create(C.byref(h), C.byref(SdrAcqCfg(fif, device,
-                                                                             int(saturate)))),
-               "gnsscorr_sdr_acq_create")
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().gnsscorr_sdr_acq_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+        self._create(C.byref(SdrAcqCfg(fif, device, int(saturate))))
 
     def strong(self, buffers, svs, doppmin=-15000, doppmax=15000) -> np.ndarray:
         """buffers: (n_rec, 2048, 2) or (2048, 2) int16; returns SDR_RESULT [n_rec, n_sv]."""
@@ -1252,13 +1081,6 @@ class SdrAcqCtx:
     def strong_dev(self, d_buff, n_rec, n_sv, d_svs, d_res, doppmin=-15000, doppmax=15000):
         _check(lib().gnsscorr_sdr_acq_strong_dev(self.h, d_buff, n_rec, n_sv, d_svs, doppmin,
                                                  doppmax, d_res), "gnsscorr_sdr_acq_strong_dev")
-
-    def sync(self):
-        _check(lib().gnsscorr_sdr_acq_sync(self.h), "gnsscorr_sdr_acq_sync")
-
-    @property
-    def stream(self) -> int:
-        return lib().gnsscorr_sdr_acq_stream(self.h)
 
 
 class OsgLoopCfg(C.Structure):
@@ -1318,20 +1140,13 @@ def pack_2bit(samples) -> np.ndarray:
     return (s[:, 0] | (s[:, 1] << 2) | (s[:, 2] << 4) | (s[:, 3] << 6)).astype(np.uint8)
 
 
-class SdrFeCtx:
+class SdrFeCtx(_Handle):
     """GPS-SDR sample front end: GN3S 2-bit unpack + NCO mix + resample, downsample."""
 
+    _prefix = "gnsscorr_sdr_fe"
+
     def __init__(self, device: int = 0):
-        h = C.c_void_p()
-        _check(lib().gnsscorr_sdr_fe_create(C.byref(h), device), "gnsscorr_sdr_fe_create")
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().gnsscorr_sdr_fe_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+        self._create(device)
 
     def gn3s(self, data, packed=False, phase=0, step=GN3S_STEP):
         """data: n_blocks * 20000 bytes (or / 4 when packed); returns (CPX [n*10240, 2], phase)."""
@@ -1362,32 +1177,16 @@ class SdrFeCtx:
         return lib().gnsscorr_sdr_downsample_count(n_src, C.c_double(fdest), C.c_double(fsource),
                                                    None)
 
-    def sync(self):
-        _check(lib().gnsscorr_sdr_fe_sync(self.h), "gnsscorr_sdr_fe_sync")
 
-    @property
-    def stream(self) -> int:
-        return lib().gnsscorr_sdr_fe_stream(self.h)
-
-
-class SdrCorrCtx:
+class SdrCorrCtx(_Handle):
     """GPS-SDR tracking correlator (Correlator class): batched Accum on the GPU,
     Correlate schedule + UpdateState/DumpAccum on the host, channel loop by callback."""
 
+    _prefix = "gnsscorr_sdr_corr"
+
     def __init__(self, device: int = 0, saturate: bool = False):
-        h = C.c_void_p()
-        _check(lib().gnsscorr_sdr_corr_create(C.byref(h), C.byref(SdrCorrCfg(device,
-                                                                               int(saturate)))),
-               "gnsscorr_sdr_corr_create")
-        self.h = h
+        self._create(C.byref(SdrCorrCfg(device, int(saturate))))
         self.device = device
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().gnsscorr_sdr_corr_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     @staticmethod
     def init_chan(sv, acq_code_phase, acq_doppler, packets_since_acq=0.0) -> np.ndarray:
@@ -1508,13 +1307,6 @@ class SdrCorrCtx:
                                             None if rxa is None else _ptr(rxa), _ptr(states),
                                             _ptr(corr), cb, user),
                "gnsscorr_sdr_correlate")
-
-    def sync(self):
-        _check(lib().gnsscorr_sdr_corr_sync(self.h), "gnsscorr_sdr_corr_sync")
-
-    @property
-    def stream(self) -> int:
-        return lib().gnsscorr_sdr_corr_stream(self.h)
 
 
 # ---------------------------------------------------------------- legacy OSG view

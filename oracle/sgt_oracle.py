@@ -36,25 +36,13 @@ import math
 
 import numpy as np
 
+import ftrack_oracle as T
 from acq_oracle import generate_ca_code, generate_st_code
+from ftrack_oracle import _raw, calc_fll_pll_loop_coef, calc_loop_coef  # noqa: F401
 
 # trackResults fields per epoch, in the order the C-ABI record stores them
 FIELDS = ("I_E", "I_P", "I_L", "Q_E", "Q_P", "Q_L", "carrFreq", "codeFreq", "absoluteSample",
           "dllDiscr", "dllDiscrFilt", "pllDiscr", "pllDiscrFilt")
-
-
-def calc_loop_coef(lbw: float, zeta: float, k: float):
-    """calcLoopCoef.sci:39-43 -> (tau1, tau2)."""
-    wn = lbw * 8 * zeta / (4 * zeta ** 2 + 1)
-    return k / (wn * wn), 2.0 * zeta / wn
-
-
-def calc_fll_pll_loop_coef(pllbw: float, fllbw: float, T: float):
-    """calcFLLPLLLoopCoef.sci:36-38 -> (k1, k2, k3)."""
-    k1 = T * ((pllbw / 0.53) ** 2) + 1.414 * (pllbw / 0.53)
-    k2 = 1.414 * (pllbw / 0.53)
-    k3 = T * (fllbw / 0.25)
-    return k1, k2, k3
 
 
 def settings(system: int, **kw) -> dict:
@@ -81,16 +69,6 @@ def padded_code(system: int, prn: int = 1) -> np.ndarray:
     """tracking.sci:171-174 (GLONASS) / :140-142 (GPS): [c(end) c c(1)]."""
     c = generate_st_code() if system == 1 else generate_ca_code(prn)
     return np.concatenate([c[-1:], c, c[:1]])
-
-
-def _raw(IF: np.ndarray, pos: int, n: int, s: dict) -> np.ndarray:
-    if s["fileType"] == 1:
-        return IF[pos:pos + n].astype(np.float64)
-    v = IF[2 * pos:2 * (pos + n)].astype(np.float64)
-    r1, r2 = v[0::2], v[1::2]
-    if s["system"] == 1 and s["switchIQ"]:
-        return r2 + 1j * r1
-    return r1 + 1j * r2
 
 
 def correlate(IF, s, code_pad, pos, rem_code, rem_carr, code_freq, carr_freq):
@@ -197,16 +175,17 @@ def replay(sums, s, code_id, code_phase_1b, acquired_freq, skip=0):
     (I_E, I_P, I_L, Q_E, Q_P, Q_L) instead of correlations of a record: blksize
     and remCodePhase chain, discriminators, filters, NCO frequencies and
     absoluteSample.  Pins the loop against a recorded trackResults."""
-    lp = Loop(s, code_id, skip + code_phase_1b - 1, acquired_freq)
-    out = {f: [] for f in FIELDS}
-    out["blksize"] = []
-    for row in np.asarray(sums, dtype=np.float64):
-        blk, step = lp.blksize()
-        lp.advance(blk, step)
-        for f, v in zip(FIELDS, lp.update(row)):
-            out[f].append(v)
-        out["blksize"].append(blk)
-    return {f: np.asarray(v) for f, v in out.items()}
+    return T.replay(Loop(s, code_id, skip + code_phase_1b - 1, acquired_freq), FIELDS, sums)
+
+
+def epoch(IF, s, code_pad, lp):
+    """One epoch of `correlate` from the state of Loop `lp`, which is advanced on success:
+    (1, the blksize that did not fit, None) or (0, blksize, sums[6])."""
+    r = correlate(IF, s, code_pad, lp.pos, lp.rem_code, lp.rem_carr, lp.code_freq, lp.carr_freq)
+    if r is None:
+        return 1, lp.blksize()[0], None
+    sums, blk, lp.pos, lp.rem_code, lp.rem_carr = r
+    return 0, blk, sums
 
 
 def track(IF, s, code_id, code_phase_1b, acquired_freq, n_ms, skip=0):
@@ -214,16 +193,4 @@ def track(IF, s, code_id, code_phase_1b, acquired_freq, n_ms, skip=0):
     Returns a dict of FIELDS arrays (length = epochs actually processed) + 'blksize'."""
     code_pad = padded_code(s["system"], code_id)
     lp = Loop(s, code_id, skip + code_phase_1b - 1, acquired_freq)   # mseek, :163-168
-    out = {f: [] for f in FIELDS}
-    out["blksize"] = []
-    for _ in range(n_ms):
-        r = correlate(IF, s, code_pad, lp.pos, lp.rem_code, lp.rem_carr, lp.code_freq,
-                      lp.carr_freq)
-        if r is None:
-            break
-        sums, blk, pos, rem_code, rem_carr = r
-        lp.pos, lp.rem_code, lp.rem_carr = pos, rem_code, rem_carr
-        for f, v in zip(FIELDS, lp.update(sums)):
-            out[f].append(v)
-        out["blksize"].append(blk)
-    return {f: np.asarray(v) for f, v in out.items()}
+    return T.track(lp, FIELDS, n_ms, lambda lp: epoch(IF, s, code_pad, lp))[0]

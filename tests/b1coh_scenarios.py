@@ -31,23 +31,12 @@ import numpy as np
 
 import b1i_scenarios as B
 import e1b_scenarios as E
+from ftrack_oracle import code_phase_range_1b
 
 MODES = {3: dict(coh=3, segments=7), 5: dict(coh=5, segments=4)}
 
 
-# ---- acquisition_7x3ms.sci:159-176 -----------------------------------------------------
-def code_phase_range_1b(code_phase, samples_per_code, samples_per_chip):
-    """codePhaseRange, 1-based, exactly as written (code_phase: the 1-based codePhase)."""
-    ex1 = code_phase - samples_per_chip                                          # :162
-    ex2 = code_phase + samples_per_chip                                          # :163
-    if ex1 < 2:                                                                   # :167
-        return np.arange(ex2, samples_per_code + ex1 + 1)                         # :168-169
-    elif ex2 > samples_per_code:                                                  # :170
-        return np.arange(ex2 - samples_per_code, ex1 + 1)                         # :171-172
-    return np.concatenate([np.arange(1, ex1 + 1),                                 # :174-175
-                           np.arange(ex2, samples_per_code + 1)])
-
-
+# ---- acquisition_7x3ms.sci:159-176 (codePhaseRange: ftrack_oracle.code_phase_range_1b) --
 def second_candidates(row_len, argmax0, spc, period):
     """0-based candidate lags of `second` in a row of row_len lags: the range of :159-176
     written on `period`, or (period 0) outside the open window circular in the row."""

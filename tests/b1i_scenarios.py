@@ -18,6 +18,7 @@ import math
 
 import numpy as np
 
+import ftrack_oracle as T
 import sgt_oracle as S
 
 FIELDS = S.FIELDS
@@ -129,38 +130,14 @@ def track(IF, s, prn, code_phase_1b, acquired_freq, n_ms, skip=0, perturb=None):
     six relative offsets applied to the sums before the loop sees them."""
     pad = padded_code(prn)
     lp = Loop(s, prn, skip + code_phase_1b - 1, acquired_freq)
-    out = {f: [] for f in FIELDS}
-    out["blksize"] = []
-    stop = None
-    for _ in range(n_ms):
-        r = S.correlate(IF, s, pad, lp.pos, lp.rem_code, lp.rem_carr, lp.code_freq, lp.carr_freq)
-        if r is None:
-            stop = lp.blksize()[0]
-            break
-        sums, blk, pos, rem_code, rem_carr = r
-        if perturb is not None:
-            sums = sums * (1.0 + np.asarray(perturb))
-        lp.pos, lp.rem_code, lp.rem_carr = pos, rem_code, rem_carr
-        for f, v in zip(FIELDS, lp.update(sums)):
-            out[f].append(v)
-        out["blksize"].append(blk)
-    res = {f: np.asarray(v) for f, v in out.items()}
-    res["stop_blksize"] = stop
+    res, status, stop = T.track(lp, FIELDS, n_ms, lambda lp: S.epoch(IF, s, pad, lp), perturb)
+    res["stop_blksize"] = stop if status else None
     return res
 
 
 def replay(sums, s, prn, code_phase_1b, acquired_freq, skip=0):
     """The loop half on given sums [n, 6] (as sgt_oracle.replay, with this file's Loop)."""
-    lp = Loop(s, prn, skip + code_phase_1b - 1, acquired_freq)
-    out = {f: [] for f in FIELDS}
-    out["blksize"] = []
-    for row in np.asarray(sums, dtype=np.float64):
-        blk, step = lp.blksize()
-        lp.advance(blk, step)
-        for f, v in zip(FIELDS, lp.update(row)):
-            out[f].append(v)
-        out["blksize"].append(blk)
-    return {f: np.asarray(v) for f, v in out.items()}
+    return T.replay(Loop(s, prn, skip + code_phase_1b - 1, acquired_freq), FIELDS, sums)
 
 
 # ---- acquisition.sci:86-168 ------------------------------------------------------------

@@ -48,6 +48,7 @@ import math
 import numpy as np
 
 import e1t_scenarios as E
+import ftrack_oracle as T
 
 SUMS, LOOP_FIELDS, FIELDS = E.SUMS, E.LOOP_FIELDS, E.FIELDS
 MODES = {"4ms": dict(epochMs=4, ambiguous=0), "amb1": dict(epochMs=1, ambiguous=1),
@@ -324,37 +325,15 @@ def track(mode, IF, s, chips, code_phase_1b, acquired_freq, n_epochs, skip=0, pe
     relative offsets applied to every epoch's sums before the loop filters."""
     tab = tables(mode, chips)
     lp = Loop(mode, s, skip + code_phase_1b - 1, acquired_freq)   # mseek
-    out = E._out()
-    status, stop_blk = 0, 0
-    for _ in range(n_epochs):
-        seg = lp.segment
-        st, blk, sums = correlate(mode, IF, s, tab, lp)
-        if st:
-            status, stop_blk = st, blk
-            break
-        out["segment"].append(seg)
-        if perturb is not None:
-            sums = sums * (1.0 + np.asarray(perturb, np.float64))
-        for f, v in zip(FIELDS, lp.update(sums)):
-            out[f].append(v)
-        out["blksize"].append(blk)
-    res = {f: np.asarray(v) for f, v in out.items()}
-    res["status"], res["stop_blksize"] = status, stop_blk
+    res, res["status"], res["stop_blksize"] = T.track(
+        lp, FIELDS, n_epochs, lambda lp: correlate(mode, IF, s, tab, lp), perturb, segment=True)
     return res
 
 
 def replay(mode, sums, s, code_phase_1b, acquired_freq, skip=0):
     """The loop half driven by given per-epoch sums [n, 10] (SUMS order)."""
-    lp = Loop(mode, s, skip + code_phase_1b - 1, acquired_freq)
-    out = E._out()
-    for row in np.asarray(sums, dtype=np.float64):
-        blk, cstep, mstep = lp.blksize()
-        out["segment"].append(lp.segment)
-        lp.advance(blk, cstep, mstep)
-        for f, v in zip(FIELDS, lp.update(row)):
-            out[f].append(v)
-        out["blksize"].append(blk)
-    return {f: np.asarray(v) for f, v in out.items()}
+    return T.replay(Loop(mode, s, skip + code_phase_1b - 1, acquired_freq), FIELDS, sums,
+                    segment=True)
 
 
 # ---------------------------------------------------------------- closed-loop scenes

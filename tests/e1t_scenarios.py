@@ -26,6 +26,9 @@ import os
 
 import numpy as np
 
+import ftrack_oracle as T
+from ftrack_oracle import _raw, calc_fll_pll_loop_coef, calc_loop_coef  # noqa: F401
+
 SUMS = ("I_E_P", "I_P_E", "I_P_P", "I_P_L", "I_L_P", "Q_E_P", "Q_P_E", "Q_P_P", "Q_P_L", "Q_L_P")
 LOOP_FIELDS = ("carrFreq", "codeFreq", "meandrFreq", "absoluteSample", "dllDiscr", "dllDiscrFilt",
                "sllDiscr", "sllDiscrFilt", "pllDiscr", "pllDiscrFilt")
@@ -37,20 +40,6 @@ def fixture_codes():
     """(codes (3, 4092) int8, prns) of tests/golden/e1b_codes.npz: E1B PRN 11, 12, 19."""
     g = np.load(GOLDEN)
     return g["codes"], [int(p) for p in g["prns"]]
-
-
-def calc_loop_coef(lbw: float, zeta: float, k: float):
-    """calcLoopCoef.sci:39-43 -> (tau1, tau2)."""
-    wn = lbw * 8 * zeta / (4 * zeta ** 2 + 1)
-    return k / (wn * wn), 2.0 * zeta / wn
-
-
-def calc_fll_pll_loop_coef(pllbw: float, fllbw: float, T: float):
-    """calcFLLPLLLoopCoef.sci:36-38 -> (k1, k2, k3)."""
-    k1 = T * ((pllbw / 0.53) ** 2) + 1.414 * (pllbw / 0.53)
-    k2 = 1.414 * (pllbw / 0.53)
-    k3 = T * (fllbw / 0.25)
-    return k1, k2, k3
 
 
 def settings(**kw) -> dict:
@@ -83,13 +72,6 @@ def meandr_table(meandr_length: int = 8184) -> np.ndarray:
     m = np.ones(meandr_length // 4)
     m[1::2] = -1                                # meandr(2:2:$) = -1
     return np.concatenate([m[-2:-1], m[-1:], m, m[0:1], m[1:2]])
-
-
-def _raw(IF, pos, n, s):
-    if s["fileType"] == 1:
-        return IF[pos:pos + n].astype(np.float64)
-    v = IF[2 * pos:2 * (pos + n)].astype(np.float64)
-    return v[0::2] + 1j * v[1::2]
 
 
 def correlate(IF, s, rows, mtab, pos, segment, rem_code, rem_meandr, rem_carr, code_freq,
@@ -208,13 +190,6 @@ class Loop:
                 meandr_err, meandr_nco, carr_err, carr_nco)
 
 
-def _out():
-    o = {f: [] for f in FIELDS}
-    o["blksize"] = []
-    o["segment"] = []
-    return o
-
-
 def track(IF, s, chips, code_phase_1b, acquired_freq, n_ms, skip=0, perturb=None):
     """tracking.sci's per-channel loop for n_ms epochs.  Returns a dict of FIELDS arrays
     (length = epochs processed) + 'blksize', 'segment' (0-based, the quarter each epoch
@@ -223,39 +198,22 @@ def track(IF, s, chips, code_phase_1b, acquired_freq, n_ms, skip=0, perturb=None
     filters (the decidability check of the closed-loop scenes)."""
     rows, mtab = split_code(chips), meandr_table(s["meandrLength"])
     lp = Loop(s, skip + code_phase_1b - 1, acquired_freq)   # mseek, :150-151
-    out = _out()
-    status, stop_blk = 0, 0
-    for _ in range(n_ms):
+
+    def epoch(lp):
         st, blk, r = correlate(IF, s, rows, mtab, lp.pos, lp.segment, lp.rem_code, lp.rem_meandr,
                                lp.rem_carr, lp.code_freq, lp.meandr_freq, lp.carr_freq)
         if st:
-            status, stop_blk = st, blk
-            break
-        sums, pos, seg, rc, rm, rcar = r
-        out["segment"].append(lp.segment)
-        lp.pos, lp.segment, lp.rem_code, lp.rem_meandr, lp.rem_carr = pos, seg, rc, rm, rcar
-        if perturb is not None:
-            sums = sums * (1.0 + np.asarray(perturb, np.float64))
-        for f, v in zip(FIELDS, lp.update(sums)):
-            out[f].append(v)
-        out["blksize"].append(blk)
-    res = {f: np.asarray(v) for f, v in out.items()}
-    res["status"], res["stop_blksize"] = status, stop_blk
+            return st, blk, None
+        sums, lp.pos, lp.segment, lp.rem_code, lp.rem_meandr, lp.rem_carr = r
+        return 0, blk, sums
+    res, res["status"], res["stop_blksize"] = T.track(lp, FIELDS, n_ms, epoch, perturb,
+                                                      segment=True)
     return res
 
 
 def replay(sums, s, code_phase_1b, acquired_freq, skip=0):
     """The loop half driven by given per-epoch sums [n, 10] (SUMS order)."""
-    lp = Loop(s, skip + code_phase_1b - 1, acquired_freq)
-    out = _out()
-    for row in np.asarray(sums, dtype=np.float64):
-        blk, cstep, mstep = lp.blksize()
-        out["segment"].append(lp.segment)
-        lp.advance(blk, cstep, mstep)
-        for f, v in zip(FIELDS, lp.update(row)):
-            out[f].append(v)
-        out["blksize"].append(blk)
-    return {f: np.asarray(v) for f, v in out.items()}
+    return T.replay(Loop(s, skip + code_phase_1b - 1, acquired_freq), FIELDS, sums, segment=True)
 
 
 def synth_e1b(n, sats, fs=16e6, IF=2.42e6, noise=6.0, seed=0):

@@ -28,6 +28,9 @@ import math
 import numpy as np
 
 import e1b_scenarios as E1B
+import ftrack_oracle as T
+from ftrack_oracle import (_raw, calc_fll_pll_loop_coef, calc_loop_coef,  # noqa: F401
+                           code_phase_range_1b)
 
 SUMS = ("I_E", "I_P", "I_L", "Q_E", "Q_P", "Q_L", "I_E2", "I_P2", "I_L2", "Q_E2", "Q_P2", "Q_L2")
 LOOP_FIELDS = ("carrFreq", "codeFreq", "absoluteSample", "dllDiscr", "dllDiscrFilt", "pllDiscr",
@@ -92,20 +95,6 @@ def settings(**kw) -> dict:
     return s
 
 
-def calc_loop_coef(lbw, zeta, k):
-    """calcLoopCoef.sci:39-43 -> (tau1, tau2)."""
-    wn = lbw * 8 * zeta / (4 * zeta ** 2 + 1)
-    return k / (wn * wn), 2.0 * zeta / wn
-
-
-def calc_fll_pll_loop_coef(pllbw, fllbw, T):
-    """calcFLLPLLLoopCoef.sci:36-38 -> (k1, k2, k3)."""
-    k1 = T * ((pllbw / 0.53) ** 2) + 1.414 * (pllbw / 0.53)
-    k2 = 1.414 * (pllbw / 0.53)
-    k3 = T * (fllbw / 0.25)
-    return k1, k2, k3
-
-
 # ---- makeCaTable.sci and the replica --------------------------------------------------
 def samples_per_code(s):
     return int(round(s["samplingFreq"] / (s["codeFreqBasis"] / s["codeLength"])))
@@ -134,18 +123,6 @@ def bins(s):
 
 
 # ---- the second-peak range of acquisition.sci:134-153 ---------------------------------
-def code_phase_range_1b(code_phase, samples_per_code_, samples_per_chip):
-    """codePhaseRange, 1-based, exactly as written (code_phase: 1-based argmax)."""
-    ex1 = code_phase - samples_per_chip                                          # :137
-    ex2 = code_phase + samples_per_chip                                          # :138
-    if ex1 < 2:                                                                   # :142
-        return np.arange(ex2, samples_per_code_ + ex1 + 1)                        # :143-144
-    elif ex2 > samples_per_code_:                                                 # :145
-        return np.arange(ex2 - samples_per_code_, ex1 + 1)                        # :146-147
-    return np.concatenate([np.arange(1, ex1 + 1),                                 # :149-150
-                           np.arange(ex2, samples_per_code_ + 1)])
-
-
 def period_second(row, argmax0, spc, period):
     """secondPeakSize (:153) of one kept row; argmax0 0-based."""
     rng = code_phase_range_1b(argmax0 + 1, period, spc)
@@ -190,12 +167,6 @@ def acquire(IF, s, prn):
 def padded(code):
     """[caCode($) caCode caCode(1)] (:174, :179)."""
     return np.concatenate([code[-1:], code, code[:1]])
-
-
-def _raw(IF, pos, n, s):
-    v = IF[2 * pos:2 * (pos + n)].astype(np.float64)
-    r1, r2 = v[0::2], v[1::2]
-    return r2 + 1j * r1 if s["switchIQ"] else r1 + 1j * r2                       # :276-282
 
 
 def correlate(IF, s, prow, drow, pos, rem_code, rem_carr, code_freq, carr_freq):
@@ -285,12 +256,6 @@ class Loop:
                            carr_err, carr_nco)
 
 
-def _out():
-    o = {f: [] for f in FIELDS}
-    o["blksize"] = []
-    return o
-
-
 def track(IF, s, prn, code_phase_1b, acquired_freq, n_ms, skip=0, perturb=None):
     """tracking.sci's per-channel loop for n_ms epochs.  Returns a dict of FIELDS arrays
     (length = epochs processed) + 'blksize', 'status' (0 or 1) and 'stop_blksize'.
@@ -298,36 +263,21 @@ def track(IF, s, prn, code_phase_1b, acquired_freq, n_ms, skip=0, perturb=None):
     filters (the decidability check of the closed-loop scene)."""
     prow, drow = padded(generate_code(prn)), padded(generate_code(prn + 32))
     lp = Loop(s, skip + code_phase_1b - 1, acquired_freq)
-    out = _out()
-    status, stop_blk = 0, 0
-    for _ in range(n_ms):
+
+    def epoch(lp):
         st, blk, r = correlate(IF, s, prow, drow, lp.pos, lp.rem_code, lp.rem_carr, lp.code_freq,
                                lp.carr_freq)
         if st:
-            status, stop_blk = st, blk
-            break
+            return st, blk, None
         sums, lp.pos, lp.rem_code, lp.rem_carr = r
-        if perturb is not None:
-            sums = sums * (1.0 + np.asarray(perturb, np.float64))
-        for f, v in zip(FIELDS, lp.update(sums)):
-            out[f].append(v)
-        out["blksize"].append(blk)
-    res = {f: np.asarray(v) for f, v in out.items()}
-    res["status"], res["stop_blksize"] = status, stop_blk
+        return 0, blk, sums
+    res, res["status"], res["stop_blksize"] = T.track(lp, FIELDS, n_ms, epoch, perturb)
     return res
 
 
 def replay(sums, s, code_phase_1b, acquired_freq, skip=0):
     """The loop half driven by given per-epoch sums [n, 12] (SUMS order)."""
-    lp = Loop(s, skip + code_phase_1b - 1, acquired_freq)
-    out = _out()
-    for row in np.asarray(sums, dtype=np.float64):
-        blk, step = lp.blksize()
-        lp.advance(blk, step)
-        for f, v in zip(FIELDS, lp.update(row)):
-            out[f].append(v)
-        out["blksize"].append(blk)
-    return {f: np.asarray(v) for f, v in out.items()}
+    return T.replay(Loop(s, skip + code_phase_1b - 1, acquired_freq), FIELDS, sums)
 
 
 # ---- scenes ---------------------------------------------------------------------------

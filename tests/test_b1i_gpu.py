@@ -12,14 +12,10 @@ import pytest
 
 import b1i_scenarios as B
 import sgt_oracle as S
+from tracker_checks import close as _close
 
 pytestmark = pytest.mark.gpu
 SUMS = B.SUMS
-
-
-def _close(a, b, rtol=1e-6, atol=1e-6):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return np.abs(a - b) <= rtol * np.abs(b) + atol
 
 
 def _random_chans(gc, rng, C, n, fs, basis=2.046e6, spread=80.0):

@@ -14,24 +14,13 @@ import pytest
 
 import e1alt_scenarios as A
 import e1t_scenarios as E
+from tracker_checks import close as _close, noise as _noise
 
 pytestmark = pytest.mark.gpu
 MODES = ("4ms", "amb1", "amb4")
 _cache = {}
 EPOCH = {"4ms": 4092.0, "amb1": 2046.0, "amb4": 8184.0}       # entries per epoch
 RATE = {"4ms": 1.023e6, "amb1": 2.046e6, "amb4": 2.046e6}
-
-
-def _close(a, b, rtol=1e-6, atol=1e-6):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return np.abs(a - b) <= rtol * np.abs(b) + atol
-
-
-def _noise(gc, n, fs, file_type):
-    key = (n, fs, file_type)
-    if key not in _cache:
-        _cache[key] = gc.ifgen(n, [], fs=fs, iq=file_type == 2, seed=21)
-    return _cache[key]
 
 
 def _tables(mode):

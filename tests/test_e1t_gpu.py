@@ -13,21 +13,10 @@ import numpy as np
 import pytest
 
 import e1t_scenarios as E
+from tracker_checks import close as _close, noise as _noise
 
 pytestmark = pytest.mark.gpu
 _cache = {}
-
-
-def _close(a, b, rtol=1e-6, atol=1e-6):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return np.abs(a - b) <= rtol * np.abs(b) + atol
-
-
-def _noise(gc, n, fs, file_type):
-    key = (n, fs, file_type)
-    if key not in _cache:
-        _cache[key] = gc.ifgen(n, [], fs=fs, iq=file_type == 2, seed=21)
-    return _cache[key]
 
 
 def _tables():

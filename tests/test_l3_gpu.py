@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import l3_scenarios as L3
+from tracker_checks import close as _close, noise
 
 pytestmark = pytest.mark.gpu
 _cache = {}
@@ -20,15 +21,8 @@ LOOP_TOL = 1e-7               # closed loop and replay: the bound of tests/test_
 SHAPES = [None, "64"]          # GNSSCORR_L3T_THREADS: the 256-thread default, one wave per channel
 
 
-def _close(a, b, rtol=1e-6, atol=1e-6):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return np.abs(a - b) <= rtol * np.abs(b) + atol
-
-
 def _noise(gc, n, fs):
-    if (n, fs) not in _cache:
-        _cache[(n, fs)] = gc.ifgen(n, [], fs=fs, iq=True, seed=33)
-    return _cache[(n, fs)]
+    return noise(gc, n, fs, seed=33)
 
 
 def _rows(prn):

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import sgt_oracle as S
+from tracker_checks import close as _close
 
 pytestmark = pytest.mark.gpu
 FS = 16e6
@@ -25,11 +26,6 @@ FS = 16e6
 # boundaries at non-integer sample positions (tracking.sci:281-302)
 RATES = [16e6, 16.368e6]
 SUMS = ("I_E", "I_P", "I_L", "Q_E", "Q_P", "Q_L")
-
-
-def _close(a, b, rtol=1e-6, atol=1e-6):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return np.abs(a - b) <= rtol * np.abs(b) + atol
 
 
 def _glo_start(cp_chips, fs=FS):

@@ -24,73 +24,26 @@ import os
 import subprocess
 import sys
 
-import numpy as np
+import ftrack_time as F
+from ftrack_time import gc
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                                "gnss-sdr.ru_amd"))
-import gnsscorr as gc  # noqa: E402
-
-PEAK = 78.6e12
-OPS = 27
-
-
-def time_ctx(ctx, chans, d_if, n, epochs, warmup, runs):
-    C = len(chans)
-    d_ch = gc.DevBuf.from_array(chans)
-    d_ep = gc.DevBuf(gc.SGT_EPOCH.itemsize * C * epochs)
-    e0, e1 = gc.Event(), gc.Event()
-    out = []
-    for r in range(warmup + runs):
-        d_ch.upload(chans)
-        e0.record(ctx.stream)
-        ctx.track_dev(d_if.ptr, 0, n, C, d_ch.ptr, epochs, d_ep.ptr, closed_loop=True)
-        e1.record(ctx.stream)
-        ctx.sync()
-        if r >= warmup:
-            out.append(e0.elapsed_ms(e1))
-    ep = d_ep.download(gc.SGT_EPOCH)
-    assert (ep["status"] == 0).all(), "a channel stopped: the record is too short"
-    return out, int(ep["blksize"].astype(np.int64).sum())
-
-
-def report(ms, samples, C, epochs):
-    med = float(np.median(ms))
-    return dict(min=round(min(ms), 4), median=round(med, 4), max=round(max(ms), 4),
-                us_per_channel_ms=round(med * 1e3 / (C * epochs), 4),
-                fp64_frac=round(samples * OPS / (med * 1e-3) / PEAK, 4))
+KEYS = ("min", "median", "max", "us_per_channel_ms", "fp64_frac")   # of ftrack_time.report
 
 
 def one(a):
-    if gc.device_count() < 1:
-        raise SystemExit("b1i_time: no HIP device visible")
-    C, E = a.channels, a.epochs
-    rng = np.random.default_rng(1)
-    n = int(a.fs * (E + 4) / 1000)
-    IF = gc.ifgen(n, [], fs=a.fs, iq=a.file_type == 2, seed=5)
-    d_if = gc.DevBuf.from_array(IF)
-    starts = rng.integers(1, int(a.fs * 0.002), C)
-    dops = rng.uniform(-4000, 4000, C)
-    res = {}
+    rng, n, d_if, starts, dops = F.setup(a, "b1i_time", a.file_type)
     b1 = gc.SgtCtx(2, fileType=a.file_type, samplingFreq=a.fs)
-    ch = b1.init_chans(rng.integers(1, 38, C), starts, 0.098e6 + dops)
-    ms, samples = time_ctx(b1, ch, d_if, n, E, a.warmup, a.runs)
-    res["b1i"] = report(ms, samples, C, E)
-    gps = gc.SgtCtx(0, fileType=a.file_type, samplingFreq=a.fs)
-    ch = gps.init_chans(rng.integers(1, 33, C), starts, 2.42e6 + dops)
-    ms, samples = time_ctx(gps, ch, d_if, n, E, a.warmup, a.runs)
-    res["gps"] = report(ms, samples, C, E)
-    print(json.dumps(res))
+    ch = b1.init_chans(rng.integers(1, 38, a.channels), starts, 0.098e6 + dops)
+    res = dict(b1i=F.time_tracker(a, b1, ch, gc.SGT_EPOCH, F.GPS_OPS, d_if, n),
+               gps=F.time_gps(a, rng, starts, dops, d_if, n, a.file_type))
+    print(json.dumps({k: {f: r[f] for f in KEYS} for k, r in res.items()}))
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--one", action="store_true", help="time one configuration in this process")
-    ap.add_argument("--channels", type=int, default=1024)
-    ap.add_argument("--epochs", type=int, default=20)
-    ap.add_argument("--fs", type=float, default=16e6)
+    F.add_args(ap, fs=16e6)
     ap.add_argument("--file-type", type=int, default=2)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--procs", type=int, default=3)
     a = ap.parse_args()
     if a.one:

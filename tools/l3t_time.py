@@ -18,44 +18,13 @@ spectra, with the period rule on and off.
 """
 import argparse
 import json
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                                "gnss-sdr.ru_amd"))
-import gnsscorr as gc  # noqa: E402
+import ftrack_time as F
+from ftrack_time import gc
 
-PEAK = 78.6e12
-OPS = dict(l3t=39, sgt=27)
-
-
-def time_ctx(ctx, chans, dtype_ep, d_if, n, epochs, warmup, runs):
-    C = len(chans)
-    d_ch = gc.DevBuf.from_array(chans)
-    d_ep = gc.DevBuf(dtype_ep.itemsize * C * epochs)
-    e0, e1 = gc.Event(), gc.Event()
-    out = []
-    for r in range(warmup + runs):
-        d_ch.upload(chans)
-        e0.record(ctx.stream)
-        ctx.track_dev(d_if.ptr, 0, n, C, d_ch.ptr, epochs, d_ep.ptr, closed_loop=True)
-        e1.record(ctx.stream)
-        ctx.sync()
-        if r >= warmup:
-            out.append(e0.elapsed_ms(e1))
-    ep = d_ep.download(dtype_ep)
-    assert (ep["status"] == 0).all(), "a channel stopped: the record is too short"
-    return out, int(ep["blksize"].astype(np.int64).sum())
-
-
-def report(name, ms, samples, C, epochs):
-    med = float(np.median(ms))
-    return dict(ms=[round(x, 4) for x in ms], min=round(min(ms), 4), median=round(med, 4),
-                max=round(max(ms), 4), us_per_channel_ms=round(med * 1e3 / (C * epochs), 4),
-                samples_per_s=round(samples / (med * 1e-3), 1),
-                fp64_frac=round(samples * OPS[name] / (med * 1e-3) / PEAK, 4))
+L3T_OPS = 39        # fp64 operations per sample
 
 
 def search(a):
@@ -92,36 +61,22 @@ def search(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--channels", type=int, default=1024)
-    ap.add_argument("--epochs", type=int, default=20)
-    ap.add_argument("--fs", type=float, default=24e6)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--runs", type=int, default=5)
+    F.add_args(ap, fs=24e6)
     ap.add_argument("--search", action="store_true")
     ap.add_argument("--codes", type=int, default=1)
     a = ap.parse_args()
-    if gc.device_count() < 1:
-        raise SystemExit("l3t_time: no HIP device visible")
     if a.search:
+        if gc.device_count() < 1:
+            raise SystemExit("l3t_time: no HIP device visible")
         return search(a)
     C, E = a.channels, a.epochs
-    rng = np.random.default_rng(1)
-    n = int(a.fs * (E + 4) / 1000)
-    IF = gc.ifgen(n, [], fs=a.fs, iq=True, seed=5)
-    d_if = gc.DevBuf.from_array(IF)
-    starts = rng.integers(1, int(a.fs * 0.002), C)
-    dops = rng.uniform(-4000, 4000, C)
+    rng, n, d_if, starts, dops = F.setup(a, "l3t_time")
 
     l3 = gc.L3tCtx(samplingFreq=a.fs)
     ch = l3.init_chans(rng.integers(1, 32, C), starts, -2.025e6 + dops)
-    ms, samples = time_ctx(l3, ch, gc.L3T_EPOCH, d_if, n, E, a.warmup, a.runs)
     res = dict(tool="l3t_time", channels=C, epochs=E, fs=a.fs,
-               l3t=report("l3t", ms, samples, C, E))
-
-    gps = gc.SgtCtx(0, fileType=2, samplingFreq=a.fs)
-    ch = gps.init_chans(rng.integers(1, 33, C), starts, 2.42e6 + dops)
-    ms, samples = time_ctx(gps, ch, gc.SGT_EPOCH, d_if, n, E, a.warmup, a.runs)
-    res["sgt_gps"] = report("sgt", ms, samples, C, E)
+               l3t=F.time_tracker(a, l3, ch, gc.L3T_EPOCH, L3T_OPS, d_if, n))
+    res["sgt_gps"] = F.time_gps(a, rng, starts, dops, d_if, n)
     res["l3t_over_sgt"] = round(res["l3t"]["median"] / res["sgt_gps"]["median"], 3)
     print(json.dumps(res))
 
