@@ -2678,6 +2678,20 @@ int m4_plan(int N);
 int mx_init(gnsscorr_acq_ctx* c);
 }  // namespace
 
+// Host only: the pass orders acq64_init stores in mix_r / mix_rp for n_samples (the
+// tests' view of mix_factor / mix_order_padded; no environment, no device)
+extern "C" int gnsscorr_acq_mix_plan(int n_samples, int* radices, int* padded, int cap) {
+  if (n_samples < 64 || n_samples > (1 << 19)) return 0;
+  int r[24] = {}, rp[24] = {};
+  const int n = mix_factor(n_samples, r);
+  mix_order_padded(r, n, rp);
+  for (int i = 0; i < n && i < cap; i++) {
+    if (radices) radices[i] = r[i];
+    if (padded) padded[i] = rp[i];
+  }
+  return n;
+}
+
 int acq64_init(gnsscorr_acq_ctx* c) {
   c->plan64 = acq64_plan_for(c->cfg.n_samples);
   if (!c->plan64) {

@@ -271,6 +271,7 @@ def _sig_table():
         "gnsscorr_acq_set_peak_period": (I, [P, I]),
         "gnsscorr_acq_second_peak_candidate": (I, [I, I, I, I, I]),
         "gnsscorr_acq_set_block_stride": (I, [P, I]),
+        "gnsscorr_acq_mix_plan": (I, [I, P, P, I]),
         **_tracker_sig("gnsscorr_sgt", SgtCfg, 5),
         **_tracker_sig("gnsscorr_e1t", E1tCfg, 7),
         "gnsscorr_e1t_set_codes": (I, [P, I, P]),
@@ -593,6 +594,15 @@ def l3_bins(if_freq: float, band_khz: float) -> np.ndarray:
     nb = int(round(band_khz * 2 * 5)) + 1
     k = np.arange(1, nb + 1)
     return if_freq - (band_khz / 2) * 1000 + (1000 / (2 * 5)) * (k - 1)
+
+
+def acq_mix_plan(n_samples: int):
+    """gnsscorr_acq_mix_plan: the radices of the generic fp64 engine's mixed-radix passes
+    at n_samples, as (unpadded order, zero-padded order); two empty lists where the
+    chirp-z engine serves the length (a prime factor above 31) or it is out of range."""
+    r, rp = np.zeros(24, np.int32), np.zeros(24, np.int32)
+    n = lib().gnsscorr_acq_mix_plan(int(n_samples), _ptr(r), _ptr(rp), 24)
+    return [int(x) for x in r[:n]], [int(x) for x in rp[:n]]
 
 
 def b1_coh_bins(if_freq: float, band_khz: float, coh: int) -> np.ndarray:

@@ -470,6 +470,17 @@ int gnsscorr_acq_set_block_stride(gnsscorr_acq_ctx *ctx, int stride);
  * mode above on or off. */
 int gnsscorr_acq_set_codes_padded(gnsscorr_acq_ctx *ctx, int n_codes, const int8_t *h_codes,
                                   int code_len);
+/* Host only: the pass plan of the generic fp64 engine's mixed-radix transform of
+ * n_samples points.  Returns the number of passes and writes their radices (each one
+ * of 2 3 4 5 7 8 11 13 16 17 19 23 29 31, product n_samples) in the order an unpadded
+ * search runs them to radices[] and in the order of a zero-padded search
+ * (gnsscorr_acq_set_zero_padded) to padded[], at most cap entries each (either
+ * may be NULL).  Returns 0, and writes nothing, where n_samples has a prime factor
+ * above 31 or is a single radix (such lengths run the chirp-z engine) or lies outside
+ * [64, 2^19].  A pure function of n_samples: it reads no environment variable and
+ * touches no device, so it also answers for the lengths that a context serves with a
+ * compiled plan (16368, 16000) or, on request, with the chirp-z engine. */
+int gnsscorr_acq_mix_plan(int n_samples, int *radices, int *padded, int cap);
 /* Debug/parity: full |ifft|^2 power row for (code, freq, block): n_samples doubles. */
 int gnsscorr_acq_power_row(gnsscorr_acq_ctx *ctx, const int8_t *h_if, int iq, int n_blocks,
                            int block, double freq, int code, double *h_power);

@@ -13,6 +13,11 @@ four global ones, GNSSCORR_ACQ_MIX4=0 keeps the passes) and Bluestein's chirp-z
 (prime factors above 31, or GNSSCORR_ACQ_BLUESTEIN=1); both are held to the
 oracle and to each other.  The generic engine also runs at N = 16368
 (GNSSCORR_ACQ_GENERIC=1) against the compiled 16 x 33 x 31 plan.
+
+These lengths run only some of the 14 compiled radices of the mixed-radix passes.  The
+per-radix tier is tests/test_acq_radix_gpu.py: every radix as first, middle and last pass,
+in every mode of mx_pass, at a bar of 1e-12 of the row maximum, and both ends of the
+accepted range of n_samples.
 """
 import numpy as np
 import pytest
