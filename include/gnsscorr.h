@@ -361,7 +361,13 @@ int gnsscorr_acq_select_dev(gnsscorr_acq_ctx *ctx, int n_groups, int n_bins, con
  * searches is coh_ms x n_samples samples, wiped off with one continuous phase
  * ramp and correlated against the code repeated coh_ms times; rows hold the
  * first code period of |ifft|^2 as acquisition.sci keeps them.  Needs
- * n_blocks * coh_ms <= max_blocks.  Default 1. */
+ * n_blocks * coh_ms <= max_blocks.  Default 1.
+ * The setting applies to both search modes and to every engine (the fp32 path,
+ * the compiled fp64 plans and the generic fp64 engine at any other n_samples):
+ * GNSSCORR_ACQ_BEST_OF_BLOCKS keeps the coh_ms-period block with the largest
+ * maximum, and GNSSCORR_ACQ_NONCOHERENT sums the power rows of the n_blocks
+ * coh_ms-period blocks, i.e. it computes the non-coherent sum of coherent
+ * blocks.  Not with a zero-padded search (gnsscorr_acq_set_zero_padded). */
 int gnsscorr_acq_set_coherent(gnsscorr_acq_ctx *ctx, int coh_ms);
 /* Several records per search (fp64 precision; n_samples 16368 or 16000, or a
  * generic n_samples with no prime factor above 31): the following searches read
