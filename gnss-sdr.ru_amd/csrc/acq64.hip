@@ -52,6 +52,10 @@
 #ifndef ACQ64_STAMP
 #define ACQ64_STAMP(i)
 #endif
+// a stamp taken once the scalar v is known (a tool may pin v before the stamp)
+#ifndef ACQ64_STAMP_AFTER
+#define ACQ64_STAMP_AFTER(i, v) ACQ64_STAMP(i)
+#endif
 
 namespace {
 
@@ -948,17 +952,56 @@ __global__ __launch_bounds__(kFwd23Threads) void acq64_fwd23_kernel(
   }
 }
 
+// ---- unit descriptors ---------------------------------------------------------------
+// One descriptor per launched workgroup of acq64_corr_kernel, in launch order (the order
+// permutation applied).  Rebuilt by every correlate call: group_code, group_freq,
+// group_rec and the frequency map are the caller's device buffers, whose contents may
+// change from call to call behind the same pointers.
+template <class P>
+__global__ __launch_bounds__(256) void acq64_unit_desc_kernel(
+    int n_units, int rs, int n_blocks, bool nc, const int* __restrict__ group_code,
+    const int* __restrict__ group_freq, int n_bins, const int* __restrict__ order,
+    const int2* __restrict__ fmap, int gpr, int nbT, const int* __restrict__ group_rec,
+    acq64_unit_desc* __restrict__ desc) {
+  const int w = blockIdx.x * 256 + threadIdx.x;
+  if (w >= n_units) return;
+  const auto [rowid, blk0] = unit_row(order[w], n_blocks, nc);
+  // records (gnsscorr_acq_set_records): virtual group gv = rec * gpr + g reads
+  // blocks rec * n_blocks .. of the nbT resident blocks per class
+  // (gnsscorr_acq_set_group_records: group g searches record group_rec[g] only)
+  const int gv = rowid / n_bins, bin = rowid % n_bins;
+  // a per-group record outside [0, nbT / n_blocks) is clamped: never a read past the spectra
+  const int rec = group_rec ? min(max(group_rec[gv], 0), nbT / n_blocks - 1) : gv / gpr;
+  const int g = group_rec ? gv : gv - rec * gpr;
+  const int2 fm = fmap[group_freq[g * n_bins + bin]];
+  const int m = fm.y;
+  acq64_unit_desc d;
+  d.x_ofs = ((long)fm.x * nbT + rec * n_blocks + blk0) * rs;
+  d.f_ofs = (long)group_code[g] * rs;
+  if constexpr (P::PFA) {
+    // digits of the shift: X_f[k] = X_r[k - m], negation of m digit-wise
+    constexpr int R1 = P::R1, R2 = P::R2, R3 = P::R3;
+    const int m1 = (m % R1) * P::INV1 % R1, m2 = (m % R2) * P::INV2 % R2,
+              m3 = (m % R3) * P::INV3 % R3;
+    d.shift = m1 | m2 << 8 | m3 << 16;
+  } else {
+    d.shift = m;
+  }
+  d.rowid = rowid;
+  d.blk0 = blk0;
+  d.slot = rowid * n_blocks + blk0;
+  desc[w] = d;
+}
+
 // ---- the correlation kernel -------------------------------------------------------
 // One workgroup = one unit: BEST_OF_BLOCKS -> (row, block); NONCOHERENT -> row,
 // |.|^2 summed over the blocks in registers.  fmap[fid] = {class, m}: the bin's
 // spectrum is the class spectrum circularly shifted by m (X_f[k] = X_r[k - m]).
 template <class P, int MODE, bool DUMP>
 __global__ __launch_bounds__(P::TB) void acq64_corr_kernel(
-    const v2d* __restrict__ X, const v2d* __restrict__ F, int rs, int n_blocks,
-    const int* __restrict__ group_code, const int* __restrict__ group_freq, int n_bins, int spc,
+    const v2d* __restrict__ X, const v2d* __restrict__ F, int rs, int n_blocks, int spc,
     gnsscorr_acq_row* __restrict__ stats, double* __restrict__ dump, int dump_block,
-    const int* __restrict__ order, const int2* __restrict__ fmap, const v2d* __restrict__ twN,
-    int gpr, int nbT, const int* __restrict__ group_rec) {
+    const acq64_unit_desc* __restrict__ desc, const v2d* __restrict__ twN) {
   constexpr int N = P::N, R1 = P::R1, R3 = P::R3, T = P::T, K3 = P::K3, L = P::L;
   constexpr bool kNC = MODE == GNSSCORR_ACQ_NONCOHERENT;
   // non-coherent: a thread's first kE running sums live in the LDS left over
@@ -985,34 +1028,27 @@ __global__ __launch_bounds__(P::TB) void acq64_corr_kernel(
   int t = threadIdx.x;
   const bool act = t < T;
   ACQ64_STAMP(0);
-  const int unit = order[blockIdx.x];
-  const auto [rowid, blk0] = unit_row(unit, n_blocks, kNC);
+  // the unit's rows and shift, resolved by acq64_unit_desc_kernel: scalar loads of one
+  // 32-byte record (blockIdx.x-indexed, issued together: one round trip) ahead of the
+  // X / F addresses
+  const acq64_unit_desc ud = desc[blockIdx.x];
+  const int rowid = ud.rowid, blk0 = ud.blk0;
   const int nblk = kNC ? n_blocks : 1;
-  // records (gnsscorr_acq_set_records): virtual group gv = rec * gpr + g reads
-  // blocks rec * n_blocks .. of the nbT resident blocks per class
-  // (gnsscorr_acq_set_group_records: group g searches record group_rec[g] only)
-  const int gv = rowid / n_bins, bin = rowid % n_bins;
-  // a per-group record outside [0, nbT / n_blocks) is clamped: never a read past the spectra
-  const int rec = group_rec ? min(max(group_rec[gv], 0), nbT / n_blocks - 1) : gv / gpr;
-  const int g = group_rec ? gv : gv - rec * gpr;
-  const int code = group_code[g];
-  const int2 fm = fmap[group_freq[g * n_bins + bin]];
-  const int m = fm.y;
   const double inv_n2 = 1.0 / ((double)N * (double)N);
-  const long fofs0 = (long)code * rs;
+  ACQ64_STAMP_AFTER(11, ud.shift);
 
   double pw[K3][R3], pwl[2] = {-1.0, -1.0};   // pwl: leftover outputs (P::lvalid)
 
   for (int i = 0; i < nblk; i++) {
     const int blk = blk0 + i;
-    const v2d* Xb = X + ((long)fm.x * nbT + rec * n_blocks + blk) * rs;
+    const v2d* Xb = X + (ud.x_ofs + (long)i * rs);
     // the code row is the same for every block: keep the compiler from
     // hoisting its loads out of the block loop (they would stay live in
     // registers across the whole transform)
     // (the offset, not the pointer, goes through the asm: an opaque pointer
     // loses its global address space, and the code loads became flat loads,
     // whose completion the waitcnt logic can only wait for all at once)
-    long fofs = fofs0;
+    long fofs = ud.f_ofs;
     asm volatile("" : "+s"(fofs));
     const v2d* Fc = F + fofs;
     // likewise every thread-dependent address: t is opaque per block, so the
@@ -1031,8 +1067,7 @@ __global__ __launch_bounds__(P::TB) void acq64_corr_kernel(
     if constexpr (P::PFA) {
       constexpr int R2 = P::R2;
       // digits of the shift: X_f[k] = X_r[k - m], negation of m digit-wise
-      const int m1 = (m % R1) * P::INV1 % R1, m2 = (m % R2) * P::INV2 % R2,
-                m3 = (m % R3) * P::INV3 % R3;
+      const int m1 = ud.shift & 0xff, m2 = (ud.shift >> 8) & 0xff, m3 = ud.shift >> 16;
       auto shifted = [&](int g) {
         int n2 = g / R3 - m2, n3 = g % R3 - m3;
         n2 += n2 < 0 ? R2 : 0;
@@ -1076,7 +1111,7 @@ __global__ __launch_bounds__(P::TB) void acq64_corr_kernel(
 #pragma unroll
         for (int n1 = 0; n1 < R1; n1++) {
           const int n = n1 * P::G1 + g;
-          int s = n - m;
+          int s = n - ud.shift;
           s += s < 0 ? N : 0;
           const v2d x = Xb[s], f = Fc[n];
           v1[j][n1] = (v2d){fma(x.x, f.x, x.y * f.y), fma(x.x, f.y, -(x.y * f.x))};
@@ -1272,8 +1307,9 @@ __global__ __launch_bounds__(P::TB) void acq64_corr_kernel(
     r.second = sv;
     r.argmax = bk;
     r.block = kNC ? -1 : blk0;
-    stats[(long)rowid * n_blocks + blk0] = r;
+    stats[ud.slot] = r;
   }
+  ACQ64_STAMP(12);
 }
 
 // Frequencies -> spectrum classes on the fs/N grid: class = canonical residue
@@ -1353,12 +1389,25 @@ int corr_launch(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_units, int n_
                 const int32_t* d_gcode, const int32_t* d_gfreq, int spc, double* d_dump,
                 int dump_block, int gpr) {
   const int nbT = n_blocks * c->spec_recs;
+  // a descriptor names its stats record with an int
+  if ((size_t)n_units * (mode == GNSSCORR_ACQ_NONCOHERENT ? n_blocks : 1) > (size_t)INT_MAX) {
+    gnsscorr_set_error("gnsscorr_acq_correlate: %d units x %d blocks: too many row records",
+                       n_units, n_blocks);
+    return GNSSCORR_EINVAL;
+  }
+  int rc = hostctx::grow(c->d_udesc, (size_t)n_units);
+  if (rc) return rc;
+  hipLaunchKernelGGL((acq64_unit_desc_kernel<P>), dim3((n_units + 255) / 256), dim3(256), 0,
+                     c->stream, n_units, c->rs64, n_blocks, mode == GNSSCORR_ACQ_NONCOHERENT,
+                     d_gcode, d_gfreq, n_bins, (const int*)c->d_order.p,
+                     (const int2*)c->d_fmap64, gpr, nbT, c->d_group_rec, c->d_udesc.p);
+  HIP_TRY(hipGetLastError());
 
 #define ACQ64_LAUNCH(M, D)                                                                  \
   hipLaunchKernelGGL((acq64_corr_kernel<P, M, D>), dim3(n_units), dim3(P::TB), 0, c->stream, \
-                     (const v2d*)c->d_X64.p, (const v2d*)c->d_F64, c->rs64, n_blocks, d_gcode, \
-                     d_gfreq, n_bins, spc, c->d_stats.p, d_dump, dump_block, c->d_order.p,     \
-                     c->d_fmap64, (const v2d*)c->d_twN, gpr, nbT, c->d_group_rec)
+                     (const v2d*)c->d_X64.p, (const v2d*)c->d_F64, c->rs64, n_blocks, spc,     \
+                     c->d_stats.p, d_dump, dump_block,                                        \
+                     (const acq64_unit_desc*)c->d_udesc.p, (const v2d*)c->d_twN)
   if (d_dump)
     ACQ64_LAUNCH(GNSSCORR_ACQ_BEST_OF_BLOCKS, true);
   else if (mode == GNSSCORR_ACQ_NONCOHERENT)
@@ -2732,7 +2781,8 @@ int acq64_init(gnsscorr_acq_ctx* c) {
 }
 
 void acq64_free(gnsscorr_acq_ctx* c) {
-  hostctx::release(c->d_F64, c->d_X64, c->d_in64, c->d_twN, c->d_fmap64, c->d_lead64, c->d_chirp,
+  hostctx::release(c->d_F64, c->d_X64, c->d_in64, c->d_twN, c->d_fmap64, c->d_lead64, c->d_udesc,
+                   c->d_chirp,
                    c->d_vf, c->d_twM, c->d_gA, c->d_gB, c->d_gpw, c->d_m4top, c->d_twm4,
                    c->lane1.Y, c->lane1.pw, c->lane1.top);
   for (hipEvent_t& ev : c->m4_ev)

@@ -16,6 +16,20 @@ struct acq_chunk_lane {
   void* top = nullptr;                  // chunk x N1 per-column top-2 (null: statistics pass)
 };
 
+// What one workgroup of acq64_corr_kernel needs that is uniform across it, resolved from
+// the caller's tables (order, group_rec, group_code, group_freq, fmap) by
+// acq64_unit_desc_kernel in every correlate call: the kernel reads it with scalar loads
+// issued together (one round trip).
+struct alignas(32) acq64_unit_desc {
+  long long x_ofs;   // element offset of the unit's first X row (block blk0 of its class, record)
+  long long f_ofs;   // element offset of its code row in F
+  int shift;         // PFA plans: m1 | m2 << 8 | m3 << 16 (digits of the bin's shift); else m
+  int rowid;         // (virtual group, bin) row
+  int blk0;          // first block of the unit
+  int slot;          // its record in stats (corr_launch refuses a launch with more than INT_MAX)
+};
+static_assert(sizeof(acq64_unit_desc) == 32, "a 32-byte record, aligned to 32, per workgroup");
+
 struct gnsscorr_acq_ctx {
   gnsscorr_acq_cfg cfg;
   hipStream_t stream = nullptr;
@@ -34,6 +48,7 @@ struct gnsscorr_acq_ctx {
   double2* d_twN = nullptr;             // W_N^j, j < N (Cooley-Tukey plans)
   int2* d_fmap64 = nullptr;             // per frequency: {class, shift m mod N}
   int* d_lead64 = nullptr;              // classify scratch: per frequency, its class leader
+  hostctx::DevBuf<acq64_unit_desc> d_udesc;   // per launched workgroup, rebuilt by every correlate
   int rs64 = 0;                         // fp64 row stride (complex elements)
   // generic-N fp64 plan (plan64 == 3, any other N): Bluestein with radix-16
   // Stockham FFTs of length M, a power of two >= 2N - 1 (acq64.hip)
