@@ -38,3 +38,14 @@ int gnsscorr_pack2(const int8_t *in, int64_t n, uint8_t *out)
   }
   return GNSSCORR_OK;
 }
+
+/* the inverse: n levels out of the (n+3)/4 bytes of codes */
+int gnsscorr_unpack2(const uint8_t *in, int64_t n, int8_t *out)
+{
+  if (!in || !out || n < 0) {
+    gnsscorr_set_error("gnsscorr_unpack2: bad arguments");
+    return GNSSCORR_EINVAL;
+  }
+  for (int64_t e = 0; e < n; e++) out[e] = (int8_t)(2 * ((in[e >> 2] >> (2 * (e & 3))) & 3) - 3);
+  return GNSSCORR_OK;
+}

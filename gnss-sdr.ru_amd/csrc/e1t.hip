@@ -227,12 +227,20 @@ __device__ __forceinline__ double flip(double v, uint32_t s) {
 }
 
 // MAXT: 64 = one wave per channel (many channels), 256 the default shape.
-template <int MODE, int FT, bool CLOSED, int MAXT>
+// FTP: settings.fileType (1, 2), + kPacked when the records are GNSSCORR_IF_PACKED2
+// streams (gnsscorr_e1t_set_packed): unpacked in registers to the int8 words both
+// paths consume, on the chunk grid of an int8 record with a 16-byte-aligned base, so
+// the sums are the int8 path's to the bit.  Kernels of their own: the int8 ones keep
+// their code and their symbols.
+constexpr int kPacked = 4;
+template <int MODE, int FTP, bool CLOSED, int MAXT>
 __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
     E1tParams p, const int8_t* __restrict__ ifbuf, int64_t stride, int64_t n_samples,
     const uint32_t* __restrict__ codes, gnsscorr_e1t_chan* __restrict__ chans, int n_epochs,
     gnsscorr_e1t_epoch* __restrict__ out) {
 #pragma clang fp contract(off)
+  constexpr int FT = FTP & 3;
+  constexpr bool PK = (FTP & kPacked) != 0;
   using M = Mode<MODE>;
   constexpr int kCodeWords = M::kCodeWords, kRowWords = M::kRowWords, kRowLen = M::kRowLen;
   constexpr int kArms = M::kArms, kSums = 2 * M::kArms;
@@ -251,6 +259,9 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
   __syncthreads();
 
   const int8_t* base = ifbuf + (int64_t)c.stream * stride;
+  // packed: the stream's bytes and the record's end (no byte at or past it is loaded)
+  const uint8_t* pbase = reinterpret_cast<const uint8_t*>(base);
+  const int64_t pend = if_bytes((FT == 2 ? 2 : 1) * n_samples, true);
   int e = 0;
   for (; e < n_epochs; e++) {
     gnsscorr_e1t_epoch* rec = out + (int64_t)ch * n_epochs + e;
@@ -284,7 +295,8 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
       }
     }
     const double A = (c.carr_freq * 2.0) * M_PI;        // (carrFreq * 2.0 * %pi)
-    const int8_t* src = base + (FT == 2 ? 2 : 1) * c.pos;
+    // (packed: sample k is sample c.pos + k of pbase; src only keeps the predicate)
+    const int8_t* src = PK ? base : base + (FT == 2 ? 2 : 1) * c.pos;
     const uint32_t* srow = s_code + (M::k4ms ? 0 : c.segment * kRowWords);   // 4 ms: one row
     // bit of padded-row entry j (0-based; the clamp only keeps a state set from
     // outside inside the row: the loop's own indices lie in [0, kRowLen - 1])
@@ -304,6 +316,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
       sincos(th0, &sn, &cs);
       sincos(thw, &sw, &cw);   // (e1t.o is built with promote-alloca-to-lds off)
       auto load = [&](int k) -> int {
+        if constexpr (PK) return if2_sample<FT>(pbase, c.pos + k);
         if (FT == 2) return *reinterpret_cast<const uint16_t*>(src + 2 * (int64_t)k);
         return src[k];
       };
@@ -382,7 +395,10 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
     constexpr int kBps = FT == 2 ? 2 : 1;
     auto run_chunks = [&]() {
       using Grid = ChunkGrid<kBps, kC>;
-      const Grid grid(src, blk, T);
+      const Grid grid = [&] {
+        if constexpr (PK) return Grid(c.pos, blk, T);
+        else return Grid(src, blk, T);
+      }();
       const double cst = uni(cstep), mst = uni(mstep);
       const double inv_c = uni(1.0 / cstep), inv_m = M::kAmb ? 0.0 : uni(1.0 / mstep);
       const double aX[3] = {uni(aE), uni(aP), uni(aL)};
@@ -398,15 +414,30 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
       sR = uni(sR);
       cR = uni(cR);
       __syncthreads();
-      constexpr int kW = Grid::kW;   // 16-byte words per chunk
-      uint4 nx[kW];
-      auto fetch = [&](int it, uint4 (&x)[kW]) {
+      constexpr int kW = Grid::kW;   // 16-byte words per chunk (packed: dwords)
+      using Word = std::conditional_t<PK, uint32_t, uint4>;
+      Word nx[kW];
+      auto fetch = [&](int it, Word (&x)[kW]) {
         const int q = it * T + tid;
+        if constexpr (PK) {
+          // the chunk's kW dwords: one load when the whole chunk lies in the epoch,
+          // else only dwords holding a sample of the epoch, cut at the record's end
+          const int k0 = q * kC - grid.mis;
+          const int64_t d0 = grid.first_dword(c.pos) + (int64_t)q * kW;
+          if (k0 + kC <= blk) {
+            if2_load_words<kW>(reinterpret_cast<const uint32_t*>(pbase) + d0, x);
+          } else {
+#pragma unroll
+            for (int u = 0; u < kW; u++)
+              x[u] = k0 + u * (16 / kBps) < blk ? if2_load_dword(pbase, d0 + u, pend) : 0u;
+          }
+        } else {
 #pragma unroll
         for (int u = 0; u < kW; u++) {
           // only words holding a sample of the epoch: none past the record's end
           const int ks = q * kC - grid.mis + u * (16 / kBps);
           x[u] = ks < blk ? grid.ab[(int64_t)q * kW + u] : make_uint4(0, 0, 0, 0);
+        }
         }
       };
       fetch(0, nx);
@@ -414,8 +445,11 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
         uint32_t wd[4 * kW];
 #pragma unroll
         for (int u = 0; u < kW; u++) {
-          wd[4 * u] = nx[u].x; wd[4 * u + 1] = nx[u].y;
-          wd[4 * u + 2] = nx[u].z; wd[4 * u + 3] = nx[u].w;
+          uint4 v;
+          if constexpr (PK) v = if2_expand_word(nx[u]);   // 16 codes -> the four int8 words
+          else v = nx[u];
+          wd[4 * u] = v.x; wd[4 * u + 1] = v.y;
+          wd[4 * u + 2] = v.z; wd[4 * u + 3] = v.w;
         }
         if (it + 1 < grid.nIt) fetch(it + 1, nx);
         const int q = it * T + tid;
@@ -653,6 +687,7 @@ struct gnsscorr_e1t_ctx {
   int max_codes = 0;
   hostctx::DevBuf<gnsscorr_e1t_chan> d_chan;   // the host wrappers' own
   hostctx::DevBuf<gnsscorr_e1t_epoch> d_ep;
+  int packed = 0;                              // gnsscorr_e1t_set_packed
 };
 
 #define E1T_BAD_CONFIG                                                            \
@@ -711,6 +746,10 @@ extern "C" int gnsscorr_e1t_init_chan(const gnsscorr_e1t_cfg* cfg, int code_id, 
 }
 
 extern "C" int gnsscorr_e1t_destroy(gnsscorr_e1t_ctx* c) { return ftrack::destroy(c); }
+
+extern "C" int gnsscorr_e1t_set_packed(gnsscorr_e1t_ctx* c, int packed) {
+  return ftrack::set_packed(__func__, c, packed);
+}
 
 // the stream and room for the code rows (gnsscorr_e1t_set_codes fills them)
 static int init_device(gnsscorr_e1t_ctx* c) {
@@ -829,6 +868,7 @@ extern "C" int gnsscorr_e1t_track_dev(gnsscorr_e1t_ctx* c, const int8_t* d_if, i
     return GNSSCORR_EINVAL;
   }
   rc = check_iq_aligned(__func__, c, d_if);
+  if (!rc) rc = check_packed_aligned(__func__, c, d_if, stride);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->cfg.device));
   // two launch shapes: one wave per channel for many channels (throughput),
@@ -849,14 +889,20 @@ extern "C" int gnsscorr_e1t_track_dev(gnsscorr_e1t_ctx* c, const int8_t* d_if, i
       hipLaunchKernelGGL((e1t_track_kernel<MD, FT, CL, 256>), grid, block, 0, c->stream,     \
                          c->p, d_if, stride, n_samples, c->d_codes, d_chan, n_epochs, d_ep);  \
   } while (0)
+#define E1T_LAUNCH_FT(MD, FT)                 \
+  do {                                        \
+    if (closed_loop) E1T_LAUNCH(MD, FT, true);   \
+    else E1T_LAUNCH(MD, FT, false);           \
+  } while (0)
+  // (packed records: the kernels of FT + kPacked)
 #define E1T_LAUNCH_MODE(MD)                   \
   do {                                        \
     if (c->cfg.file_type == 2) {              \
-      if (closed_loop) E1T_LAUNCH(MD, 2, true);  \
-      else E1T_LAUNCH(MD, 2, false);          \
+      if (c->packed) E1T_LAUNCH_FT(MD, 2 + kPacked);  \
+      else E1T_LAUNCH_FT(MD, 2);              \
     } else {                                  \
-      if (closed_loop) E1T_LAUNCH(MD, 1, true);  \
-      else E1T_LAUNCH(MD, 1, false);          \
+      if (c->packed) E1T_LAUNCH_FT(MD, 1 + kPacked);  \
+      else E1T_LAUNCH_FT(MD, 1);              \
     }                                         \
   } while (0)
   switch (c->mode) {
@@ -866,6 +912,7 @@ extern "C" int gnsscorr_e1t_track_dev(gnsscorr_e1t_ctx* c, const int8_t* d_if, i
     default: E1T_LAUNCH_MODE(3); break;
   }
 #undef E1T_LAUNCH_MODE
+#undef E1T_LAUNCH_FT
 #undef E1T_LAUNCH
   HIP_TRY(hipGetLastError());
   return GNSSCORR_OK;

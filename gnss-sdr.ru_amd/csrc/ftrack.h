@@ -20,6 +20,7 @@
 #include <stdint.h>
 #include "gnsscorr_internal.h"
 #include "hostctx.h"
+#include "if2.h"
 
 namespace ftrack {
 
@@ -89,6 +90,19 @@ struct ChunkGrid {
     ab = reinterpret_cast<const uint4*>(src - mis * kBps);
     nC = (blk + mis + kC - 1) / kC;
     nIt = (nC + T - 1) / T;
+  }
+  // Packed records (if2.h): the grid is a function of the sample position alone,
+  // the int8 grid of a record whose stream base is 16-byte aligned.  A chunk is
+  // then the kW whole dwords from dword first_dword(pos) + q*kW of the stream; ab
+  // is not used.
+  __device__ __forceinline__ ChunkGrid(int64_t pos, int blk, int T) {
+    mis = (int)((kBps * pos) & 15) / kBps;
+    ab = nullptr;
+    nC = (blk + mis + kC - 1) / kC;
+    nIt = (nC + T - 1) / T;
+  }
+  __device__ __forceinline__ int64_t first_dword(int64_t pos) const {
+    return (kBps * (pos - mis)) >> 4;
   }
 
   // Where an index a + k*step next exceeds j: sample k has index > j iff
@@ -203,6 +217,27 @@ template <class Ctx>
 int check_iq_aligned(const char* fn, const Ctx* c, const int8_t* d_if) {
   if (c->cfg.file_type == 2 && ((uintptr_t)d_if & 1)) {
     gnsscorr_set_error("%s: IQ record must be 2-byte aligned", fn);
+    return GNSSCORR_EINVAL;
+  }
+  return GNSSCORR_OK;
+}
+
+// *_set_packed: the records of later track calls are GNSSCORR_IF_PACKED2 streams
+template <class Ctx>
+int set_packed(const char* fn, Ctx* c, int packed) {
+  if (!c || (packed != 0 && packed != 1)) {
+    gnsscorr_set_error("%s: bad arguments (a context, packed 0 or 1)", fn);
+    return GNSSCORR_EINVAL;
+  }
+  c->packed = packed;
+  return GNSSCORR_OK;
+}
+// packed records: whole 16-byte words from an aligned base, for every stream
+template <class Ctx>
+int check_packed_aligned(const char* fn, const Ctx* c, const int8_t* d_if, int64_t stride) {
+  if (c->packed && (((uintptr_t)d_if & 15) || (stride & 15))) {
+    gnsscorr_set_error("%s: packed records need a 16-byte-aligned d_if and a stream_stride "
+                       "that is a multiple of 16 bytes", fn);
     return GNSSCORR_EINVAL;
   }
   return GNSSCORR_OK;

@@ -40,4 +40,51 @@ __device__ __forceinline__ int if_elem(const int8_t* __restrict__ base, int64_t 
 __host__ __device__ __forceinline__ int64_t if_bytes(int64_t n_elems, bool packed) {
   return packed ? (n_elems + 3) >> 2 : n_elems;
 }
+
+// ---- packed records of the float trackers (sgt, e1t, l3t; gnsscorr_*_set_packed).
+// A record is the element stream above from a 16-byte-aligned stream base; FT is
+// settings.fileType: 2 = sample s is elements 2s, 2s+1 (the int8 pair), 1 = element s.
+
+// sample s of a record as the int8 path's per-sample load returns it: FT 2 the pair
+// as a 16-bit word (first element in the low byte), FT 1 the level
+template <int FT>
+__device__ __forceinline__ int if2_sample(const uint8_t* __restrict__ base, int64_t s) {
+  if (FT == 2) {
+    // both elements of a pair sit in one nibble
+    const uint32_t b = (uint32_t)base[s >> 1] >> (4 * (int)(s & 1));
+    const uint32_t t = (b & 3u) | ((b & 0xCu) << 6) | 0x0C0C0000u;   // selector 0x0C: byte 0x00
+    return (int)__builtin_amdgcn_perm(0u, 0x0301FFFDu, t);
+  }
+  return 2 * (int)(((uint32_t)base[s >> 2] >> (2 * (int)(s & 3))) & 3u) - 3;
+}
+
+// dword d of a record that ends at byte `end` (if_bytes of its elements): a dword
+// the end cuts is read byte by byte, nothing at or past the end is loaded
+__device__ __forceinline__ uint32_t if2_load_dword(const uint8_t* __restrict__ base, int64_t d,
+                                                   int64_t end) {
+  const uint8_t* p = base + 4 * d;
+  if (4 * d + 4 <= end) return *reinterpret_cast<const uint32_t*>(p);
+  uint32_t v = 0;
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+    if (4 * d + i < end) v |= (uint32_t)p[i] << (8 * i);
+  return v;
+}
+
+// kW consecutive dwords from a dword boundary in one dword / dwordx2 / dwordx4 load
+typedef uint32_t if2_u32x2a4 __attribute__((ext_vector_type(2), aligned(4)));
+typedef uint32_t if2_u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
+template <int kW>
+__device__ __forceinline__ void if2_load_words(const uint32_t* __restrict__ p, uint32_t (&x)[kW]) {
+  static_assert(kW == 1 || kW == 2 || kW == 4, "a chunk is 4, 8 or 16 packed bytes");
+  if constexpr (kW == 1) {
+    x[0] = p[0];
+  } else if constexpr (kW == 2) {
+    const if2_u32x2a4 v = *reinterpret_cast<const if2_u32x2a4*>(p);
+    x[0] = v.x; x[1] = v.y;
+  } else {
+    const if2_u32x4a4 v = *reinterpret_cast<const if2_u32x4a4*>(p);
+    x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+  }
+}
 #endif

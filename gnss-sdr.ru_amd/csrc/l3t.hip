@@ -122,12 +122,20 @@ __device__ __forceinline__ double flip(double v, uint32_t s) {
 
 // MAXT: the workgroup size: 64 = one wave per channel (many channels), 256 the default
 // shape, 128 by override.
-template <bool CLOSED, int MAXT>
-__global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void l3t_track_kernel(
+// MAXTP: MAXT, + kPacked when the records are GNSSCORR_IF_PACKED2 streams
+// (gnsscorr_l3t_set_packed): a sample's pair of 2-bit codes is unpacked to the int8 pair
+// the per-sample pass consumes.  Kernels of their own: the int8 ones keep their code and
+// their symbols.
+constexpr int kPacked = 4096;
+template <bool CLOSED, int MAXTP>
+__global__ __launch_bounds__(MAXTP & (kPacked - 1), (MAXTP & (kPacked - 1)) == 64 ? 2 : 1) void
+l3t_track_kernel(
     L3tParams p, const int8_t* __restrict__ ifbuf, int64_t stride, int64_t n_samples,
     const uint32_t* __restrict__ codes, gnsscorr_l3t_chan* __restrict__ chans, int n_epochs,
     gnsscorr_l3t_epoch* __restrict__ out) {
 #pragma clang fp contract(off)
+  constexpr int MAXT = MAXTP & (kPacked - 1);
+  constexpr bool PK = (MAXTP & kPacked) != 0;
   __shared__ uint32_t s_code[2 * kRowWords];     // pilot row, data row as bits (1 = chip -1)
   __shared__ double s_part[2][kMaxWaves][12];
   const int ch = blockIdx.x;
@@ -168,7 +176,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void l3t_track_kernel(
     const int blk = (int)blk_d;
     const double aE = c.rem_code - p.spc, aL = c.rem_code + p.spc, aP = c.rem_code;
     const double A = (c.carr_freq * 2.0) * M_PI;        // (carrFreq * 2.0 * %pi)
-    const int8_t* src = base + 2 * c.pos;
+    const int8_t* src = base + (PK ? 0 : 2) * c.pos;
     double acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     {
       const double th0 = A * ((double)tid / p.fs) + c.rem_carr, thw = A * ((double)T / p.fs);
@@ -176,6 +184,8 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void l3t_track_kernel(
       sincos(th0, &sn, &cs);
       sincos(thw, &sw, &cw);   // (l3t.o is built with promote-alloca-to-lds off)
       auto load = [&](int k) -> int {
+        if constexpr (PK)
+          return if2_sample<2>(reinterpret_cast<const uint8_t*>(src), c.pos + k);
         return *reinterpret_cast<const uint16_t*>(src + 2 * (int64_t)k);
       };
       auto sample = [&](int k, int w) {
@@ -303,6 +313,7 @@ struct gnsscorr_l3t_ctx {
   uint32_t* d_codes = nullptr;                 // kIds padded rows as bits
   hostctx::DevBuf<gnsscorr_l3t_chan> d_chan;   // the host wrappers' own
   hostctx::DevBuf<gnsscorr_l3t_epoch> d_ep;
+  int packed = 0;                              // gnsscorr_l3t_set_packed
 };
 
 extern "C" void gnsscorr_l3t_loop_coefs(const gnsscorr_l3t_cfg* cfg, double* tau1, double* tau2,
@@ -342,6 +353,10 @@ extern "C" int gnsscorr_l3t_init_chan(const gnsscorr_l3t_cfg* cfg, int prn, int 
 }
 
 extern "C" int gnsscorr_l3t_destroy(gnsscorr_l3t_ctx* c) { return ftrack::destroy(c); }
+
+extern "C" int gnsscorr_l3t_set_packed(gnsscorr_l3t_ctx* c, int packed) {
+  return ftrack::set_packed(__func__, c, packed);
+}
 
 // the stream and the resident code rows of ids 0..64
 static int init_device(gnsscorr_l3t_ctx* c) {
@@ -402,6 +417,7 @@ extern "C" int gnsscorr_l3t_track_dev(gnsscorr_l3t_ctx* c, const int8_t* d_if, i
   int rc = check_track_dev(__func__, c, d_if, d_chan, d_ep, n_ch, n_epochs, n_samples, stride);
   if (rc) return rc;
   rc = check_iq_aligned(__func__, c, d_if);
+  if (!rc) rc = check_packed_aligned(__func__, c, d_if, stride);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->cfg.device));
   // two launch shapes: one wave per channel for many channels (throughput),
@@ -413,20 +429,25 @@ extern "C" int gnsscorr_l3t_track_dev(gnsscorr_l3t_ctx* c, const int8_t* d_if, i
     if (v == 64 || v == 128 || v == 256) T = v;
   }
   dim3 grid(n_ch), block(T);
-#define L3T_LAUNCH(CL)                                                                        \
+#define L3T_LAUNCH(CL, PK)                                                                    \
   do {                                                                                        \
     if (T == 64)                                                                              \
-      hipLaunchKernelGGL((l3t_track_kernel<CL, 64>), grid, block, 0, c->stream, c->p, d_if,   \
-                         stride, n_samples, c->d_codes, d_chan, n_epochs, d_ep);              \
+      hipLaunchKernelGGL((l3t_track_kernel<CL, 64 + PK>), grid, block, 0, c->stream, c->p,    \
+                         d_if, stride, n_samples, c->d_codes, d_chan, n_epochs, d_ep);        \
     else if (T == 128)                                                                        \
-      hipLaunchKernelGGL((l3t_track_kernel<CL, 128>), grid, block, 0, c->stream, c->p, d_if,  \
-                         stride, n_samples, c->d_codes, d_chan, n_epochs, d_ep);              \
+      hipLaunchKernelGGL((l3t_track_kernel<CL, 128 + PK>), grid, block, 0, c->stream, c->p,   \
+                         d_if, stride, n_samples, c->d_codes, d_chan, n_epochs, d_ep);        \
     else                                                                                      \
-      hipLaunchKernelGGL((l3t_track_kernel<CL, 256>), grid, block, 0, c->stream, c->p, d_if,  \
-                         stride, n_samples, c->d_codes, d_chan, n_epochs, d_ep);              \
+      hipLaunchKernelGGL((l3t_track_kernel<CL, 256 + PK>), grid, block, 0, c->stream, c->p,   \
+                         d_if, stride, n_samples, c->d_codes, d_chan, n_epochs, d_ep);        \
   } while (0)
-  if (closed_loop) L3T_LAUNCH(true);
-  else L3T_LAUNCH(false);
+  if (c->packed) {
+    if (closed_loop) L3T_LAUNCH(true, kPacked);
+    else L3T_LAUNCH(false, kPacked);
+  } else {
+    if (closed_loop) L3T_LAUNCH(true, 0);
+    else L3T_LAUNCH(false, 0);
+  }
 #undef L3T_LAUNCH
   HIP_TRY(hipGetLastError());
   return GNSSCORR_OK;

@@ -47,6 +47,7 @@ constexpr int kPadLenB1 = kMaxCodeB1 + 2;
 constexpr int kMaxPrnB1 = 37;
 __host__ __device__ constexpr int sgt_row_pitch(bool b1) { return b1 ? kPadLenB1 : kPadLen; }
 constexpr int kMaxWaves = 16;
+constexpr int kPacked = 4;   // added to a kernel's FT: 2-bit packed records
 // wave mode asks for 3 waves per SIMD (<= 168 VGPRs): measured 3 % faster than 2
 constexpr int kWaveOcc = 3;
 // run_chunks with prefix columns: per-lane prefix sums of W_n*raw over sub-blocks
@@ -143,12 +144,19 @@ __device__ __forceinline__ int xcd_channel(int b, int G) {
 // B1: the BeiDou B1I instantiation (system 2): 2048-word code rows, the B1I epoch end,
 // the select form on 8-sample chunks in the wave kernel and the per-sample loop in the
 // others.  Its own kernels, so the GPS / GLONASS ones keep their code.
-template <int FT, bool CLOSED, int MAXT, bool B1 = false>
+// FTP: settings.fileType (1, 2), + kPacked when the records are GNSSCORR_IF_PACKED2
+// streams (gnsscorr_sgt_set_packed): unpacked in registers to the int8 words every
+// path below consumes; the chunk partition is that of an int8 record on a
+// 16-byte-aligned base, so the sums are the int8 path's to the bit.  Its own kernels
+// too: the int8 ones keep their code and their symbols.
+template <int FTP, bool CLOSED, int MAXT, bool B1 = false>
 __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_kernel(
     SgtParams p, const int8_t* __restrict__ ifbuf, int64_t stride, int64_t n_samples,
     const uint32_t* __restrict__ codes, gnsscorr_sgt_chan* __restrict__ chans, int n_epochs,
     gnsscorr_sgt_epoch* __restrict__ out) {
 #pragma clang fp contract(off)
+  constexpr int FT = FTP & 3;
+  constexpr bool PK = (FTP & kPacked) != 0;
   // the code as +-1.0 (E/P/L accumulate with one fma), L + 2 entries: dynamic,
   // so a 511-chip GLONASS table takes 4.1 KB, not the 1023-chip maximum
   extern __shared__ double s_sgn[];
@@ -178,6 +186,9 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
   __syncthreads();
 
   const int8_t* base = ifbuf + (int64_t)c.stream * stride;
+  // packed: the stream's bytes and the record's end (no byte at or past it is loaded)
+  const uint8_t* pbase = reinterpret_cast<const uint8_t*>(base);
+  const int64_t pend = if_bytes((FT == 2 ? 2 : 1) * n_samples, true);
   const double dL = (double)L;
   int e = 0;
   for (; e < n_epochs; e++) {
@@ -190,7 +201,8 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
     const double blk_d = ceil((dL - c.rem_code) / step);
     // tracking.sci:273-277: not enough samples (NaN or huge blksize from a
     // corrupted state stops too, as does a blksize of 2^31 or more)
-    if (!(blk_d <= (double)(n_samples - c.pos) && blk_d < 2147483648.0)) {
+    // (packed: a position before the record stops as well)
+    if (!(blk_d <= (double)(n_samples - c.pos) && blk_d < 2147483648.0) || (PK && c.pos < 0)) {
       c.status = 1;
       if (tid == 0) {
         gnsscorr_sgt_epoch z = {};
@@ -204,7 +216,8 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
     const double aE = c.rem_code - p.spc, aL = c.rem_code + p.spc, aP = c.rem_code;
     const double A = (c.carr_freq * 2.0) * M_PI;        // (carrFreq * 2.0 * %pi)
     double ie = 0, ip = 0, il = 0, qe = 0, qp = 0, ql = 0;
-    const int8_t* src = base + (FT == 2 ? 2 : 1) * c.pos;
+    // (packed: sample k is sample c.pos + k of pbase; src only keeps the predicates)
+    const int8_t* src = PK ? base : base + (FT == 2 ? 2 : 1) * c.pos;
     // I/Q byte order as bit-field offsets (switchIQ without a per-sample select)
     const int sh_re = p.switch_iq ? 8 : 0, sh_im = 8 - sh_re;
     // kU samples per thread per pass.  The IF words of pass n+1 are loaded
@@ -213,6 +226,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
     // last, partial pass is guarded per sample.
     constexpr int kU = 8;
     auto load = [&](int k) -> int {
+      if constexpr (PK) return if2_sample<FT>(pbase, c.pos + k);
       if (FT == 2) return *reinterpret_cast<const uint16_t*>(src + 2 * k);
       return src[k];
     };
@@ -304,7 +318,10 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
     auto run_chunks = [&](auto kc_tag) {
       constexpr int kC = decltype(kc_tag)::value;
       using Grid = ChunkGrid<kBps, kC>;
-      const Grid grid(src, blk, T);
+      const Grid grid = [&] {
+        if constexpr (PK) return Grid(c.pos, blk, T);
+        else return Grid(src, blk, T);
+      }();
       const double inv_step = uni(1.0 / step), stp = uni(step);
       const double aX[3] = {uni(aE), uni(aP), uni(aL)};
       double sb, cb, sR, cR;
@@ -329,15 +346,30 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
       }
       __syncthreads();
       double accI[3] = {0.0, 0.0, 0.0}, accQ[3] = {0.0, 0.0, 0.0};
-      constexpr int kW = Grid::kW;   // 16-byte words per chunk
-      uint4 nx[kW];
-      auto fetch = [&](int it, uint4 (&x)[kW]) {
+      constexpr int kW = Grid::kW;   // 16-byte words per chunk (packed: dwords)
+      using Word = std::conditional_t<PK, uint32_t, uint4>;
+      Word nx[kW];
+      auto fetch = [&](int it, Word (&x)[kW]) {
         const int q = it * T + tid;
+        if constexpr (PK) {
+          // the chunk's kW dwords: one load when the whole chunk lies in the epoch,
+          // else only dwords holding a sample of the epoch, cut at the record's end
+          const int k0 = q * kC - grid.mis;
+          const int64_t d0 = grid.first_dword(c.pos) + (int64_t)q * kW;
+          if (k0 + kC <= blk) {
+            if2_load_words<kW>(reinterpret_cast<const uint32_t*>(pbase) + d0, x);
+          } else {
+#pragma unroll
+            for (int u = 0; u < kW; u++)
+              x[u] = k0 + u * (16 / kBps) < blk ? if2_load_dword(pbase, d0 + u, pend) : 0u;
+          }
+        } else {
 #pragma unroll
         for (int u = 0; u < kW; u++) {
           // only words holding a sample of the epoch: none past the stream's end
           const int ks = q * kC - grid.mis + u * (16 / kBps);
           x[u] = ks < blk ? grid.ab[q * kW + u] : make_uint4(0, 0, 0, 0);
+        }
         }
       };
       fetch(0, nx);
@@ -345,8 +377,11 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
         uint32_t wd[4 * kW];
 #pragma unroll
         for (int u = 0; u < kW; u++) {
-          wd[4 * u] = nx[u].x; wd[4 * u + 1] = nx[u].y;
-          wd[4 * u + 2] = nx[u].z; wd[4 * u + 3] = nx[u].w;
+          uint4 v;
+          if constexpr (PK) v = if2_expand_word(nx[u]);   // 16 codes -> the four int8 words
+          else v = nx[u];
+          wd[4 * u] = v.x; wd[4 * u + 1] = v.y;
+          wd[4 * u + 2] = v.z; wd[4 * u + 3] = v.w;
         }
         if (it + 1 < grid.nIt) fetch(it + 1, nx);
         const int q = it * T + tid;
@@ -489,6 +524,9 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
       constexpr int kHW = 5, kTW = 9;               // capture windows: n < kHW, n >= kC - kTW
       constexpr int kNR = (kC * kBps + 3) / 4;      // realigned dwords holding kC samples
       constexpr int kNW = kNR + 1;                  // loaded dwords (any byte alignment)
+      // packed: kC samples are kC * kBps 2-bit codes from any code of a dword on
+      constexpr int kPR = (kC * kBps + 15) / 16;    // realigned packed dwords holding them
+      constexpr int kLW = PK ? kPR + 1 : kNW;       // dwords a fetch loads
       const double inv_step = uni(1.0 / step), stp = uni(step);
       const double aPu = uni(aP), aEu = uni(aE), aLu = uni(aL);
       const int jF = (int)ceil(aPu);                                     // k = 0's prompt chip
@@ -536,7 +574,33 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
         return b;
       };
       typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
-      auto fetch = [&](const Bd& b, uint32_t (&w)[kNW]) {
+      auto fetch = [&](const Bd& b, uint32_t (&w)[kLW]) {
+        if constexpr (PK) {
+          // elements counted from the epoch's first; dword 0 holds the chunk's first
+          const int rel = kBps * b.kS;
+          const int64_t el = (int64_t)kBps * c.pos + rel;
+          const int first = rel - (int)(el & 15);
+          const uint32_t* p4 = reinterpret_cast<const uint32_t*>(pbase) + (el >> 4);
+          const bool inside = first >= 0 && first + 16 * kLW <= kBps * blk;
+          if (__builtin_amdgcn_ballot_w64(!inside) == 0) {
+#pragma unroll
+            for (int u = 0; u + 4 <= kLW; u += 4) {
+              const if2_u32x4a4 v = *reinterpret_cast<const if2_u32x4a4*>(p4 + u);
+              w[u] = v.x; w[u + 1] = v.y; w[u + 2] = v.z; w[u + 3] = v.w;
+            }
+#pragma unroll
+            for (int u = kLW & ~3; u < kLW; u++) w[u] = p4[u];
+          } else {
+            // only dwords holding an element of the epoch, cut at the record's end
+#pragma unroll
+            for (int u = 0; u < kLW; u++) {
+              const int fe = first + 16 * u;
+              w[u] = (fe + 16 > 0 && fe < kBps * blk) ? if2_load_dword(pbase, (el >> 4) + u, pend)
+                                                      : 0u;
+            }
+          }
+          return;
+        }
         const uintptr_t a0 = (uintptr_t)(src + (int64_t)kBps * b.kS);
         const uint32_t* p4 = reinterpret_cast<const uint32_t*>(a0 & ~(uintptr_t)3);
         // a wave whose lanes all read inside the epoch loads without guards
@@ -567,12 +631,12 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
       Bd b = bounds(jF + tid);
       double sb, cb;   // carrier at the chunk's first sample
       sincos(A * ((double)b.kS / p.fs) + c.rem_carr, &sb, &cb);
-      uint32_t nx[kNW];
+      uint32_t nx[kLW];
       fetch(b, nx);   // the next chunk's IF words load during this chunk
       for (int it = 0; it < nIt; it++) {
-        uint32_t w[kNW];
+        uint32_t w[kLW];
 #pragma unroll
-        for (int u = 0; u < kNW; u++) w[u] = nx[u];
+        for (int u = 0; u < kLW; u++) w[u] = nx[u];
         const int j = jF + it * T + tid;
         Bd bn = b;
         if (it + 1 < nIt) {
@@ -585,6 +649,16 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
         // the chunk's samples from byte a0 & 3 on, realigned to dword 0
         const uint32_t sh = (uint32_t)((uintptr_t)(src + (int64_t)kBps * b.kS) & 3);
         uint32_t r[kNR];
+        if constexpr (PK) {
+          // the chunk's codes from code (element & 15) of dword 0 on, realigned by a
+          // funnel shift, then a byte of codes per int8 word
+          const uint32_t shb = 2u * (uint32_t)(((int64_t)kBps * (c.pos + b.kS)) & 15);
+          uint32_t pr[kPR];
+#pragma unroll
+          for (int u = 0; u < kPR; u++) pr[u] = __builtin_amdgcn_alignbit(w[u + 1], w[u], shb);
+#pragma unroll
+          for (int u = 0; u < kNR; u++) r[u] = if2_expand_byte((pr[u >> 2] >> (8 * (u & 3))) & 0xFFu);
+        } else
 #pragma unroll
         for (int u = 0; u < kNR; u++) r[u] = __builtin_amdgcn_alignbyte(w[u + 1], w[u], sh);
         // samples outside [0, blk) count as 0 (the epoch's first and last chunks)
@@ -661,7 +735,15 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
                                   s_sgn[clampu((int)ceil(aPu + t), L + 1)],
                                   s_sgn[clampu((int)ceil(aLu + t), L + 1)]};
             double re, im = 0.0;
-            if constexpr (FT == 2) {
+            if constexpr (PK) {
+              const int wv = if2_sample<FT>(pbase, c.pos + k);
+              if constexpr (FT == 2) {
+                re = (double)(int)__builtin_amdgcn_sbfe(wv, sh_re, 8);
+                im = (double)(int)__builtin_amdgcn_sbfe(wv, sh_im, 8);
+              } else {
+                re = (double)wv;
+              }
+            } else if constexpr (FT == 2) {
               const int wv = *reinterpret_cast<const uint16_t*>(src + 2 * (int64_t)k);
               re = (double)(int)__builtin_amdgcn_sbfe(wv, sh_re, 8);
               im = (double)(int)__builtin_amdgcn_sbfe(wv, sh_im, 8);
@@ -812,6 +894,7 @@ struct gnsscorr_sgt_ctx {
   uint32_t* d_codes = nullptr;
   hostctx::DevBuf<gnsscorr_sgt_chan> d_chan;   // the host wrappers' own
   hostctx::DevBuf<gnsscorr_sgt_epoch> d_ep;
+  int packed = 0;                              // gnsscorr_sgt_set_packed
 };
 
 extern "C" void gnsscorr_sgt_loop_coefs(const gnsscorr_sgt_cfg* cfg, double* tau1, double* tau2,
@@ -874,6 +957,10 @@ extern "C" int gnsscorr_sgt_init_chan(const gnsscorr_sgt_cfg* cfg, int code_id, 
 }
 
 extern "C" int gnsscorr_sgt_destroy(gnsscorr_sgt_ctx* c) { return ftrack::destroy(c); }
+
+extern "C" int gnsscorr_sgt_set_packed(gnsscorr_sgt_ctx* c, int packed) {
+  return ftrack::set_packed(__func__, c, packed);
+}
 
 // the stream and the code rows h on the device
 static int init_device(gnsscorr_sgt_ctx* c, const uint32_t* h, size_t bytes) {
@@ -943,6 +1030,7 @@ extern "C" int gnsscorr_sgt_track_dev(gnsscorr_sgt_ctx* c, const int8_t* d_if, i
                                       int n_epochs, int closed_loop, gnsscorr_sgt_epoch* d_ep) {
   int rc = check_track_dev(__func__, c, d_if, d_chan, d_ep, n_ch, n_epochs, n_samples, stride);
   if (!rc) rc = check_iq_aligned(__func__, c, d_if);
+  if (!rc) rc = check_packed_aligned(__func__, c, d_if, stride);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->cfg.device));
   // many channels: one wave per channel (throughput); fewer: 256-thread
@@ -981,13 +1069,20 @@ extern "C" int gnsscorr_sgt_track_dev(gnsscorr_sgt_ctx* c, const int8_t* d_if, i
     if (b1) SGT_LAUNCH(FT, CL, true);                                                          \
     else SGT_LAUNCH(FT, CL, false);                                                            \
   } while (0)
+  // (packed records: the kernels of FT + kPacked)
+#define SGT_LAUNCH_FT(FT)                                                                      \
+  do {                                                                                         \
+    if (closed_loop) SGT_LAUNCH_SYS(FT, true);                                                 \
+    else SGT_LAUNCH_SYS(FT, false);                                                            \
+  } while (0)
   if (c->cfg.file_type == 2) {
-    if (closed_loop) SGT_LAUNCH_SYS(2, true);
-    else SGT_LAUNCH_SYS(2, false);
+    if (c->packed) SGT_LAUNCH_FT(2 + kPacked);
+    else SGT_LAUNCH_FT(2);
   } else {
-    if (closed_loop) SGT_LAUNCH_SYS(1, true);
-    else SGT_LAUNCH_SYS(1, false);
+    if (c->packed) SGT_LAUNCH_FT(1 + kPacked);
+    else SGT_LAUNCH_FT(1);
   }
+#undef SGT_LAUNCH_FT
 #undef SGT_LAUNCH_SYS
 #undef SGT_LAUNCH
   HIP_TRY(hipGetLastError());

@@ -231,6 +231,7 @@ def _tracker_sig(prefix, Cfg, n_coefs):
             prefix + "_init_chan": (_I, [cfg, _I, _I, _I64, _I64, _D, _P]),
             **_ctx_sig(prefix, cfg),
             prefix + "_track_dev": run, prefix + "_track": run,
+            prefix + "_set_packed": (_I, [_P, _I]),
             prefix + "_replay": rep, prefix + "_replay_dev": rep}
 
 
@@ -251,6 +252,7 @@ def _sig_table():
         "gnsscorr_track_next_tic": (I64, [P, I64]),
         "gnsscorr_track_if_bytes": (I64, [P, I64]),
         "gnsscorr_pack2": (I, [P, I64, P]),
+        "gnsscorr_unpack2": (I, [P, I64, P]),
         "gnsscorr_track_replay_dev": (I, [P, P, I64, I64, I, P, P]),
         "gnsscorr_track_get_state": (I, [P, P]),
         "gnsscorr_track_set_state": (I, [P, P]),
@@ -421,6 +423,17 @@ def pack2(levels) -> np.ndarray:
     lv = np.ascontiguousarray(levels, np.int8).ravel()
     out = np.empty((lv.size + 3) // 4, np.uint8)
     _check(lib().gnsscorr_pack2(_ptr(lv), lv.size, _ptr(out)), "gnsscorr_pack2")
+    return out
+
+
+def unpack2(packed, n) -> np.ndarray:
+    """The first n int8 levels of GNSSCORR_IF_PACKED2 bytes (gnsscorr_unpack2)."""
+    b = np.ascontiguousarray(packed).view(np.uint8).ravel()
+    n = int(n)
+    if n > 4 * b.size:
+        raise ValueError(f"{b.size} packed bytes hold fewer than {n} elements")
+    out = np.empty(max(n, 0), np.int8)
+    _check(lib().gnsscorr_unpack2(_ptr(b), n, _ptr(out)), "gnsscorr_unpack2")
     return out
 
 
@@ -871,6 +884,13 @@ class _FloatTracker(_Handle):
     def _open(self, cfg):
         self.cfg = cfg
         self._create(C.byref(cfg), ops=("track", "track_dev", "replay"))
+
+    def set_packed(self, packed=True):
+        """<prefix>_set_packed: the records of later track / track_dev calls are 2-bit
+        packed (pack2 of the int8 levels; 16-byte-aligned d_if, strides multiples of 16
+        bytes, counts and positions still in samples) instead of int8."""
+        fn = getattr(lib(), self._prefix + "_set_packed")
+        _check(fn(self.h, int(packed)), fn)
 
     def loop_coefs(self):
         """sgt, l3t: (tau1code, tau2code, k1, k2, k3); e1t: *_loop_coefs' seven."""

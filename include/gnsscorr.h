@@ -73,6 +73,8 @@ int gnsscorr_hip_runtime(char *path, int len, int *version);
  * GNSSCORR_IF_PACKED2 codes.  Returns GNSSCORR_EINVAL (and packs nothing) if a
  * value is not one of the four levels. */
 int gnsscorr_pack2(const int8_t *h_in, int64_t n, uint8_t *h_out);
+/* The inverse of gnsscorr_pack2: the n levels held by the first (n+3)/4 bytes. */
+int gnsscorr_unpack2(const uint8_t *h_in, int64_t n, int8_t *h_out);
 
 /* ======================================================================
  * Tracking correlator (GP2021 integer semantics)
@@ -508,13 +510,27 @@ void *gnsscorr_acq_stream(gnsscorr_acq_ctx *ctx);
  * loop) the FLL-assisted PLL and the DLL of tracking.sci:329-375 on the GPU.
  * The IF record(s) stay resident in HBM; each channel reads from its own
  * position (the reference's per-channel mseek, tracking.sci:163-168).
+ *
+ * Packed records (gnsscorr_sgt_set_packed, and the same for the e1t and l3t
+ * families below).  With packed = 1 a record is a GNSSCORR_IF_PACKED2 element
+ * stream: element e in bits 2*(e%4)..2*(e%4)+1 of byte e/4, code c is level
+ * 2c-3.  file_type 1: sample k is element k.  file_type 2: sample k is elements
+ * 2k and 2k+1, the two bytes of the int8 pair in the same order; switch_iq acts
+ * on the unpacked pair as it does on int8 records.  n_samples, chan.pos and
+ * skip_samples stay in samples; stream s still starts at d_if + s*stream_stride
+ * bytes, and a record occupies (elements + 3)/4 bytes: no byte at or past that
+ * end is loaded.  d_if must be 16-byte aligned and stream_stride a multiple of
+ * 16 bytes, else the track call returns GNSSCORR_EINVAL before any launch.
+ * Epoch records and channel states equal, to the bit, those of the int8 path on
+ * the unpacked levels held in a record with a 16-byte-aligned base.
  * ==================================================================== */
 typedef struct gnsscorr_sgt_ctx gnsscorr_sgt_ctx;
 
 typedef struct {          /* initSettings.sci fields used by tracking.sci     */
   int32_t system;         /* 0 = GPS L1 C/A (C/A code per PRN), 1 = GLONASS L1OF (ST),
                              2 = BeiDou B1I (ranging code per PRN)              */
-  int32_t file_type;      /* settings.fileType: 1 = int8 real, 2 = int8 interleaved I,Q */
+  int32_t file_type;      /* settings.fileType: 1 = real, 2 = interleaved I,Q (int8, or
+                             2-bit packed after gnsscorr_sgt_set_packed)          */
   int32_t switch_iq;      /* settings.switchIQ (GLONASS only, tracking.sci:263-267) */
   int32_t code_length;    /* settings.codeLength: 1023 / 511 / 2046 (system 0 / 1 / 2) */
   int32_t device;
@@ -571,6 +587,11 @@ int gnsscorr_sgt_init_chan(const gnsscorr_sgt_cfg *cfg, int code_id, int stream,
                            gnsscorr_sgt_chan *out);
 int gnsscorr_sgt_create(gnsscorr_sgt_ctx **out, const gnsscorr_sgt_cfg *cfg);
 int gnsscorr_sgt_destroy(gnsscorr_sgt_ctx *ctx);
+/* packed = 1: the records of every later gnsscorr_sgt_track / _track_dev call on
+ * this context are 2-bit packed (layout above); 0 (the default): int8.  Any other
+ * value, or a null context, returns GNSSCORR_EINVAL.  gnsscorr_sgt_replay* takes
+ * no record and is unaffected. */
+int gnsscorr_sgt_set_packed(gnsscorr_sgt_ctx *ctx, int packed);
 /* Run n_epochs epochs of n_ch channels (state in d_chan, updated in place).
  * d_if: the records, stream s at d_if + s*stream_stride bytes, each
  * n_samples samples long.  closed_loop=1: the loop filters of tracking.sci
@@ -658,7 +679,8 @@ void *gnsscorr_sgt_stream(gnsscorr_sgt_ctx *ctx);
 typedef struct gnsscorr_e1t_ctx gnsscorr_e1t_ctx;
 
 typedef struct {          /* initSettings.sci fields used by tracking.sci     */
-  int32_t file_type;      /* settings.fileType: 1 = int8 real, 2 = int8 interleaved I,Q */
+  int32_t file_type;      /* settings.fileType: 1 = real, 2 = interleaved I,Q (int8, or
+                             2-bit packed after gnsscorr_e1t_set_packed)          */
   int32_t device;
   int32_t max_channels;
   int32_t max_codes;      /* rows gnsscorr_e1t_set_codes may upload (0 = 50)   */
@@ -725,6 +747,8 @@ int gnsscorr_e1t_destroy(gnsscorr_e1t_ctx *ctx);
  * rows of tracking.sci:157-160, or the rows of the context's mode (above), are
  * built here, once per code. */
 int gnsscorr_e1t_set_codes(gnsscorr_e1t_ctx *ctx, int n_codes, const int8_t *chips);
+/* 2-bit packed records for later track calls, as gnsscorr_sgt_set_packed. */
+int gnsscorr_e1t_set_packed(gnsscorr_e1t_ctx *ctx, int packed);
 /* Run n_epochs epochs of n_ch channels (state in d_chan, updated in place);
  * arguments as gnsscorr_sgt_track_dev.  closed_loop=0 holds the three
  * frequencies.  Tracking before gnsscorr_e1t_set_codes is GNSSCORR_EINVAL. */
@@ -767,7 +791,8 @@ void *gnsscorr_e1t_stream(gnsscorr_e1t_ctx *ctx);
 typedef struct gnsscorr_l3t_ctx gnsscorr_l3t_ctx;
 
 typedef struct {          /* initSettings.sci fields used by tracking.sci     */
-  int32_t file_type;      /* settings.fileType: 2 = int8 interleaved I,Q only; 1 (real
+  int32_t file_type;      /* settings.fileType: 2 = interleaved I,Q only (int8, or 2-bit packed
+                             after gnsscorr_l3t_set_packed); 1 (real
                              samples) is refused with GNSSCORR_EINVAL          */
   int32_t switch_iq;      /* settings.switchIQ (:278-282)                      */
   int32_t code_length;    /* settings.codeLength: 10230 only                   */
@@ -825,6 +850,8 @@ int gnsscorr_l3t_init_chan(const gnsscorr_l3t_cfg *cfg, int prn, int stream,
 /* The padded code rows of every id are built here, once, and stay resident. */
 int gnsscorr_l3t_create(gnsscorr_l3t_ctx **out, const gnsscorr_l3t_cfg *cfg);
 int gnsscorr_l3t_destroy(gnsscorr_l3t_ctx *ctx);
+/* 2-bit packed records for later track calls, as gnsscorr_sgt_set_packed. */
+int gnsscorr_l3t_set_packed(gnsscorr_l3t_ctx *ctx, int packed);
 /* Run n_epochs epochs of n_ch channels (state in d_chan, updated in place);
  * arguments as gnsscorr_sgt_track_dev.  closed_loop=0 holds both frequencies. */
 int gnsscorr_l3t_track_dev(gnsscorr_l3t_ctx *ctx, const int8_t *d_if, int64_t stream_stride,
