@@ -1986,7 +1986,7 @@ extern "C" int gnsscorr_acq_set_records(gnsscorr_acq_ctx* c, int n_records) {
   }
   // the generic engine takes records on its mixed-radix / four-step plans (the units of
   // every record in one chunk loop), not on Bluestein's
-  if (n_records > 1 && (c->prec != GNSSCORR_ACQ_F64 || (c->plan64 == 3 && !c->mix_nr))) {
+  if (n_records > 1 && (c->prec != GNSSCORR_ACQ_F64 || (c->plan64 == 3 && !c->gen.mix.nr))) {
     gnsscorr_set_error("gnsscorr_acq_set_records: several records per search need the fp64 "
                        "precision and a compiled plan (n_samples %d or %d) or a mixed-radix "
                        "generic plan (no prime factor above 31)", 16368, 16000);

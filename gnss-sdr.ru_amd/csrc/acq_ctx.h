@@ -1,5 +1,5 @@
 // acq_ctx.h -- the acquisition context shared by the fp32 (acq.hip) and the
-// reference-precision fp64 (acq64.hip) kernels.  Internal to libgnsscorr.
+// reference-precision fp64 (acq64.hip, acq64_gen.hip) kernels.  Internal to libgnsscorr.
 // Buffers of a size fixed at create are raw pointers; the ones a call may grow
 // are DevBufs (hostctx.h).
 #ifndef GNSSCORR_ACQ_CTX_H
@@ -30,6 +30,41 @@ struct alignas(32) acq64_unit_desc {
 };
 static_assert(sizeof(acq64_unit_desc) == 32, "a 32-byte record, aligned to 32, per workgroup");
 
+// The generic-N fp64 engine's part of the context (plan64 == 3; acq64_gen.hip): what its
+// three engines share, then what each owns.
+struct acq64_gen_ctx {
+  int chunk = 0;                        // rows per chunk
+  double2 *d_A = nullptr, *d_B = nullptr;   // chunk work rows (of M, N or the four-step Y pitch)
+  double* d_pw = nullptr;               // chunk x N power rows
+  // Bluestein: radix-16 Stockham FFTs of length M, a power of two >= 2N - 1
+  struct {
+    int M = 0;
+    double2* d_chirp = nullptr;         // c_n = exp(-i pi n^2 / N), n < N
+    double2* d_vf = nullptr;            // FFT_M of the conjugate chirp (two-sided)
+    double2* d_twM = nullptr;           // W_M^t, t < M
+  } bz;
+  // mixed-radix Stockham plan (N a product of radices in {2..16, 17, 19, 23, 29, 31}):
+  // nr passes of radix r[i] in global memory, twiddles d_twN (W_N^j); nr == 0: Bluestein
+  struct {
+    int nr = 0;
+    int r[24] = {};
+    int rp[24] = {};                    // the order of a zero-padded search's passes (an even
+                                        // radix last: mix_order_padded)
+  } mix;
+  // four-step plan (N = N1 N2, two-radix sub-transforms in LDS, two passes over the rows)
+  struct {
+    int plan = 0;                       // 0 none, else its plan index
+    void* d_top = nullptr;              // per-column top-2 of the power rows, chunk x N1 (null:
+                                        // the statistics run as their own pass)
+    double2* d_tw = nullptr;            // W_N1^j (j < N1) then W_N2^j (j < N2)
+    // lanes == 2: odd chunks run on a second stream with their own Y, power rows and column
+    // top-2.  Lane 0 is the context's stream with d_A, d_pw and d_top (chunk_lane).
+    int lanes = 1;
+    acq_chunk_lane lane1;
+    hipEvent_t ev[2] = {nullptr, nullptr};   // fork (after lane 0's first column pass), join
+  } m4;
+};
+
 struct gnsscorr_acq_ctx {
   gnsscorr_acq_cfg cfg;
   hipStream_t stream = nullptr;
@@ -50,38 +85,7 @@ struct gnsscorr_acq_ctx {
   int* d_lead64 = nullptr;              // classify scratch: per frequency, its class leader
   hostctx::DevBuf<acq64_unit_desc> d_udesc;   // per launched workgroup, rebuilt by every correlate
   int rs64 = 0;                         // fp64 row stride (complex elements)
-  // generic-N fp64 plan (plan64 == 3, any other N): Bluestein with radix-16
-  // Stockham FFTs of length M, a power of two >= 2N - 1 (acq64.hip)
-  int gM = 0;
-  double2* d_chirp = nullptr;           // c_n = exp(-i pi n^2 / N), n < N
-  double2* d_vf = nullptr;              // FFT_M of the conjugate chirp (two-sided)
-  double2* d_twM = nullptr;             // W_M^t, t < M
-  double2 *d_gA = nullptr, *d_gB = nullptr;   // chunk x M work rows
-  double* d_gpw = nullptr;              // chunk x N power rows
-  int g_chunk = 0;                      // rows per chunk
-  // mixed-radix Stockham plan of the generic path (N a product of radices in
-  // {2..16, 17, 19, 23, 29, 31}; Bluestein otherwise or with GNSSCORR_ACQ_BLUESTEIN=1):
-  // mix_nr passes of radix mix_r[i] in global memory, twiddles d_twN (W_N^j)
-  int mix_nr = 0;
-  int mix_r[24] = {};
-  // the same radices in the order of a zero-padded search's correlation passes
-  // (set_zero_padded): an even radix last where N has one, so that with keep = N/2 the
-  // last pass forms only the kept half of its outputs
-  int mix_rp[24] = {};
-  // four-step plan of the generic path (N = N1 N2, N1 = A B and N2 = C D two-radix
-  // sub-transforms in LDS, two passes over the rows): 0 none, else its plan index
-  int m4 = 0;
-  // the four-step plan's per-column top-2 of the power rows (row statistics fused into
-  // m4_rows): chunk x N1 entries, or null when the statistics run as their own pass
-  void* d_m4top = nullptr;
-  double2* d_twm4 = nullptr;            // four-step: W_N1^j (j < N1) then W_N2^j (j < N2)
-  // four-step plan, two chunk lanes: odd chunks run on a second stream with their own
-  // Y, power rows and column top-2 (m4_lanes == 2), so one chunk's column pass overlaps
-  // the other's row pass.  Lane 0 is the context's stream with d_gA, d_gpw and d_m4top
-  // (acq64.hip: chunk_lane); lane1 is what the second lane owns.
-  int m4_lanes = 1;
-  acq_chunk_lane lane1;
-  hipEvent_t m4_ev[2] = {nullptr, nullptr};   // fork (after lane 0's first column pass), join
+  acq64_gen_ctx gen;                    // generic-N fp64 engine (plan64 == 3, acq64_gen.hip)
   // ---- shared
   int n_codes = 0;
   int spec_blocks = 0, spec_freqs = 0;  // shape of the resident IF spectra
@@ -115,7 +119,8 @@ struct gnsscorr_acq_ctx {
   double* d_dump = nullptr;
 };
 
-// ---- acq64.hip: the fp64 engine behind the same context
+// ---- acq64.hip: the fp64 engine behind the same context (compiled plans; it hands a
+// context on plan 3 to the generic engine below)
 // plan id for N (0: N not supported by a compiled plan)
 int acq64_plan_for(int n_samples);
 int acq64_init(gnsscorr_acq_ctx* c);             // device tables for the plan
@@ -129,4 +134,18 @@ int acq64_spectra(gnsscorr_acq_ctx* c, const int8_t* d_if, int iq, int n_blocks,
 int acq64_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int n_bins,
                     const int32_t* d_gcode, const int32_t* d_gfreq, int spc, double* d_dump,
                     int dump_block);
+// acq64_classify_kernel on the context's stream: d_fmap64, d_cfreq and d_nclass of d_freqs
+int acq64_classify_launch(gnsscorr_acq_ctx* c, const double* d_freqs, int n_freqs);
+
+// ---- acq64_gen.hip: the generic-N engine (plan64 == 3), same arguments as the above
+int acq64_gen_init(gnsscorr_acq_ctx* c);
+void acq64_gen_free(gnsscorr_acq_ctx* c);
+int acq64_gen_preload(gnsscorr_acq_ctx* c);      // its own code-object load
+int acq64_gen_set_codes(gnsscorr_acq_ctx* c, const int8_t* d_codes, int n_codes, int code_len);
+int acq64_gen_set_zero_padded(gnsscorr_acq_ctx* c, int keep);
+int acq64_gen_spectra(gnsscorr_acq_ctx* c, const int8_t* d_if, int iq, int n_blocks, int n_freqs,
+                      const double* d_freqs);
+int acq64_gen_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int n_bins,
+                        const int32_t* d_gcode, const int32_t* d_gfreq, int spc, double* d_dump,
+                        int dump_block);
 #endif

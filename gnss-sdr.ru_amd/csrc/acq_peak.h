@@ -1,7 +1,7 @@
 // acq_peak.h -- the row statistics of every acquisition engine, defined once.
 //
-// Every engine (acq.hip: fp32; acq64.hip: the compiled fp64 plans, the generic
-// passes, the four-step plans) reports per correlation row
+// Every engine (acq.hip: fp32; acq64.hip: the compiled fp64 plans; acq64_gen.hip: the
+// generic passes, the four-step plans, chirp-z) reports per correlation row
 //   peak    the row maximum,
 //   argmax  its index,
 //   second  the maximum outside the open circular window (argmax - spc, argmax + spc)

@@ -1,4 +1,4 @@
-"""The per-radix tier of the generic fp64 acquisition engine (csrc/acq64.hip mx_pass):
+"""The per-radix tier of the generic fp64 acquisition engine (csrc/acq64_gen.hip mx_pass):
 the lengths, the scenes and the references that tests/test_acq_mixplan_cpu.py and
 tests/test_acq_radix_gpu.py share.
 

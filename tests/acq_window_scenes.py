@@ -66,7 +66,7 @@ STATS_THREADS = 1024     # kStatsThreads of the generic engine's one-pass statis
 
 
 def stats1_exact(n, spc):
-    """The generic engine's test for its one-pass statistics (csrc/acq64.hip)."""
+    """The generic engine's test for its one-pass statistics (csrc/acq64_gen.hip)."""
     r = STATS_THREADS if n <= STATS_THREADS else n - STATS_THREADS * ((n - 1) // STATS_THREADS)
     return 2 * spc - 1 <= min(r, STATS_THREADS)
 

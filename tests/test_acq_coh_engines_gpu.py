@@ -2,7 +2,7 @@
 
 The setter is implemented three times -- acq_fwd16_kernel (fp32, csrc/acq.hip),
 acq64_wipe_kernel<P> (the compiled fp64 plans) and g_wipe_kernel (the generic fp64
-engine: mixed-radix passes, four-step plan, chirp-z; csrc/acq64.hip) -- and each folds
+engine: mixed-radix passes, four-step plan, chirp-z; csrc/acq64_gen.hip) -- and each folds
 coh code periods of a block into one N-point row with the carrier phase running on over
 n + p*N.  The scenes of tests/acq_coh_scenes.py make every way of getting that fold wrong
 change the signal row by 0.37 of its peak or more (tests/test_acq_coh_cpu.py), and here

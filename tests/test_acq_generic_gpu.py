@@ -1,4 +1,4 @@
-"""GPU parity of the generic-N fp64 acquisition (csrc/acq64.hip): any
+"""GPU parity of the generic-N fp64 acquisition (csrc/acq64_gen.hip): any
 samplesPerCode = round(fs / (codeFreqBasis / codeLength)) (acquisition.sci:47-48)
 without a compiled prime-factor plan, e.g. fs = 5 MHz (N = 5000) or the classic
 SoftGNSS front end at 38.192 MHz (N = 38192).
@@ -279,6 +279,41 @@ def test_generic_multi_chunk_38192(gpu, mode, m4stats, monkeypatch):
             for r in rr:
                 r["block"] = -1
     check_rows(res, rows, ref, ref_rows, True, label=f"chunked-38192-{mode}-m4stats{m4stats}")
+    assert res[0]["metric"] > 2.5 and res[2]["metric"] > 2.5
+
+
+@pytest.mark.parametrize("mode", ["best", "noncoherent"])
+@pytest.mark.parametrize("engine", ["bluestein", "passes"])
+def test_generic_multi_chunk_small(gpu, engine, mode, monkeypatch):
+    """The search driver's chunk loop on the two engines that the tests above leave in their
+    first chunk, at 1 MiB of work rows per chunk (3 codes x 5 bins x 2 blocks).  Bluestein at
+    N = 4111 (prime; M = 16384: 4 rows per chunk, 8 chunks of the 30 best-of-blocks units, 4
+    of the 15 non-coherent rows); the mixed-radix passes at N = 5000 (13 rows per chunk: 3
+    and 2 chunks; max_freqs = 8 keeps the context's cap of codes x frequencies x blocks
+    above that).  Every chunk after the first runs with u0 > 0 in g_corr_pre_kernel, in
+    mx_pass and in the statistics.  Against the fp64 oracle, the file's fp64 class."""
+    monkeypatch.setenv("GNSSCORR_ACQ_GCHUNK_MB", "1")
+    if engine == "passes":
+        monkeypatch.setenv("GNSSCORR_ACQ_BLUESTEIN", "0")
+    fs, n = (4.111e6, 4111) if engine == "bluestein" else (5.0e6, 5000)
+    nb = 2
+    ctx = gpu.AcqCtx(fs, n, max_freqs=8, max_blocks=nb, max_codes=3)
+    prns = [6, 11, 19]
+    codes = np.stack([A.make_ca_table_row(p, fs) for p in prns])
+    ctx.set_codes(codes)
+    IF = _scene(gpu, fs, nb, 0x5EED002B)
+    freqs = 2.42e6 + 500.0 * np.array([-3.5, -1.5, 0.5, 2.5, 4.5])
+    gf = np.tile(np.arange(len(freqs)), (3, 1))
+    spc = int(round(fs / 1.023e6))
+    m = gpu.ACQ_NONCOHERENT if mode == "noncoherent" else gpu.ACQ_BEST_OF_BLOCKS
+    res, rows = ctx.search(IF, nb, freqs, np.arange(3), gf, spc=spc, mode=m)
+    ref, ref_rows = A.acquire(IF, fs, codes, freqs, gf, spc=spc, n_blocks=nb,
+                              noncoherent=mode == "noncoherent", return_rows=True)
+    if mode == "noncoherent":
+        for rr in ref_rows:
+            for r in rr:
+                r["block"] = -1
+    check_rows(res, rows, ref, ref_rows, True, label=f"chunked-{engine}-{n}-{mode}")
     assert res[0]["metric"] > 2.5 and res[2]["metric"] > 2.5
 
 

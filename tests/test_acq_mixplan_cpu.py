@@ -1,4 +1,4 @@
-"""CPU: the pass plan of the generic fp64 acquisition engine (csrc/acq64.hip mix_factor /
+"""CPU: the pass plan of the generic fp64 acquisition engine (csrc/acq64_gen.hip mix_factor /
 mix_order_padded, read through gnsscorr_acq_mix_plan) and the reference floor of the
 per-radix GPU tier (tests/test_acq_radix_gpu.py).
 

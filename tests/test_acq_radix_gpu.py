@@ -1,5 +1,5 @@
 """GPU: every compiled radix of the generic fp64 acquisition engine's mixed-radix passes
-(csrc/acq64.hip mx_pass<R, MODE>, R in 16 8 4 2 3 5 7 11 13 17 19 23 29 31) in every
+(csrc/acq64_gen.hip mx_pass<R, MODE>, R in 16 8 4 2 3 5 7 11 13 17 19 23 29 31) in every
 position and mode, against the fp64 oracle (oracle/acq_oracle.py; the zero-padded
 searches against tests/e1b_scenarios.py).
 

@@ -17,7 +17,7 @@ The acquisition side followed: acq.hip's phase-ablation mask (ACQ_SKIP), cache-p
 sweep (ACQ_LOAD_AUX), plane stride (ACQ_PLANE) and load-group (ACQ_LDGROUP) switches,
 the one-unit kernel's ACQ_STAMP hook (pinned with its parenthesis; ACQ_PSTAMP and
 ACQ64_STAMP stay) and GNSSCORR_ACQ_PIPE, which alone reached the best-of-blocks form
-of acq_corr_kernel; and acq64.hip's generic-engine switches M4_COLS2_PLANE (the
+of acq_corr_kernel; and acq64_gen.hip's generic-engine switches M4_COLS2_PLANE (the
 complex exchange of m4_cols2), M4_COLS2_WPE, M4_ROWS2_WPE, M4_ROWS2_ROWS, MX_WAVES,
 M4_CT, M4_T2 and M4_RT, constants now (kM4ColThreads, kM4T2 and kM4RowThreads do not
 contain the old spellings; M4_CASE stays).
@@ -60,7 +60,7 @@ def test_measured_out_switches_are_gone():
             # (with the parenthesis: ACQ_PSTAMP stays) and the route past the pipelined kernel
             "ACQ_SKIP", "ACQ_LOAD_AUX", "ACQ_PLANE", "ACQ_LDGROUP", "ACQ_STAMP(",
             "GNSSCORR_ACQ_PIPE",
-            # acq64.hip: the generic engine's settled compile-time switches
+            # acq64_gen.hip: the generic engine's settled compile-time switches
             "M4_COLS2_PLANE", "M4_COLS2_WPE", "M4_ROWS2_WPE", "M4_ROWS2_ROWS", "MX_WAVES",
             "M4_CT", "M4_T2", "M4_RT")
     for f, lines in _sources():

@@ -1,6 +1,8 @@
 // tools/acq64_stamps.hip -- diagnostic build of the fp64 acquisition
 // correlation kernel with s_memtime stamps at its barriers (thread 0 of each
-// workgroup).  Not part of the library.  On the GPU box (tools/acq64_stamps.sh):
+// workgroup).  Not part of the library.  It includes csrc/acq64.hip, i.e. the compiled
+// plans only; the generic engine (acq64_gen.o) is linked as the library built it.
+// On the GPU box (tools/acq64_stamps.sh):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Ignss-sdr.ru_amd/csrc \
 //         -c tools/acq64_stamps.hip -o /tmp/s64.o
 //   hipcc --offload-arch=gfx950 /tmp/s64.o <library objects except acq64.o> -o /tmp/s64

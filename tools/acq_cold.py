@@ -1,6 +1,7 @@
 """Where a context's first code spectra and first search spend their time.
 
-python tools/acq_cold.py  -> one JSON line: milliseconds for gnsscorr_acq_create,
+python tools/acq_cold.py [fs_hz]  -> one JSON line (fs_hz: another sampling rate, e.g.
+38192000 for the generic engine's first use; default 16.368 MHz): milliseconds for gnsscorr_acq_create,
 the first and a later set_prn_codes (+ sync), the first and a later config-2
 search (spectra + correlate + select + sync), for the process's first context
 and for a second one created after it (code objects already loaded).
@@ -17,7 +18,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
                                 "gnss-sdr.ru_amd"))
 import gnsscorr as gc  # noqa: E402
 
-FS, N, NB, NPRN, NBIN = 16.368e6, 16368, 2, 32, 41
+FS = float(sys.argv[1]) if len(sys.argv) > 1 else 16.368e6
+N, NB, NPRN, NBIN = int(round(FS / 1000.0)), 2, 32, 41
 
 
 def one_context(dev=0):
@@ -55,4 +57,4 @@ def one_context(dev=0):
 
 if __name__ == "__main__":
     print(json.dumps({"first_context": one_context(), "second_context": one_context(),
-                      "lib": os.environ.get("GNSSCORR_LIB", "in-tree")}))
+                      "n_samples": N, "lib": os.environ.get("GNSSCORR_LIB", "in-tree")}))
