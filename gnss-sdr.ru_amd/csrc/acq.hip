@@ -1303,7 +1303,8 @@ static int codes_preload(gnsscorr_acq_ctx* c);
 static int init_shared(gnsscorr_acq_ctx* c) {
   const gnsscorr_acq_cfg* cfg = &c->cfg;
   HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  HIP_TRY(hipMalloc(&c->d_if, (size_t)cfg->n_samples * 2 * cfg->max_blocks));
+  c->if_cap = (size_t)cfg->n_samples * 2 * cfg->max_blocks;
+  HIP_TRY(hipMalloc(&c->d_if, c->if_cap));
   HIP_TRY(hipMalloc(&c->d_freqs, sizeof(double) * cfg->max_freqs));
   HIP_TRY(hipMalloc(&c->d_cfreq, sizeof(double) * cfg->max_freqs));
   HIP_TRY(hipMalloc(&c->d_resid, sizeof(double) * cfg->max_freqs));
@@ -1657,13 +1658,41 @@ static int check_search(gnsscorr_acq_ctx* c, int n_blocks, int n_freqs, int mode
   return GNSSCORR_OK;
 }
 
+// the record format flags of a call: checked before any device work (the host entry
+// points check them before they stage the record)
+static int check_if_flags(const gnsscorr_acq_ctx* c, int iq) {
+  if (iq & ~(GNSSCORR_IF_IQ | GNSSCORR_IF_PACKED2 | GNSSCORR_IF_INT16)) {
+    gnsscorr_set_error("gnsscorr_acq: iq must be a set of GNSSCORR_IF_* flags (got %d)", iq);
+    return GNSSCORR_EINVAL;
+  }
+  if (iq & GNSSCORR_IF_INT16) {
+    if (iq & GNSSCORR_IF_PACKED2) {
+      gnsscorr_set_error("gnsscorr_acq: GNSSCORR_IF_INT16 and GNSSCORR_IF_PACKED2 exclude "
+                         "each other");
+      return GNSSCORR_EINVAL;
+    }
+    if (c->prec != GNSSCORR_ACQ_F64) {
+      gnsscorr_set_error("gnsscorr_acq: GNSSCORR_IF_INT16 records need a GNSSCORR_ACQ_F64 "
+                         "context");
+      return GNSSCORR_EINVAL;
+    }
+  }
+  return GNSSCORR_OK;
+}
+
 static int spectra_launch(gnsscorr_acq_ctx* c, const int8_t* d_if, int iq, int n_blocks,
                           int n_freqs, const double* d_freqs) {
   int rc = check_search(c, n_blocks, n_freqs, GNSSCORR_ACQ_BEST_OF_BLOCKS);
+  if (!rc) rc = check_if_flags(c, iq);
   if (rc) return rc;
-  if (iq & ~(GNSSCORR_IF_IQ | GNSSCORR_IF_PACKED2)) {
-    gnsscorr_set_error("gnsscorr_acq: iq must be a set of GNSSCORR_IF_* flags (got %d)", iq);
-    return GNSSCORR_EINVAL;
+  if (iq & GNSSCORR_IF_INT16) {
+    // an I,Q pair is one dword load, a real sample one 16-bit load
+    const uintptr_t mask = (iq & GNSSCORR_IF_IQ) ? 3 : 1;
+    if ((uintptr_t)d_if & mask) {
+      gnsscorr_set_error("gnsscorr_acq: an int16 record must be %d-byte aligned",
+                         (int)mask + 1);
+      return GNSSCORR_EINVAL;
+    }
   }
   if (c->prec == GNSSCORR_ACQ_F64) {
     // records are contiguous, so they are recs * n_blocks blocks of one IF
@@ -1860,8 +1889,10 @@ static int stage_host(gnsscorr_acq_ctx* c, const int8_t* h_if, int iq, int n_blo
       }
     }
   }
+  int rc = check_if_flags(c, iq);
+  if (rc) return rc;
   const size_t R = (size_t)n_groups * n_bins;
-  int rc = hostctx::grow(c->d_rows, R * c->recs);
+  rc = hostctx::grow(c->d_rows, R * c->recs);
   if (!rc) rc = hostctx::grow(c->d_res, (size_t)n_groups * c->recs);
   if (!rc) rc = hostctx::grow(c->d_gcode, n_groups);
   if (!rc) rc = hostctx::grow(c->d_gfreq, R);
@@ -1870,10 +1901,20 @@ static int stage_host(gnsscorr_acq_ctx* c, const int8_t* h_if, int iq, int n_blo
   // end (one record and one code period per block then: set_zero_padded)
   const int64_t n_if = c->bstride ? (int64_t)(n_blocks - 1) * c->bstride + c->cfg.n_samples
                                   : (int64_t)c->recs * n_blocks * c->coh * c->cfg.n_samples;
-  HIP_TRY(hipMemcpyAsync(c->d_if, h_if,
-                         (size_t)if_bytes(n_if * ((iq & GNSSCORR_IF_IQ) ? 2 : 1),
-                                          iq & GNSSCORR_IF_PACKED2),
-                         hipMemcpyHostToDevice, c->stream));
+  size_t bytes = (size_t)if_bytes(n_if * ((iq & GNSSCORR_IF_IQ) ? 2 : 1),
+                                  iq & GNSSCORR_IF_PACKED2);
+  if (iq & GNSSCORR_IF_INT16) {
+    // twice the bytes: the staging buffer grows once (work queued on it has drained)
+    bytes *= 2;
+    if (bytes > c->if_cap) {
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      hostctx::release(c->d_if);
+      c->if_cap = 0;
+      HIP_TRY(hipMalloc(&c->d_if, bytes));
+      c->if_cap = bytes;
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(c->d_if, h_if, bytes, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->d_freqs, h_freqs, sizeof(double) * n_freqs, hipMemcpyHostToDevice,
                          c->stream));
   HIP_TRY(hipMemcpyAsync(c->d_gcode.p, h_gcode, sizeof(int) * n_groups, hipMemcpyHostToDevice,

@@ -43,6 +43,7 @@
 #include "acq64_dft.h"
 #include "acq_ctx.h"
 #include "if2.h"
+#include "if16.h"
 
 // Diagnostic hook: tools/acq64_stamps.hip defines ACQ64_STAMP(i) to record
 // s_memtime at the barriers of the correlation kernel; nothing in the library.
@@ -398,8 +399,11 @@ __device__ __forceinline__ void fft_core(double* lds, double* side,
 // at the class frequency f = cfreq[cls]; row = cls * n_blocks + blk.  With
 // fuse_n > 0 (short frequency tables) every workgroup first classifies the
 // table itself (acq64_classify_kernel's job) and workgroup 0 publishes it.
+// I16: the record is GNSSCORR_IF_INT16 (if16.h): an I,Q pair is one dword load, a real
+// sample one 16-bit load, both halves converted from their full 16 bits.  A kernel of
+// its own: the int8 / packed one keeps its code.
 constexpr int kFuseClass = 64;
-template <class P>
+template <class P, bool I16 = false>
 __global__ __launch_bounds__(256) void acq64_wipe_kernel(
     const int8_t* __restrict__ src, int iq, int n_blocks, int coh, const double* __restrict__ cfreq_in,
     const int* __restrict__ n_cls_dev, double ts, v2d* __restrict__ out, int fuse_n,
@@ -458,8 +462,16 @@ __global__ __launch_bounds__(256) void acq64_wipe_kernel(
     double re = 0.0, im = 0.0;
     for (int p = 0; p < coh; p++) {
       const long m = n + (long)p * N;
-      const double I = (double)if_elem(src, e0 + ne * m, pk);
-      const double Q = cplx ? (double)if_elem(src, e0 + 2 * m + 1, pk) : 0.0;
+      double I, Q;
+      if constexpr (I16) {
+        const int w = cplx ? if16_sample<2>(reinterpret_cast<const uint8_t*>(src), (e0 >> 1) + m)
+                           : if16_sample<1>(reinterpret_cast<const uint8_t*>(src), e0 + m);
+        I = cplx ? (double)if16_half(w, 0) : (double)w;
+        Q = cplx ? (double)if16_half(w, 16) : 0.0;
+      } else {
+        I = (double)if_elem(src, e0 + ne * m, pk);
+        Q = cplx ? (double)if_elem(src, e0 + 2 * m + 1, pk) : 0.0;
+      }
       const double th = f * ((((double)m * 2.0) * M_PI) * ts);
       double sn, cs;
       sincos(th, &sn, &cs);
@@ -1093,6 +1105,12 @@ int spectra_launch(gnsscorr_acq_ctx* c, const int8_t* d_if, int iq, int n_blocks
   }
   const long work = (long)rows * N;
   const int grid = (int)((work + 255) / 256 < 2048 ? (work + 255) / 256 : 2048);
+  if (iq & GNSSCORR_IF_INT16)
+    hipLaunchKernelGGL((acq64_wipe_kernel<P, true>), dim3(grid), dim3(256), 0, c->stream, d_if, iq,
+                       n_blocks, c->coh, c->d_cfreq, c->d_nclass, 1.0 / c->cfg.samp_rate,
+                       (v2d*)c->d_in64.p, fuse, d_freqs, delta, c->d_fmap64, c->d_cfreq,
+                       c->d_nclass);
+  else
   hipLaunchKernelGGL(acq64_wipe_kernel<P>, dim3(grid), dim3(256), 0, c->stream, d_if, iq,
                      n_blocks, c->coh, c->d_cfreq, c->d_nclass, 1.0 / c->cfg.samp_rate,
                      (v2d*)c->d_in64.p, fuse, d_freqs, delta, c->d_fmap64, c->d_cfreq,

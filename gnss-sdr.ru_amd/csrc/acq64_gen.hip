@@ -18,6 +18,7 @@
 #include "acq64_dft.h"
 #include "acq_ctx.h"
 #include "if2.h"
+#include "if16.h"
 
 namespace {
 
@@ -270,7 +271,9 @@ int g_stats_concat_launch(gnsscorr_acq_ctx* c, hipStream_t st, const double* pw,
   return GNSSCORR_OK;
 }
 
-// wipe-off rows in natural order (acq64_wipe_kernel with a runtime N)
+// wipe-off rows in natural order (acq64_wipe_kernel with a runtime N; I16 as there: the
+// GNSSCORR_IF_INT16 kernel, the int8 / packed one keeps its code)
+template <bool I16 = false>
 __global__ __launch_bounds__(256) void g_wipe_kernel(const int8_t* __restrict__ src, int iq,
                                                      int n_blocks, int coh, long bstride,
                                                      const double* __restrict__ cfreq,
@@ -290,8 +293,16 @@ __global__ __launch_bounds__(256) void g_wipe_kernel(const int8_t* __restrict__ 
     double re = 0.0, im = 0.0;
     for (int p = 0; p < coh; p++) {
       const long m = n + (long)p * N;
-      const double I = (double)if_elem(src, e0 + ne * m, pk);
-      const double Q = cplx ? (double)if_elem(src, e0 + 2 * m + 1, pk) : 0.0;
+      double I, Q;
+      if constexpr (I16) {
+        const int w = cplx ? if16_sample<2>(reinterpret_cast<const uint8_t*>(src), (e0 >> 1) + m)
+                           : if16_sample<1>(reinterpret_cast<const uint8_t*>(src), e0 + m);
+        I = cplx ? (double)if16_half(w, 0) : (double)w;
+        Q = cplx ? (double)if16_half(w, 16) : 0.0;
+      } else {
+        I = (double)if_elem(src, e0 + ne * m, pk);
+        Q = cplx ? (double)if_elem(src, e0 + 2 * m + 1, pk) : 0.0;
+      }
       const double th = f * ((((double)m * 2.0) * M_PI) * ts);
       double sn, cs;
       sincos(th, &sn, &cs);
@@ -1220,7 +1231,13 @@ int acq64_gen_spectra(gnsscorr_acq_ctx* c, const int8_t* d_if, int iq, int n_blo
   const int rows = n_freqs * n_blocks;   // upper bound: classes <= frequencies
   const long work = (long)rows * N;
   const int grid = (int)((work + 255) / 256 < 2048 ? (work + 255) / 256 : 2048);
-  hipLaunchKernelGGL(g_wipe_kernel, dim3(grid), dim3(256), 0, c->stream, d_if, iq, n_blocks,
+  if (iq & GNSSCORR_IF_INT16)
+    hipLaunchKernelGGL(g_wipe_kernel<true>, dim3(grid), dim3(256), 0, c->stream, d_if, iq,
+                       n_blocks, c->coh, c->bstride ? (long)c->bstride : (long)c->coh * N,
+                       (const double*)c->d_cfreq, (const int*)c->d_nclass,
+                       1.0 / c->cfg.samp_rate, N, (v2d*)c->d_in64.p);
+  else
+  hipLaunchKernelGGL(g_wipe_kernel<false>, dim3(grid), dim3(256), 0, c->stream, d_if, iq, n_blocks,
                      c->coh, c->bstride ? (long)c->bstride : (long)c->coh * N,
                      (const double*)c->d_cfreq, (const int*)c->d_nclass,
                      1.0 / c->cfg.samp_rate, N, (v2d*)c->d_in64.p);

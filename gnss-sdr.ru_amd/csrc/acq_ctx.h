@@ -112,6 +112,7 @@ struct gnsscorr_acq_ctx {
   int8_t* d_chips = nullptr;            // chip table: rows 0..31 GPS C/A PRN 1..32, row 32 the
                                         // GLONASS ST code (511 chips), 1023 B each (set_prn_codes)
   int8_t* d_if = nullptr;
+  size_t if_cap = 0;                    // its bytes (grown for GNSSCORR_IF_INT16 records)
   double* d_freqs = nullptr;
   hostctx::DevBuf<int> d_gcode, d_gfreq;
   hostctx::DevBuf<gnsscorr_acq_row> d_rows;

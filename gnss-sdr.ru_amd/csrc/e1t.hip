@@ -232,7 +232,11 @@ __device__ __forceinline__ double flip(double v, uint32_t s) {
 // paths consume, on the chunk grid of an int8 record with a 16-byte-aligned base, so
 // the sums are the int8 path's to the bit.  Kernels of their own: the int8 ones keep
 // their code and their symbols.
+// FTP + kInt16 (gnsscorr_e1t_set_record_format(ctx, 2)): int16 records (if16.h).  Both
+// paths take the int8 path's samples (the same chunk grid, in samples: a 16-sample I,Q
+// chunk is 64 bytes) and convert the full 16 bits; kernels of their own again.
 constexpr int kPacked = 4;
+constexpr int kInt16 = 8;
 template <int MODE, int FTP, bool CLOSED, int MAXT>
 __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
     E1tParams p, const int8_t* __restrict__ ifbuf, int64_t stride, int64_t n_samples,
@@ -241,6 +245,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
 #pragma clang fp contract(off)
   constexpr int FT = FTP & 3;
   constexpr bool PK = (FTP & kPacked) != 0;
+  constexpr bool I16 = (FTP & kInt16) != 0;
   using M = Mode<MODE>;
   constexpr int kCodeWords = M::kCodeWords, kRowWords = M::kRowWords, kRowLen = M::kRowLen;
   constexpr int kArms = M::kArms, kSums = 2 * M::kArms;
@@ -262,6 +267,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
   // packed: the stream's bytes and the record's end (no byte at or past it is loaded)
   const uint8_t* pbase = reinterpret_cast<const uint8_t*>(base);
   const int64_t pend = if_bytes((FT == 2 ? 2 : 1) * n_samples, true);
+  const int64_t end16 = (int64_t)if16_sample_bytes<FT>() * n_samples;   // int16: likewise
   int e = 0;
   for (; e < n_epochs; e++) {
     gnsscorr_e1t_epoch* rec = out + (int64_t)ch * n_epochs + e;
@@ -296,7 +302,8 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
     }
     const double A = (c.carr_freq * 2.0) * M_PI;        // (carrFreq * 2.0 * %pi)
     // (packed: sample k is sample c.pos + k of pbase; src only keeps the predicate)
-    const int8_t* src = PK ? base : base + (FT == 2 ? 2 : 1) * c.pos;
+    // (int16: the epoch's first sample, at twice the bytes)
+    const int8_t* src = PK ? base : base + (I16 ? 2 : 1) * (FT == 2 ? 2 : 1) * c.pos;
     const uint32_t* srow = s_code + (M::k4ms ? 0 : c.segment * kRowWords);   // 4 ms: one row
     // bit of padded-row entry j (0-based; the clamp only keeps a state set from
     // outside inside the row: the loop's own indices lie in [0, kRowLen - 1])
@@ -317,6 +324,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
       sincos(thw, &sw, &cw);   // (e1t.o is built with promote-alloca-to-lds off)
       auto load = [&](int k) -> int {
         if constexpr (PK) return if2_sample<FT>(pbase, c.pos + k);
+        if constexpr (I16) return if16_sample<FT>(pbase, c.pos + k);
         if (FT == 2) return *reinterpret_cast<const uint16_t*>(src + 2 * (int64_t)k);
         return src[k];
       };
@@ -339,7 +347,10 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
           sg[3] = (mP ^ gL) << 31; sg[4] = (mL ^ gP) << 31;
         }
         double re, im;
-        if (FT == 2) {
+        if constexpr (I16 && FT == 2) {
+          re = (double)if16_half(w, 0);
+          im = (double)if16_half(w, 16);
+        } else if (FT == 2) {
           re = (double)(int)__builtin_amdgcn_sbfe(w, 0, 8);
           im = (double)(int)__builtin_amdgcn_sbfe(w, 8, 8);
         } else {
@@ -396,7 +407,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
     auto run_chunks = [&]() {
       using Grid = ChunkGrid<kBps, kC>;
       const Grid grid = [&] {
-        if constexpr (PK) return Grid(c.pos, blk, T);
+        if constexpr (PK || I16) return Grid(c.pos, blk, T);
         else return Grid(src, blk, T);
       }();
       const double cst = uni(cstep), mst = uni(mstep);
@@ -415,11 +426,23 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
       cR = uni(cR);
       __syncthreads();
       constexpr int kW = Grid::kW;   // 16-byte words per chunk (packed: dwords)
+      constexpr int kXW = I16 ? 2 * kW : kW;   // int16: the same samples in twice the words
       using Word = std::conditional_t<PK, uint32_t, uint4>;
-      Word nx[kW];
-      auto fetch = [&](int it, Word (&x)[kW]) {
+      Word nx[kXW];
+      auto fetch = [&](int it, Word (&x)[kXW]) {
         const int q = it * T + tid;
-        if constexpr (PK) {
+        if constexpr (I16) {
+          // only words holding a sample of the epoch, cut at the record's end
+          constexpr int kSw = 8 / kBps;   // samples per 16-byte word
+          const int k0 = q * kC - grid.mis;
+          const int64_t o = grid.first_byte16(c.pos, q);
+#pragma unroll
+          for (int u = 0; u < kXW; u++) {
+            const int ks = k0 + u * kSw;
+            x[u] = (ks < blk && ks + kSw > 0) ? if16_load_word(pbase, o + 16 * u, end16)
+                                              : make_uint4(0, 0, 0, 0);
+          }
+        } else if constexpr (PK) {
           // the chunk's kW dwords: one load when the whole chunk lies in the epoch,
           // else only dwords holding a sample of the epoch, cut at the record's end
           const int k0 = q * kC - grid.mis;
@@ -442,9 +465,9 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
       };
       fetch(0, nx);
       for (int it = 0; it < grid.nIt; it++) {
-        uint32_t wd[4 * kW];
+        uint32_t wd[4 * kXW];
 #pragma unroll
-        for (int u = 0; u < kW; u++) {
+        for (int u = 0; u < kXW; u++) {
           uint4 v;
           if constexpr (PK) v = if2_expand_word(nx[u]);   // 16 codes -> the four int8 words
           else v = nx[u];
@@ -459,6 +482,11 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
 #pragma unroll
           for (int n = 0; n < kC; n++) {
             const bool v = (unsigned)(k0 + n) < (unsigned)blk;
+            if constexpr (I16) {
+              if constexpr (FT == 2) wd[n] = v ? wd[n] : 0u;
+              else wd[n >> 1] &= v ? 0xffffffffu : ~(0xffffu << (16 * (n & 1)));
+              continue;
+            }
             constexpr int kSpw = 4 / kBps;   // samples per dword
             const uint32_t m = (kBps == 2 ? 0xffffu : 0xffu) << (8 * kBps * (n % kSpw));
             wd[n / kSpw] &= v ? 0xffffffffu : ~m;
@@ -535,7 +563,18 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? 2 : 1) void e1t_track_kernel(
         for (int n = 0; n < kC; n++) {
           double ur, ui;
           const double2 W = s_w[n + wo];   // broadcast read
-          if constexpr (FT == 2) {
+          if constexpr (I16) {
+            // the int8 forms below on the full 16 bits
+            const double re = (double)if16_re<FT>(wd, n, 0);
+            if constexpr (FT == 2) {
+              const double im = (double)if16_im<FT>(wd, n, 0);
+              ur = fma(W.x, re, -(W.y * im));
+              ui = fma(W.x, im, W.y * re);
+            } else {
+              ur = W.x * re;
+              ui = W.y * re;
+            }
+          } else if constexpr (FT == 2) {
             const uint32_t w = wd[n >> 1];
             const int sh = (n & 1) * 16;
             const double re = (double)(int)__builtin_amdgcn_sbfe(w, sh, 8);
@@ -688,6 +727,7 @@ struct gnsscorr_e1t_ctx {
   hostctx::DevBuf<gnsscorr_e1t_chan> d_chan;   // the host wrappers' own
   hostctx::DevBuf<gnsscorr_e1t_epoch> d_ep;
   int packed = 0;                              // gnsscorr_e1t_set_packed
+  int i16 = 0;                                 // gnsscorr_e1t_set_record_format(ctx, 2)
 };
 
 #define E1T_BAD_CONFIG                                                            \
@@ -749,6 +789,9 @@ extern "C" int gnsscorr_e1t_destroy(gnsscorr_e1t_ctx* c) { return ftrack::destro
 
 extern "C" int gnsscorr_e1t_set_packed(gnsscorr_e1t_ctx* c, int packed) {
   return ftrack::set_packed(__func__, c, packed);
+}
+extern "C" int gnsscorr_e1t_set_record_format(gnsscorr_e1t_ctx* c, int fmt) {
+  return ftrack::set_record_format(__func__, c, fmt);
 }
 
 // the stream and room for the code rows (gnsscorr_e1t_set_codes fills them)
@@ -894,14 +937,16 @@ extern "C" int gnsscorr_e1t_track_dev(gnsscorr_e1t_ctx* c, const int8_t* d_if, i
     if (closed_loop) E1T_LAUNCH(MD, FT, true);   \
     else E1T_LAUNCH(MD, FT, false);           \
   } while (0)
-  // (packed records: the kernels of FT + kPacked)
+  // (packed records: the kernels of FT + kPacked; int16 records: FT + kInt16)
 #define E1T_LAUNCH_MODE(MD)                   \
   do {                                        \
     if (c->cfg.file_type == 2) {              \
       if (c->packed) E1T_LAUNCH_FT(MD, 2 + kPacked);  \
+      else if (c->i16) E1T_LAUNCH_FT(MD, 2 + kInt16);  \
       else E1T_LAUNCH_FT(MD, 2);              \
     } else {                                  \
       if (c->packed) E1T_LAUNCH_FT(MD, 1 + kPacked);  \
+      else if (c->i16) E1T_LAUNCH_FT(MD, 1 + kInt16);  \
       else E1T_LAUNCH_FT(MD, 1);              \
     }                                         \
   } while (0)

@@ -21,6 +21,7 @@
 #include "gnsscorr_internal.h"
 #include "hostctx.h"
 #include "if2.h"
+#include "if16.h"
 
 namespace ftrack {
 
@@ -103,6 +104,12 @@ struct ChunkGrid {
   }
   __device__ __forceinline__ int64_t first_dword(int64_t pos) const {
     return (kBps * (pos - mis)) >> 4;
+  }
+  // int16 records (if16.h) take the same constructor, kBps still the int8 record's:
+  // the grid is defined in samples, chunk q holds the samples it holds on int8, in
+  // the 2 * kW 16-byte words from this byte of the stream on
+  __device__ __forceinline__ int64_t first_byte16(int64_t pos, int q) const {
+    return 2 * (int64_t)kBps * (pos - mis + (int64_t)q * kC);
   }
 
   // Where an index a + k*step next exceeds j: sample k has index > j iff
@@ -230,6 +237,19 @@ int set_packed(const char* fn, Ctx* c, int packed) {
     return GNSSCORR_EINVAL;
   }
   c->packed = packed;
+  c->i16 = 0;
+  return GNSSCORR_OK;
+}
+// *_set_record_format: 0 = int8, 1 = GNSSCORR_IF_PACKED2 (set_packed(1)), 2 = int16
+template <class Ctx>
+int set_record_format(const char* fn, Ctx* c, int fmt) {
+  if (!c || fmt < 0 || fmt > 2) {
+    gnsscorr_set_error("%s: bad arguments (a context, fmt 0 = int8, 1 = 2-bit packed, "
+                       "2 = int16)", fn);
+    return GNSSCORR_EINVAL;
+  }
+  c->packed = fmt == 1;
+  c->i16 = fmt == 2;
   return GNSSCORR_OK;
 }
 // packed records: whole 16-byte words from an aligned base, for every stream
@@ -237,6 +257,12 @@ template <class Ctx>
 int check_packed_aligned(const char* fn, const Ctx* c, const int8_t* d_if, int64_t stride) {
   if (c->packed && (((uintptr_t)d_if & 15) || (stride & 15))) {
     gnsscorr_set_error("%s: packed records need a 16-byte-aligned d_if and a stream_stride "
+                       "that is a multiple of 16 bytes", fn);
+    return GNSSCORR_EINVAL;
+  }
+  // int16 records: the chunks are dwordx4 loads from 32-byte steps of the stream
+  if (c->i16 && (((uintptr_t)d_if & 15) || (stride & 15))) {
+    gnsscorr_set_error("%s: int16 records need a 16-byte-aligned d_if and a stream_stride "
                        "that is a multiple of 16 bytes", fn);
     return GNSSCORR_EINVAL;
   }

@@ -126,7 +126,11 @@ __device__ __forceinline__ double flip(double v, uint32_t s) {
 // (gnsscorr_l3t_set_packed): a sample's pair of 2-bit codes is unpacked to the int8 pair
 // the per-sample pass consumes.  Kernels of their own: the int8 ones keep their code and
 // their symbols.
+// MAXTP + kInt16 (gnsscorr_l3t_set_record_format(ctx, 2)): int16 records (if16.h), a
+// sample's pair one dword whose halves convert from their full 16 bits; kernels of their
+// own again.
 constexpr int kPacked = 4096;
+constexpr int kInt16 = 8192;
 template <bool CLOSED, int MAXTP>
 __global__ __launch_bounds__(MAXTP & (kPacked - 1), (MAXTP & (kPacked - 1)) == 64 ? 2 : 1) void
 l3t_track_kernel(
@@ -136,6 +140,7 @@ l3t_track_kernel(
 #pragma clang fp contract(off)
   constexpr int MAXT = MAXTP & (kPacked - 1);
   constexpr bool PK = (MAXTP & kPacked) != 0;
+  constexpr bool I16 = (MAXTP & kInt16) != 0;
   __shared__ uint32_t s_code[2 * kRowWords];     // pilot row, data row as bits (1 = chip -1)
   __shared__ double s_part[2][kMaxWaves][12];
   const int ch = blockIdx.x;
@@ -176,7 +181,7 @@ l3t_track_kernel(
     const int blk = (int)blk_d;
     const double aE = c.rem_code - p.spc, aL = c.rem_code + p.spc, aP = c.rem_code;
     const double A = (c.carr_freq * 2.0) * M_PI;        // (carrFreq * 2.0 * %pi)
-    const int8_t* src = base + (PK ? 0 : 2) * c.pos;
+    const int8_t* src = base + (PK ? 0 : (I16 ? 4 : 2)) * c.pos;
     double acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     {
       const double th0 = A * ((double)tid / p.fs) + c.rem_carr, thw = A * ((double)T / p.fs);
@@ -186,6 +191,7 @@ l3t_track_kernel(
       auto load = [&](int k) -> int {
         if constexpr (PK)
           return if2_sample<2>(reinterpret_cast<const uint8_t*>(src), c.pos + k);
+        if constexpr (I16) return (int)reinterpret_cast<const uint32_t*>(src)[k];
         return *reinterpret_cast<const uint16_t*>(src + 2 * (int64_t)k);
       };
       auto sample = [&](int k, int w) {
@@ -201,8 +207,10 @@ l3t_track_kernel(
                                 (s_code[kRowWords + wE] >> (jE & 31)) << 31,
                                 (s_code[kRowWords + wP] >> (jP & 31)) << 31,
                                 (s_code[kRowWords + wL] >> (jL & 31)) << 31};
-        const double re = (double)(int)__builtin_amdgcn_sbfe(w, sh_re, 8);
-        const double im = (double)(int)__builtin_amdgcn_sbfe(w, sh_im, 8);
+        const double re = I16 ? (double)if16_half(w, 2 * sh_re)
+                              : (double)(int)__builtin_amdgcn_sbfe(w, sh_re, 8);
+        const double im = I16 ? (double)if16_half(w, 2 * sh_im)
+                              : (double)(int)__builtin_amdgcn_sbfe(w, sh_im, 8);
         // (explicit fma: the carrier and the sums only need fp64 accuracy; the
         // indices above stay uncontracted and bit-exact)
         const double qb = fma(cs, re, -(sn * im));   // real(carrsig .* rawSignal)
@@ -314,6 +322,7 @@ struct gnsscorr_l3t_ctx {
   hostctx::DevBuf<gnsscorr_l3t_chan> d_chan;   // the host wrappers' own
   hostctx::DevBuf<gnsscorr_l3t_epoch> d_ep;
   int packed = 0;                              // gnsscorr_l3t_set_packed
+  int i16 = 0;                                 // gnsscorr_l3t_set_record_format(ctx, 2)
 };
 
 extern "C" void gnsscorr_l3t_loop_coefs(const gnsscorr_l3t_cfg* cfg, double* tau1, double* tau2,
@@ -356,6 +365,9 @@ extern "C" int gnsscorr_l3t_destroy(gnsscorr_l3t_ctx* c) { return ftrack::destro
 
 extern "C" int gnsscorr_l3t_set_packed(gnsscorr_l3t_ctx* c, int packed) {
   return ftrack::set_packed(__func__, c, packed);
+}
+extern "C" int gnsscorr_l3t_set_record_format(gnsscorr_l3t_ctx* c, int fmt) {
+  return ftrack::set_record_format(__func__, c, fmt);
 }
 
 // the stream and the resident code rows of ids 0..64
@@ -444,6 +456,9 @@ extern "C" int gnsscorr_l3t_track_dev(gnsscorr_l3t_ctx* c, const int8_t* d_if, i
   if (c->packed) {
     if (closed_loop) L3T_LAUNCH(true, kPacked);
     else L3T_LAUNCH(false, kPacked);
+  } else if (c->i16) {
+    if (closed_loop) L3T_LAUNCH(true, kInt16);
+    else L3T_LAUNCH(false, kInt16);
   } else {
     if (closed_loop) L3T_LAUNCH(true, 0);
     else L3T_LAUNCH(false, 0);

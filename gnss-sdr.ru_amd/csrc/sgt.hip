@@ -48,6 +48,7 @@ constexpr int kMaxPrnB1 = 37;
 __host__ __device__ constexpr int sgt_row_pitch(bool b1) { return b1 ? kPadLenB1 : kPadLen; }
 constexpr int kMaxWaves = 16;
 constexpr int kPacked = 4;   // added to a kernel's FT: 2-bit packed records
+constexpr int kInt16 = 8;    // added to a kernel's FT: int16 records (if16.h)
 // wave mode asks for 3 waves per SIMD (<= 168 VGPRs): measured 3 % faster than 2
 constexpr int kWaveOcc = 3;
 // run_chunks with prefix columns: per-lane prefix sums of W_n*raw over sub-blocks
@@ -149,6 +150,9 @@ __device__ __forceinline__ int xcd_channel(int b, int G) {
 // path below consumes; the chunk partition is that of an int8 record on a
 // 16-byte-aligned base, so the sums are the int8 path's to the bit.  Its own kernels
 // too: the int8 ones keep their code and their symbols.
+// FTP + kInt16 (gnsscorr_sgt_set_record_format(ctx, 2)): int16 records.  Every path
+// takes the samples of the int8 path (the same chunk grid, in samples) from twice the
+// bytes and converts the full 16 bits; kernels of their own again.
 template <int FTP, bool CLOSED, int MAXT, bool B1 = false>
 __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_kernel(
     SgtParams p, const int8_t* __restrict__ ifbuf, int64_t stride, int64_t n_samples,
@@ -157,6 +161,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
 #pragma clang fp contract(off)
   constexpr int FT = FTP & 3;
   constexpr bool PK = (FTP & kPacked) != 0;
+  constexpr bool I16 = (FTP & kInt16) != 0;
   // the code as +-1.0 (E/P/L accumulate with one fma), L + 2 entries: dynamic,
   // so a 511-chip GLONASS table takes 4.1 KB, not the 1023-chip maximum
   extern __shared__ double s_sgn[];
@@ -189,6 +194,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
   // packed: the stream's bytes and the record's end (no byte at or past it is loaded)
   const uint8_t* pbase = reinterpret_cast<const uint8_t*>(base);
   const int64_t pend = if_bytes((FT == 2 ? 2 : 1) * n_samples, true);
+  const int64_t end16 = (int64_t)if16_sample_bytes<FT>() * n_samples;   // int16: likewise
   const double dL = (double)L;
   int e = 0;
   for (; e < n_epochs; e++) {
@@ -201,8 +207,9 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
     const double blk_d = ceil((dL - c.rem_code) / step);
     // tracking.sci:273-277: not enough samples (NaN or huge blksize from a
     // corrupted state stops too, as does a blksize of 2^31 or more)
-    // (packed: a position before the record stops as well)
-    if (!(blk_d <= (double)(n_samples - c.pos) && blk_d < 2147483648.0) || (PK && c.pos < 0)) {
+    // (packed, int16: a position before the record stops as well)
+    if (!(blk_d <= (double)(n_samples - c.pos) && blk_d < 2147483648.0) ||
+        ((PK || I16) && c.pos < 0)) {
       c.status = 1;
       if (tid == 0) {
         gnsscorr_sgt_epoch z = {};
@@ -217,7 +224,8 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
     const double A = (c.carr_freq * 2.0) * M_PI;        // (carrFreq * 2.0 * %pi)
     double ie = 0, ip = 0, il = 0, qe = 0, qp = 0, ql = 0;
     // (packed: sample k is sample c.pos + k of pbase; src only keeps the predicates)
-    const int8_t* src = PK ? base : base + (FT == 2 ? 2 : 1) * c.pos;
+    // (int16: the epoch's first sample, at twice the bytes)
+    const int8_t* src = PK ? base : base + (I16 ? 2 : 1) * (FT == 2 ? 2 : 1) * c.pos;
     // I/Q byte order as bit-field offsets (switchIQ without a per-sample select)
     const int sh_re = p.switch_iq ? 8 : 0, sh_im = 8 - sh_re;
     // kU samples per thread per pass.  The IF words of pass n+1 are loaded
@@ -227,6 +235,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
     constexpr int kU = 8;
     auto load = [&](int k) -> int {
       if constexpr (PK) return if2_sample<FT>(pbase, c.pos + k);
+      if constexpr (I16) return if16_sample<FT>(pbase, c.pos + k);
       if (FT == 2) return *reinterpret_cast<const uint16_t*>(src + 2 * k);
       return src[k];
     };
@@ -253,7 +262,10 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
       const double gP = s_sgn[index(aP + t)];
       const double gL = s_sgn[index(aL + t)];
       double re, im;
-      if (FT == 2) {
+      if constexpr (I16 && FT == 2) {
+        re = (double)if16_half(w, 2 * sh_re);
+        im = (double)if16_half(w, 16 - 2 * sh_re);
+      } else if (FT == 2) {
         re = (double)(int)__builtin_amdgcn_sbfe(w, sh_re, 8);   // (the builtin is typed unsigned)
         im = (double)(int)__builtin_amdgcn_sbfe(w, sh_im, 8);
       } else {
@@ -319,7 +331,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
       constexpr int kC = decltype(kc_tag)::value;
       using Grid = ChunkGrid<kBps, kC>;
       const Grid grid = [&] {
-        if constexpr (PK) return Grid(c.pos, blk, T);
+        if constexpr (PK || I16) return Grid(c.pos, blk, T);
         else return Grid(src, blk, T);
       }();
       const double inv_step = uni(1.0 / step), stp = uni(step);
@@ -347,11 +359,23 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
       __syncthreads();
       double accI[3] = {0.0, 0.0, 0.0}, accQ[3] = {0.0, 0.0, 0.0};
       constexpr int kW = Grid::kW;   // 16-byte words per chunk (packed: dwords)
+      constexpr int kXW = I16 ? 2 * kW : kW;   // int16: the same samples in twice the words
       using Word = std::conditional_t<PK, uint32_t, uint4>;
-      Word nx[kW];
-      auto fetch = [&](int it, Word (&x)[kW]) {
+      Word nx[kXW];
+      auto fetch = [&](int it, Word (&x)[kXW]) {
         const int q = it * T + tid;
-        if constexpr (PK) {
+        if constexpr (I16) {
+          // only words holding a sample of the epoch, cut at the record's end
+          constexpr int kSw = 8 / kBps;   // samples per 16-byte word
+          const int k0 = q * kC - grid.mis;
+          const int64_t o = grid.first_byte16(c.pos, q);
+#pragma unroll
+          for (int u = 0; u < kXW; u++) {
+            const int ks = k0 + u * kSw;
+            x[u] = (ks < blk && ks + kSw > 0) ? if16_load_word(pbase, o + 16 * u, end16)
+                                              : make_uint4(0, 0, 0, 0);
+          }
+        } else if constexpr (PK) {
           // the chunk's kW dwords: one load when the whole chunk lies in the epoch,
           // else only dwords holding a sample of the epoch, cut at the record's end
           const int k0 = q * kC - grid.mis;
@@ -374,9 +398,9 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
       };
       fetch(0, nx);
       for (int it = 0; it < grid.nIt; it++) {
-        uint32_t wd[4 * kW];
+        uint32_t wd[4 * kXW];
 #pragma unroll
-        for (int u = 0; u < kW; u++) {
+        for (int u = 0; u < kXW; u++) {
           uint4 v;
           if constexpr (PK) v = if2_expand_word(nx[u]);   // 16 codes -> the four int8 words
           else v = nx[u];
@@ -391,6 +415,11 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
 #pragma unroll
           for (int n = 0; n < kC; n++) {
             const bool v = (unsigned)(k0 + n) < (unsigned)blk;
+            if constexpr (I16) {
+              if constexpr (FT == 2) wd[n] = v ? wd[n] : 0u;
+              else wd[n >> 1] &= v ? 0xffffffffu : ~(0xffffu << (16 * (n & 1)));
+              continue;
+            }
             constexpr int kSpw = 4 / kBps;   // samples per dword
             const uint32_t m = (kBps == 2 ? 0xffffu : 0xffu) << (8 * kBps * (n % kSpw));
             wd[n / kSpw] &= v ? 0xffffffffu : ~m;
@@ -438,7 +467,9 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
             for (int m = 0; m < kSub; m++) {
               const int n = h * kSub + m;
               double ur, ui;
-              if constexpr (FT == 2) {
+              if constexpr (I16) {
+                if16_wraw<FT>(wd, n, 2 * sh_re, s_w[n + wo], ur, ui);
+              } else if constexpr (FT == 2) {
                 const uint32_t w = wd[n >> 1];
                 const int sh = (n & 1) * 16;
                 const double re = (double)(int)__builtin_amdgcn_sbfe(w, sh + sh_re, 8);
@@ -469,7 +500,9 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
 #pragma unroll
         for (int n = 0; n < kC; n++) {
           double ur, ui;
-          if constexpr (FT == 2) {
+          if constexpr (I16) {
+            if16_wraw<FT>(wd, n, 2 * sh_re, s_w[n + wo], ur, ui);
+          } else if constexpr (FT == 2) {
             const uint32_t w = wd[n >> 1];
             const int sh = (n & 1) * 16;
             const double re = (double)(int)__builtin_amdgcn_sbfe(w, sh + sh_re, 8);
@@ -522,8 +555,11 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
     auto run_chips = [&](auto kc_tag) {
       constexpr int kC = decltype(kc_tag)::value;   // 16, 17, 32 or 33: longest chunk
       constexpr int kHW = 5, kTW = 9;               // capture windows: n < kHW, n >= kC - kTW
-      constexpr int kNR = (kC * kBps + 3) / 4;      // realigned dwords holding kC samples
-      constexpr int kNW = kNR + 1;                  // loaded dwords (any byte alignment)
+      constexpr int kSB = I16 ? 2 * kBps : kBps;    // bytes per sample
+      constexpr int kNR = (kC * kSB + 3) / 4;       // realigned dwords holding kC samples
+      // loaded dwords (any byte alignment; an int16 pair is a dword of its own)
+      constexpr bool kDwordSamples = I16 && FT == 2;
+      constexpr int kNW = kDwordSamples ? kNR : kNR + 1;
       // packed: kC samples are kC * kBps 2-bit codes from any code of a dword on
       constexpr int kPR = (kC * kBps + 15) / 16;    // realigned packed dwords holding them
       constexpr int kLW = PK ? kPR + 1 : kNW;       // dwords a fetch loads
@@ -601,10 +637,10 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
           }
           return;
         }
-        const uintptr_t a0 = (uintptr_t)(src + (int64_t)kBps * b.kS);
+        const uintptr_t a0 = (uintptr_t)(src + (int64_t)kSB * b.kS);
         const uint32_t* p4 = reinterpret_cast<const uint32_t*>(a0 & ~(uintptr_t)3);
         // a wave whose lanes all read inside the epoch loads without guards
-        const bool inside = b.kS >= 0 && b.kS + (4 * kNW + kBps - 1) / kBps <= blk;
+        const bool inside = b.kS >= 0 && b.kS + (4 * kNW + kSB - 1) / kSB <= blk;
         if (__builtin_amdgcn_ballot_w64(!inside) == 0) {
 #pragma unroll
           for (int u = 0; u + 4 <= kNW; u += 4) {
@@ -615,10 +651,15 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
           for (int u = kNW & ~3; u < kNW; u++) w[u] = p4[u];
         } else {
           // only dwords holding a byte of the epoch [src, src + kBps blk)
-          const uintptr_t lo = (uintptr_t)src, hi = lo + (uintptr_t)((int64_t)kBps * blk);
+          const uintptr_t lo = (uintptr_t)src, hi = lo + (uintptr_t)((int64_t)kSB * blk);
 #pragma unroll
           for (int u = 0; u < kNW; u++) {
             const uintptr_t a = (uintptr_t)(p4 + u);
+            // (int16: a dword the record's end cuts gives its first element alone)
+            if constexpr (I16)
+              w[u] = (a + 4 > lo && a < hi)
+                         ? if16_load_dword(pbase, (int64_t)(a - (uintptr_t)pbase), end16) : 0u;
+            else
             w[u] = (a + 4 > lo && a < hi) ? p4[u] : 0u;
           }
         }
@@ -647,7 +688,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
         const bool ok = len <= kC && len >= kC - 3 && bE >= 0 && bE <= kHW && bL - 1 >= kC - kTW &&
                         bL <= len;
         // the chunk's samples from byte a0 & 3 on, realigned to dword 0
-        const uint32_t sh = (uint32_t)((uintptr_t)(src + (int64_t)kBps * b.kS) & 3);
+        const uint32_t sh = (uint32_t)((uintptr_t)(src + (int64_t)kSB * b.kS) & 3);
         uint32_t r[kNR];
         if constexpr (PK) {
           // the chunk's codes from code (element & 15) of dword 0 on, realigned by a
@@ -658,6 +699,9 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
           for (int u = 0; u < kPR; u++) pr[u] = __builtin_amdgcn_alignbit(w[u + 1], w[u], shb);
 #pragma unroll
           for (int u = 0; u < kNR; u++) r[u] = if2_expand_byte((pr[u >> 2] >> (8 * (u & 3))) & 0xFFu);
+        } else if constexpr (kDwordSamples) {
+#pragma unroll
+          for (int u = 0; u < kNR; u++) r[u] = w[u];
         } else
 #pragma unroll
         for (int u = 0; u < kNR; u++) r[u] = __builtin_amdgcn_alignbyte(w[u + 1], w[u], sh);
@@ -677,11 +721,14 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
               // sample's table entry and conversion to the chunk's start
               asm volatile("" : "+v"(wo) : "v"(Tr));
 #pragma unroll
-              for (int u = n * kBps / 4; u < kNR && u < (n + kChipGroup) * kBps / 4 + 1; u++)
+              for (int u = n * kSB / 4; u < kNR && u < (n + kChipGroup) * kSB / 4 + 1; u++)
                 asm volatile("" : "+v"(r[u]) : "v"(Ti));
             }
             int re, im = 0;
-            if constexpr (FT == 2) {
+            if constexpr (I16) {
+              re = if16_re<FT>(r, n, 2 * sh_re);
+              im = if16_im<FT>(r, n, 2 * sh_re);
+            } else if constexpr (FT == 2) {
               re = (int)__builtin_amdgcn_sbfe(r[n >> 1], (n & 1) * 16 + sh_re, 8);
               im = (int)__builtin_amdgcn_sbfe(r[n >> 1], (n & 1) * 16 + sh_im, 8);
             } else {
@@ -740,6 +787,14 @@ __global__ __launch_bounds__(MAXT, MAXT == 64 ? kWaveOcc : 1) void sgt_track_ker
               if constexpr (FT == 2) {
                 re = (double)(int)__builtin_amdgcn_sbfe(wv, sh_re, 8);
                 im = (double)(int)__builtin_amdgcn_sbfe(wv, sh_im, 8);
+              } else {
+                re = (double)wv;
+              }
+            } else if constexpr (I16) {
+              const int wv = if16_sample<FT>(pbase, c.pos + k);
+              if constexpr (FT == 2) {
+                re = (double)if16_half(wv, 2 * sh_re);
+                im = (double)if16_half(wv, 16 - 2 * sh_re);
               } else {
                 re = (double)wv;
               }
@@ -895,6 +950,7 @@ struct gnsscorr_sgt_ctx {
   hostctx::DevBuf<gnsscorr_sgt_chan> d_chan;   // the host wrappers' own
   hostctx::DevBuf<gnsscorr_sgt_epoch> d_ep;
   int packed = 0;                              // gnsscorr_sgt_set_packed
+  int i16 = 0;                                 // gnsscorr_sgt_set_record_format(ctx, 2)
 };
 
 extern "C" void gnsscorr_sgt_loop_coefs(const gnsscorr_sgt_cfg* cfg, double* tau1, double* tau2,
@@ -960,6 +1016,9 @@ extern "C" int gnsscorr_sgt_destroy(gnsscorr_sgt_ctx* c) { return ftrack::destro
 
 extern "C" int gnsscorr_sgt_set_packed(gnsscorr_sgt_ctx* c, int packed) {
   return ftrack::set_packed(__func__, c, packed);
+}
+extern "C" int gnsscorr_sgt_set_record_format(gnsscorr_sgt_ctx* c, int fmt) {
+  return ftrack::set_record_format(__func__, c, fmt);
 }
 
 // the stream and the code rows h on the device
@@ -1069,7 +1128,7 @@ extern "C" int gnsscorr_sgt_track_dev(gnsscorr_sgt_ctx* c, const int8_t* d_if, i
     if (b1) SGT_LAUNCH(FT, CL, true);                                                          \
     else SGT_LAUNCH(FT, CL, false);                                                            \
   } while (0)
-  // (packed records: the kernels of FT + kPacked)
+  // (packed records: the kernels of FT + kPacked; int16 records: FT + kInt16)
 #define SGT_LAUNCH_FT(FT)                                                                      \
   do {                                                                                         \
     if (closed_loop) SGT_LAUNCH_SYS(FT, true);                                                 \
@@ -1077,9 +1136,11 @@ extern "C" int gnsscorr_sgt_track_dev(gnsscorr_sgt_ctx* c, const int8_t* d_if, i
   } while (0)
   if (c->cfg.file_type == 2) {
     if (c->packed) SGT_LAUNCH_FT(2 + kPacked);
+    else if (c->i16) SGT_LAUNCH_FT(2 + kInt16);
     else SGT_LAUNCH_FT(2);
   } else {
     if (c->packed) SGT_LAUNCH_FT(1 + kPacked);
+    else if (c->i16) SGT_LAUNCH_FT(1 + kInt16);
     else SGT_LAUNCH_FT(1);
   }
 #undef SGT_LAUNCH_FT

@@ -151,6 +151,7 @@ SDR_RESULT = np.dtype([("sv", "<i4"), ("code_phase", "<i4"), ("doppler", "<i4"),
 
 IF_IQ = 1        # GNSSCORR_IF_IQ: interleaved I,Q
 IF_PACKED2 = 2   # GNSSCORR_IF_PACKED2: 2-bit codes, 4 elements per byte (GN3S LUT {-3,-1,1,3})
+IF_INT16 = 4     # GNSSCORR_IF_INT16: little-endian int16 elements (fp64 acquisition)
 ACQ_BEST_OF_BLOCKS = 0
 ACQ_NONCOHERENT = 1
 ACQ_CONCAT = 2   # GNSSCORR_ACQ_CONCAT: the blocks' kept lags end to end (set_block_stride)
@@ -232,6 +233,7 @@ def _tracker_sig(prefix, Cfg, n_coefs):
             **_ctx_sig(prefix, cfg),
             prefix + "_track_dev": run, prefix + "_track": run,
             prefix + "_set_packed": (_I, [_P, _I]),
+            prefix + "_set_record_format": (_I, [_P, _I]),
             prefix + "_replay": rep, prefix + "_replay_dev": rep}
 
 
@@ -406,16 +408,26 @@ def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data
 
 
-def _if_bytes(a) -> np.ndarray:
-    """IF samples as the C ABI's int8 byte buffer (packed data may come as uint8)."""
+def _if_bytes(a, iq=0) -> np.ndarray:
+    """IF samples as the C ABI's int8 byte buffer (packed data may come as uint8).  With
+    GNSSCORR_IF_INT16 in iq the record is an int16 array, handed over as its little-endian
+    bytes, or those bytes as uint8; an array of another type holds no 16-bit elements (an
+    int8 array is int8 samples, whatever its size) and is refused."""
     a = np.ascontiguousarray(a)
+    if int(iq) & IF_INT16:
+        if a.dtype.kind == "i" and a.dtype.itemsize == 2:
+            return a.astype("<i2", copy=False).reshape(-1).view(np.int8)
+        if a.dtype != np.uint8:
+            raise GnssCorrError(f"GNSSCORR_IF_INT16 needs an int16 array (or its bytes as "
+                                f"uint8), got {a.dtype}")
     return a.view(np.int8) if a.dtype == np.uint8 else np.ascontiguousarray(a, np.int8)
 
 
-def iq_flags(iq, packed=False) -> int:
+def iq_flags(iq, packed=False, int16=False) -> int:
     """The `iq` argument of the C ABI: GNSSCORR_IF_* flags (iq may already be flags)."""
     f = int(iq)
-    return f | IF_PACKED2 if packed else f
+    f = f | IF_PACKED2 if packed else f
+    return f | IF_INT16 if int16 else f
 
 
 def pack2(levels) -> np.ndarray:
@@ -774,7 +786,7 @@ class AcqCtx(_Handle):
 
     def search(self, if_samples, n_blocks, freqs, group_code, group_freq, spc=16, iq=True,
                mode=ACQ_BEST_OF_BLOCKS):
-        if_samples = _if_bytes(if_samples)
+        if_samples = _if_bytes(if_samples, iq)
         freqs = np.ascontiguousarray(freqs, np.float64)
         group_code = np.ascontiguousarray(group_code, np.int32)
         group_freq = np.ascontiguousarray(group_freq, np.int32).reshape(len(group_code), -1)
@@ -784,6 +796,7 @@ class AcqCtx(_Handle):
             # the library copies the strided record's length: refuse a shorter host array
             n_el = ((n_blocks - 1) * stride + self.n) * (2 if int(iq) & IF_IQ else 1)
             need = (n_el + 3) // 4 if int(iq) & IF_PACKED2 else n_el
+            need = 2 * n_el if int(iq) & IF_INT16 else need
             if if_samples.size < need:
                 raise GnssCorrError(f"gnsscorr_acq_search: {n_blocks} blocks at stride {stride} "
                                     f"need {need} bytes of IF, got {if_samples.size}")
@@ -840,7 +853,7 @@ class AcqCtx(_Handle):
                                              d_rows, d_res), "gnsscorr_acq_select_dev")
 
     def power_row(self, if_samples, n_blocks, block, freq, code, iq=True) -> np.ndarray:
-        if_samples = _if_bytes(if_samples)
+        if_samples = _if_bytes(if_samples, iq)
         out = np.empty(self.n, np.float64)
         _check(lib().gnsscorr_acq_power_row(self.h, _ptr(if_samples), int(iq), n_blocks, block,
                                             freq, code, _ptr(out)), "gnsscorr_acq_power_row")
@@ -891,6 +904,18 @@ class _FloatTracker(_Handle):
         bytes, counts and positions still in samples) instead of int8."""
         fn = getattr(lib(), self._prefix + "_set_packed")
         _check(fn(self.h, int(packed)), fn)
+
+    RECORD_FORMATS = {"int8": 0, "packed2": 1, "int16": 2}
+
+    def set_format(self, fmt):
+        """<prefix>_set_record_format: the records of later track / track_dev calls are
+        "int8", "packed2" (what set_packed selects) or "int16" (little-endian int16
+        elements, 2 * elements bytes; 16-byte-aligned d_if, strides multiples of 16 bytes,
+        counts and positions still in samples)."""
+        if fmt not in self.RECORD_FORMATS:
+            raise ValueError(f"record format {fmt!r}: one of {sorted(self.RECORD_FORMATS)}")
+        fn = getattr(lib(), self._prefix + "_set_record_format")
+        _check(fn(self.h, self.RECORD_FORMATS[fmt]), fn)
 
     def loop_coefs(self):
         """sgt, l3t: (tau1code, tau2code, k1, k2, k3); e1t: *_loop_coefs' seven."""

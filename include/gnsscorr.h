@@ -63,12 +63,28 @@ int gnsscorr_hip_runtime(char *path, int len, int *version);
  *                          (REALTIME_RECEIVERS/GPS/GPS_SDR_REAL_TIME_GPS_RECEIVER/
  *                          objects/gps_source.cpp:692).  Results equal the int8
  *                          path on the unpacked levels; HBM and PCIe bytes are 1/4.
+ *   | GNSSCORR_IF_INT16    native little-endian int16_t elements: settings.dataType
+ *                          'sl' of the Scilab receivers (dataTypeSizeInBytes = 2) and
+ *                          the CPX packets GPS_Source::Read records
+ *                          (objects/gps_source.cpp:167-176).  With GNSSCORR_IF_IQ sample
+ *                          k is elements 2k, 2k+1, without it element k.  Accepted by
+ *                          the gnsscorr_acq_* calls that take a record (search,
+ *                          search_dev, spectra_dev, power_row) on a GNSSCORR_ACQ_F64
+ *                          context; on a GNSSCORR_ACQ_F32 context, or combined with
+ *                          GNSSCORR_IF_PACKED2, they return GNSSCORR_EINVAL.  The
+ *                          pointer type stays const int8_t *.  A device record must
+ *                          be 4-byte aligned with GNSSCORR_IF_IQ (a pair is one dword
+ *                          load), 2-byte aligned without; this is checked before any
+ *                          launch.  Every value enters the fp64 arithmetic from its
+ *                          full 16 bits; block, record and stride offsets stay in
+ *                          samples, so their byte offsets double.
  * Strides and sample counts stay in samples; byte offsets of packed data are
  * element offsets / 4 (stream strides must make them whole 16-byte multiples
  * on the device).
  * ==================================================================== */
 #define GNSSCORR_IF_IQ      1
 #define GNSSCORR_IF_PACKED2 2
+#define GNSSCORR_IF_INT16   4
 /* Host helper: pack n int8 levels in {-3,-1,1,3} into (n+3)/4 bytes of
  * GNSSCORR_IF_PACKED2 codes.  Returns GNSSCORR_EINVAL (and packs nothing) if a
  * value is not one of the four levels. */
@@ -317,7 +333,8 @@ int gnsscorr_acq_set_codes(gnsscorr_acq_ctx *ctx, int n_codes, const int8_t *h_c
 int gnsscorr_acq_set_prn_codes(gnsscorr_acq_ctx *ctx, int n_codes, const int32_t *h_code_ids);
 
 /* Search.  IF: n_blocks consecutive blocks of n_samples samples, format
- * `iq` (GNSSCORR_IF_* flags: interleaved I,Q or real, int8 or 2-bit packed).  freqs: n_freqs carrier
+ * `iq` (GNSSCORR_IF_* flags: interleaved I,Q or real; int8, 2-bit packed or, fp64 contexts
+ * only, int16).  freqs: n_freqs carrier
  * frequencies [Hz] (wipe-off exp(i*2*pi*f*t), t = n/fs).  Groups: n_groups
  * searches, each of n_bins rows: group g uses code group_code[g] and
  * frequency index group_freq[g*n_bins + b] for bin b.
@@ -523,6 +540,22 @@ void *gnsscorr_acq_stream(gnsscorr_acq_ctx *ctx);
  * 16 bytes, else the track call returns GNSSCORR_EINVAL before any launch.
  * Epoch records and channel states equal, to the bit, those of the int8 path on
  * the unpacked levels held in a record with a 16-byte-aligned base.
+ *
+ * Record formats (gnsscorr_sgt_set_record_format, and the same for e1t and l3t):
+ * fmt 0 = int8 (the default), 1 = 2-bit packed (what set_packed(ctx, 1) selects),
+ * 2 = int16: native little-endian int16_t elements (GNSSCORR_IF_INT16 above).
+ * file_type 1: sample k is element k; file_type 2: sample k is elements 2k, 2k+1;
+ * switch_iq acts on the pair as it does on int8.  n_samples, chan.pos and
+ * skip_samples stay in samples; stream s starts at d_if + s*stream_stride bytes and
+ * a record occupies 2 * elements bytes: no byte at or past that end is loaded.
+ * d_if must be 16-byte aligned and stream_stride a multiple of 16 bytes (the chunks
+ * are 16-byte loads from 32-byte steps of the stream), else the track call returns
+ * GNSSCORR_EINVAL before any launch.  Values use the whole int16 range; a record of
+ * int8-range levels gives, to the bit, the int8 path's epochs and states (int8
+ * record on a 16-byte-aligned base).  absolute_sample stays a sample position, as
+ * defined for pos; the Scilab receivers count currentSample in bytes instead
+ * (GLONASS/L1/tracking.sci:166-168,258,384 and L3/tracking.sci:167-169,273,401
+ * scale it by dataTypeSizeInBytes).
  * ==================================================================== */
 typedef struct gnsscorr_sgt_ctx gnsscorr_sgt_ctx;
 
@@ -592,6 +625,11 @@ int gnsscorr_sgt_destroy(gnsscorr_sgt_ctx *ctx);
  * value, or a null context, returns GNSSCORR_EINVAL.  gnsscorr_sgt_replay* takes
  * no record and is unaffected. */
 int gnsscorr_sgt_set_packed(gnsscorr_sgt_ctx *ctx, int packed);
+/* The record format of every later gnsscorr_sgt_track / _track_dev call: 0 = int8,
+ * 1 = 2-bit packed, 2 = int16 (layouts above).  set_packed(ctx, p) is
+ * set_record_format(ctx, p).  Any other value, or a null context, returns
+ * GNSSCORR_EINVAL. */
+int gnsscorr_sgt_set_record_format(gnsscorr_sgt_ctx *ctx, int fmt);
 /* Run n_epochs epochs of n_ch channels (state in d_chan, updated in place).
  * d_if: the records, stream s at d_if + s*stream_stride bytes, each
  * n_samples samples long.  closed_loop=1: the loop filters of tracking.sci
@@ -749,6 +787,8 @@ int gnsscorr_e1t_destroy(gnsscorr_e1t_ctx *ctx);
 int gnsscorr_e1t_set_codes(gnsscorr_e1t_ctx *ctx, int n_codes, const int8_t *chips);
 /* 2-bit packed records for later track calls, as gnsscorr_sgt_set_packed. */
 int gnsscorr_e1t_set_packed(gnsscorr_e1t_ctx *ctx, int packed);
+/* The record format of later track calls, as gnsscorr_sgt_set_record_format. */
+int gnsscorr_e1t_set_record_format(gnsscorr_e1t_ctx *ctx, int fmt);
 /* Run n_epochs epochs of n_ch channels (state in d_chan, updated in place);
  * arguments as gnsscorr_sgt_track_dev.  closed_loop=0 holds the three
  * frequencies.  Tracking before gnsscorr_e1t_set_codes is GNSSCORR_EINVAL. */
@@ -852,6 +892,8 @@ int gnsscorr_l3t_create(gnsscorr_l3t_ctx **out, const gnsscorr_l3t_cfg *cfg);
 int gnsscorr_l3t_destroy(gnsscorr_l3t_ctx *ctx);
 /* 2-bit packed records for later track calls, as gnsscorr_sgt_set_packed. */
 int gnsscorr_l3t_set_packed(gnsscorr_l3t_ctx *ctx, int packed);
+/* The record format of later track calls, as gnsscorr_sgt_set_record_format. */
+int gnsscorr_l3t_set_record_format(gnsscorr_l3t_ctx *ctx, int fmt);
 /* Run n_epochs epochs of n_ch channels (state in d_chan, updated in place);
  * arguments as gnsscorr_sgt_track_dev.  closed_loop=0 holds both frequencies. */
 int gnsscorr_l3t_track_dev(gnsscorr_l3t_ctx *ctx, const int8_t *d_if, int64_t stream_stride,

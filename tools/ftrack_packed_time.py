@@ -1,9 +1,11 @@
-"""Packed against int8 records in the float trackers ("Packed records").
+"""Packed and int16 against int8 records in the float trackers ("Packed
+records", "int16 records").
 
 Closed loop, device-resident (track_dev), HIP events on the context's stream; the channel
 state is uploaded again before every launch, so each launch does the same work.  The int8
-and the packed launch of a shape alternate, `--warmup` untimed pairs first, then `--runs`
-timed pairs: min / median / max per format and the ratio of the medians.
+and the packed launch of a shape alternate (with --int16 the int16 launch too, the same
+levels stored as int16), `--warmup` untimed rounds first, then `--runs` timed ones: min /
+median / max per format and the ratio of the medians.
 
 Shapes:
   sgt_bench   bench.py's GLONASS shape: 256 records x 14 FCH = 3584 channels x 30 epochs
@@ -39,6 +41,8 @@ def time_pair(a, ctx, rec, stride, n, chans, dtype_ep, epochs):
     bufs = {"int8": (gc.DevBuf.from_array(rec), stride)}
     if not a.int8_only:
         bufs["packed"] = (gc.DevBuf.from_array(gc.pack2(rec)), stride // 4)
+    if a.int16:
+        bufs["int16"] = (gc.DevBuf.from_array(rec.astype(np.int16)), 2 * stride)
     d_ch = gc.DevBuf.from_array(chans)
     d_ep = gc.DevBuf(dtype_ep.itemsize * C * epochs)
     e0, e1 = gc.Event(), gc.Event()
@@ -46,7 +50,9 @@ def time_pair(a, ctx, rec, stride, n, chans, dtype_ep, epochs):
     last = {}
     for r in range(a.warmup + a.runs):
         for k, (d_if, st) in bufs.items():
-            if not a.int8_only:
+            if a.int16:
+                ctx.set_format({"packed": "packed2"}.get(k, k))
+            elif not a.int8_only:
                 ctx.set_packed(k == "packed")
             d_ch.upload(chans)
             e0.record(ctx.stream)
@@ -64,6 +70,9 @@ def time_pair(a, ctx, rec, stride, n, chans, dtype_ep, epochs):
            for k, v in ms.items()}
     if "packed" in out:
         out["packed_over_int8"] = round(out["packed"]["median"] / out["int8"]["median"], 4)
+    if "int16" in out:
+        assert last["int16"].tobytes() == last["int8"].tobytes(), "int16 differs from int8"
+        out["int16_over_int8"] = round(out["int16"]["median"] / out["int8"]["median"], 4)
     out.update(channels=C, epochs=epochs)
     return out
 
@@ -112,12 +121,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--int8-only", action="store_true")
+    ap.add_argument("--int16", action="store_true", help="time int16 records as well")
     a = ap.parse_args()
     if gc.device_count() < 1:
         raise SystemExit("ftrack_packed_time: no HIP device visible")
     run = {"sgt_bench": lambda: sgt_bench(a, 256), "sgt_config4": lambda: sgt_bench(a, 1),
            "e1t": lambda: e1t(a), "l3t": lambda: l3t(a)}
-    out = {"lib": os.path.realpath(gc.LIB_PATH), "int8_only": a.int8_only}
+    formats = ["int8"] + ([] if a.int8_only else ["packed"]) + (["int16"] if a.int16 else [])
+    out = {"lib": os.path.realpath(gc.LIB_PATH), "formats": formats}
     for s in a.shapes.split(","):
         out[s] = run[s]()
     print(json.dumps(out))
