@@ -620,6 +620,9 @@ struct gnsscorr_sdr_acq_ctx {
   // per-record persistent baseband_rows store (kStoreRows x 2048 CPX)
   uint32_t *d_wipe10 = nullptr, *d_dft = nullptr, *d_store = nullptr;
   size_t store_rec = 0;
+  // what the read-back calls may copy: the (magnitude, index) pairs the last
+  // search wrote to d_rows, and the records the last strong search left in d_X
+  size_t rows_held = 0, x_rec = 0;
 };
 
 extern "C" int gnsscorr_sdr_acq_destroy(gnsscorr_sdr_acq_ctx* c) {
@@ -743,6 +746,7 @@ extern "C" int gnsscorr_sdr_acq_strong_dev(gnsscorr_sdr_acq_ctx* c, const int16_
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->cfg.device));
   const int lmin = doppmin / 1000, n_rows = 4 * (doppmax / 1000 - lmin);
+  c->rows_held = c->x_rec = 0;   // a failed growth leaves nothing to read back
   rc = hostctx::grow(c->d_X, (size_t)n_rec * 4 * kN);
   if (!rc) rc = hostctx::grow(c->d_rows, (size_t)n_rec * n_sv * n_rows);
   if (rc) return rc;
@@ -755,6 +759,8 @@ extern "C" int gnsscorr_sdr_acq_strong_dev(gnsscorr_sdr_acq_ctx* c, const int16_
   hipLaunchKernelGGL(sdr_select_kernel, dim3(G), dim3(64), 0, c->stream, c->d_rows.p,
                      d_svs, n_sv, n_rec, lmin, n_rows, d_res);
   HIP_TRY(hipGetLastError());
+  c->rows_held = (size_t)n_rec * n_sv * n_rows;
+  c->x_rec = (size_t)n_rec;
   return GNSSCORR_OK;
 }
 
@@ -863,6 +869,7 @@ extern "C" int gnsscorr_sdr_acq_search_dev(gnsscorr_sdr_acq_ctx* c, int type, in
     return GNSSCORR_EINVAL;
   }
   HIP_TRY(hipSetDevice(c->cfg.device));
+  c->rows_held = 0;   // a failed growth leaves nothing to read back
   int rc = hostctx::grow(c->d_rows, (size_t)n_rec * n_sv * n_rows);
   if (rc) return rc;
   const dim3 grid(n_rec * n_sv * n_rows);
@@ -879,6 +886,7 @@ extern "C" int gnsscorr_sdr_acq_search_dev(gnsscorr_sdr_acq_ctx* c, int type, in
                      d_svs, n_sv, n_rec, lmin, n_rows, type == GNSSCORR_SDR_ACQ_WEAK ? 1 : 0,
                      d_res);
   HIP_TRY(hipGetLastError());
+  c->rows_held = (size_t)n_rec * n_sv * n_rows;
   return GNSSCORR_OK;
 }
 
@@ -908,4 +916,50 @@ extern "C" int gnsscorr_sdr_acq_acquire(gnsscorr_sdr_acq_ctx* c, int type, const
     rc = gnsscorr_sdr_acq_search_dev(c, type, n_rec, n_sv, st.svs.p, doppmin, doppmax, st.res.p);
   if (rc) return rc;
   return st.download(c, h_res);
+}
+
+// ============================================================================
+// read-back of what the last calls left on the device (tests and diagnosis;
+// host code only, nothing is launched)
+// ============================================================================
+extern "C" int gnsscorr_sdr_acq_read_rows(gnsscorr_sdr_acq_ctx* c, int32_t* h_out, size_t n_pairs) {
+  if (!c || !h_out) return GNSSCORR_EINVAL;
+  if (n_pairs < 1 || n_pairs > c->rows_held) {
+    gnsscorr_set_error("gnsscorr_sdr_acq_read_rows: %zu pairs asked, the last search left %zu "
+                       "(none before the first search)", n_pairs, c->rows_held);
+    return GNSSCORR_EINVAL;
+  }
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  static_assert(sizeof(int2) == 2 * sizeof(int32_t), "pair layout");
+  HIP_TRY(hipMemcpy(h_out, c->d_rows.p, sizeof(int2) * n_pairs, hipMemcpyDeviceToHost));
+  return GNSSCORR_OK;
+}
+
+extern "C" int gnsscorr_sdr_acq_read_spectra(gnsscorr_sdr_acq_ctx* c, int type, int rec, int row0,
+                                             int n_rows, int16_t* h_out) {
+  if (!c || !h_out) return GNSSCORR_EINVAL;
+  const bool strong = type == GNSSCORR_SDR_ACQ_STRONG;
+  if (prep_ms(type) == 0) {
+    gnsscorr_set_error("gnsscorr_sdr_acq_read_spectra: type must be STRONG (0), MEDIUM (1) or "
+                       "WEAK (2)");
+    return GNSSCORR_EINVAL;
+  }
+  const size_t held = strong ? c->x_rec : c->store_rec;
+  const int per = strong ? 4 : kStoreRows;
+  if (rec < 0 || (size_t)rec >= held) {
+    gnsscorr_set_error("gnsscorr_sdr_acq_read_spectra: record %d, but %zu held (%s)", rec, held,
+                       strong ? "by the last strong search" : "in the row store");
+    return GNSSCORR_EINVAL;
+  }
+  if (row0 < 0 || n_rows < 1 || row0 > per - n_rows) {
+    gnsscorr_set_error("gnsscorr_sdr_acq_read_spectra: rows %d..+%d outside 0..%d", row0, n_rows,
+                       per - 1);
+    return GNSSCORR_EINVAL;
+  }
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const uint32_t* src = (strong ? c->d_X.p : c->d_store) + ((size_t)rec * per + row0) * kN;
+  HIP_TRY(hipMemcpy(h_out, src, sizeof(uint32_t) * (size_t)n_rows * kN, hipMemcpyDeviceToHost));
+  return GNSSCORR_OK;
 }

@@ -292,6 +292,8 @@ def _sig_table():
         "gnsscorr_sdr_track_dev": (I, [P, P, I, I, I, P, P, P, P, P, P, I, P, P, P, I, P]),
         "gnsscorr_sdr_acq_search_dev": (I, [P, I, I, I, P, I, I, P]),
         "gnsscorr_sdr_acq_acquire": (I, [P, I, P, I, I, P, I, I, P]),
+        "gnsscorr_sdr_acq_read_rows": (I, [P, P, C.c_size_t]),
+        "gnsscorr_sdr_acq_read_spectra": (I, [P, I, I, I, I, P]),
         **_ctx_sig("gnsscorr_sdr_corr", C.POINTER(SdrCorrCfg)),
         "gnsscorr_sdr_init_chan": (I, [P, I, I, I, D]),
         "gnsscorr_sdr_accum_dev": (I, [P, P, I, P, P]),
@@ -1136,6 +1138,23 @@ class SdrAcqCtx(_Handle):
     def strong_dev(self, d_buff, n_rec, n_sv, d_svs, d_res, doppmin=-15000, doppmax=15000):
         _check(lib().gnsscorr_sdr_acq_strong_dev(self.h, d_buff, n_rec, n_sv, d_svs, doppmin,
                                                  doppmax, d_res), "gnsscorr_sdr_acq_strong_dev")
+
+    def read_rows(self, n_rec, n_sv, n_rows) -> np.ndarray:
+        """The last search's per-row (magnitude, index) table, int32
+        [n_rec, n_sv, n_rows, 2]; the three counts are that search's."""
+        out = np.zeros((n_rec, n_sv, n_rows, 2), np.int32)
+        _check(lib().gnsscorr_sdr_acq_read_rows(self.h, _ptr(out), n_rec * n_sv * n_rows),
+               "gnsscorr_sdr_acq_read_rows")
+        return out
+
+    def read_spectra(self, acq_type, rec, row0, n_rows) -> np.ndarray:
+        """Prepared spectra, int16 [n_rows, 2048, 2]: rows of the last strong
+        search's four (SDR_ACQ_STRONG) or of the persistent 1240-row store
+        (SDR_ACQ_MEDIUM / SDR_ACQ_WEAK) of record rec, as last written."""
+        out = np.zeros((max(int(n_rows), 1), 2048, 2), np.int16)
+        _check(lib().gnsscorr_sdr_acq_read_spectra(self.h, acq_type, rec, row0, n_rows,
+                                                   _ptr(out)), "gnsscorr_sdr_acq_read_spectra")
+        return out
 
 
 class OsgLoopCfg(C.Structure):

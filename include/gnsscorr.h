@@ -985,6 +985,31 @@ int gnsscorr_sdr_acq_search_dev(gnsscorr_sdr_acq_ctx *ctx, int type, int n_rec, 
 int gnsscorr_sdr_acq_acquire(gnsscorr_sdr_acq_ctx *ctx, int type, const int16_t *h_buff,
                              int n_rec, int n_sv, const int32_t *h_svs, int doppmin, int doppmax,
                              gnsscorr_sdr_acq_result *h_res);
+/* ---- read-back of what the searches leave on the device, for tests and
+ * diagnosis (the int16 counterpart of gnsscorr_acq_power_row).  Both wait for
+ * the context's stream and then copy; nothing is launched.  The contents are
+ * those of the LAST call that wrote the buffer: a later search or prep on the
+ * context replaces them.
+ *
+ * gnsscorr_sdr_acq_read_rows: the first n_pairs entries of the per-row table
+ * of the last strong / medium / weak search, h_out[2*e] = magnitude,
+ * h_out[2*e + 1] = index of the row's first strict maximum ((0, 0) when no
+ * cell is above 0), e = (rec*n_sv + s)*n_rows + row with that search's n_sv
+ * and n_rows, row as in gnsscorr_sdr_acq_result.row.  Strong: index = argmax
+ * over the 2048 delays (code_phase = 2048 - index); medium / weak: index =
+ * j*2048 + column over the 10 post-correlation DFT rows j.  GNSSCORR_EINVAL
+ * when n_pairs is 0 or more than n_rec*n_sv*n_rows of the last search, or
+ * before any search. */
+int gnsscorr_sdr_acq_read_rows(gnsscorr_sdr_acq_ctx *ctx, int32_t *h_out, size_t n_pairs);
+/* gnsscorr_sdr_acq_read_spectra: n_rows prepared spectra of record rec from
+ * row row0, each 2048 (I, Q) int16 pairs in natural order.  type STRONG: the
+ * four doPrepIF rows of the last strong search (row = 250 Hz sub-bin, 0..3,
+ * rec below that search's n_rec).  type MEDIUM or WEAK: the persistent row
+ * store (rows 0..1239, rec below the records it holds), whatever prep wrote
+ * each row last.  GNSSCORR_EINVAL for another type, a record not held (any
+ * record before the first strong search / prep) or rows outside the range. */
+int gnsscorr_sdr_acq_read_spectra(gnsscorr_sdr_acq_ctx *ctx, int type, int rec, int row0,
+                                  int n_rows, int16_t *h_out);
 int gnsscorr_sdr_acq_sync(gnsscorr_sdr_acq_ctx *ctx);
 void *gnsscorr_sdr_acq_stream(gnsscorr_sdr_acq_ctx *ctx);
 

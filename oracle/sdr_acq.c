@@ -19,6 +19,8 @@
  *                      into the persistent baseband_rows store (1240 rows)
  *   sdro_acq_medium    Acquisition::doAcqMedium, acquisition.cpp:309-425
  *   sdro_acq_weak      Acquisition::doAcqWeak, acquisition.cpp:433-570
+ *   sdro_acq_*_rows    the (magnitude, index) of x86_max for every row of the three
+ *                      searches, in the reference's loop order (test read-out)
  *
  * Parity pinned: tests/test_oracle_sdr.py checks every function against the
  * reference primitives compiled from their own sources with -DNO_SIMD
@@ -139,25 +141,41 @@ void sdro_prep_if(const sdro_cpx *buff, double fif, int saturate, sdro_cpx rows[
   for (int j = 0; j < 4; j++) sdro_fft(rows[j], SDRO_N, w, r1);
 }
 
+static const int32_t k_r2[16] = {0, 0, 0, 0, 0, 0, 0, 1, 0, 1, 0, 1, 1, 1, 1, 1};
+
+/* one (lcv, lcv2) row of doAcqStrong (acquisition.cpp:262-283): the correlation ... */
+static void strong_corr(sdro_cpx rows[4][SDRO_N], const sdro_cpx *code, int lcv, int lcv2,
+                        int saturate, const sdro_mix *iw, sdro_cpx *buf)
+{
+  sdro_cpx sh[SDRO_N];
+  /* baseband_rows[lcv2][100 + lcv]: the row read circularly from offset lcv */
+  for (int k = 0; k < SDRO_N; k++) sh[k] = rows[lcv2][(k + lcv + SDRO_N) & (SDRO_N - 1)];
+  sdro_cmulsc(sh, code, buf, SDRO_N, 10, saturate);
+  sdro_fft(buf, SDRO_N, iw, k_r2);
+}
+
+/* ... and its x86_cmag + x86_max */
+static void strong_row(sdro_cpx rows[4][SDRO_N], const sdro_cpx *code, int lcv, int lcv2,
+                       int saturate, const sdro_mix *iw, int32_t *idx, int32_t *m)
+{
+  sdro_cpx buf[SDRO_N];
+  strong_corr(rows, code, lcv, lcv2, saturate, iw, buf);
+  sdro_cmag_max(buf, SDRO_N, idx, m);
+}
+
 sdro_result sdro_acq_strong(sdro_cpx rows[4][SDRO_N], const sdro_cpx *code, int sv, int doppmin,
                             int doppmax, int saturate)
 {
-  static const int32_t r2[16] = {0, 0, 0, 0, 0, 0, 0, 1, 0, 1, 0, 1, 1, 1, 1, 1};
   sdro_mix w[SDRO_N / 2], iw[SDRO_N / 2];
   sdro_twiddles(SDRO_N, w, iw);
   sdro_result r;
   memset(&r, 0, sizeof r);
   r.sv = sv;
   int32_t mag = 0;
-  sdro_cpx sh[SDRO_N], buf[SDRO_N];
   for (int lcv = doppmin / 1000; lcv < doppmax / 1000; lcv++)
     for (int lcv2 = 0; lcv2 < 4; lcv2++) {
-      /* baseband_rows[lcv2][100 + lcv]: the row read circularly from offset lcv */
-      for (int k = 0; k < SDRO_N; k++) sh[k] = rows[lcv2][(k + lcv + SDRO_N) & (SDRO_N - 1)];
-      sdro_cmulsc(sh, code, buf, SDRO_N, 10, saturate);
-      sdro_fft(buf, SDRO_N, iw, r2);
       int32_t idx, m;
-      sdro_cmag_max(buf, SDRO_N, &idx, &m);
+      strong_row(rows, code, lcv, lcv2, saturate, iw, &idx, &m);
       if (m > mag) {
         mag = m;
         r.code_phase = SDRO_N - idx;
@@ -168,6 +186,18 @@ sdro_result sdro_acq_strong(sdro_cpx rows[4][SDRO_N], const sdro_cpx *code, int 
     }
   r.success = r.magnitude > 0;   /* THRESH_STRONG = 0 (config.h:72) */
   return r;
+}
+
+int sdro_acq_strong_rows(sdro_cpx rows[4][SDRO_N], const sdro_cpx *code, int doppmin, int doppmax,
+                         int saturate, int32_t *out)
+{
+  sdro_mix w[SDRO_N / 2], iw[SDRO_N / 2];
+  sdro_twiddles(SDRO_N, w, iw);
+  int n = 0;
+  for (int lcv = doppmin / 1000; lcv < doppmax / 1000; lcv++)
+    for (int lcv2 = 0; lcv2 < 4; lcv2++, n++)
+      strong_row(rows, code, lcv, lcv2, saturate, iw, &out[2 * n + 1], &out[2 * n]);
+  return n;
 }
 
 /* ---- medium / weak acquisition ------------------------------------------ */
@@ -247,24 +277,58 @@ static void max_first(const int32_t *a, int n, int32_t *index, int32_t *mag)
 static void coherent_10(const sdro_cpx *rows, int row0, int lcv, const sdro_cpx *code, int shift,
                         int saturate, const sdro_mix *iw, sdro_cpx *coh)
 {
-  static const int32_t r2[16] = {0, 0, 0, 0, 0, 0, 0, 1, 0, 1, 0, 1, 1, 1, 1, 1};
   sdro_cpx sh[SDRO_N];
   for (int m = 0; m < 10; m++) {
     const sdro_cpx *row = rows + (size_t)(row0 + m) * SDRO_N;
     for (int k = 0; k < SDRO_N; k++) sh[k] = row[(k + lcv + SDRO_N) & (SDRO_N - 1)];
     sdro_cmulsc(sh, code, coh + (size_t)m * SDRO_N, SDRO_N, shift, saturate);
-    sdro_fft(coh + (size_t)m * SDRO_N, SDRO_N, iw, r2);
+    sdro_fft(coh + (size_t)m * SDRO_N, SDRO_N, iw, k_r2);
   }
+}
+
+/* the tables and scratch one medium / weak search uses */
+typedef struct {
+  sdro_mix iw[SDRO_N / 2], dft[10][10];
+  sdro_cpx *coh;      /* 10 x 2048 coherent 1-ms correlations */
+  uint32_t *power;    /* 10 x 2048 powers, [dft row][delay column] */
+} mw_work;
+
+static void mw_open(mw_work *t)
+{
+  sdro_mix w[SDRO_N / 2];
+  sdro_twiddles(SDRO_N, w, t->iw);
+  for (int j = 0; j < 10; j++) sdro_wipeoff_gen(t->dft[j], (float)j * 25.0 - 112.5, 1000.0, 10);
+  t->coh = (sdro_cpx *)malloc(sizeof(sdro_cpx) * 10 * SDRO_N);
+  t->power = (uint32_t *)malloc(sizeof(uint32_t) * 10 * SDRO_N);
+}
+
+static void mw_close(mw_work *t)
+{
+  free(t->coh);
+  free(t->power);
+}
+
+/* one (lcv, lcv2) row of doAcqMedium (acquisition.cpp:326-395) */
+static void medium_row(const sdro_cpx *rows, const sdro_cpx *code, int lcv, int lcv2, int saturate,
+                       mw_work *t, int32_t *idx, int32_t *m)
+{
+  /* baseband_rows[lcv2*20 + lcv3 + k*10] with k = 0 (:341): a 20-row stride
+   * over a 10-ms prep, so lcv2 = 1 reads the 500 Hz rows and lcv2 >= 2 reads
+   * rows 40..79, which this prep did not write */
+  coherent_10(rows, lcv2 * 20, lcv, code, 10, saturate, t->iw, t->coh);
+  int32_t pw[10];
+  for (int c = 0; c < SDRO_N; c++) {
+    post_dft(t->coh, c, t->dft, pw);
+    for (int j = 0; j < 10; j++) t->power[j * SDRO_N + c] = (uint32_t)pw[j];
+  }
+  max_first((const int32_t *)t->power, 10 * SDRO_N, idx, m);
 }
 
 sdro_result sdro_acq_medium(const sdro_cpx *rows, const sdro_cpx *code, int sv, int doppmin,
                             int doppmax, int saturate)
 {
-  sdro_mix w[SDRO_N / 2], iw[SDRO_N / 2], dft[10][10];
-  sdro_twiddles(SDRO_N, w, iw);
-  for (int j = 0; j < 10; j++) sdro_wipeoff_gen(dft[j], (float)j * 25.0 - 112.5, 1000.0, 10);
-  sdro_cpx *coh = (sdro_cpx *)malloc(sizeof(sdro_cpx) * 10 * SDRO_N);
-  int32_t *power = (int32_t *)malloc(sizeof(int32_t) * 10 * SDRO_N);
+  mw_work t;
+  mw_open(&t);
   sdro_result r;
   memset(&r, 0, sizeof r);
   r.sv = sv;
@@ -272,17 +336,8 @@ sdro_result sdro_acq_medium(const sdro_cpx *rows, const sdro_cpx *code, int sv, 
   const int lmin = doppmin / 1000;
   for (int lcv = lmin; lcv <= doppmax / 1000; lcv++)      /* inclusive, :324 */
     for (int lcv2 = 0; lcv2 < 4; lcv2++) {
-      /* baseband_rows[lcv2*20 + lcv3 + k*10] with k = 0 (:341): a 20-row stride
-       * over a 10-ms prep, so lcv2 = 1 reads the 500 Hz rows and lcv2 >= 2 reads
-       * rows 40..79, which this prep did not write */
-      coherent_10(rows, lcv2 * 20, lcv, code, 10, saturate, iw, coh);
-      int32_t pw[10];
-      for (int c = 0; c < SDRO_N; c++) {
-        post_dft(coh, c, dft, pw);
-        for (int j = 0; j < 10; j++) power[j * SDRO_N + c] = pw[j];
-      }
       int32_t idx, m;
-      max_first(power, 10 * SDRO_N, &idx, &m);
+      medium_row(rows, code, lcv, lcv2, saturate, &t, &idx, &m);
       if (m > mag) {
         mag = m;
         r.code_phase = idx % SDRO_N;
@@ -292,9 +347,21 @@ sdro_result sdro_acq_medium(const sdro_cpx *rows, const sdro_cpx *code, int sv, 
       }
     }
   r.success = r.magnitude > 0;   /* THRESH_MEDIUM = 0 (config.h:73) */
-  free(coh);
-  free(power);
+  mw_close(&t);
   return r;
+}
+
+int sdro_acq_medium_rows(const sdro_cpx *rows, const sdro_cpx *code, int doppmin, int doppmax,
+                         int saturate, int32_t *out)
+{
+  mw_work t;
+  mw_open(&t);
+  int n = 0;
+  for (int lcv = doppmin / 1000; lcv <= doppmax / 1000; lcv++)
+    for (int lcv2 = 0; lcv2 < 4; lcv2++, n++)
+      medium_row(rows, code, lcv, lcv2, saturate, &t, &out[2 * n + 1], &out[2 * n]);
+  mw_close(&t);
+  return n;
 }
 
 int sdro_weak_shift(int i, int lcv, int lcv2)
@@ -305,14 +372,30 @@ int sdro_weak_shift(int i, int lcv, int lcv2)
   return (int)floor(code_doppler);
 }
 
+/* one (lcv, lcv2, k) row of doAcqWeak (acquisition.cpp:458-541): 15 coherent
+ * 10-ms powers summed at the code-Doppler-shifted column */
+static void weak_row(const sdro_cpx *rows, const sdro_cpx *code, int lcv, int lcv2, int k,
+                     int saturate, mw_work *t, int32_t *idx, int32_t *m)
+{
+  memset(t->power, 0, sizeof(uint32_t) * 10 * SDRO_N);
+  for (int i = 0; i < 15; i++) {
+    coherent_10(rows, lcv2 * 310 + i * 20 + k * 10, lcv, code, 9, saturate, t->iw, t->coh);
+    const int shift = sdro_weak_shift(i, lcv, lcv2);
+    int32_t pw[10];
+    for (int c = 0; c < SDRO_N; c++) {
+      post_dft(t->coh, c, t->dft, pw);
+      const int dst = (c + shift + SDRO_N) % SDRO_N;
+      for (int j = 0; j < 10; j++) t->power[j * SDRO_N + dst] += (uint32_t)pw[j];
+    }
+  }
+  max_first((const int32_t *)t->power, 10 * SDRO_N, idx, m);
+}
+
 sdro_result sdro_acq_weak(const sdro_cpx *rows, const sdro_cpx *code, int sv, int doppmin,
                           int doppmax, int saturate)
 {
-  sdro_mix w[SDRO_N / 2], iw[SDRO_N / 2], dft[10][10];
-  sdro_twiddles(SDRO_N, w, iw);
-  for (int j = 0; j < 10; j++) sdro_wipeoff_gen(dft[j], (float)j * 25.0 - 112.5, 1000.0, 10);
-  sdro_cpx *coh = (sdro_cpx *)malloc(sizeof(sdro_cpx) * 10 * SDRO_N);
-  uint32_t *power = (uint32_t *)malloc(sizeof(uint32_t) * 10 * SDRO_N);
+  mw_work t;
+  mw_open(&t);
   sdro_result r;
   memset(&r, 0, sizeof r);
   r.sv = sv;
@@ -321,19 +404,8 @@ sdro_result sdro_acq_weak(const sdro_cpx *rows, const sdro_cpx *code, int sv, in
   for (int lcv = lmin; lcv < doppmax / 1000; lcv++)       /* exclusive, :452 */
     for (int lcv2 = 0; lcv2 < 4; lcv2++)
       for (int k = 0; k < 2; k++) {
-        memset(power, 0, sizeof(uint32_t) * 10 * SDRO_N);
-        for (int i = 0; i < 15; i++) {
-          coherent_10(rows, lcv2 * 310 + i * 20 + k * 10, lcv, code, 9, saturate, iw, coh);
-          const int shift = sdro_weak_shift(i, lcv, lcv2);
-          int32_t pw[10];
-          for (int c = 0; c < SDRO_N; c++) {
-            post_dft(coh, c, dft, pw);
-            const int dst = (c + shift + SDRO_N) % SDRO_N;
-            for (int j = 0; j < 10; j++) power[j * SDRO_N + dst] += (uint32_t)pw[j];
-          }
-        }
         int32_t idx, m;
-        max_first((const int32_t *)power, 10 * SDRO_N, &idx, &m);
+        weak_row(rows, code, lcv, lcv2, k, saturate, &t, &idx, &m);
         if (m > mag) {
           mag = m;
           r.code_phase = idx % SDRO_N;
@@ -343,9 +415,44 @@ sdro_result sdro_acq_weak(const sdro_cpx *rows, const sdro_cpx *code, int sv, in
         }
       }
   r.success = r.magnitude > 0;   /* THRESH_WEAK = 0 (config.h:74) */
-  free(coh);
-  free(power);
+  mw_close(&t);
   return r;
+}
+
+int sdro_acq_weak_rows(const sdro_cpx *rows, const sdro_cpx *code, int doppmin, int doppmax,
+                       int saturate, int32_t *out)
+{
+  mw_work t;
+  mw_open(&t);
+  int n = 0;
+  for (int lcv = doppmin / 1000; lcv < doppmax / 1000; lcv++)
+    for (int lcv2 = 0; lcv2 < 4; lcv2++)
+      for (int k = 0; k < 2; k++, n++)
+        weak_row(rows, code, lcv, lcv2, k, saturate, &t, &out[2 * n + 1], &out[2 * n]);
+  mw_close(&t);
+  return n;
+}
+
+int sdro_acq_row_powers(int kind, const sdro_cpx *rows, const sdro_cpx *code, int lcv, int lcv2,
+                        int k, int saturate, int32_t *power)
+{
+  int32_t idx, m;
+  if (kind == 0) {
+    sdro_mix w[SDRO_N / 2], iw[SDRO_N / 2];
+    sdro_cpx buf[SDRO_N];
+    sdro_twiddles(SDRO_N, w, iw);
+    strong_corr((sdro_cpx(*)[SDRO_N])rows, code, lcv, lcv2, saturate, iw, buf);
+    for (int c = 0; c < SDRO_N; c++)
+      power[c] = (int32_t)((uint32_t)(buf[c].i * buf[c].i) + (uint32_t)(buf[c].q * buf[c].q));
+    return SDRO_N;
+  }
+  mw_work t;
+  mw_open(&t);
+  if (kind == 1) medium_row(rows, code, lcv, lcv2, saturate, &t, &idx, &m);
+  else weak_row(rows, code, lcv, lcv2, k, saturate, &t, &idx, &m);
+  memcpy(power, t.power, sizeof(int32_t) * 10 * SDRO_N);
+  mw_close(&t);
+  return 10 * SDRO_N;
 }
 
 /* ---- PRN_Codes (gen_fft_codes.m with prn_gen.m) ------------------------ */

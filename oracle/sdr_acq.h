@@ -38,4 +38,20 @@ sdro_result sdro_acq_medium(const sdro_cpx *rows, const sdro_cpx *code, int sv, 
                             int doppmax, int saturate);
 sdro_result sdro_acq_weak(const sdro_cpx *rows, const sdro_cpx *code, int sv, int doppmin,
                           int doppmax, int saturate);
+/* Every row of the three searches in the reference's loop order: out[2*row] =
+ * magnitude, out[2*row + 1] = index of x86_max (the row's first strict maximum
+ * above 0; (0, 0) if none).  Strong: index = argmax over the 2048 delays;
+ * medium / weak: j*2048 + column over the 10 x 2048 powers.  Returns the row
+ * count: 4 (lmax - lmin), 4 (lmax - lmin + 1), 8 (lmax - lmin). */
+int sdro_acq_strong_rows(sdro_cpx rows[4][SDRO_N], const sdro_cpx *code, int doppmin, int doppmax,
+                         int saturate, int32_t *out);
+int sdro_acq_medium_rows(const sdro_cpx *rows, const sdro_cpx *code, int doppmin, int doppmax,
+                         int saturate, int32_t *out);
+int sdro_acq_weak_rows(const sdro_cpx *rows, const sdro_cpx *code, int doppmin, int doppmax,
+                       int saturate, int32_t *out);
+/* Every cell of one row, before its x86_max: kind 0 strong (rows = the four
+ * prep_if spectra, 2048 powers), 1 medium, 2 weak (rows = the store, 10 x 2048
+ * powers [j][column]; k only for weak).  Returns the cell count. */
+int sdro_acq_row_powers(int kind, const sdro_cpx *rows, const sdro_cpx *code, int lcv, int lcv2,
+                        int k, int saturate, int32_t *power);
 #endif

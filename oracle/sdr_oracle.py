@@ -57,6 +57,11 @@ class OracleSDR:
         L.sdro_acq_weak.restype = _Res
         L.sdro_weak_shift.argtypes = [I, I, I]
         L.sdro_weak_shift.restype = I
+        for fn in (L.sdro_acq_strong_rows, L.sdro_acq_medium_rows, L.sdro_acq_weak_rows):
+            fn.argtypes = [P, P, I, I, I, P]
+            fn.restype = I
+        L.sdro_acq_row_powers.argtypes = [I, P, P, I, I, I, I, P]
+        L.sdro_acq_row_powers.restype = I
         L.orc_gn3s_block.argtypes = [P, P, C.c_uint32, P, P]
         L.orc_downsample.argtypes = [P, P, D, D, I]
         L.orc_downsample.restype = I
@@ -151,6 +156,77 @@ class OracleSDR:
 
     def weak_shift(self, i, lcv, lcv2):
         return self.L.sdro_weak_shift(i, lcv, lcv2)
+
+    # -- every row's (magnitude, index), [n_sv, n_rows, 2] int32, reference loop order
+    def strong_rows(self, rows4, codes, svs, doppmin=-15000, doppmax=15000, saturate=False):
+        """rows4: prep_if's four spectra."""
+        rows4 = np.ascontiguousarray(rows4, np.int16)
+        out = np.zeros((len(svs), n_rows("strong", doppmin, doppmax), 2), np.int32)
+        for k, sv in enumerate(svs):
+            code = np.ascontiguousarray(codes[sv], np.int16)
+            n = self.L.sdro_acq_strong_rows(_p(rows4), _p(code), doppmin, doppmax, int(saturate),
+                                            _p(out[k]))
+            assert n == out.shape[1]
+        return out
+
+    def search_rows(self, kind, rows, codes, svs, doppmin=-15000, doppmax=15000, saturate=False):
+        """rows: the 1240-row store (new_rows / prep_rows)."""
+        fn = self.L.sdro_acq_medium_rows if kind == "medium" else self.L.sdro_acq_weak_rows
+        out = np.zeros((len(svs), n_rows(kind, doppmin, doppmax), 2), np.int32)
+        for k, sv in enumerate(svs):
+            code = np.ascontiguousarray(codes[sv], np.int16)
+            n = fn(_p(rows), _p(code), doppmin, doppmax, int(saturate), _p(out[k]))
+            assert n == out.shape[1]
+        return out
+
+    def row_powers(self, kind, rows, code, lcv, lcv2, k=0, saturate=False):
+        """All cells of one row before its maximum: int32 [2048] (strong, rows =
+        prep_if's four) or [10, 2048] (medium / weak, rows = the store)."""
+        rows = np.ascontiguousarray(rows, np.int16)
+        code = np.ascontiguousarray(code, np.int16)
+        out = np.zeros(N if kind == "strong" else 10 * N, np.int32)
+        n = self.L.sdro_acq_row_powers(("strong", "medium", "weak").index(kind), _p(rows),
+                                       _p(code), lcv, lcv2, k, int(saturate), _p(out))
+        assert n == out.size
+        return out if kind == "strong" else out.reshape(10, N)
+
+
+def _trunc_khz(d):
+    return int(d / 1000)          # C truncation toward zero, as the reference's doppmin/1000
+
+
+def n_rows(kind, doppmin, doppmax):
+    """Rows of one search: lcv in [lmin, lmax) x 4 (strong), [lmin, lmax] x 4
+    (medium, acquisition.cpp:324), [lmin, lmax) x 4 x 2 (weak, :452)."""
+    lo, hi = _trunc_khz(doppmin), _trunc_khz(doppmax)
+    return {"strong": 4 * (hi - lo), "medium": 4 * (hi - lo + 1), "weak": 8 * (hi - lo)}[kind]
+
+
+def scan_rows(kind, table, svs, doppmin):
+    """The reference's scan over a [..., n_sv, n_rows, 2] (magnitude, index)
+    table: rows in order, strict '>' from 0 (acquisition.cpp:285, :397, :543),
+    so the first row holding the maximum wins.  Returns RESULT [..., n_sv]."""
+    table = np.asarray(table)
+    lmin = _trunc_khz(doppmin)
+    out = np.zeros(table.shape[:-2], RESULT)
+    svs_b = np.broadcast_to(np.asarray(svs, np.int32), out.shape)
+    for at in np.ndindex(*out.shape):
+        mag, r = 0, dict(sv=int(svs_b[at]), code_phase=0, doppler=0, magnitude=0, row=0)
+        for row, (m, idx) in enumerate(table[at].tolist()):
+            if m > mag:
+                mag = m
+                if kind == "strong":
+                    lcv, lcv2 = lmin + row // 4, row % 4
+                    r.update(code_phase=N - idx, doppler=lcv * 1000 + lcv2 * 250)
+                else:
+                    q = row // 2 if kind == "weak" else row
+                    lcv, lcv2 = lmin + q // 4, q % 4
+                    r.update(code_phase=idx % N,
+                             doppler=lcv * 1000 + lcv2 * 250 + (idx // N) * 25)
+                r.update(magnitude=m, row=row)
+        out[at] = (r["sv"], r["code_phase"], r["doppler"], r["magnitude"],
+                   int(r["magnitude"] > 0), r["row"])
+    return out
 
 
 class _Res(C.Structure):
