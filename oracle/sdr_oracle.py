@@ -459,6 +459,21 @@ class RefSdrChannel:
                    ("reset_1ms", "<u4"), ("reset_20ms", "<u4"), ("set_z_count", "<u4"),
                    ("z_count", "<u4"), ("length", "<u4"), ("navigate", "<u4"), ("pad", "<u4")])
     SUB = np.dtype([("sv", "<i4"), ("subframe", "<i4"), ("word_buff", "<u4", (12,))])
+    # RefChanState of oracle/sdr_chan_ref.cpp
+    STATE = np.dtype([("carrier_nco", "<f8"), ("code_nco", "<f8"), ("len", "<i4"),
+                      ("count", "<i4"), ("state", "<i4"), ("sv", "<i4"), ("chan", "<i4"),
+                      ("I", "<i4", (3,)), ("Q", "<i4", (3,)), ("P", "<i4", (3,)),
+                      ("I_prev", "<i4"), ("Q_prev", "<i4"), ("I_avg", "<f4"), ("Q_var", "<f4"),
+                      ("P_avg", "<f4"), ("cn0", "<f4"), ("bit_lock", "<i4"),
+                      ("bit_lock_pend", "<i4"), ("bit_lock_ticks", "<i4"), ("I_sum20", "<i4"),
+                      ("Q_sum20", "<i4"), ("I_buff", "<i4", (20,)), ("Q_buff", "<i4", (20,)),
+                      ("P_buff", "<i4", (20,)), ("epoch_20ms", "<i4"), ("epoch_1ms", "<i4"),
+                      ("best_epoch", "<i4"), ("valid_frame", "<i4", (5,)), ("navigate", "<i4"),
+                      ("z_lock", "<i4"), ("converged", "<i4"), ("frame_z", "<i4"),
+                      ("z_count", "<i4"), ("z_count_pend", "<i4"), ("word_buff", "<u4", (12,)),
+                      ("frame_lock", "<i4"), ("frame_lock_pend", "<i4"), ("bit_number", "<i4"),
+                      ("subframe", "<i4"), ("freq_lock", "<i4"), ("freq_lock_ticks", "<i4"),
+                      ("pll", "<f4", (17,)), ("dll", "<f4", (7,)), ("_pad", "<u4")])
 
     def __init__(self, chan=0):
         L = C.CDLL(REF_CHAN_SO)
@@ -490,18 +505,23 @@ class RefSdrChannel:
         self.L.ref_chan_state(self.h, _p(out))
         return out
 
-    def run(self, corr):
+    def run(self, corr, trace=None):
         """Accum over corr (n_ms, 6) int32; returns (feedback FB[n_ms], subframes as
-        (ms, SUB record) pairs, final state bytes)."""
+        (ms, SUB record) pairs, final state bytes).  trace: a STATE[n_ms] array that
+        receives the object's state after every call."""
         corr = np.ascontiguousarray(corr, np.int32)
         fb = np.zeros(len(corr), self.FB)
         subs = []
         buf = np.zeros(64, self.SUB)
+        assert trace is None or (trace.dtype == self.STATE and len(trace) == len(corr) and
+                                 self.ssize == self.STATE.itemsize)
         for m in range(len(corr)):
             row = np.ascontiguousarray(corr[m])
             self.L.ref_chan_accum(self.h, _p(row), fb[m:m + 1].ctypes.data)
             n = self.L.ref_chan_read_subframes(_p(buf), 64)
             subs.extend((m, buf[k].copy()) for k in range(n))
+            if trace is not None:
+                self.L.ref_chan_state(self.h, trace[m:m + 1].ctypes.data)
         return fb, subs, self.state()
 
     def parity(self, word: int) -> bool:

@@ -123,3 +123,72 @@ SCENARIOS = [
     (11, 400, 20, 0, 3500.0, 700.0, 0.0, -1),     # started with 20-ms integration
     (20, 7000, 1, 19, 4000.0, 800.0, 0.1, 9000),  # fades: P_avg < 8e4 -> Kill
 ]
+
+
+# ---------------------------------------------------------------- branch streams
+def correlations_sched(n_ms: int, bits: np.ndarray, bit_offset_ms: int, sched, seed: int,
+                       q_bias: float = 0.0, el_frac: float = 0.5, sign: int = 1,
+                       slip=None) -> np.ndarray:
+    """correlations() with a piecewise (from_ms, amp, noise) schedule, a polarity
+    sign on the signal (-1: the Costas loop locked upside down) and one bit
+    boundary slip (ms, new_offset): from that ms on, bit k covers
+    [new_offset + 20k, new_offset + 20k + 20).  One segment, sign = 1 and no slip
+    give correlations()' rows bit for bit."""
+    rng = np.random.default_rng(seed)
+    ms = np.arange(n_ms)
+    off = np.full(n_ms, bit_offset_ms)
+    if slip is not None:
+        off[slip[0]:] = slip[1]
+    k = np.clip((ms - off) // 20, 0, len(bits) - 1)
+    amp, noise = np.empty(n_ms), np.empty(n_ms)
+    for m0, a, s in sched:
+        amp[m0:], noise[m0:] = a, s
+    s = (2.0 * bits[k].astype(np.float64) - 1.0) * amp * sign
+    out = np.empty((n_ms, 6), np.int64)
+    g = rng.standard_normal((n_ms, 6)) * noise[:, None]
+    out[:, 0] = np.rint(el_frac * s + g[:, 0])
+    out[:, 1] = np.rint(s + g[:, 1])
+    out[:, 2] = np.rint(el_frac * s + g[:, 2])
+    out[:, 3] = np.rint(q_bias * el_frac * s + g[:, 3])
+    out[:, 4] = np.rint(q_bias * s + g[:, 4])
+    out[:, 5] = np.rint(q_bias * el_frac * s + g[:, 5])
+    return out.astype(np.int32)
+
+
+BRANCH_MS = 32000
+_STRONG = [(0, 4000.0, 900.0)]
+# one stream per Channel branch that SCENARIOS leaves unreached; keys beyond
+# (name, sv, doppler): corr_len 1, offset 7, sched _STRONG, q_bias 0.02, sid0 1,
+# sign 1, flips (), slip None, data True unless given.  Bit 760 is d11 of word 6
+# of the third subframe.
+BRANCH_SCENARIOS = [
+    dict(name="upright", sv=2, doppler=1250),
+    dict(name="inverted", sv=2, doppler=1250, sign=-1),              # twin of "upright"
+    dict(name="wrap", sv=7, doppler=-2200, sid0=4),                  # subframe 5 -> 1
+    dict(name="parity", sv=9, doppler=3100, sid0=4, flips=(760,)),   # frame lock lost, found again
+    dict(name="slip", sv=14, doppler=-600, sid0=4, slip=(5000, 17)),  # bit lock lost, found again
+    dict(name="carrier", sv=17, doppler=500, data=False),            # never bit-locks: count > 30000
+    dict(name="qbias", sv=23, doppler=2000, q_bias=1.0),             # carrier NCO leaves the search band
+    dict(name="cn0", sv=28, doppler=-4100,                           # len 1 -> 20 -> 1
+         sched=[(0, 4000.0, 900.0), (8000, 1500.0, 1300.0), (18000, 4000.0, 900.0)]),
+]
+
+
+def branch_bits(sc) -> np.ndarray:
+    if not sc.get("data", True):
+        return np.ones(1, np.uint8)                                  # unmodulated carrier
+    bits = nav_bits(6, seed=sc["sv"] + 1, sid0=sc.get("sid0", 1))
+    for i in sc.get("flips", ()):
+        bits[i] ^= 1
+    return bits
+
+
+def branch_corr(sc, n_ms: int = BRANCH_MS) -> np.ndarray:
+    return correlations_sched(n_ms, branch_bits(sc), sc.get("offset", 7), sc.get("sched", _STRONG),
+                              seed=sc["sv"] + 100, q_bias=sc.get("q_bias", 0.02),
+                              sign=sc.get("sign", 1), slip=sc.get("slip"))
+
+
+def branch_start(sc) -> tuple:
+    """(sv, acq_doppler, corr_len) of Channel::Start."""
+    return sc["sv"], sc["doppler"], sc.get("corr_len", 1)

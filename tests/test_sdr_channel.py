@@ -56,6 +56,64 @@ def test_scenario_inputs_pinned():
         assert hashlib.sha256(corr.tobytes()).hexdigest() == str(g["corr_sha256"][k])
 
 
+def _branch_golden():
+    return np.load(os.path.join(GOLD, "sdr_channel_branches.npz"))
+
+
+def test_branch_inputs_pinned():
+    g = _branch_golden()
+    assert list(g["names"]) == [sc["name"] for sc in N.BRANCH_SCENARIOS]
+    for k, sc in enumerate(N.BRANCH_SCENARIOS):
+        corr = N.branch_corr(sc)
+        assert corr.shape == (int(g["n_ms"]), 6)
+        assert hashlib.sha256(corr.tobytes()).hexdigest() == str(g["corr_sha256"][k]), sc["name"]
+
+
+def test_sched_generator_equals_plain():
+    """One segment, upright, no slip: correlations_sched is correlations."""
+    bits = N.nav_bits(2, seed=9)
+    a = N.correlations(3000, bits, 13, 2600.0, 1300.0, seed=3, q_bias=-0.05)
+    b = N.correlations_sched(3000, bits, 13, [(0, 2600.0, 1300.0)], seed=3, q_bias=-0.05)
+    assert a.tobytes() == b.tobytes()
+
+
+def test_branch_golden_reaches_branches():
+    """The committed arrays themselves show each stream's defining event."""
+    import make_sdr_chan_branches_golden as B
+    g = _branch_golden()
+    rows, words = g["sub_rows"], g["sub_words"]
+    subs = [[(int(r[1]), int(r[3]), w) for r, w in zip(rows, words) if r[0] == k]
+            for k in range(len(N.BRANCH_SCENARIOS))]
+    e = int(g["nco_every"])
+    lens = g["snap_state"].view(S.RefSdrChannel.STATE)["len"].reshape(-1)
+    for k, sc in enumerate(N.BRANCH_SCENARIOS):
+        flags = g["flags"][k]
+        nco = np.repeat(g["nco"][k][:, 0], e)[:len(flags)]   # held between the stored calls
+        B.reach(sc["name"], flags, nco, subs[k], twin=(g["flags"][0], subs[0]), lens=lens)
+
+
+@need_ref
+def test_branch_golden_matches_reference_build():
+    """Re-run the reference on every branch stream: reach, decidability, and the
+    fixture's flags, final state and subframes."""
+    import make_sdr_chan_branches_golden as B
+    g = _branch_golden()
+    twin = None
+    for k, sc in enumerate(N.BRANCH_SCENARIOS):
+        corr, fb, subs, st, tr = B.run_reference(k, sc)
+        flags, snaps, _ = B.check_run(sc, fb, subs, tr, twin)
+        if sc["name"] == "upright":
+            twin = (flags, subs)
+        assert (flags == g["flags"][k]).all(), sc["name"]
+        assert st.tobytes() == g["state"][k].tobytes(), sc["name"]
+        rows = g["sub_rows"][g["sub_rows"][:, 0] == k]
+        assert [m for m, _, _ in subs] == list(rows[:, 1])
+        assert [s for _, s, _ in subs] == list(rows[:, 3])
+        if sc["name"] == "cn0":
+            assert list(snaps) == list(g["snap_calls"])
+            assert tr[snaps].tobytes() == g["snap_state"].tobytes()
+
+
 @need_ref
 def test_host_start_matches_reference(gc):
     ref = S.RefSdrChannel(3)
