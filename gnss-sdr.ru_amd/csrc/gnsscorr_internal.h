@@ -37,6 +37,12 @@ int gnsscorr_track_dev_isr(gnsscorr_track_ctx *ctx, const int8_t *d_if, int64_t 
                            gnsscorr_track_result *d_res, int n_loops,
                            const gnsscorr_osg_loop_cfg *cfg, gnsscorr_osg_loop *d_loops,
                            gnsscorr_osg_loop *d_loop_hist);
+/* nsamp and the IF alignment (gnsscorr.h, "IF alignment of the device calls") of
+ * every step of a request that runs one gnsscorr_track_dev call per step, step k
+ * at d_if + gnsscorr_track_if_bytes(k * nsamp).  Launches and changes nothing;
+ * GNSSCORR_EINVAL names the first refused step and its rule. */
+int gnsscorr_track_check_steps(const gnsscorr_track_ctx *ctx, const int8_t *d_if,
+                               int64_t stream_stride, int64_t nsamp, int n_steps);
 /* GPS-SDR tables (sdr_host.c): packed (i, q) int16 pairs, N = 2048 */
 void gnsscorr_sdr_twiddles(int16_t *w, int16_t *iw);
 void gnsscorr_sdr_code_gen(int sv, uint8_t *chips);

@@ -145,6 +145,10 @@ extern "C" int gnsscorr_osg_closed_loop_dev(gnsscorr_track_ctx* ctx,
                                           d_res_hist, n_ch, cfg, d_loops, d_loop_hist);
     if (rf != GNSSCORR_TRACK_NOT_FUSED) return rf;
   }
+  // all or nothing: a call whose IF starts misaligned (nsamp not a whole number of
+  // aligned units) is refused before the first launch, not after k calls have moved
+  // the channel state, the loops, the commands and the TIC counter
+  if (int rc = gnsscorr_track_check_steps(ctx, d_if, stream_stride, nsamp, n_calls)) return rc;
   for (int k = 0; k < n_calls; k++) {
     gnsscorr_track_result* r = d_res_hist + (size_t)k * n_ch;
     const int64_t tic = gnsscorr_track_next_tic(ctx, nsamp);

@@ -1395,6 +1395,54 @@ extern "C" int64_t gnsscorr_track_next_tic(gnsscorr_track_ctx* c, int64_t nsamp)
   return -1;
 }
 
+// nsamp and the IF alignment of one call (gnsscorr.h, "IF alignment of the
+// device calls"); launches nothing and changes nothing.  step: the call's index
+// in a multi-step request, named in the error text (-1: a single call).
+//   IQ int8      16-byte base and stream stride (LDS-DMA chunks of 16 bytes)
+//   IQ packed    8-byte base and stream stride (packed runs are read in 8-byte words)
+//   I-only int8  16-byte base and stream stride (osg_track_kernel's int4 loads)
+//   I-only packed any base, whole-byte stream stride (osg_track_kernel<true>
+//                reads its runs byte by byte, and a run starts on a multiple of
+//                64 elements of its stream)
+static int check_call(const gnsscorr_track_ctx* c, const int8_t* d_if, int64_t stride,
+                      int64_t nsamp, int step) {
+  if (nsamp < 1 || nsamp > c->cfg.max_nsamp) {
+    gnsscorr_set_error("nsamp %lld outside [1, max_nsamp=%d]", (long long)nsamp, c->cfg.max_nsamp);
+    return GNSSCORR_EINVAL;
+  }
+  const int bps = bps_of(c);
+  const bool pk = packed(c), iq = bps == 2;
+  const int base_al = pk ? (iq ? 8 : 1) : 16;
+  const int stride_al = base_al;   // bytes
+  const int64_t stride_elems = stride * bps;
+  // packed: four elements per byte, so the stride and a later step's offset
+  // must be whole bytes before their alignment means anything
+  const bool whole = !pk || (((stride_elems | (step > 0 ? step * nsamp * bps : 0)) & 3) == 0);
+  if (((uintptr_t)d_if & (uintptr_t)(base_al - 1)) || !whole ||
+      (if_bytes(stride_elems, pk) & (stride_al - 1))) {
+    char at[96] = "";
+    if (step >= 0) snprintf(at, sizeof at, "step %d (IF at element offset %lld): ", step,
+                            (long long)((int64_t)step * nsamp * bps));
+    gnsscorr_set_error("%s%s %s IF needs a %d-byte aligned base and a stream stride of whole "
+                       "%d-byte units%s", at, iq ? "IQ" : "I-only", pk ? "packed" : "int8", base_al,
+                       stride_al, pk ? " (4 elements per byte)" : "");
+    return GNSSCORR_EINVAL;
+  }
+  return GNSSCORR_OK;
+}
+
+// Every step of a multi-step request (step k reads the IF at + k * nsamp
+// samples) before any of them runs: a refused request leaves the channel
+// state, the TIC counter and the result arrays as they were.
+extern "C" int gnsscorr_track_check_steps(const gnsscorr_track_ctx* c, const int8_t* d_if,
+                                          int64_t stride, int64_t nsamp, int n_steps) {
+  for (int k = 0; k < n_steps; k++)
+    if (int rc = check_call(c, d_if + gnsscorr_track_if_bytes(c, (int64_t)k * nsamp), stride, nsamp,
+                            n_steps > 1 ? k : -1))
+      return rc;
+  return GNSSCORR_OK;
+}
+
 // osg_stream_kernel: n_calls consecutive calls of every channel in one launch
 // (call k reads the IF at + k * nsamp samples of each stream and the commands
 // at d_cmds + k * cmd_step; the results go to d_res + k * n_channels).  tic: the
@@ -1410,14 +1458,7 @@ static int launch_stream(gnsscorr_track_ctx* c, const int8_t* d_if, int64_t stri
                          gnsscorr_osg_loop* d_loops, gnsscorr_osg_loop* d_hist) {
   const bool pk = packed(c), iq = bps_of(c) == 2;
   if (!iq) return GNSSCORR_TRACK_NOT_FUSED;
-  if (nsamp < 1 || nsamp > c->cfg.max_nsamp) {
-    gnsscorr_set_error("nsamp %lld outside [1, max_nsamp=%d]", (long long)nsamp, c->cfg.max_nsamp);
-    return GNSSCORR_EINVAL;
-  }
-  if (((uintptr_t)d_if & (pk ? 7 : 15)) || ((stride * 2) & (pk ? 31 : 15))) {
-    gnsscorr_set_error("IF base and stream stride must be %d-byte aligned", pk ? 8 : 16);
-    return GNSSCORR_EINVAL;
-  }
+  if (int rc = check_call(c, d_if, stride, nsamp, -1)) return rc;
   // later calls start at + k * nsamp samples: the same alignment, and whole
   // 8-sample chunks (the partial-chunk path is for single calls)
   if (n_calls > 1 && ((nsamp * 2) & (pk ? 31 : 15))) return GNSSCORR_TRACK_NOT_FUSED;
@@ -1482,17 +1523,8 @@ static int launch_stream(gnsscorr_track_ctx* c, const int8_t* d_if, int64_t stri
 static int launch(gnsscorr_track_ctx* c, const int8_t* d_if, int64_t stride, int64_t nsamp,
                   const gnsscorr_nco_cmd* d_cmds, gnsscorr_track_result* d_res,
                   int32_t* d_dumps, int64_t tic_count) {
-  if (nsamp < 1 || nsamp > c->cfg.max_nsamp) {
-    gnsscorr_set_error("nsamp %lld outside [1, max_nsamp=%d]", (long long)nsamp, c->cfg.max_nsamp);
-    return GNSSCORR_EINVAL;
-  }
-  const int bps = bps_of(c);
-  const bool pk = packed(c), iq = bps == 2;
-  // 16-byte aligned int8 runs; packed runs are read in 8-byte words
-  if (((uintptr_t)d_if & (pk ? 7 : 15)) || ((stride * bps) & (pk ? 31 : 15))) {
-    gnsscorr_set_error("IF base and stream stride must be %d-byte aligned", pk ? 8 : 16);
-    return GNSSCORR_EINVAL;
-  }
+  if (int rc = check_call(c, d_if, stride, nsamp, -1)) return rc;
+  const bool pk = packed(c), iq = bps_of(c) == 2;
   if (iq)   // (one call of an IQ context is never GNSSCORR_TRACK_NOT_FUSED)
     return launch_stream(c, d_if, stride, nsamp, 1, const_cast<gnsscorr_nco_cmd*>(d_cmds), 0, d_res,
                          d_dumps, tic_count, 1, nullptr, nullptr, nullptr);
@@ -1622,6 +1654,10 @@ extern "C" int gnsscorr_track_replay_dev(gnsscorr_track_ctx* c, const int8_t* d_
     return GNSSCORR_OK;
   }
   if (rc != GNSSCORR_TRACK_NOT_FUSED) return rc;
+  // one launch per step (every I-only context; IQ steps that start off the
+  // fused kernel's alignment).  All or nothing: every step's IF is checked
+  // before the first launch and before the TIC counter moves.
+  if ((rc = gnsscorr_track_check_steps(c, d_if, stride, nsamp, n_steps))) return rc;
   for (int k = 0; k < n_steps; k++) {
     const int64_t tic = gnsscorr_track_next_tic(c, nsamp);
     rc = launch(c, d_if + gnsscorr_track_if_bytes(c, (int64_t)k * nsamp), stride, nsamp,

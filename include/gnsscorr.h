@@ -170,7 +170,18 @@ int gnsscorr_track(gnsscorr_track_ctx *ctx, const int8_t *h_if, int64_t stream_s
  * asynchronous on the context stream (no host sync).  d_cmds / d_res /
  * d_all_dumps are device arrays sized as in gnsscorr_track().
  * tic_count: sample index of the TIC in this call or -1 (host computes it with
- * gnsscorr_track_next_tic()). */
+ * gnsscorr_track_next_tic()).
+ *
+ * IF alignment of the device calls (gnsscorr_track_dev, every step of
+ * gnsscorr_track_replay_dev and of gnsscorr_osg_closed_loop_dev), by context
+ * format; the stream stride is given in samples, its rule is on its bytes:
+ *   IQ,     int8    d_if 16-byte aligned, stream stride a multiple of 16 bytes
+ *   IQ,     packed  d_if  8-byte aligned, stream stride a multiple of  8 bytes
+ *   I-only, int8    d_if 16-byte aligned, stream stride a multiple of 16 bytes
+ *   I-only, packed  d_if any byte,        stream stride whole bytes (4 samples)
+ * A call that breaks its rule returns GNSSCORR_EINVAL and launches nothing.
+ * (gnsscorr_track() re-strides host streams itself and takes any stride; packed
+ * host streams need a whole-byte stride.) */
 int gnsscorr_track_dev(gnsscorr_track_ctx *ctx, const int8_t *d_if, int64_t stream_stride,
                        int64_t nsamp, const gnsscorr_nco_cmd *d_cmds,
                        gnsscorr_track_result *d_res, int32_t *d_all_dumps, int64_t tic_count);
@@ -182,7 +193,15 @@ int64_t gnsscorr_track_next_tic(gnsscorr_track_ctx *ctx, int64_t nsamp);
 
 /* Open-loop replay: n_steps consecutive calls of nsamp samples; step k reads
  * IF at d_if + k*nsamp*(iq?2:1) of every stream and commands
- * d_cmds[k*n_channels ..]; results d_res[k*n_channels ..].  Asynchronous. */
+ * d_cmds[k*n_channels ..]; results d_res[k*n_channels ..].  Asynchronous.
+ * Step k starts gnsscorr_track_if_bytes(k*nsamp) bytes into every stream and
+ * must meet the alignment rule above there (packed: on a whole byte), so the
+ * bytes of one step must be a multiple of the base alignment: nsamp a multiple
+ * of 8 (IQ int8), 16 (IQ packed, I-only int8) or 4 (I-only packed; the 1-ms
+ * call of 16368 samples is 4092 bytes).  All or nothing: every step is checked
+ * before anything is launched, and a refused replay (GNSSCORR_EINVAL, the error
+ * text names the step and the rule) leaves the channel state, the TIC counter
+ * and d_res untouched. */
 int gnsscorr_track_replay_dev(gnsscorr_track_ctx *ctx, const int8_t *d_if, int64_t stream_stride,
                               int64_t nsamp, int n_steps, const gnsscorr_nco_cmd *d_cmds,
                               gnsscorr_track_result *d_res);

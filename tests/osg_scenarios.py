@@ -116,6 +116,12 @@ SCENARIOS = {
     "ms1": dict(seed=41, n_calls=20, nsamp=16368),
     # TIC latch every 0.01 s at fs = 16.0 MHz (reference tic_ref = SAMP_RATE*tic_period)
     "tic": dict(seed=53, n_calls=48, nsamp=8192, tic_period=0.004),
+    # I-only with the TIC latch: the real-sample kernel's TIC registers and carrier
+    # cycle count, full-range input, large slews and arbitrary code words
+    "ionly_tic": dict(seed=61, n_calls=48, nsamp=8192, iq=False, tic_period=0.004,
+                      heavy_slew=True, full_range=True),
+    # I-only 1-ms calls (16368 real samples: 256 threads per channel)
+    "ionly_ms1": dict(seed=67, n_calls=20, nsamp=16368, iq=False, heavy_slew=True),
 }
 
 

@@ -40,7 +40,7 @@ def test_golden_exercises_quirks():
 
 
 @pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference not mounted")
-@pytest.mark.parametrize("name", ["track12", "wild"])
+@pytest.mark.parametrize("name", ["track12", "wild", "ionly_tic", "ionly_ms1"])
 def test_oracle_matches_reference_build(oracle, name):
     oracle.build(ref=True)
     scn = S.get(name)
