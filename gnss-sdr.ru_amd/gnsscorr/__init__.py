@@ -281,6 +281,14 @@ def _sig_table():
         "gnsscorr_e1t_set_codes": (I, [P, I, P]),
         "gnsscorr_l3_code": (I, [I, P]),
         **_tracker_sig("gnsscorr_l3t", L3tCfg, 5),
+        **_ctx_sig("gnsscorr_nav", I),
+        "gnsscorr_nav_conv_encode": (I, [P, I, P]),
+        "gnsscorr_nav_viterbi_dev": (I, [P, P, I64, I, I, I, P]),
+        "gnsscorr_nav_viterbi": (I, [P, P, I64, I, I, I, P]),
+        "gnsscorr_nav_e1_pages_dev": (I, [P, P, I64, I64, I, I, I, P, P, P]),
+        "gnsscorr_nav_e1_pages": (I, [P, P, I64, I64, I, I, I, P, P, P]),
+        "gnsscorr_nav_l3_decode_dev": (I, [P, P, P, I64, I64, I, I, I, P, P, P, P, P]),
+        "gnsscorr_nav_l3_decode": (I, [P, P, P, I64, I64, I, I, I, P, P, P, P, P]),
         "gnsscorr_sdr_prn_codes": (I, [P]),
         "gnsscorr_sdr_sine_gen": (None, [P, D, D, I]),
         **_ctx_sig("gnsscorr_sdr_acq", C.POINTER(SdrAcqCfg)),
@@ -898,7 +906,7 @@ class _FloatTracker(_Handle):
 
     def _open(self, cfg):
         self.cfg = cfg
-        self._create(C.byref(cfg), ops=("track", "track_dev", "replay"))
+        self._create(C.byref(cfg), ops=("track", "track_dev", "replay", "replay_dev"))
 
     def set_packed(self, packed=True):
         """<prefix>_set_packed: the records of later track / track_dev calls are 2-bit
@@ -957,6 +965,12 @@ class _FloatTracker(_Handle):
         _check(self._replay(self.h, n_ch, _ptr(chans), n_ep, _ptr(sums), _ptr(ep)),
                self._replay)
         return ep
+
+    def replay_dev(self, n_ch, d_chan, n_epochs, d_sums, d_epochs):
+        """replay on device arrays: channels in/out at d_chan, sums [n_ch, n_epochs, n_sums]
+        at d_sums, epochs [n_ch, n_epochs] to d_epochs; queued on the context's stream."""
+        _check(self._replay_dev(self.h, n_ch, d_chan, n_epochs, d_sums, d_epochs),
+               self._replay_dev)
 
 
 # ---------------------------------------------------------------- SoftGNSS float tracking
@@ -1079,6 +1093,101 @@ class L3tCtx(_FloatTracker):
 
     def init_chans(self, prns, code_phases_1b, acq_freqs, streams=None, skip=0):
         return super().init_chans(prns, code_phases_1b, acq_freqs, streams, skip)
+
+
+# ---------------------------------------------------------------- E1B / L3OC navigation symbols
+def epoch_field(epoch_dtype, name):
+    """(byte offset, epoch stride in bytes) of an fp64 field of E1T_EPOCH or L3T_EPOCH, e.g.
+    epoch_field(E1T_EPOCH, "I_P_P"): d_epochs + offset with that stride is the series
+    argument of NavCtx.e1_pages_dev, read in place."""
+    dt = np.dtype(epoch_dtype)
+    if name not in (dt.names or ()) or dt.fields[name][0] != np.dtype("<f8"):
+        raise ValueError(f"{name!r} is not an fp64 field of the epoch record")
+    return dt.fields[name][1], dt.itemsize
+
+
+def nav_conv_encode(msg) -> np.ndarray:
+    """convol_encoder.sci for the K = 7 code: (len(msg) + 6) * 2 symbols 0/1 (host only)."""
+    msg = np.ascontiguousarray(msg, np.uint8).ravel()
+    out = np.zeros((msg.size + 6) * 2, np.uint8)
+    _check(lib().gnsscorr_nav_conv_encode(_ptr(msg), msg.size, _ptr(out)),
+           "gnsscorr_nav_conv_encode")
+    return out
+
+
+class NavCtx(_Handle):
+    """Navigation symbols of Galileo E1B and GLONASS L3OC on the device (csrc/navsym.hip):
+    page and overlay synchronisation, deinterleaving and the Scilab receiver's K = 7
+    Viterbi decoder, one wave per stream.  The *_dev calls are queued on the context's
+    stream and read the trackers' epoch records in place (epoch_field)."""
+
+    _prefix = "gnsscorr_nav"
+
+    def __init__(self, device: int = 0):
+        self.device = device
+        self._create(device, ops=("viterbi", "viterbi_dev", "e1_pages", "e1_pages_dev",
+                                  "l3_decode", "l3_decode_dev"))
+
+    conv_encode = staticmethod(nav_conv_encode)
+
+    def viterbi(self, code, soft=False) -> np.ndarray:
+        """code [n_streams, 2 L] (or [2 L]): uint8 0/1 symbols, or fp64 with soft=True;
+        returns bits [n_streams, L] uint8."""
+        code = np.ascontiguousarray(code, np.float64 if soft else np.uint8)
+        code = code.reshape(1, -1) if code.ndim == 1 else code
+        assert code.ndim == 2 and code.shape[1] % 2 == 0
+        n, L = code.shape[0], code.shape[1] // 2
+        bits = np.zeros((n, L), np.uint8)
+        _check(self._viterbi(self.h, _ptr(code), code.strides[0], n, L, int(soft), _ptr(bits)),
+               self._viterbi)
+        return bits
+
+    def viterbi_dev(self, d_code, stream_stride_bytes, n_streams, L, soft, d_bits):
+        _check(self._viterbi_dev(self.h, d_code, stream_stride_bytes, n_streams, L, int(soft),
+                                 d_bits), self._viterbi_dev)
+
+    def e1_pages(self, series, max_pages=None):
+        """series [n_ch, n_epochs] fp64 (I_P_P); returns first_page [n_ch], n_pages [n_ch]
+        and bits [n_ch, max_pages, 120] (max_pages: every whole page part by default)."""
+        series = np.ascontiguousarray(series, np.float64)
+        series = series.reshape(1, -1) if series.ndim == 1 else series
+        n_ch, n_ep = series.shape
+        max_pages = max(n_ep // 1000, 1) if max_pages is None else int(max_pages)
+        first, n_pages = np.zeros(n_ch, np.int32), np.zeros(n_ch, np.int32)
+        bits = np.zeros((n_ch, max_pages, 120), np.uint8)
+        _check(self._e1_pages(self.h, _ptr(series), 8, max(series.strides[0], 8), n_ep, n_ch,
+                              max_pages, _ptr(first), _ptr(n_pages), _ptr(bits)), self._e1_pages)
+        return first, n_pages, bits
+
+    def e1_pages_dev(self, d_series, epoch_stride_bytes, chan_stride_bytes, n_epochs, n_ch,
+                     max_pages, d_first_page, d_n_pages, d_bits):
+        _check(self._e1_pages_dev(self.h, d_series, epoch_stride_bytes, chan_stride_bytes,
+                                  n_epochs, n_ch, max_pages, d_first_page, d_n_pages, d_bits),
+               self._e1_pages_dev)
+
+    def l3_decode(self, pilot, data, max_marks=64):
+        """pilot (I_P), data (Q_P2): [n_ch, n_epochs] fp64; returns start [n_ch], n_bits
+        [n_ch], bits [n_ch, n_epochs // 10], n_marks [n_ch], marks [n_ch, max_marks]."""
+        pilot = np.ascontiguousarray(pilot, np.float64)
+        data = np.ascontiguousarray(data, np.float64)
+        pilot = pilot.reshape(1, -1) if pilot.ndim == 1 else pilot
+        data = data.reshape(pilot.shape)
+        n_ch, n_ep = pilot.shape
+        start, n_bits = np.zeros(n_ch, np.int32), np.zeros(n_ch, np.int32)
+        bits = np.zeros((n_ch, n_ep // 10), np.uint8)
+        n_marks = np.zeros(n_ch, np.int32)
+        marks = np.full((n_ch, int(max_marks)), -1, np.int32)
+        _check(self._l3_decode(self.h, _ptr(pilot), _ptr(data), 8, max(pilot.strides[0], 8),
+                               n_ep, n_ch, int(max_marks), _ptr(start), _ptr(n_bits),
+                               _ptr(bits), _ptr(n_marks), _ptr(marks)),
+               self._l3_decode)
+        return start, n_bits, bits, n_marks, marks
+
+    def l3_decode_dev(self, d_pilot, d_data, epoch_stride_bytes, chan_stride_bytes, n_epochs,
+                      n_ch, max_marks, d_start, d_n_bits, d_bits, d_n_marks, d_marks):
+        _check(self._l3_decode_dev(self.h, d_pilot, d_data, epoch_stride_bytes,
+                                   chan_stride_bytes, n_epochs, n_ch, max_marks, d_start,
+                                   d_n_bits, d_bits, d_n_marks, d_marks), self._l3_decode_dev)
 
 
 # ---------------------------------------------------------------- GPS-SDR integer acquisition

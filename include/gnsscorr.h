@@ -935,6 +935,106 @@ int gnsscorr_l3t_sync(gnsscorr_l3t_ctx *ctx);
 void *gnsscorr_l3t_stream(gnsscorr_l3t_ctx *ctx);
 
 /* ======================================================================
+ * Navigation symbols of Galileo E1B and GLONASS L3OC ("nav"): the Scilab
+ * receiver's symbol chain from the trackers' prompt sums to decoded bits
+ *   GALILEO/E1/findPageStart.sci:39-63, GALILEO/E1/include/decode_gll_data.sci:16-39
+ *   GLONASS/L3/test_data_decode.sce:19-83
+ *   convolution_decoding/convol_decoder.sci, convol_decoder_soft.sci (the K = 7
+ *   decoder both call), convol_encoder.sci:50-57
+ * Bits and positions are exact.  No field decoding, CRC or PVT: the output is
+ * the decoded bit stream and the synchronisation positions, where the
+ * reference's own E1 and L3 scripts stop.
+ *
+ * The decoder (n = 2, m = 7, generators [1 0 1 1 0 1 1], [1 1 1 1 0 0 1], input
+ * first) is the files', not a textbook Viterbi:
+ *  - state s in 0..63 is the last six inputs, the newest in bit 5; start metrics
+ *    0 for state 0 and 10000 for the others; T = L + 41 steps, the received pairs
+ *    past L being (0, 0): the trellis is not flushed, so the last six bits of a
+ *    message that does not end in six zeros can be wrong on clean input;
+ *  - new state l takes predecessor 2 (l mod 32), or 2 (l mod 32) + 1 only when
+ *    that cost is strictly smaller.  Hard cost: Hamming distance + metric, int32,
+ *    never normalised (L above the bound that keeps 10000 + 2 T inside an int32
+ *    is GNSSCORR_EINVAL).  Soft cost: ((r1 - o1)^2 + (r2 - o2)^2) + metric in
+ *    fp64, in that order, without contraction;
+ *  - bit c, 0-based: every state after step c + 41 is followed back through the
+ *    decisions of steps c + 41 .. c + 1; of the states after step c that are
+ *    reached, the one with the smallest metric after step c, the lowest state on
+ *    ties, gives the bit: state div 32.
+ *
+ * A series argument points at an fp64 field inside an array of epoch records:
+ * element (ch, e) at ch * chan_stride_bytes + e * epoch_stride_bytes from it, so
+ * &d_epochs[0].i_p_p with strides sizeof(gnsscorr_e1t_epoch) and n_epochs *
+ * sizeof(gnsscorr_e1t_epoch) reads tracker output in place.  The pointer and both
+ * strides are multiples of 8 and the strides at least 8.  sign(0) = 0, and
+ * samples past the end of a series count as 0.
+ *
+ * Bad arguments (a null pointer, L < 1, n_epochs < 1, n_ch < 1, a stride smaller
+ * than 8 or misaligned, L or n_epochs / 10 past the overflow bound) return
+ * GNSSCORR_EINVAL before any device call.
+ * ==================================================================== */
+typedef struct gnsscorr_nav_ctx gnsscorr_nav_ctx;
+
+int gnsscorr_nav_create(gnsscorr_nav_ctx **out, int device);
+int gnsscorr_nav_destroy(gnsscorr_nav_ctx *ctx);
+int gnsscorr_nav_sync(gnsscorr_nav_ctx *ctx);
+void *gnsscorr_nav_stream(gnsscorr_nav_ctx *ctx);
+/* Host only: convol_encoder.sci:50-57 for the generators above.  out receives
+ * (n_bits + 6) * 2 symbols 0/1, the two outputs of one step next to each other
+ * (the file's W(:)'). */
+int gnsscorr_nav_conv_encode(const uint8_t *msg, int n_bits, uint8_t *out);
+/* n_streams independent streams of L pairs in one launch (one wave64 each),
+ * stream s at d_code + s * stream_stride_bytes: uint8 0/1 pairs (soft = 0) or
+ * fp64 pairs (soft = 1; pointer and stride multiples of 8).  d_bits: one uint8
+ * per bit, stream s at s * L. */
+int gnsscorr_nav_viterbi_dev(gnsscorr_nav_ctx *ctx, const void *d_code,
+                             int64_t stream_stride_bytes, int n_streams, int L, int soft,
+                             uint8_t *d_bits);
+/* Same with host arrays (synchronous); h_code holds (n_streams - 1) *
+ * stream_stride_bytes + one stream. */
+int gnsscorr_nav_viterbi(gnsscorr_nav_ctx *ctx, const void *h_code, int64_t stream_stride_bytes,
+                         int n_streams, int L, int soft, uint8_t *h_bits);
+/* Galileo E1B, per channel over n_epochs prompt sums (gnsscorr_e1t_epoch.i_p_p):
+ *  - r[k] = sum_{i<40} w[i / 4] sign(x[k + i]), w = [-1 1 -1 1 1 -1 -1 -1 -1 -1];
+ *    k is a hit when |r[k]| > 38; d_first_page[ch] = the smallest hit k for which
+ *    k + 1000 is a hit too, else -1;
+ *  - d_n_pages[ch] = min(floor((n_epochs - first_page) / 1000), max_pages), 0
+ *    without a first page; page part i starts at p = first_page + 1000 i:
+ *    y[j] = sign(sum of the signs of x[p + 4 j .. p + 4 j + 3]), j < 250, negated
+ *    when sum_{j<10} y[j] w[j] < 0; out[c + 8 r] = y[10 + r + 30 c]; symbol out > 0;
+ *    the hard decoder with L = 120.  (The reference decodes the first page part
+ *    only, ephemeris.sci:27-29.)
+ * d_bits: [n_ch][max_pages][120] uint8, zeros for page parts that are not there. */
+int gnsscorr_nav_e1_pages_dev(gnsscorr_nav_ctx *ctx, const void *d_series,
+                              int64_t epoch_stride_bytes, int64_t chan_stride_bytes,
+                              int n_epochs, int n_ch, int max_pages, int32_t *d_first_page,
+                              int32_t *d_n_pages, uint8_t *d_bits);
+int gnsscorr_nav_e1_pages(gnsscorr_nav_ctx *ctx, const void *h_series,
+                          int64_t epoch_stride_bytes, int64_t chan_stride_bytes, int n_epochs,
+                          int n_ch, int max_pages, int32_t *h_first_page, int32_t *h_n_pages,
+                          uint8_t *h_bits);
+/* GLONASS L3OC, per channel, pilot I (gnsscorr_l3t_epoch.i_p) and data Q
+ * (.q_p2), both with the same strides:
+ *  - d_start[ch] = the first k with |sum_{j<10} sign(I[k + j]) NH[j]| == 10,
+ *    NH = [-1 -1 -1 -1 1 1 -1 1 -1 1], else -1.  An inverted stream is not turned
+ *    round: test_data_decode.sce:29 compares that sum with -20, which it never is;
+ *  - d_n_bits[ch] = n10 = floor((n_epochs - start) / 10), 0 without a start;
+ *    symbol i < 2 n10 is sum_{j<5} sign(Q[start + 5 i + j]) BK[j] > 0 with
+ *    BK = [-1 -1 -1 1 -1]; the hard decoder with L = n10;
+ *  - time marks: every k with |sum_{j<20} (2 bit[k + j] - 1) tm[j]| == 20 (tm: :82);
+ *    d_n_marks[ch] counts them all, d_marks[ch][0 .. max_marks) holds the first
+ *    max_marks in ascending order, -1 after the last.
+ * d_bits: [n_ch][floor(n_epochs / 10)] uint8, zeros past n_bits.  max_marks >= 1. */
+int gnsscorr_nav_l3_decode_dev(gnsscorr_nav_ctx *ctx, const void *d_pilot, const void *d_data,
+                               int64_t epoch_stride_bytes, int64_t chan_stride_bytes,
+                               int n_epochs, int n_ch, int max_marks, int32_t *d_start,
+                               int32_t *d_n_bits, uint8_t *d_bits, int32_t *d_n_marks,
+                               int32_t *d_marks);
+int gnsscorr_nav_l3_decode(gnsscorr_nav_ctx *ctx, const void *h_pilot, const void *h_data,
+                           int64_t epoch_stride_bytes, int64_t chan_stride_bytes, int n_epochs,
+                           int n_ch, int max_marks, int32_t *h_start, int32_t *h_n_bits,
+                           uint8_t *h_bits, int32_t *h_n_marks, int32_t *h_marks);
+
+/* ======================================================================
  * GPS-SDR integer strong acquisition ("sdr"), bit-exact with the real-time
  * receiver's int16 path (REALTIME_RECEIVERS/GPS/GPS_SDR_REAL_TIME_GPS_RECEIVER):
  *   Acquisition::doPrepIF    objects/acquisition.cpp:191-236 (1 ms buffer)
