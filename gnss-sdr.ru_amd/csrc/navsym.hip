@@ -28,6 +28,7 @@
 #include <type_traits>
 #include "gnsscorr_internal.h"
 #include "hostctx.h"
+#include "nav_host.h"
 
 namespace {
 
@@ -326,20 +327,9 @@ __global__ __launch_bounds__(64) void nav_l3_marks_kernel(
 // ============================================================================
 // host side
 // ============================================================================
-struct gnsscorr_nav_ctx {
-  struct { int device; } cfg;
-  hipStream_t stream = nullptr;
-  // work buffers of the *_dev calls: the decoder's input symbols and the
-  // length of each of its streams.  grow() frees the old block with hipFree,
-  // which waits for launches still queued on it.
-  hostctx::DevBuf<uint8_t> d_code;
-  hostctx::DevBuf<int32_t> d_len;
-};
-
-static int bad_arguments(const char* fn, const char* what) {
-  gnsscorr_set_error("%s: bad arguments (%s)", fn, what);
-  return GNSSCORR_EINVAL;
-}
+using navhost::bad_arguments;
+using navhost::check_series;
+using navhost::series_bytes;
 
 extern "C" int gnsscorr_nav_conv_encode(const uint8_t* msg, int n_bits, uint8_t* out) {
   if (!msg || !out || n_bits < 1) return bad_arguments(__func__, "msg, out, n_bits >= 1");
@@ -371,7 +361,7 @@ extern "C" int gnsscorr_nav_create(gnsscorr_nav_ctx** out, int device) {
 }
 
 extern "C" int gnsscorr_nav_destroy(gnsscorr_nav_ctx* c) {
-  return hostctx::destroy(c, [&] { hostctx::release(c->d_code, c->d_len); });
+  return hostctx::destroy(c, [&] { hostctx::release(c->d_code, c->d_len, c->d_hitmap); });
 }
 
 extern "C" int gnsscorr_nav_sync(gnsscorr_nav_ctx* c) { return hostctx::sync(c); }
@@ -437,22 +427,6 @@ extern "C" int gnsscorr_nav_viterbi(gnsscorr_nav_ctx* c, const void* h_code,
   HIP_TRY(hipMemcpyAsync(h_bits, d_out.p, n_out, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return GNSSCORR_OK;
-}
-
-// the checks the series entry points share
-static int check_series(const char* fn, const gnsscorr_nav_ctx* c, const void* series,
-                        int64_t epoch_stride, int64_t chan_stride, int n_epochs, int n_ch) {
-  if (!c || !series) return bad_arguments(fn, "null pointer");
-  if (n_epochs < 1 || n_ch < 1) return bad_arguments(fn, "n_epochs >= 1, n_ch >= 1");
-  if (epoch_stride < 8 || chan_stride < 8) return bad_arguments(fn, "a stride smaller than 8");
-  if (((uintptr_t)series & 7) || (epoch_stride & 7) || (chan_stride & 7))
-    return bad_arguments(fn, "fp64 fields: 8-byte aligned pointer and strides");
-  return GNSSCORR_OK;
-}
-
-// bytes from the first channel's first epoch to the end of the last one's last
-static size_t series_bytes(int64_t epoch_stride, int64_t chan_stride, int n_epochs, int n_ch) {
-  return (size_t)(n_ch - 1) * chan_stride + (size_t)(n_epochs - 1) * epoch_stride + 8;
 }
 
 extern "C" int gnsscorr_nav_e1_pages_dev(gnsscorr_nav_ctx* c, const void* d_series,

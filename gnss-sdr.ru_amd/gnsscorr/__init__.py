@@ -289,6 +289,14 @@ def _sig_table():
         "gnsscorr_nav_e1_pages": (I, [P, P, I64, I64, I, I, I, P, P, P]),
         "gnsscorr_nav_l3_decode_dev": (I, [P, P, P, I64, I64, I, I, I, P, P, P, P, P]),
         "gnsscorr_nav_l3_decode": (I, [P, P, P, I64, I64, I, I, I, P, P, P, P, P]),
+        "gnsscorr_nav_pattern_hits_dev": (I, [P, P, I64, I64, I, I, P, I, I, I, I, P, P, P]),
+        "gnsscorr_nav_pattern_hits": (I, [P, P, I64, I64, I, I, P, I, I, I, I, P, P, P]),
+        "gnsscorr_nav_gps_frames_dev": (I, [P, P, I64, I64, I, I, I, I, P, P, P]),
+        "gnsscorr_nav_gps_frames": (I, [P, P, I64, I64, I, I, I, I, P, P, P]),
+        "gnsscorr_nav_glo_strings_dev": (I, [P, P, I64, I64, I, I, I, P, P, P]),
+        "gnsscorr_nav_glo_strings": (I, [P, P, I64, I64, I, I, I, P, P, P]),
+        "gnsscorr_nav_b1_subframes_dev": (I, [P, P, I64, I64, I, I, I, P, P, P]),
+        "gnsscorr_nav_b1_subframes": (I, [P, P, I64, I64, I, I, I, P, P, P]),
         "gnsscorr_sdr_prn_codes": (I, [P]),
         "gnsscorr_sdr_sine_gen": (None, [P, D, D, I]),
         **_ctx_sig("gnsscorr_sdr_acq", C.POINTER(SdrAcqCfg)),
@@ -1097,9 +1105,9 @@ class L3tCtx(_FloatTracker):
 
 # ---------------------------------------------------------------- E1B / L3OC navigation symbols
 def epoch_field(epoch_dtype, name):
-    """(byte offset, epoch stride in bytes) of an fp64 field of E1T_EPOCH or L3T_EPOCH, e.g.
-    epoch_field(E1T_EPOCH, "I_P_P"): d_epochs + offset with that stride is the series
-    argument of NavCtx.e1_pages_dev, read in place."""
+    """(byte offset, epoch stride in bytes) of an fp64 field of E1T_EPOCH, L3T_EPOCH or
+    SGT_EPOCH, e.g. epoch_field(E1T_EPOCH, "I_P_P"): d_epochs + offset with that stride is
+    the series argument of NavCtx.e1_pages_dev, read in place."""
     dt = np.dtype(epoch_dtype)
     if name not in (dt.names or ()) or dt.fields[name][0] != np.dtype("<f8"):
         raise ValueError(f"{name!r} is not an fp64 field of the epoch record")
@@ -1118,15 +1126,20 @@ def nav_conv_encode(msg) -> np.ndarray:
 class NavCtx(_Handle):
     """Navigation symbols of Galileo E1B and GLONASS L3OC on the device (csrc/navsym.hip):
     page and overlay synchronisation, deinterleaving and the Scilab receiver's K = 7
-    Viterbi decoder, one wave per stream.  The *_dev calls are queued on the context's
-    stream and read the trackers' epoch records in place (epoch_field)."""
+    Viterbi decoder, one wave per stream; and frame synchronisation and data bits of GPS
+    L1 C/A, GLONASS L1OF and BeiDou B1I (csrc/navbits.hip) from SgtCtx epoch records.  The
+    *_dev calls are queued on the context's stream and read the trackers' epoch records in
+    place (epoch_field)."""
 
     _prefix = "gnsscorr_nav"
 
     def __init__(self, device: int = 0):
         self.device = device
         self._create(device, ops=("viterbi", "viterbi_dev", "e1_pages", "e1_pages_dev",
-                                  "l3_decode", "l3_decode_dev"))
+                                  "l3_decode", "l3_decode_dev", "pattern_hits",
+                                  "pattern_hits_dev", "gps_frames", "gps_frames_dev",
+                                  "glo_strings", "glo_strings_dev", "b1_subframes",
+                                  "b1_subframes_dev"))
 
     conv_encode = staticmethod(nav_conv_encode)
 
@@ -1188,6 +1201,83 @@ class NavCtx(_Handle):
         _check(self._l3_decode_dev(self.h, d_pilot, d_data, epoch_stride_bytes,
                                    chan_stride_bytes, n_epochs, n_ch, max_marks, d_start,
                                    d_n_bits, d_bits, d_n_marks, d_marks), self._l3_decode_dev)
+
+    @staticmethod
+    def _series(series):
+        """[n_ch, n_epochs] fp64 (or one channel), its channel stride, n_epochs, n_ch"""
+        series = np.ascontiguousarray(series, np.float64)
+        series = series.reshape(1, -1) if series.ndim == 1 else series
+        return series, max(series.strides[0], 8), series.shape[1], series.shape[0]
+
+    def pattern_hits(self, series, pattern, threshold, first_k=0, max_hits=16):
+        """series [n_ch, n_epochs] fp64, pattern int8 [T] in {-1, 0, 1}: the k >= first_k with
+        |sum_i pattern[i] sign(x[k + i])| > threshold.  Returns first [n_ch], n_hits [n_ch]
+        and hits [n_ch, max_hits] (ascending, -1 after the last)."""
+        series, cs, n_ep, n_ch = self._series(series)
+        pattern = np.ascontiguousarray(pattern, np.int8).ravel()
+        first, n_hits = np.zeros(n_ch, np.int32), np.zeros(n_ch, np.int32)
+        hits = np.full((n_ch, max(int(max_hits), 1)), -1, np.int32)
+        _check(self._pattern_hits(self.h, _ptr(series), 8, cs, n_ep, n_ch, _ptr(pattern),
+                                  pattern.size, int(threshold), int(first_k), int(max_hits),
+                                  _ptr(first), _ptr(n_hits), _ptr(hits)), self._pattern_hits)
+        return first, n_hits, hits
+
+    def pattern_hits_dev(self, d_series, epoch_stride_bytes, chan_stride_bytes, n_epochs, n_ch,
+                         pattern, threshold, first_k, max_hits, d_first, d_n_hits, d_hits):
+        """pattern: a host int8 array (it reaches the kernel as two masks in its arguments)."""
+        pattern = np.ascontiguousarray(pattern, np.int8).ravel()
+        _check(self._pattern_hits_dev(self.h, d_series, epoch_stride_bytes, chan_stride_bytes,
+                                      n_epochs, n_ch, _ptr(pattern), pattern.size,
+                                      int(threshold), int(first_k), int(max_hits), d_first,
+                                      d_n_hits, d_hits), self._pattern_hits_dev)
+
+    def gps_frames(self, series, search_start=5000, max_subframes=5):
+        """GPS L1 C/A: series [n_ch, n_epochs] fp64 (SGT_EPOCH I_P); returns first_subframe
+        [n_ch], n_bits [n_ch] and bits [n_ch, 1500] (0 / 1, 2 for an undecided bit)."""
+        series, cs, n_ep, n_ch = self._series(series)
+        first, n_bits = np.zeros(n_ch, np.int32), np.zeros(n_ch, np.int32)
+        bits = np.zeros((n_ch, 1500), np.uint8)
+        _check(self._gps_frames(self.h, _ptr(series), 8, cs, n_ep, n_ch, int(search_start),
+                                int(max_subframes), _ptr(first), _ptr(n_bits), _ptr(bits)),
+               self._gps_frames)
+        return first, n_bits, bits
+
+    def gps_frames_dev(self, d_series, epoch_stride_bytes, chan_stride_bytes, n_epochs, n_ch,
+                       search_start, max_subframes, d_first_subframe, d_n_bits, d_bits):
+        _check(self._gps_frames_dev(self.h, d_series, epoch_stride_bytes, chan_stride_bytes,
+                                    n_epochs, n_ch, search_start, max_subframes,
+                                    d_first_subframe, d_n_bits, d_bits), self._gps_frames_dev)
+
+    def glo_strings(self, series, max_strings=15):
+        """GLONASS L1OF: returns first_mark [n_ch], n_strings [n_ch] and bits
+        [n_ch, 15, 85]."""
+        series, cs, n_ep, n_ch = self._series(series)
+        first, n_str = np.zeros(n_ch, np.int32), np.zeros(n_ch, np.int32)
+        bits = np.zeros((n_ch, 15, 85), np.uint8)
+        _check(self._glo_strings(self.h, _ptr(series), 8, cs, n_ep, n_ch, int(max_strings),
+                                 _ptr(first), _ptr(n_str), _ptr(bits)), self._glo_strings)
+        return first, n_str, bits
+
+    def glo_strings_dev(self, d_series, epoch_stride_bytes, chan_stride_bytes, n_epochs, n_ch,
+                        max_strings, d_first_mark, d_n_strings, d_bits):
+        _check(self._glo_strings_dev(self.h, d_series, epoch_stride_bytes, chan_stride_bytes,
+                                     n_epochs, n_ch, max_strings, d_first_mark, d_n_strings,
+                                     d_bits), self._glo_strings_dev)
+
+    def b1_subframes(self, series, max_subframes=5):
+        """BeiDou B1I: returns first [n_ch], n_subframes [n_ch] and bits [n_ch, 5, 213]."""
+        series, cs, n_ep, n_ch = self._series(series)
+        first, n_sub = np.zeros(n_ch, np.int32), np.zeros(n_ch, np.int32)
+        bits = np.zeros((n_ch, 5, 213), np.uint8)
+        _check(self._b1_subframes(self.h, _ptr(series), 8, cs, n_ep, n_ch, int(max_subframes),
+                                  _ptr(first), _ptr(n_sub), _ptr(bits)), self._b1_subframes)
+        return first, n_sub, bits
+
+    def b1_subframes_dev(self, d_series, epoch_stride_bytes, chan_stride_bytes, n_epochs, n_ch,
+                         max_subframes, d_first, d_n_subframes, d_bits):
+        _check(self._b1_subframes_dev(self.h, d_series, epoch_stride_bytes, chan_stride_bytes,
+                                      n_epochs, n_ch, max_subframes, d_first, d_n_subframes,
+                                      d_bits), self._b1_subframes_dev)
 
 
 # ---------------------------------------------------------------- GPS-SDR integer acquisition

@@ -1034,6 +1034,114 @@ int gnsscorr_nav_l3_decode(gnsscorr_nav_ctx *ctx, const void *h_pilot, const voi
                            int n_ch, int max_marks, int32_t *h_start, int32_t *h_n_bits,
                            uint8_t *h_bits, int32_t *h_n_marks, int32_t *h_marks);
 
+/* ----------------------------------------------------------------------
+ * Frame synchronisation and data bits of GPS L1 C/A, GLONASS L1OF and BeiDou
+ * B1I (csrc/navbits.hip): what the Scilab receiver does between the float
+ * tracker's prompt sums (gnsscorr_sgt_epoch.i_p) and field decoding
+ *   GPS/L1/findPreambles.sci:49-153, include/navPartyChk.sci:56-103,
+ *   postNavigation.sci:91-106, include/checkPhase.sci:45-52, include/ephemeris.sci:68-80
+ *   GLONASS/L1/findTimeMarks.sci:42-65, include/decode_gl_data.sci:17-34
+ *   COMPASS/B1/findSubframeStart.sci:39-62, include/decode_bd_data.sci:16-38
+ * Same context, series arguments and refusals as above: &d_epochs[0].i_p with
+ * strides sizeof(gnsscorr_sgt_epoch) and n_epochs * sizeof(gnsscorr_sgt_epoch)
+ * reads tracker output in place.  Positions are 0-based epoch indices into the
+ * series as passed, -1 for "none".  Bits are uint8 0 or 1, and 2 where the files
+ * have 0.5 (a decision sum of exactly 0).  No field decoding, TOW, BCH or
+ * Hamming checks, pseudoranges or PVT; the files run no BCH or Hamming check on
+ * these paths either.  Bits and positions are exact.
+ *
+ * Pattern search, the files' convol(pattern, sign(x)) cut to its valid part:
+ *   r[k] = sum_{i<T} pattern[i] sign(x[k + i]),  first_k <= k < n_epochs,
+ * samples past the end counting 0; k is a hit when |r[k]| > threshold.  pattern
+ * is a HOST array of T int8 values in {-1, 0, 1} in both forms (it travels to
+ * the kernel as two bit masks in its arguments), already in correlation order:
+ * the files' convol vector reversed.  d_first[ch]: the smallest hit, else -1;
+ * d_n_hits[ch]: the number of hits; d_hits[ch][0 .. max_hits): the first
+ * max_hits hits in ascending order, -1 after the last.  1 <= T <= 512,
+ * 0 <= threshold < T, first_k >= 0, max_hits >= 1 (and n_ch * max_hits < 2^31
+ * for the host form). */
+int gnsscorr_nav_pattern_hits_dev(gnsscorr_nav_ctx *ctx, const void *d_series,
+                                  int64_t epoch_stride_bytes, int64_t chan_stride_bytes,
+                                  int n_epochs, int n_ch, const int8_t *pattern, int T,
+                                  int threshold, int first_k, int max_hits, int32_t *d_first,
+                                  int32_t *d_n_hits, int32_t *d_hits);
+int gnsscorr_nav_pattern_hits(gnsscorr_nav_ctx *ctx, const void *h_series,
+                              int64_t epoch_stride_bytes, int64_t chan_stride_bytes, int n_epochs,
+                              int n_ch, const int8_t *pattern, int T, int threshold, int first_k,
+                              int max_hits, int32_t *h_first, int32_t *h_n_hits, int32_t *h_hits);
+/* GPS L1 C/A, per channel:
+ *  - hits of pattern kron([1 -1 -1 -1 1 -1 1 1], ones(20)) (findPreambles.sci:56-60
+ *    reversed: the file uses convol), threshold 153, first_k = search_start (the
+ *    file's searchStartOffset is 5000; below 40 is GNSSCORR_EINVAL, the parity
+ *    check reads 40 epochs before a hit);
+ *  - a hit p is a candidate when p + 6000 is a hit too (:116-118); then
+ *    b[j] = sign(sum_{t<20} x[p - 40 + 20 j + t]), j < 62, the sum being fp64 adds
+ *    one after another in ascending t (sum(.., 'r') of a 20-row matrix), and
+ *    navPartyChk runs on b[0..31] and on b[30..61] with values in {-1, 0, 1} as
+ *    the file does: ndat(3:26) negated when ndat(2) ~= 1, six products compared
+ *    with ndat(27:32), status -ndat(2) when all six agree.  Both must be non-zero;
+ *  - d_first_subframe[ch] = the smallest candidate that passes, else -1;
+ *  - n_sub = min(max_subframes, 5, floor((n_epochs - p) / 6000)), d_n_bits[ch] =
+ *    300 n_sub.  raw[j] = (sign(sum_{t<20} x[p - 20 + 20 j + t]) + 1) / 2 for
+ *    j <= 300 n_sub, same add order (postNavigation.sci:91-106); raw[0] is D30*;
+ *  - every 30-bit word goes through checkPhase with D30* chained from the word
+ *    before, across subframes (ephemeris.sci:74-80): bits 1-24 of a word become
+ *    1 - bit only when D30* is exactly 1, and a 0.5 stays 0.5.
+ * d_bits: [n_ch][1500] uint8, zeros past n_bits.  The reference takes all five
+ * subframes or stops with an index error; returning the whole subframes that
+ * fit is the one deliberate widening.  max_subframes >= 1. */
+int gnsscorr_nav_gps_frames_dev(gnsscorr_nav_ctx *ctx, const void *d_series,
+                                int64_t epoch_stride_bytes, int64_t chan_stride_bytes,
+                                int n_epochs, int n_ch, int search_start, int max_subframes,
+                                int32_t *d_first_subframe, int32_t *d_n_bits, uint8_t *d_bits);
+int gnsscorr_nav_gps_frames(gnsscorr_nav_ctx *ctx, const void *h_series,
+                            int64_t epoch_stride_bytes, int64_t chan_stride_bytes, int n_epochs,
+                            int n_ch, int search_start, int max_subframes,
+                            int32_t *h_first_subframe, int32_t *h_n_bits, uint8_t *h_bits);
+/* GLONASS L1OF, per channel (the L2 receiver's findTimeMarks.sci is other text
+ * with the same search):
+ *  - d_first_mark[ch] = the first hit of the 300-tap pattern kron(-tm_bits,
+ *    ones(10)) reversed (findTimeMarks.sci:45-46), threshold 290, from k = 0;
+ *  - string i < min(max_strings, 15) starts at s = first_mark + 300 + 2000 i and is
+ *    there when s + 1700 <= n_epochs; d_n_strings[ch] counts them;
+ *  - y[j] = sign(sum_{t<20} sign(x[s + 20 j + t]) m[t]), m = -1 for t < 10 and +1
+ *    after, j < 85; dec[83 - i] = -y[i] y[i + 1], i < 84; dec[84] = -1
+ *    (decode_gl_data.sci:19-34); bit = (dec + 1) / 2, 2 for 0.5.  An inverted
+ *    series gives the same bits.
+ * d_bits: [n_ch][15][85] uint8, zeros for strings that are not there.  The
+ * receiver's skipNumberOfFirstBits is the caller's: offset the series pointer
+ * by that many epochs and pass n_epochs less.  max_strings >= 1. */
+int gnsscorr_nav_glo_strings_dev(gnsscorr_nav_ctx *ctx, const void *d_series,
+                                 int64_t epoch_stride_bytes, int64_t chan_stride_bytes,
+                                 int n_epochs, int n_ch, int max_strings, int32_t *d_first_mark,
+                                 int32_t *d_n_strings, uint8_t *d_bits);
+int gnsscorr_nav_glo_strings(gnsscorr_nav_ctx *ctx, const void *h_series,
+                             int64_t epoch_stride_bytes, int64_t chan_stride_bytes, int n_epochs,
+                             int n_ch, int max_strings, int32_t *h_first_mark,
+                             int32_t *h_n_strings, uint8_t *h_bits);
+/* BeiDou B1I, per channel:
+ *  - d_first[ch] = the first hit of the 220-tap pattern kron(preamble_bits,
+ *    -secondary_code) reversed (findSubframeStart.sci:42-44), threshold 200, from
+ *    k = 0;
+ *  - subframe i < min(max_subframes, 5) starts at s = first + 6000 i and is there
+ *    when s + 6000 <= n_epochs; d_n_subframes[ch] counts them;
+ *  - y[j] = sign(sum_{t<20} sign(x[s + 20 j + t]) nh[t]), j < 300, nh the
+ *    secondary_code of decode_bd_data.sci:19; all of y is negated only when
+ *    sign(sum_{j<11} y[j] preamble[j]) is exactly -1 (:29-31);
+ *  - output: y[11..25], then for words w = 1..9 the values at even offsets
+ *    0, 2, .., 20 and then at odd offsets 1, 3, .., 21 of y[30 w ..] (:33-38): 213
+ *    values as (y + 1) / 2, 2 for 0.5.
+ * d_bits: [n_ch][5][213] uint8, zeros for subframes that are not there.
+ * max_subframes >= 1. */
+int gnsscorr_nav_b1_subframes_dev(gnsscorr_nav_ctx *ctx, const void *d_series,
+                                  int64_t epoch_stride_bytes, int64_t chan_stride_bytes,
+                                  int n_epochs, int n_ch, int max_subframes, int32_t *d_first,
+                                  int32_t *d_n_subframes, uint8_t *d_bits);
+int gnsscorr_nav_b1_subframes(gnsscorr_nav_ctx *ctx, const void *h_series,
+                              int64_t epoch_stride_bytes, int64_t chan_stride_bytes, int n_epochs,
+                              int n_ch, int max_subframes, int32_t *h_first,
+                              int32_t *h_n_subframes, uint8_t *h_bits);
+
 /* ======================================================================
  * GPS-SDR integer strong acquisition ("sdr"), bit-exact with the real-time
  * receiver's int16 path (REALTIME_RECEIVERS/GPS/GPS_SDR_REAL_TIME_GPS_RECEIVER):
