@@ -361,7 +361,7 @@ extern "C" int gnsscorr_nav_create(gnsscorr_nav_ctx** out, int device) {
 }
 
 extern "C" int gnsscorr_nav_destroy(gnsscorr_nav_ctx* c) {
-  return hostctx::destroy(c, [&] { hostctx::release(c->d_code, c->d_len, c->d_hitmap); });
+  return hostctx::destroy(c, [&] { hostctx::release(c->d_code, c->d_len, c->d_hitmap, c->d_rx_first); });
 }
 
 extern "C" int gnsscorr_nav_sync(gnsscorr_nav_ctx* c) { return hostctx::sync(c); }

@@ -101,6 +101,34 @@ L3T_EPOCH = np.dtype([(f, "<f8") for f in L3T_SUMS] +
                       ("dllDiscr", "<f8"), ("dllDiscrFilt", "<f8"), ("pllDiscr", "<f8"),
                       ("pllDiscrFilt", "<f8"), ("blksize", "<i4"), ("status", "<i4")])
 assert L3T_CHAN.itemsize == 128 and L3T_EPOCH.itemsize == 160
+GPS_EPH_FIELDS = ("T_GD", "t_oc", "a_f2", "a_f1", "a_f0", "C_rs", "deltan", "M_0", "C_uc", "e",
+                  "C_us", "sqrtA", "t_oe", "C_ic", "omega_0", "C_is", "i_0", "C_rc", "omega",
+                  "omegaDot", "iDot")   # ephemeris.sci:92-205, the file's order
+GPS_EPH_INTS = ("weekNumber", "accuracy", "health", "IODC", "IODE_sf2", "IODE_sf3", "TOW",
+                "have", "status", "reserved")
+GPS_EPH_OK, GPS_EPH_SHORT, GPS_EPH_UNDECIDED = 0, 1, 2
+GPS_FIX_OK, GPS_FIX_FEW, GPS_FIX_RANK = 0, 1, 2
+
+
+class GpsEph(C.Structure):
+    """gnsscorr_gps_eph"""
+    _fields_ = [(f, C.c_double) for f in GPS_EPH_FIELDS] + [(f, C.c_int32) for f in GPS_EPH_INTS]
+
+
+class GpsFixCfg(C.Structure):
+    """gnsscorr_gps_fix_cfg"""
+    _fields_ = [("samplesPerCode", C.c_double), ("startOffset", C.c_double), ("c", C.c_double),
+                ("elevationMask", C.c_double), ("navSolPeriod", C.c_int32),
+                ("useTropCorr", C.c_int32), ("max_meas", C.c_int32), ("reserved", C.c_int32)]
+
+
+GPS_EPH = np.dtype(GpsEph)
+GPS_FIX_SOL = np.dtype([("X", "<f8"), ("Y", "<f8"), ("Z", "<f8"), ("dt", "<f8"),
+                        ("DOP", "<f8", (5,)), ("lat", "<f8"), ("lon", "<f8"), ("height", "<f8"),
+                        ("status", "<i4"), ("n_used", "<i4")])
+GPS_FIX_CHAN = np.dtype([("el", "<f8"), ("az", "<f8"), ("rawP", "<f8"), ("corrP", "<f8"),
+                         ("used", "<i4"), ("reserved", "<i4")])
+assert GPS_EPH.itemsize == 208 and GPS_FIX_SOL.itemsize == 104 and GPS_FIX_CHAN.itemsize == 40
 SDR_CHAN = np.dtype([("code_phase", "<f8"), ("carrier_phase", "<f8"),
                      ("carrier_phase_prev", "<f8"), ("code_phase_mod", "<f8"),
                      ("carrier_phase_mod", "<f8"), ("code_nco", "<f8"), ("carrier_nco", "<f8"),
@@ -297,6 +325,11 @@ def _sig_table():
         "gnsscorr_nav_glo_strings": (I, [P, P, I64, I64, I, I, I, P, P, P]),
         "gnsscorr_nav_b1_subframes_dev": (I, [P, P, I64, I64, I, I, I, P, P, P]),
         "gnsscorr_nav_b1_subframes": (I, [P, P, I64, I64, I, I, I, P, P, P]),
+        "gnsscorr_nav_gps_ephemeris_dev": (I, [P, P, P, P, I, P]),
+        "gnsscorr_nav_gps_ephemeris": (I, [P, P, P, P, I, P]),
+        "gnsscorr_nav_gps_fix_cfg_init": (None, [P]),
+        "gnsscorr_nav_gps_fix_dev": (I, [P, P, P, P, I64, I64, I, I, P, P, P, P, P]),
+        "gnsscorr_nav_gps_fix": (I, [P, P, P, P, I64, I64, I, I, P, P, P, P, P]),
         "gnsscorr_sdr_prn_codes": (I, [P]),
         "gnsscorr_sdr_sine_gen": (None, [P, D, D, I]),
         **_ctx_sig("gnsscorr_sdr_acq", C.POINTER(SdrAcqCfg)),
@@ -1127,7 +1160,9 @@ class NavCtx(_Handle):
     """Navigation symbols of Galileo E1B and GLONASS L3OC on the device (csrc/navsym.hip):
     page and overlay synchronisation, deinterleaving and the Scilab receiver's K = 7
     Viterbi decoder, one wave per stream; and frame synchronisation and data bits of GPS
-    L1 C/A, GLONASS L1OF and BeiDou B1I (csrc/navbits.hip) from SgtCtx epoch records.  The
+    L1 C/A, GLONASS L1OF and BeiDou B1I (csrc/navbits.hip) from SgtCtx epoch records; and
+    the rest of the GPS L1 receiver (csrc/navfix.hip): ephemeris fields and TOW from those
+    bits, then pseudoranges, satellite positions and least-squares positions.  The
     *_dev calls are queued on the context's stream and read the trackers' epoch records in
     place (epoch_field)."""
 
@@ -1139,7 +1174,8 @@ class NavCtx(_Handle):
                                   "l3_decode", "l3_decode_dev", "pattern_hits",
                                   "pattern_hits_dev", "gps_frames", "gps_frames_dev",
                                   "glo_strings", "glo_strings_dev", "b1_subframes",
-                                  "b1_subframes_dev"))
+                                  "b1_subframes_dev", "gps_ephemeris", "gps_ephemeris_dev",
+                                  "gps_fix", "gps_fix_dev"))
 
     conv_encode = staticmethod(nav_conv_encode)
 
@@ -1278,6 +1314,68 @@ class NavCtx(_Handle):
         _check(self._b1_subframes_dev(self.h, d_series, epoch_stride_bytes, chan_stride_bytes,
                                       n_epochs, n_ch, max_subframes, d_first, d_n_subframes,
                                       d_bits), self._b1_subframes_dev)
+
+    def gps_ephemeris(self, bits, n_bits, first_subframe) -> np.ndarray:
+        """GPS L1: bits [n_ch, 1500], n_bits [n_ch] and first_subframe [n_ch] as gps_frames
+        returns them -> GPS_EPH [n_ch] (ephemeris.sci:82-226; status GPS_EPH_*)."""
+        bits = np.ascontiguousarray(bits, np.uint8).reshape(-1, 1500)
+        n_ch = bits.shape[0]
+        n_bits = np.ascontiguousarray(n_bits, np.int32).reshape(n_ch)
+        first = np.ascontiguousarray(first_subframe, np.int32).reshape(n_ch)
+        eph = np.zeros(n_ch, GPS_EPH)
+        _check(self._gps_ephemeris(self.h, _ptr(bits), _ptr(n_bits), _ptr(first), n_ch,
+                                   _ptr(eph)), self._gps_ephemeris)
+        return eph
+
+    def gps_ephemeris_dev(self, d_bits, d_n_bits, d_first_subframe, n_ch, d_eph):
+        _check(self._gps_ephemeris_dev(self.h, d_bits, d_n_bits, d_first_subframe, n_ch, d_eph),
+               self._gps_ephemeris_dev)
+
+    def gps_fix(self, eph, first_subframe, abs_sample, rx_first, cfg, n_meas=None, sol=None,
+                chan=None):
+        """GPS L1: eph GPS_EPH [n_ch], first_subframe [n_ch], abs_sample [n_ch, n_epochs] fp64
+        (SGT_EPOCH absoluteSample), rx_first [n_rx + 1] channel offsets, cfg from gps_fix_cfg.
+        Returns n_meas [n_rx], sol GPS_FIX_SOL [n_rx, max_meas] and chan GPS_FIX_CHAN
+        [n_ch, max_meas]; rows past n_meas keep what sol and chan held (zeros by default)."""
+        eph = np.ascontiguousarray(eph, GPS_EPH).ravel()
+        n_ch = eph.size
+        first = np.ascontiguousarray(first_subframe, np.int32).reshape(n_ch)
+        series, cs, n_ep, _ = self._series(abs_sample)
+        assert series.shape[0] == n_ch
+        rx_first = np.ascontiguousarray(rx_first, np.int32).ravel()
+        n_rx = rx_first.size - 1
+        n_meas = np.zeros(n_rx, np.int32) if n_meas is None else n_meas
+        sol = np.zeros((n_rx, cfg.max_meas), GPS_FIX_SOL) if sol is None else sol
+        chan = np.zeros((n_ch, cfg.max_meas), GPS_FIX_CHAN) if chan is None else chan
+        _check(self._gps_fix(self.h, _ptr(eph), _ptr(first), _ptr(series), 8, cs, n_ep, n_rx,
+                             _ptr(rx_first), C.addressof(cfg), _ptr(n_meas), _ptr(sol),
+                             _ptr(chan)), self._gps_fix)
+        return n_meas, sol, chan
+
+    def gps_fix_dev(self, d_eph, d_first_subframe, d_abs_sample, epoch_stride_bytes,
+                    chan_stride_bytes, n_epochs, rx_first, cfg, d_n_meas, d_sol, d_chan):
+        """rx_first: a host int32 array of n_rx + 1 offsets (checked before the launch)."""
+        rx_first = np.ascontiguousarray(rx_first, np.int32).ravel()
+        _check(self._gps_fix_dev(self.h, d_eph, d_first_subframe, d_abs_sample,
+                                 epoch_stride_bytes, chan_stride_bytes, n_epochs,
+                                 rx_first.size - 1, _ptr(rx_first),
+                                 C.addressof(cfg) if cfg is not None else None, d_n_meas, d_sol,
+                                 d_chan), self._gps_fix_dev)
+
+
+def gps_fix_cfg(max_meas=1, **kw) -> GpsFixCfg:
+    """GPS/L1/initSettings.sci:103-125 defaults (samplesPerCode 16000, startOffset 68.802,
+    c 299792458, navSolPeriod 500, elevationMask 10, useTropCorr 1); keyword overrides use
+    the Scilab names."""
+    cfg = GpsFixCfg()
+    lib().gnsscorr_nav_gps_fix_cfg_init(C.byref(cfg))
+    cfg.max_meas = int(max_meas)
+    for k, v in kw.items():
+        if k not in ("samplesPerCode", "startOffset", "c", "elevationMask", "navSolPeriod",
+                     "useTropCorr"):
+            raise GnssCorrError(f"gps_fix_cfg: unknown setting {k!r}")
+        setattr(cfg, k, v)
+    return cfg
 
 
 # ---------------------------------------------------------------- GPS-SDR integer acquisition

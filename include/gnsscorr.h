@@ -1047,8 +1047,10 @@ int gnsscorr_nav_l3_decode(gnsscorr_nav_ctx *ctx, const void *h_pilot, const voi
  * reads tracker output in place.  Positions are 0-based epoch indices into the
  * series as passed, -1 for "none".  Bits are uint8 0 or 1, and 2 where the files
  * have 0.5 (a decision sum of exactly 0).  No field decoding, TOW, BCH or
- * Hamming checks, pseudoranges or PVT; the files run no BCH or Hamming check on
- * these paths either.  Bits and positions are exact.
+ * Hamming checks, pseudoranges or PVT here; the files run no BCH or Hamming check
+ * on these paths either.  GPS L1 goes on from these bits to a position in
+ * gnsscorr_nav_gps_ephemeris and gnsscorr_nav_gps_fix below; GLONASS and BeiDou
+ * stop here.  Bits and positions are exact.
  *
  * Pattern search, the files' convol(pattern, sign(x)) cut to its valid part:
  *   r[k] = sum_{i<T} pattern[i] sign(x[k + i]),  first_k <= k < n_epochs,
@@ -1141,6 +1143,142 @@ int gnsscorr_nav_b1_subframes(gnsscorr_nav_ctx *ctx, const void *h_series,
                               int64_t epoch_stride_bytes, int64_t chan_stride_bytes, int n_epochs,
                               int n_ch, int max_subframes, int32_t *h_first,
                               int32_t *h_n_subframes, uint8_t *h_bits);
+
+/* ----------------------------------------------------------------------
+ * GPS L1 position fix (csrc/navfix.hip): what the Scilab GPS receiver does
+ * after the data bits
+ *   GPS/L1/include/ephemeris.sci:82-226, postNavigation.sci:117-282,
+ *   calculatePseudoranges.sci:55-72, geoFunctions/satpos.sci:49-147, check_t.sci,
+ *   leastSquarePos.sci:32-111, e_r_corr.sci, topocent.sci, togeod.sci, tropo.sci,
+ *   cart2geo.sci
+ * Same context as above.  UTM (findUtmZone, cart2utm) is presentation and is not
+ * computed; the GLONASS, BeiDou and Galileo solutions are not part of the library.
+ *
+ * Stage 1, gps_ephemeris: d_bits [n_ch][1500], d_n_bits and d_first_subframe as
+ * gnsscorr_nav_gps_frames_dev writes them (bits already through checkPhase) ->
+ * one gnsscorr_gps_eph per channel.  The subframe ID is bits 50-52 (the file's
+ * 1-based positions) of each of the five subframes; a later subframe with the
+ * same ID overwrites an earlier one; IDs 0, 4, 5, 6, 7 decode nothing.  A field
+ * is the unsigned value of its bit ranges, minus first bit * 2^length where the
+ * file does so, times its scale factors in the file's order (gpsPi =
+ * 3.1415926535898 last): bit-exact.  TOW = value(bits 31-47 of the FIFTH
+ * subframe) * 6 - 30 (:226).  have: bit 0, 1, 2 set when a subframe with ID 1, 2,
+ * 3 was decoded; fields of a subframe that is not there are 0.  The reference
+ * stops on a 0.5 bit and on fewer than five subframes; here n_bits < 1500 or
+ * first_subframe < 0 gives status SHORT, else any bit above 1 inside the 1500
+ * gives UNDECIDED, and for both have = 0 and every field is 0.
+ * ---------------------------------------------------------------------- */
+#define GNSSCORR_GPS_EPH_OK        0
+#define GNSSCORR_GPS_EPH_SHORT     1
+#define GNSSCORR_GPS_EPH_UNDECIDED 2
+
+typedef struct {          /* ephemeris.sci:92-205, in the file's order */
+  double  T_GD, t_oc, a_f2, a_f1, a_f0;
+  double  C_rs, deltan, M_0, C_uc, e, C_us, sqrtA, t_oe;
+  double  C_ic, omega_0, C_is, i_0, C_rc, omega, omegaDot, iDot;
+  int32_t weekNumber, accuracy, health, IODC, IODE_sf2, IODE_sf3;
+  int32_t TOW;
+  int32_t have;
+  int32_t status;
+  int32_t reserved;
+} gnsscorr_gps_eph;
+
+int gnsscorr_nav_gps_ephemeris_dev(gnsscorr_nav_ctx *ctx, const uint8_t *d_bits,
+                                   const int32_t *d_n_bits, const int32_t *d_first_subframe,
+                                   int n_ch, gnsscorr_gps_eph *d_eph);
+int gnsscorr_nav_gps_ephemeris(gnsscorr_nav_ctx *ctx, const uint8_t *h_bits,
+                               const int32_t *h_n_bits, const int32_t *h_first_subframe,
+                               int n_ch, gnsscorr_gps_eph *h_eph);
+
+/* Stage 2, gps_fix: the measurement loop of postNavigation.sci:138-282, one
+ * wave per receiver.  Receiver r owns channels rx_first[r] .. rx_first[r + 1] - 1
+ * (rx_first: a HOST array of n_rx + 1 ascending offsets from 0 in both forms, 1
+ * to 64 channels each); ephemerides are kept per channel, not per PRN.
+ * d_abs_sample is a series argument (above): &d_epochs[0].absolute_sample with
+ * strides sizeof(gnsscorr_sgt_epoch) and n_epochs * sizeof(gnsscorr_sgt_epoch)
+ * reads tracker output in place.  Indices below are 0-based.
+ *  - ready: first_subframe >= 0, status OK and have == 7 (:120-126).  Fewer than
+ *    4 ready channels: n_meas = 0 (:130).  Else n_meas = min(max_meas,
+ *    fix((n_epochs - (max p + 1)) / navSolPeriod)), the max over every channel of
+ *    the receiver with first_subframe = p >= 0 (:163).
+ *  - transmitTime starts as the TOW of the receiver's highest-numbered channel
+ *    with first_subframe >= 0 and status OK, ready or not: the file's loop
+ *    variable is overwritten per channel (:117,152).  satElev starts at +inf.
+ *  - measurement m: active = ready and satElev >= elevationMask; el, az of every
+ *    channel NaN (so an excluded satellite never returns: the file's known issue
+ *    :271-275); rawP = (absoluteSample[ch][p_ch + navSolPeriod m] / samplesPerCode
+ *    - floor(min over active) + startOffset) * (c / 1000), +inf for the others
+ *    (NaN for all when none is active): bit-exact;
+ *  - satpos.sci per active channel from its own ephemeris; the two-argument
+ *    atand of Scilab is read as (180 / %pi) * atan(y, x);
+ *  - fewer than 4 active: X Y Z dt lat lon height NaN, DOP 0, status FEW, satElev
+ *    kept (:245-269);
+ *  - else leastSquarePos.sci: 7 iterations from 0, e_r_corr, topocent / togeod,
+ *    tropo(sin(el), 0, 1013, 293, 50, 0, 0, 0) when useTropCorr == 1, rows of A
+ *    divided by obs(i) as the file has them.  A \ omc is solved through the normal
+ *    equations A'A x = A'omc by an LDL' factorisation in column order, Q = inv(A'A)
+ *    from the same factors; then corrP = rawP + satClkCorr c + dt (:220-222),
+ *    cart2geo(X, Y, Z, 5), satElev = el (NaN for channels outside active);
+ *  - rank rule: rank(A) ~= 4 when a pivot of that factorisation is not above
+ *    1e-12 times the same column's diagonal entry of A'A (column k of A within
+ *    1e-6 rad of the span of the columns before it; a NaN counts as deficient).
+ *    The file returns a zero position and its caller stops on an unset variable;
+ *    here X Y Z dt lat lon height and DOP are 0, el and az NaN, status RANK,
+ *    satElev kept, and the loop goes on: the one widening;
+ *  - transmitTime += navSolPeriod / 1000.
+ * Outputs: d_n_meas[n_rx]; d_sol [n_rx][max_meas]; d_chan [n_ch][max_meas]
+ * (corrP is 0 where the file assigns none); rows m >= n_meas are not written.
+ * The _dev form queues one copy of rx_first (pageable host memory, n_rx + 1
+ * words) in front of the kernel, into a buffer of the context that is replaced,
+ * with a device synchronisation, only when n_rx exceeds every earlier call's.
+ * Refused with GNSSCORR_EINVAL before any device call: a null pointer, n_rx < 1,
+ * rx_first not ascending from 0, a receiver of more than 64 channels,
+ * navSolPeriod < 1, samplesPerCode <= 0, max_meas < 1, a bad series argument. */
+#define GNSSCORR_GPS_FIX_OK   0
+#define GNSSCORR_GPS_FIX_FEW  1
+#define GNSSCORR_GPS_FIX_RANK 2
+
+typedef struct {          /* initSettings.sci:103-125 */
+  double  samplesPerCode; /* 16000 = 16e6 / (1.023e6 / 1023)                  */
+  double  startOffset;    /* 68.802 [ms]                                      */
+  double  c;              /* 299792458                                        */
+  double  elevationMask;  /* 10 [deg]                                         */
+  int32_t navSolPeriod;   /* 500 [ms]                                         */
+  int32_t useTropCorr;    /* 1                                                */
+  int32_t max_meas;       /* rows of d_sol and d_chan per receiver / channel  */
+  int32_t reserved;
+} gnsscorr_gps_fix_cfg;
+
+typedef struct {
+  double  X, Y, Z, dt;
+  double  DOP[5];         /* GDOP PDOP HDOP VDOP TDOP                         */
+  double  lat, lon, height;
+  int32_t status;
+  int32_t n_used;         /* channels in active                               */
+} gnsscorr_gps_fix_sol;
+
+typedef struct {
+  double  el, az, rawP, corrP;
+  int32_t used;           /* 1: in active at this measurement                 */
+  int32_t reserved;
+} gnsscorr_gps_fix_chan;
+
+/* the defaults above, max_meas = 1 */
+void gnsscorr_nav_gps_fix_cfg_init(gnsscorr_gps_fix_cfg *cfg);
+int gnsscorr_nav_gps_fix_dev(gnsscorr_nav_ctx *ctx, const gnsscorr_gps_eph *d_eph,
+                             const int32_t *d_first_subframe, const void *d_abs_sample,
+                             int64_t epoch_stride_bytes, int64_t chan_stride_bytes,
+                             int n_epochs, int n_rx, const int32_t *rx_first,
+                             const gnsscorr_gps_fix_cfg *cfg, int32_t *d_n_meas,
+                             gnsscorr_gps_fix_sol *d_sol, gnsscorr_gps_fix_chan *d_chan);
+/* Same with host arrays (synchronous); rows m >= n_meas of h_sol and h_chan keep
+ * what the caller put there. */
+int gnsscorr_nav_gps_fix(gnsscorr_nav_ctx *ctx, const gnsscorr_gps_eph *h_eph,
+                         const int32_t *h_first_subframe, const void *h_abs_sample,
+                         int64_t epoch_stride_bytes, int64_t chan_stride_bytes, int n_epochs,
+                         int n_rx, const int32_t *rx_first, const gnsscorr_gps_fix_cfg *cfg,
+                         int32_t *h_n_meas, gnsscorr_gps_fix_sol *h_sol,
+                         gnsscorr_gps_fix_chan *h_chan);
 
 /* ======================================================================
  * GPS-SDR integer strong acquisition ("sdr"), bit-exact with the real-time
