@@ -1,5 +1,5 @@
-// ftrack.h -- what the two float trackers (sgt.hip, e1t.hip) share: lane
-// helpers and the carrier rotation, the chunk grid of the chunked paths
+// ftrack.h -- what the three float trackers (sgt.hip, e1t.hip, l3t.hip) share:
+// lane helpers and the carrier rotation, the chunk grid of the chunked paths
 // (geometry and the crossing estimate with its margin), the loop-filter steps
 // of the epoch end and the host wrappers around a tracking context (on the
 // shared host scaffolding of hostctx.h).
@@ -307,22 +307,13 @@ int replay(const char* fn, Ctx* c, int n_ch, Chan* h_chan, int n_epochs, const d
   if (!c || !h_chan || !h_sums || !h_ep || n_ch < 1 || n_epochs < 1) return bad_arguments(fn);
   HIP_TRY(hipSetDevice(c->cfg.device));
   const size_t nc = (size_t)n_ch, ne = nc * (size_t)n_epochs;
-  hostctx::TempBuf<Chan> d_chan;
-  hostctx::TempBuf<double> d_sums;
-  hostctx::TempBuf<Epoch> d_ep;
-  int rc = hostctx::grow(d_chan, nc);
-  if (!rc) rc = hostctx::grow(d_sums, ne * N);
-  if (!rc) rc = hostctx::grow(d_ep, ne);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(d_chan.p, h_chan, nc * sizeof(Chan), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d_sums.p, h_sums, ne * N * sizeof(double), hipMemcpyHostToDevice,
-                         c->stream));
-  rc = replay_dev(d_chan.p, d_sums.p, d_ep.p);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h_chan, d_chan.p, nc * sizeof(Chan), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(h_ep, d_ep.p, ne * sizeof(Epoch), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GNSSCORR_OK;
+  hostctx::Staging st(c->stream);
+  Chan* d_chan = st.inout(h_chan, nc);
+  double* d_sums = st.in(h_sums, ne * N);
+  Epoch* d_ep = st.out(h_ep, ne);
+  if (st.status()) return st.status();
+  const int rc = replay_dev(d_chan, d_sums, d_ep);
+  return rc ? rc : st.finish();
 }
 
 }  // namespace ftrack

@@ -14,9 +14,17 @@
 //    is already freed, nothing dangles, and a later grow() starts from scratch.
 //    Work queued on the old block must have finished before grow() is called;
 //    the host wrappers that use it end in a stream synchronise.
-//  - A TempBuf belongs to the scope that declares it and is freed on every
-//    path out of that scope.  hipFree waits for the device, so copies and
-//    kernels still queued on the buffer at an early return finish first.
+//  - A Staging belongs to one host-array call, the twin of a *_dev call, and
+//    owns the device copies of that call's host arrays: up to kMaxBlocks blocks,
+//    each from a hipMalloc of its own, freed on every path out of the scope that
+//    declares it.  hipFree waits for the device, so copies and kernels still
+//    queued on a block at an early return finish first.  in() queues the upload
+//    as it allocates; out() and inout() remember the host array, and finish()
+//    queues those downloads in the order they were declared and synchronises the
+//    stream.  The first failing call makes status() sticky: later in / out /
+//    inout calls do nothing and return null, so the twin tests status() once,
+//    before it hands the pointers to the *_dev call.  The host arrays stay the
+//    caller's; only finish() writes to them.
 //  - create() builds the context and then runs the family's init helper, which
 //    returns early on the first failing HIP call (HIP_TRY: the call's own error
 //    string, GNSSCORR_EDEVICE) or host allocation (GNSSCORR_ENOMEM).  A failed
@@ -77,13 +85,72 @@ int grow(DevBuf<T>& b, size_t n) {
   return GNSSCORR_OK;
 }
 
-// a device buffer that lives for one host call
-template <class T>
-struct TempBuf : DevBuf<T> {
-  TempBuf() = default;
-  TempBuf(const TempBuf&) = delete;
-  TempBuf& operator=(const TempBuf&) = delete;
-  ~TempBuf() { release(*this); }
+// the device copies of one host-array call's arguments, on the context's stream:
+//   Staging st(c->stream);
+//   const T* d_x = st.in(h_x, n);  U* d_y = st.out(h_y, m);
+//   if (st.status()) return st.status();
+//   rc = ..._dev(c, d_x, ..., d_y);
+//   return rc ? rc : st.finish();
+// n counts elements and may be 0: the block is still a valid device pointer, and
+// nothing is copied either way.  A block is the call's own copy, so in() hands
+// it out non-const as well.
+class Staging {
+ public:
+  static constexpr int kMaxBlocks = 8;
+  explicit Staging(hipStream_t stream) : stream_(stream) {}
+  Staging(const Staging&) = delete;
+  Staging& operator=(const Staging&) = delete;
+  ~Staging() {
+    for (int i = 0; i < n_; i++) (void)hipFree(blk_[i].d);
+  }
+
+  template <class T>
+  T* in(const T* h, size_t n) { return (T*)stage(h, nullptr, n * sizeof(T)); }
+  template <class T>
+  T* out(T* h, size_t n) { return (T*)stage(nullptr, h, n * sizeof(T)); }
+  template <class T>
+  T* inout(T* h, size_t n) { return (T*)stage(h, h, n * sizeof(T)); }
+
+  int status() const { return rc_; }
+
+  // the downloads in declaration order, then one synchronise
+  int finish() {
+    if (rc_) return rc_;
+    for (int i = 0; i < n_; i++)
+      if (blk_[i].h_out && blk_[i].bytes)
+        HIP_TRY(hipMemcpyAsync(blk_[i].h_out, blk_[i].d, blk_[i].bytes, hipMemcpyDeviceToHost,
+                               stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    return GNSSCORR_OK;
+  }
+
+ private:
+  struct Block {
+    void* d;
+    void* h_out;     // null: nothing to download
+    size_t bytes;
+  };
+
+  void* stage(const void* h_in, void* h_out, size_t bytes) {
+    void* d = nullptr;
+    if (!rc_) rc_ = add(h_in, h_out, bytes, &d);
+    return rc_ ? nullptr : d;
+  }
+  int add(const void* h_in, void* h_out, size_t bytes, void** d) {
+    if (n_ == kMaxBlocks) {
+      gnsscorr_set_error("hostctx::Staging: more than %d blocks in one call", kMaxBlocks);
+      return GNSSCORR_EINVAL;
+    }
+    HIP_TRY(hipMalloc(d, bytes ? bytes : 1));
+    blk_[n_++] = Block{*d, h_out, bytes};        // owned from here on
+    if (h_in && bytes) HIP_TRY(hipMemcpyAsync(*d, h_in, bytes, hipMemcpyHostToDevice, stream_));
+    return GNSSCORR_OK;
+  }
+
+  hipStream_t stream_;
+  Block blk_[kMaxBlocks];
+  int n_ = 0;
+  int rc_ = GNSSCORR_OK;
 };
 
 // Ctx below: any context with cfg.device and stream.

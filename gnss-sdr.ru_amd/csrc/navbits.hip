@@ -461,42 +461,6 @@ extern "C" int gnsscorr_nav_pattern_hits_dev(gnsscorr_nav_ctx* c, const void* d_
   return GNSSCORR_OK;
 }
 
-namespace {
-// a host-array twin's device copies: the series in, up to three results out
-struct HostTwin {
-  gnsscorr_nav_ctx* c;
-  hostctx::TempBuf<double> d_in;
-  hostctx::TempBuf<int32_t> d_a, d_b, d_hits;
-  hostctx::TempBuf<uint8_t> d_bits;
-  int n_ch;
-  int upload(const void* h_series, int64_t epoch_stride, int64_t chan_stride, int n_epochs,
-             size_t n_hits, size_t n_bits) {
-    const size_t n_in = series_bytes(epoch_stride, chan_stride, n_epochs, n_ch);
-    int rc = hostctx::grow(d_in, (n_in + 7) / 8);
-    if (!rc) rc = hostctx::grow(d_a, (size_t)n_ch);
-    if (!rc) rc = hostctx::grow(d_b, (size_t)n_ch);
-    if (!rc && n_hits) rc = hostctx::grow(d_hits, n_hits);
-    if (!rc && n_bits) rc = hostctx::grow(d_bits, n_bits);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(d_in.p, h_series, n_in, hipMemcpyHostToDevice, c->stream));
-    return GNSSCORR_OK;
-  }
-  int download(int32_t* h_a, int32_t* h_b, int32_t* h_hits, size_t n_hits, uint8_t* h_bits,
-               size_t n_bits) {
-    const size_t ni = (size_t)n_ch * sizeof(int32_t);
-    HIP_TRY(hipMemcpyAsync(h_a, d_a.p, ni, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(h_b, d_b.p, ni, hipMemcpyDeviceToHost, c->stream));
-    if (n_hits)
-      HIP_TRY(hipMemcpyAsync(h_hits, d_hits.p, n_hits * sizeof(int32_t), hipMemcpyDeviceToHost,
-                             c->stream));
-    if (n_bits)
-      HIP_TRY(hipMemcpyAsync(h_bits, d_bits.p, n_bits, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return GNSSCORR_OK;
-  }
-};
-}  // namespace
-
 extern "C" int gnsscorr_nav_pattern_hits(gnsscorr_nav_ctx* c, const void* h_series,
                                          int64_t epoch_stride_bytes, int64_t chan_stride_bytes,
                                          int n_epochs, int n_ch, const int8_t* pattern, int T,
@@ -508,16 +472,17 @@ extern "C" int gnsscorr_nav_pattern_hits(gnsscorr_nav_ctx* c, const void* h_seri
   if (rc) return rc;
   if ((int64_t)n_ch * max_hits > INT_MAX) return bad_arguments(__func__, "n_ch * max_hits < 2^31");
   HIP_TRY(hipSetDevice(c->cfg.device));
-  HostTwin t{c};
-  t.n_ch = n_ch;
-  const size_t nh = (size_t)n_ch * max_hits;
-  rc = t.upload(h_series, epoch_stride_bytes, chan_stride_bytes, n_epochs, nh, 0);
-  if (rc) return rc;
-  rc = gnsscorr_nav_pattern_hits_dev(c, t.d_in.p, epoch_stride_bytes, chan_stride_bytes, n_epochs,
-                                     n_ch, pattern, T, threshold, first_k, max_hits, t.d_a.p,
-                                     t.d_b.p, t.d_hits.p);
-  if (rc) return rc;
-  return t.download(h_first, h_n_hits, h_hits, nh, nullptr, 0);
+  hostctx::Staging st(c->stream);
+  const char* d_series = st.in(
+      (const char*)h_series, series_bytes(epoch_stride_bytes, chan_stride_bytes, n_epochs, n_ch));
+  int32_t* d_first = st.out(h_first, (size_t)n_ch);
+  int32_t* d_n_hits = st.out(h_n_hits, (size_t)n_ch);
+  int32_t* d_hits = st.out(h_hits, (size_t)n_ch * max_hits);
+  if (st.status()) return st.status();
+  rc = gnsscorr_nav_pattern_hits_dev(c, d_series, epoch_stride_bytes, chan_stride_bytes, n_epochs,
+                                     n_ch, pattern, T, threshold, first_k, max_hits, d_first,
+                                     d_n_hits, d_hits);
+  return rc ? rc : st.finish();
 }
 
 // what the three chains check after the series
@@ -575,16 +540,17 @@ extern "C" int gnsscorr_nav_gps_frames(gnsscorr_nav_ctx* c, const void* h_series
                      search_start, max_subframes, h_first_subframe, h_n_bits, h_bits);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->cfg.device));
-  HostTwin t{c};
-  t.n_ch = n_ch;
-  const size_t nb = (size_t)n_ch * kGpsBits;
-  rc = t.upload(h_series, epoch_stride_bytes, chan_stride_bytes, n_epochs, 0, nb);
-  if (rc) return rc;
-  rc = gnsscorr_nav_gps_frames_dev(c, t.d_in.p, epoch_stride_bytes, chan_stride_bytes, n_epochs,
-                                   n_ch, search_start, max_subframes, t.d_a.p, t.d_b.p,
-                                   t.d_bits.p);
-  if (rc) return rc;
-  return t.download(h_first_subframe, h_n_bits, nullptr, 0, h_bits, nb);
+  hostctx::Staging st(c->stream);
+  const char* d_series = st.in(
+      (const char*)h_series, series_bytes(epoch_stride_bytes, chan_stride_bytes, n_epochs, n_ch));
+  int32_t* d_first_subframe = st.out(h_first_subframe, (size_t)n_ch);
+  int32_t* d_n_bits = st.out(h_n_bits, (size_t)n_ch);
+  uint8_t* d_bits = st.out(h_bits, (size_t)n_ch * kGpsBits);
+  if (st.status()) return st.status();
+  rc = gnsscorr_nav_gps_frames_dev(c, d_series, epoch_stride_bytes, chan_stride_bytes, n_epochs,
+                                   n_ch, search_start, max_subframes, d_first_subframe, d_n_bits,
+                                   d_bits);
+  return rc ? rc : st.finish();
 }
 
 // ---- GLONASS L1OF and BeiDou B1I: the first hit, then one block per string
@@ -613,27 +579,6 @@ static int first_hit_chain(const char* fn, gnsscorr_nav_ctx* c, const void* d_se
   return GNSSCORR_OK;
 }
 
-template <class DevCall>
-static int first_hit_chain_host(const char* fn, gnsscorr_nav_ctx* c, const void* h_series,
-                                int64_t epoch_stride, int64_t chan_stride, int n_epochs, int n_ch,
-                                int limit, const char* limit_text, size_t bits_per_ch,
-                                DevCall dev_call, int32_t* h_first, int32_t* h_count,
-                                uint8_t* h_bits) {
-  int rc = check_series(fn, c, h_series, epoch_stride, chan_stride, n_epochs, n_ch);
-  if (!rc) rc = check_chain(fn, limit, limit_text, h_first, h_count, h_bits);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  HostTwin t{c};
-  t.n_ch = n_ch;
-  const size_t nb = (size_t)n_ch * bits_per_ch;
-  rc = t.upload(h_series, epoch_stride, chan_stride, n_epochs, 0, nb);
-  if (rc) return rc;
-  rc = dev_call(c, t.d_in.p, epoch_stride, chan_stride, n_epochs, n_ch, limit, t.d_a.p, t.d_b.p,
-                t.d_bits.p);
-  if (rc) return rc;
-  return t.download(h_first, h_count, nullptr, 0, h_bits, nb);
-}
-
 extern "C" int gnsscorr_nav_glo_strings_dev(gnsscorr_nav_ctx* c, const void* d_series,
                                             int64_t epoch_stride_bytes,
                                             int64_t chan_stride_bytes, int n_epochs, int n_ch,
@@ -650,10 +595,22 @@ extern "C" int gnsscorr_nav_glo_strings(gnsscorr_nav_ctx* c, const void* h_serie
                                         int n_epochs, int n_ch, int max_strings,
                                         int32_t* h_first_mark, int32_t* h_n_strings,
                                         uint8_t* h_bits) {
-  return first_hit_chain_host(__func__, c, h_series, epoch_stride_bytes, chan_stride_bytes,
-                              n_epochs, n_ch, max_strings, "max_strings >= 1",
-                              (size_t)kGloMaxStrings * kGloBits, gnsscorr_nav_glo_strings_dev,
-                              h_first_mark, h_n_strings, h_bits);
+  int rc = check_series(__func__, c, h_series, epoch_stride_bytes, chan_stride_bytes, n_epochs,
+                        n_ch);
+  if (!rc)
+    rc = check_chain(__func__, max_strings, "max_strings >= 1", h_first_mark, h_n_strings, h_bits);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  hostctx::Staging st(c->stream);
+  const char* d_series = st.in(
+      (const char*)h_series, series_bytes(epoch_stride_bytes, chan_stride_bytes, n_epochs, n_ch));
+  int32_t* d_first_mark = st.out(h_first_mark, (size_t)n_ch);
+  int32_t* d_n_strings = st.out(h_n_strings, (size_t)n_ch);
+  uint8_t* d_bits = st.out(h_bits, (size_t)n_ch * kGloMaxStrings * kGloBits);
+  if (st.status()) return st.status();
+  rc = gnsscorr_nav_glo_strings_dev(c, d_series, epoch_stride_bytes, chan_stride_bytes, n_epochs,
+                                    n_ch, max_strings, d_first_mark, d_n_strings, d_bits);
+  return rc ? rc : st.finish();
 }
 
 extern "C" int gnsscorr_nav_b1_subframes_dev(gnsscorr_nav_ctx* c, const void* d_series,
@@ -672,8 +629,20 @@ extern "C" int gnsscorr_nav_b1_subframes(gnsscorr_nav_ctx* c, const void* h_seri
                                          int n_epochs, int n_ch, int max_subframes,
                                          int32_t* h_first, int32_t* h_n_subframes,
                                          uint8_t* h_bits) {
-  return first_hit_chain_host(__func__, c, h_series, epoch_stride_bytes, chan_stride_bytes,
-                              n_epochs, n_ch, max_subframes, "max_subframes >= 1",
-                              (size_t)kB1MaxSub * kB1Bits, gnsscorr_nav_b1_subframes_dev, h_first,
-                              h_n_subframes, h_bits);
+  int rc = check_series(__func__, c, h_series, epoch_stride_bytes, chan_stride_bytes, n_epochs,
+                        n_ch);
+  if (!rc)
+    rc = check_chain(__func__, max_subframes, "max_subframes >= 1", h_first, h_n_subframes, h_bits);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  hostctx::Staging st(c->stream);
+  const char* d_series = st.in(
+      (const char*)h_series, series_bytes(epoch_stride_bytes, chan_stride_bytes, n_epochs, n_ch));
+  int32_t* d_first = st.out(h_first, (size_t)n_ch);
+  int32_t* d_n_subframes = st.out(h_n_subframes, (size_t)n_ch);
+  uint8_t* d_bits = st.out(h_bits, (size_t)n_ch * kB1MaxSub * kB1Bits);
+  if (st.status()) return st.status();
+  rc = gnsscorr_nav_b1_subframes_dev(c, d_series, epoch_stride_bytes, chan_stride_bytes, n_epochs,
+                                     n_ch, max_subframes, d_first, d_n_subframes, d_bits);
+  return rc ? rc : st.finish();
 }

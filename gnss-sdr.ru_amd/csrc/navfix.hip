@@ -578,24 +578,15 @@ extern "C" int gnsscorr_nav_gps_ephemeris(gnsscorr_nav_ctx* c, const uint8_t* h_
   int rc = check_eph(__func__, c, h_bits, h_n_bits, h_first_subframe, n_ch, h_eph);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->cfg.device));
-  hostctx::TempBuf<uint8_t> d_bits;
-  hostctx::TempBuf<int32_t> d_n, d_first;
-  hostctx::TempBuf<gnsscorr_gps_eph> d_eph;
   const size_t n = (size_t)n_ch;
-  rc = hostctx::grow(d_bits, n * kGpsBits);
-  if (!rc) rc = hostctx::grow(d_n, n);
-  if (!rc) rc = hostctx::grow(d_first, n);
-  if (!rc) rc = hostctx::grow(d_eph, n);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(d_bits.p, h_bits, n * kGpsBits, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d_n.p, h_n_bits, n * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d_first.p, h_first_subframe, n * 4, hipMemcpyHostToDevice, c->stream));
-  rc = gnsscorr_nav_gps_ephemeris_dev(c, d_bits.p, d_n.p, d_first.p, n_ch, d_eph.p);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h_eph, d_eph.p, n * sizeof(gnsscorr_gps_eph), hipMemcpyDeviceToHost,
-                         c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GNSSCORR_OK;
+  hostctx::Staging st(c->stream);
+  const uint8_t* d_bits = st.in(h_bits, n * kGpsBits);
+  const int32_t* d_n_bits = st.in(h_n_bits, n);
+  const int32_t* d_first_subframe = st.in(h_first_subframe, n);
+  gnsscorr_gps_eph* d_eph = st.out(h_eph, n);
+  if (st.status()) return st.status();
+  rc = gnsscorr_nav_gps_ephemeris_dev(c, d_bits, d_n_bits, d_first_subframe, n_ch, d_eph);
+  return rc ? rc : st.finish();
 }
 
 static int check_fix(const char* fn, const gnsscorr_nav_ctx* c, const void* eph,
@@ -683,32 +674,17 @@ extern "C" int gnsscorr_nav_gps_fix(gnsscorr_nav_ctx* c, const gnsscorr_gps_eph*
   HIP_TRY(hipSetDevice(c->cfg.device));
   const size_t n_ch = (size_t)rx_first[n_rx], mm = (size_t)cfg->max_meas;
   const size_t n_in = series_bytes(epoch_stride_bytes, chan_stride_bytes, n_epochs, (int)n_ch);
-  hostctx::TempBuf<gnsscorr_gps_eph> d_eph;
-  hostctx::TempBuf<int32_t> d_first, d_n_meas;
-  hostctx::TempBuf<double> d_in;
-  hostctx::TempBuf<gnsscorr_gps_fix_sol> d_sol;
-  hostctx::TempBuf<gnsscorr_gps_fix_chan> d_chan;
-  rc = hostctx::grow(d_eph, n_ch);
-  if (!rc) rc = hostctx::grow(d_first, n_ch);
-  if (!rc) rc = hostctx::grow(d_n_meas, (size_t)n_rx);
-  if (!rc) rc = hostctx::grow(d_in, (n_in + 7) / 8);
-  if (!rc) rc = hostctx::grow(d_sol, (size_t)n_rx * mm);
-  if (!rc) rc = hostctx::grow(d_chan, n_ch * mm);
-  if (rc) return rc;
-  const hipStream_t s = c->stream;
-  HIP_TRY(hipMemcpyAsync(d_eph.p, h_eph, n_ch * sizeof *h_eph, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_first.p, h_first_subframe, n_ch * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_in.p, h_abs_sample, n_in, hipMemcpyHostToDevice, s));
-  // rows past n_meas stay as the caller has them
-  HIP_TRY(hipMemcpyAsync(d_sol.p, h_sol, (size_t)n_rx * mm * sizeof *h_sol, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_chan.p, h_chan, n_ch * mm * sizeof *h_chan, hipMemcpyHostToDevice, s));
-  rc = gnsscorr_nav_gps_fix_dev(c, d_eph.p, d_first.p, d_in.p, epoch_stride_bytes,
-                                chan_stride_bytes, n_epochs, n_rx, rx_first, cfg, d_n_meas.p,
-                                d_sol.p, d_chan.p);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h_n_meas, d_n_meas.p, (size_t)n_rx * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(h_sol, d_sol.p, (size_t)n_rx * mm * sizeof *h_sol, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(h_chan, d_chan.p, n_ch * mm * sizeof *h_chan, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return GNSSCORR_OK;
+  hostctx::Staging st(c->stream);
+  const gnsscorr_gps_eph* d_eph = st.in(h_eph, n_ch);
+  const int32_t* d_first_subframe = st.in(h_first_subframe, n_ch);
+  int32_t* d_n_meas = st.out(h_n_meas, (size_t)n_rx);
+  const char* d_abs_sample = st.in((const char*)h_abs_sample, n_in);
+  // uploaded too: rows past n_meas stay as the caller has them
+  gnsscorr_gps_fix_sol* d_sol = st.inout(h_sol, (size_t)n_rx * mm);
+  gnsscorr_gps_fix_chan* d_chan = st.inout(h_chan, n_ch * mm);
+  if (st.status()) return st.status();
+  rc = gnsscorr_nav_gps_fix_dev(c, d_eph, d_first_subframe, d_abs_sample, epoch_stride_bytes,
+                                chan_stride_bytes, n_epochs, n_rx, rx_first, cfg, d_n_meas, d_sol,
+                                d_chan);
+  return rc ? rc : st.finish();
 }

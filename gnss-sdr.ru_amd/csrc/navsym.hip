@@ -415,17 +415,23 @@ extern "C" int gnsscorr_nav_viterbi(gnsscorr_nav_ctx* c, const void* h_code,
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->cfg.device));
   const size_t n_in = (size_t)(n_streams - 1) * stream_stride_bytes + (size_t)(soft ? 16 : 2) * L;
-  const size_t n_out = (size_t)n_streams * L;
-  hostctx::TempBuf<double> d_in;               // fp64 elements: aligned for either input
-  hostctx::TempBuf<uint8_t> d_out;
-  rc = hostctx::grow(d_in, (n_in + 7) / 8);
-  if (!rc) rc = hostctx::grow(d_out, n_out);
+  hostctx::Staging st(c->stream);
+  const char* d_code = st.in((const char*)h_code, n_in);
+  uint8_t* d_bits = st.out(h_bits, (size_t)n_streams * L);
+  if (st.status()) return st.status();
+  rc = gnsscorr_nav_viterbi_dev(c, d_code, stream_stride_bytes, n_streams, L, soft, d_bits);
+  return rc ? rc : st.finish();
+}
+
+static int check_e1(const char* fn, const gnsscorr_nav_ctx* c, const void* series,
+                    int64_t epoch_stride, int64_t chan_stride, int n_epochs, int n_ch,
+                    int max_pages, const void* first_page, const void* n_pages,
+                    const void* bits) {
+  int rc = check_series(fn, c, series, epoch_stride, chan_stride, n_epochs, n_ch);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(d_in.p, h_code, n_in, hipMemcpyHostToDevice, c->stream));
-  rc = gnsscorr_nav_viterbi_dev(c, d_in.p, stream_stride_bytes, n_streams, L, soft, d_out.p);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h_bits, d_out.p, n_out, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (!first_page || !n_pages || !bits) return bad_arguments(fn, "null pointer");
+  if (max_pages < 1 || (int64_t)n_ch * max_pages > INT_MAX)
+    return bad_arguments(fn, "max_pages >= 1, n_ch * max_pages < 2^31");
   return GNSSCORR_OK;
 }
 
@@ -434,12 +440,9 @@ extern "C" int gnsscorr_nav_e1_pages_dev(gnsscorr_nav_ctx* c, const void* d_seri
                                          int n_epochs, int n_ch, int max_pages,
                                          int32_t* d_first_page, int32_t* d_n_pages,
                                          uint8_t* d_bits) {
-  int rc = check_series(__func__, c, d_series, epoch_stride_bytes, chan_stride_bytes, n_epochs,
-                        n_ch);
+  int rc = check_e1(__func__, c, d_series, epoch_stride_bytes, chan_stride_bytes, n_epochs, n_ch,
+                    max_pages, d_first_page, d_n_pages, d_bits);
   if (rc) return rc;
-  if (!d_first_page || !d_n_pages || !d_bits) return bad_arguments(__func__, "null pointer");
-  if (max_pages < 1 || (int64_t)n_ch * max_pages > INT_MAX)
-    return bad_arguments(__func__, "max_pages >= 1, n_ch * max_pages < 2^31");
   HIP_TRY(hipSetDevice(c->cfg.device));
   const int64_t n_streams = (int64_t)n_ch * max_pages;
   rc = hostctx::grow(c->d_code, (size_t)n_streams * kE1Syms);
@@ -461,33 +464,20 @@ extern "C" int gnsscorr_nav_e1_pages(gnsscorr_nav_ctx* c, const void* h_series,
                                      int64_t epoch_stride_bytes, int64_t chan_stride_bytes,
                                      int n_epochs, int n_ch, int max_pages, int32_t* h_first_page,
                                      int32_t* h_n_pages, uint8_t* h_bits) {
-  int rc = check_series(__func__, c, h_series, epoch_stride_bytes, chan_stride_bytes, n_epochs,
-                        n_ch);
+  int rc = check_e1(__func__, c, h_series, epoch_stride_bytes, chan_stride_bytes, n_epochs, n_ch,
+                    max_pages, h_first_page, h_n_pages, h_bits);
   if (rc) return rc;
-  if (!h_first_page || !h_n_pages || !h_bits) return bad_arguments(__func__, "null pointer");
-  if (max_pages < 1 || (int64_t)n_ch * max_pages > INT_MAX)
-    return bad_arguments(__func__, "max_pages >= 1, n_ch * max_pages < 2^31");
   HIP_TRY(hipSetDevice(c->cfg.device));
-  const size_t n_in = series_bytes(epoch_stride_bytes, chan_stride_bytes, n_epochs, n_ch);
-  const size_t n_out = (size_t)n_ch * max_pages * kE1Bits;
-  hostctx::TempBuf<double> d_in;
-  hostctx::TempBuf<int32_t> d_first, d_np;
-  hostctx::TempBuf<uint8_t> d_out;
-  rc = hostctx::grow(d_in, (n_in + 7) / 8);
-  if (!rc) rc = hostctx::grow(d_first, (size_t)n_ch);
-  if (!rc) rc = hostctx::grow(d_np, (size_t)n_ch);
-  if (!rc) rc = hostctx::grow(d_out, n_out);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(d_in.p, h_series, n_in, hipMemcpyHostToDevice, c->stream));
-  rc = gnsscorr_nav_e1_pages_dev(c, d_in.p, epoch_stride_bytes, chan_stride_bytes, n_epochs, n_ch,
-                                 max_pages, d_first.p, d_np.p, d_out.p);
-  if (rc) return rc;
-  const size_t ni = (size_t)n_ch * sizeof(int32_t);
-  HIP_TRY(hipMemcpyAsync(h_first_page, d_first.p, ni, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(h_n_pages, d_np.p, ni, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(h_bits, d_out.p, n_out, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GNSSCORR_OK;
+  hostctx::Staging st(c->stream);
+  const char* d_series = st.in(
+      (const char*)h_series, series_bytes(epoch_stride_bytes, chan_stride_bytes, n_epochs, n_ch));
+  int32_t* d_first_page = st.out(h_first_page, (size_t)n_ch);
+  int32_t* d_n_pages = st.out(h_n_pages, (size_t)n_ch);
+  uint8_t* d_bits = st.out(h_bits, (size_t)n_ch * max_pages * kE1Bits);
+  if (st.status()) return st.status();
+  rc = gnsscorr_nav_e1_pages_dev(c, d_series, epoch_stride_bytes, chan_stride_bytes, n_epochs,
+                                 n_ch, max_pages, d_first_page, d_n_pages, d_bits);
+  return rc ? rc : st.finish();
 }
 
 static int check_l3(const char* fn, const gnsscorr_nav_ctx* c, const void* pilot,
@@ -546,30 +536,18 @@ extern "C" int gnsscorr_nav_l3_decode(gnsscorr_nav_ctx* c, const void* h_pilot,
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->cfg.device));
   const size_t n_in = series_bytes(epoch_stride_bytes, chan_stride_bytes, n_epochs, n_ch);
-  const size_t n_out = (size_t)n_ch * (size_t)(n_epochs / 10);
-  const size_t ni = (size_t)n_ch * sizeof(int32_t), nm = ni * (size_t)max_marks;
-  hostctx::TempBuf<double> d_pilot, d_data;
-  hostctx::TempBuf<int32_t> d_start, d_nb, d_nm, d_marks;
-  hostctx::TempBuf<uint8_t> d_out;
-  rc = hostctx::grow(d_pilot, (n_in + 7) / 8);
-  if (!rc) rc = hostctx::grow(d_data, (n_in + 7) / 8);
-  if (!rc) rc = hostctx::grow(d_start, (size_t)n_ch);
-  if (!rc) rc = hostctx::grow(d_nb, (size_t)n_ch);
-  if (!rc) rc = hostctx::grow(d_nm, (size_t)n_ch);
-  if (!rc) rc = hostctx::grow(d_marks, (size_t)n_ch * max_marks);
-  if (!rc) rc = hostctx::grow(d_out, n_out > 0 ? n_out : 1);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(d_pilot.p, h_pilot, n_in, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d_data.p, h_data, n_in, hipMemcpyHostToDevice, c->stream));
-  rc = gnsscorr_nav_l3_decode_dev(c, d_pilot.p, d_data.p, epoch_stride_bytes, chan_stride_bytes,
-                                  n_epochs, n_ch, max_marks, d_start.p, d_nb.p, d_out.p, d_nm.p,
-                                  d_marks.p);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h_start, d_start.p, ni, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(h_n_bits, d_nb.p, ni, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(h_n_marks, d_nm.p, ni, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(h_marks, d_marks.p, nm, hipMemcpyDeviceToHost, c->stream));
-  if (n_out) HIP_TRY(hipMemcpyAsync(h_bits, d_out.p, n_out, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GNSSCORR_OK;
+  const size_t n = (size_t)n_ch;
+  hostctx::Staging st(c->stream);
+  const char* d_pilot = st.in((const char*)h_pilot, n_in);
+  const char* d_data = st.in((const char*)h_data, n_in);
+  int32_t* d_start = st.out(h_start, n);
+  int32_t* d_n_bits = st.out(h_n_bits, n);
+  int32_t* d_n_marks = st.out(h_n_marks, n);
+  int32_t* d_marks = st.out(h_marks, n * max_marks);
+  uint8_t* d_bits = st.out(h_bits, n * (size_t)(n_epochs / 10));   // none below ten epochs
+  if (st.status()) return st.status();
+  rc = gnsscorr_nav_l3_decode_dev(c, d_pilot, d_data, epoch_stride_bytes, chan_stride_bytes,
+                                  n_epochs, n_ch, max_marks, d_start, d_n_bits, d_bits, d_n_marks,
+                                  d_marks);
+  return rc ? rc : st.finish();
 }

@@ -701,32 +701,6 @@ extern "C" int gnsscorr_sdr_acq_create(gnsscorr_sdr_acq_ctx** out, const gnsscor
   return GNSSCORR_OK;
 }
 
-// device copies of one host call's records and satellite list and room for its
-// results, freed when the call returns
-struct HostStaging {
-  hostctx::TempBuf<int16_t> buff;   // records of (I, Q) pairs
-  hostctx::TempBuf<int32_t> svs;
-  hostctx::TempBuf<gnsscorr_sdr_acq_result> res;
-
-  int upload(gnsscorr_sdr_acq_ctx* c, const int16_t* h_buff, size_t n_pairs, const int32_t* h_svs,
-             int n_sv, size_t n_res) {
-    int rc = hostctx::grow(buff, 2 * n_pairs);
-    if (!rc) rc = hostctx::grow(svs, (size_t)n_sv);
-    if (!rc) rc = hostctx::grow(res, n_res);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(buff.p, h_buff, sizeof(uint32_t) * n_pairs, hipMemcpyHostToDevice,
-                           c->stream));
-    HIP_TRY(hipMemcpyAsync(svs.p, h_svs, sizeof(int32_t) * n_sv, hipMemcpyHostToDevice, c->stream));
-    return GNSSCORR_OK;
-  }
-  int download(gnsscorr_sdr_acq_ctx* c, gnsscorr_sdr_acq_result* h_res) {
-    HIP_TRY(hipMemcpyAsync(h_res, res.p, sizeof(gnsscorr_sdr_acq_result) * res.cap,
-                           hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return GNSSCORR_OK;
-  }
-};
-
 static int check_range(int n_rec, int n_sv, int doppmin, int doppmax) {
   const int lmin = doppmin / 1000, lmax = doppmax / 1000;   // C truncation, as the reference
   if (n_rec < 1 || n_sv < 1 || lmax <= lmin || lmin < -kMaxLcv || lmax > kMaxLcv + 1) {
@@ -777,11 +751,13 @@ extern "C" int gnsscorr_sdr_acq_strong(gnsscorr_sdr_acq_ctx* c, const int16_t* h
     }
   HIP_TRY(hipSetDevice(c->cfg.device));
   static_assert(sizeof(gnsscorr_sdr_acq_result) == 24, "result layout");
-  HostStaging st;
-  if ((rc = st.upload(c, h_buff, (size_t)n_rec * kN, h_svs, n_sv, (size_t)n_rec * n_sv))) return rc;
-  rc = gnsscorr_sdr_acq_strong_dev(c, st.buff.p, n_rec, n_sv, st.svs.p, doppmin, doppmax, st.res.p);
-  if (rc) return rc;
-  return st.download(c, h_res);
+  hostctx::Staging st(c->stream);
+  const int16_t* d_buff = st.in(h_buff, 2 * (size_t)n_rec * kN);   // (I, Q) pairs
+  const int32_t* d_svs = st.in(h_svs, (size_t)n_sv);
+  gnsscorr_sdr_acq_result* d_res = st.out(h_res, (size_t)n_rec * n_sv);
+  if (st.status()) return st.status();
+  rc = gnsscorr_sdr_acq_strong_dev(c, d_buff, n_rec, n_sv, d_svs, doppmin, doppmax, d_res);
+  return rc ? rc : st.finish();
 }
 
 extern "C" int gnsscorr_sdr_acq_sync(gnsscorr_sdr_acq_ctx* c) { return hostctx::sync(c); }
@@ -908,14 +884,14 @@ extern "C" int gnsscorr_sdr_acq_acquire(gnsscorr_sdr_acq_ctx* c, int type, const
     }
   HIP_TRY(hipSetDevice(c->cfg.device));
   const int ms = prep_ms(type);
-  HostStaging st;
-  int rc = st.upload(c, h_buff, (size_t)n_rec * ms * kN, h_svs, n_sv, (size_t)n_rec * n_sv);
-  if (rc) return rc;
-  rc = gnsscorr_sdr_acq_prep_dev(c, type, st.buff.p, n_rec);
-  if (!rc)
-    rc = gnsscorr_sdr_acq_search_dev(c, type, n_rec, n_sv, st.svs.p, doppmin, doppmax, st.res.p);
-  if (rc) return rc;
-  return st.download(c, h_res);
+  hostctx::Staging st(c->stream);
+  const int16_t* d_buff = st.in(h_buff, 2 * (size_t)n_rec * ms * kN);   // (I, Q) pairs
+  const int32_t* d_svs = st.in(h_svs, (size_t)n_sv);
+  gnsscorr_sdr_acq_result* d_res = st.out(h_res, (size_t)n_rec * n_sv);
+  if (st.status()) return st.status();
+  int rc = gnsscorr_sdr_acq_prep_dev(c, type, d_buff, n_rec);
+  if (!rc) rc = gnsscorr_sdr_acq_search_dev(c, type, n_rec, n_sv, d_svs, doppmin, doppmax, d_res);
+  return rc ? rc : st.finish();
 }
 
 // ============================================================================

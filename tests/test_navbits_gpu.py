@@ -7,6 +7,7 @@ tests/test_navbits_cpu.py, which holds the literal and the fast restatement equa
 import numpy as np
 import pytest
 
+import nav_twin as T
 import navbits_scenarios as S
 
 pytestmark = pytest.mark.gpu
@@ -221,6 +222,20 @@ def test_host_twin_of_the_primitive(gpu):
     dev = _hits_dev(gpu, nav, x, pattern, thr, 0, 3)
     twin = nav.pattern_hits(x, pattern, thr, 0, 3)
     assert all(a.tobytes() == b.tobytes() for a, b in zip(dev, twin))
+
+
+@pytest.mark.parametrize("name", ["glo_strings", "b1_subframes"])
+def test_first_hit_chain_twins_equal_the_device_forms(gpu, name):
+    """The short scenes through the exported host twin and through the device form, both on
+    sentinel-filled outputs: the same bytes in first, count and bits, none past them."""
+    scene, units, per = {"glo_strings": (S.glo_short_scene, 15, 85),
+                         "b1_subframes": (S.b1_short_scene, 5, 213)}[name]
+    x, firsts, counts = scene()
+    n_ch = len(x)
+    first, count, bits = T.twin_and_dev(
+        gpu, gpu.NavCtx(), name, [x], [units],
+        [(np.int32, n_ch), (np.int32, n_ch), (np.uint8, n_ch * units * per)])
+    assert first.tolist() == firsts and count.tolist() == counts
 
 
 def test_sgt_replay_epochs_feed_the_gps_chain_on_the_device(gpu):

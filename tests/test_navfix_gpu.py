@@ -255,3 +255,18 @@ def test_bad_arguments_are_refused_and_nothing_is_written(gpu):
     nav.sync()
     for d in (d_n, d_sol, d_chan):
         assert d.download(np.uint8).tobytes() == fill.tobytes()
+
+
+def test_refused_ephemeris_twin_leaves_its_array_alone(gpu):
+    """gnsscorr_nav_gps_ephemeris with n_ch = 0: refused by the check it shares with the
+    device form, and every byte of the host output is still the sentinel."""
+    gc = gpu
+    nav = gc.NavCtx()
+    bits, n_bits, first, _ = S.eph_scene(3)
+    bits, n_bits, first = (np.ascontiguousarray(a) for a in (bits, n_bits, first))
+    eph = np.frombuffer(_poison(3, gc.GPS_EPH), gc.GPS_EPH).copy()
+    rc = nav._gps_ephemeris(nav.h, bits.ctypes.data, n_bits.ctypes.data, first.ctypes.data, 0,
+                            eph.ctypes.data)
+    assert rc == -1
+    assert "n_ch >= 1" in gc.lib().gnsscorr_last_error().decode()
+    assert (eph.view(np.uint8) == 0xAA).all()

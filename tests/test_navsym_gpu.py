@@ -12,6 +12,7 @@ import functools
 import numpy as np
 import pytest
 
+import nav_twin as T
 import navsym_scenarios as S
 
 pytestmark = pytest.mark.gpu
@@ -264,6 +265,74 @@ def test_e1t_replay_epochs_feed_the_page_decoder_on_the_device(gpu):
               d_bits.download(np.uint8).reshape(n_ch, 2, 120), want)
     ep = d_ep.download(gc.E1T_EPOCH).reshape(n_ch, n_ep)
     assert ep["I_P_P"].tobytes() == series.tobytes()
+
+
+# ---- host-array twins against the device forms -------------------------------------------
+def _l3_outs(n_ch, n_ep, max_marks):
+    """start, n_bits, bits, n_marks, marks"""
+    return [(np.int32, n_ch), (np.int32, n_ch), (np.uint8, n_ch * (n_ep // 10)),
+            (np.int32, n_ch), (np.int32, n_ch * max_marks)]
+
+
+def test_l3_host_twin_equals_the_device_form(gpu):
+    """Two channels, overlay starts 0 and 7 (the second inverted, with zeros), a time mark in
+    each message: every output of the twin is the device form's, byte for byte, and nothing
+    past it is written."""
+    rng = np.random.default_rng(31)
+    a = S.l3_series(rng, 600, 0, mark_at=10)
+    b = S.l3_series(rng, 600, 7, polarity=-1, mark_at=25, n_zeros=4)
+    pilot, data = np.stack([a[0], b[0]]), np.stack([a[1], b[1]])
+    start, n_bits, bits, n_marks, marks = T.twin_and_dev(
+        gpu, gpu.NavCtx(), "l3_decode", [pilot, data], [4], _l3_outs(2, 600, 4))
+    assert start.tolist() == [0, 7] and n_bits.tolist() == [60, 59]
+    assert n_marks.tolist() == [1, 1] and marks.reshape(2, 4)[:, 0].tolist() == [10, 25]
+
+
+def test_l3_host_twin_with_fewer_than_ten_epochs(gpu):
+    """n_epochs = 9: n_epochs // 10 == 0, the bits output has no element and its host array is
+    left alone; start, n_bits, n_marks and marks still come back (nine epochs cannot reach the
+    overlay's |sum| = 10: no start, no bits, no marks)."""
+    rng = np.random.default_rng(32)
+    a, b = S.l3_series(rng, 9, 0), S.l3_series(rng, 9, 2)
+    pilot, data = np.stack([a[0], b[0]]), np.stack([a[1], b[1]])
+    start, n_bits, bits, n_marks, marks = T.twin_and_dev(
+        gpu, gpu.NavCtx(), "l3_decode", [pilot, data], [3], _l3_outs(2, 9, 3))
+    assert bits.size == 0
+    assert start.tolist() == [-1, -1] and n_bits.tolist() == [0, 0]
+    assert n_marks.tolist() == [0, 0] and marks.tolist() == [-1] * 6
+
+
+def test_e1_host_twin_equals_the_device_form(gpu):
+    """Two channels, max_pages = 2: page start 37 (inverted, with zeros) and a channel of
+    noise, which has no page start."""
+    rng = np.random.default_rng(33)
+    series = np.stack([S.e1_series(rng, 2200, 37, polarity=-1, n_zeros=6)[0],
+                       1500.0 * rng.standard_normal(2200)])
+    first, n_pages, bits = T.twin_and_dev(
+        gpu, gpu.NavCtx(), "e1_pages", [series], [2],
+        [(np.int32, 2), (np.int32, 2), (np.uint8, 2 * 2 * 120)])
+    assert first.tolist() == [37, -1] and n_pages.tolist() == [2, 0]
+    assert not bits.reshape(2, 240)[1].any()
+
+
+def test_refused_host_twins_leave_their_arrays_alone(gpu):
+    """l3_decode and e1_pages with n_ch = 0 and with an odd epoch stride: the shared series
+    check refuses both before anything is staged, and every output byte is still the
+    sentinel."""
+    gc = gpu
+    nav = gc.NavCtx()
+    x = np.ones((2, 1200))
+    p = x.ctypes.data
+    for es, n_ch in ((8, 0), (9, 2)):
+        outs = [T.sentinel(n, dt) for dt, n in _l3_outs(2, 1200, 4)]
+        rc = nav._l3_decode(nav.h, p, p, es, 8 * 1200, 1200, n_ch, 4,
+                            *[o.ctypes.data for o in outs])
+        assert rc == -1, (es, n_ch)
+        assert all(T.intact(o) for o in outs), (es, n_ch)
+        outs = [T.sentinel(n, dt) for dt, n in ((np.int32, 2), (np.int32, 2), (np.uint8, 240))]
+        rc = nav._e1_pages(nav.h, p, es, 8 * 1200, 1200, n_ch, 1, *[o.ctypes.data for o in outs])
+        assert rc == -1, (es, n_ch)
+        assert all(T.intact(o) for o in outs), (es, n_ch)
 
 
 # ---- bad arguments ---------------------------------------------------------------------
