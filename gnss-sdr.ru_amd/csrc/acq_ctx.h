@@ -1,12 +1,26 @@
-// acq_ctx.h -- the acquisition context shared by the fp32 (acq.hip) and the
-// reference-precision fp64 (acq64.hip, acq64_gen.hip) kernels.  Internal to libgnsscorr.
+// acq_ctx.h -- the acquisition context and the interface between its front (acq.hip: the
+// C ABI, checks, tile order, per-group selection) and its three engines: fp32 (acq32.hip)
+// and the reference-precision fp64 ones (acq64.hip, acq64_gen.hip).  Each engine keeps its
+// state in a part of the context of its own and is reached through plain functions, the
+// same set per engine.  Internal to libgnsscorr.
 // Buffers of a size fixed at create are raw pointers; the ones a call may grow
 // are DevBufs (hostctx.h).
 #ifndef GNSSCORR_ACQ_CTX_H
 #define GNSSCORR_ACQ_CTX_H
 #include <hip/hip_runtime.h>
+#include <stdlib.h>
 #include "gnsscorr_internal.h"
 #include "hostctx.h"
+
+// The fp32 engine's part of the context (prec == GNSSCORR_ACQ_F32, N = 16368 only; acq32.hip)
+struct acq32_ctx {
+  int* d_sigma = nullptr;
+  float2* d_F = nullptr;     // code spectra, permuted, [max_codes][N]
+  float2* d_X = nullptr;     // IF spectra, permuted, [max_freqs*max_blocks][N]
+  int4* d_fmap = nullptr;               // per frequency: spectrum class + PFA shift coordinates
+  hostctx::DevBuf<float2> d_stage;      // forward-FFT staging rows
+  int n_cu = 256;                       // persistent grid of the pipelined kernel
+};
 
 // where one chunk of the generic engine's four-step correlation runs and what it writes
 struct acq_chunk_lane {
@@ -69,12 +83,8 @@ struct gnsscorr_acq_ctx {
   gnsscorr_acq_cfg cfg;
   hipStream_t stream = nullptr;
   int prec = GNSSCORR_ACQ_F64;          // cfg.precision, validated
-  // ---- fp32 path (prec == GNSSCORR_ACQ_F32, N = 16368 only)
-  int* d_sigma = nullptr;
-  float2* d_F = nullptr;     // code spectra, permuted, [max_codes][N]
-  float2* d_X = nullptr;     // IF spectra, permuted, [max_freqs*max_blocks][N]
-  int4* d_fmap = nullptr;               // per frequency: spectrum class + PFA shift coordinates
-  hostctx::DevBuf<float2> d_stage;      // forward-FFT staging rows
+  // ---- fp32 path (prec == GNSSCORR_ACQ_F32)
+  acq32_ctx f32;                        // fp32 engine (acq32.hip)
   // ---- fp64 path (prec == GNSSCORR_ACQ_F64)
   int plan64 = 0;                       // acq64 plan id (acq64_plan_for)
   double2* d_F64 = nullptr;             // code spectra, storage order of the plan, [max_codes][rs64]
@@ -86,7 +96,7 @@ struct gnsscorr_acq_ctx {
   hostctx::DevBuf<acq64_unit_desc> d_udesc;   // per launched workgroup, rebuilt by every correlate
   int rs64 = 0;                         // fp64 row stride (complex elements)
   acq64_gen_ctx gen;                    // generic-N fp64 engine (plan64 == 3, acq64_gen.hip)
-  // ---- shared
+  // ---- the front's, and what every engine uses
   int n_codes = 0;
   int spec_blocks = 0, spec_freqs = 0;  // shape of the resident IF spectra
   hostctx::DevBuf<int> d_order;         // workgroup -> work-unit permutation (XCD tiles)
@@ -94,7 +104,6 @@ struct gnsscorr_acq_ctx {
   double* d_cfreq = nullptr;            // per class: the residue frequency whose spectrum is computed
   double* d_resid = nullptr;            // per frequency: its fs/N-grid residue (classify scratch)
   int* d_nclass = nullptr;
-  int n_cu = 256;                       // persistent grid of the pipelined kernel
   int coh = 1;                          // code periods per coherent block (set_coherent)
   int recs = 1;                         // records per search (set_records, fp64 plans)
   int keep = 0;                         // zero-padded search: lags kept (set_zero_padded; 0: off)
@@ -119,6 +128,42 @@ struct gnsscorr_acq_ctx {
   hostctx::DevBuf<gnsscorr_acq_result> d_res;
   double* d_dump = nullptr;
 };
+
+// XCD-aware workgroup order.  Workgroups are dealt round-robin over the 8
+// XCDs (blockIdx % 8 share an L2; MI355X_MICROARCH.md "Workgroup dispatch").
+// Rows are cut into tiles of 4 bins x 8 groups (= the 32 CUs of one XCD), so
+// the workgroups an XCD runs concurrently read 4 IF-spectrum rows and 8 code
+// spectra (~2 MB) from its 4 MB L2 instead of 32 distinct pairs.  Placement
+// only changes speed, never results.
+inline void build_tile_order(int n_groups, int n_bins, int units_per_row, int* perm) {
+  const int R = n_groups * n_bins * units_per_row;
+  constexpr int TB = 4, TG = 8, NX = 8;
+  int* seq = (int*)malloc(sizeof(int) * R);
+  int k = 0;
+  for (int g0 = 0; g0 < n_groups; g0 += TG)
+    for (int b0 = 0; b0 < n_bins; b0 += TB)
+      for (int u = 0; u < units_per_row; u++)
+        for (int bi = b0; bi < b0 + TB && bi < n_bins; bi++)
+          for (int gi = g0; gi < g0 + TG && gi < n_groups; gi++)
+            seq[k++] = (gi * n_bins + bi) * units_per_row + u;
+  int start[NX + 1];
+  start[0] = 0;
+  for (int x = 0; x < NX; x++) start[x + 1] = start[x] + (R - x + NX - 1) / NX;
+  for (int b = 0; b < R; b++) perm[b] = seq[start[b % NX] + b / NX];
+  free(seq);
+}
+
+// ---- acq32.hip: the fp32 engine (N = 16368), same arguments as its fp64 counterparts
+int acq32_supports(int n_samples);               // N == 16368
+int acq32_init(gnsscorr_acq_ctx* c);             // device tables, the PFA map self-check
+void acq32_free(gnsscorr_acq_ctx* c);
+int acq32_preload(gnsscorr_acq_ctx* c);          // its own code-object load
+int acq32_set_codes(gnsscorr_acq_ctx* c, const int8_t* d_codes, int n_codes, int code_len);
+int acq32_spectra(gnsscorr_acq_ctx* c, const int8_t* d_if, int iq, int n_blocks, int n_freqs,
+                  const double* d_freqs);
+int acq32_correlate(gnsscorr_acq_ctx* c, int n_blocks, int mode, int n_groups, int n_bins,
+                    const int32_t* d_gcode, const int32_t* d_gfreq, int spc, double* d_dump,
+                    int dump_block);
 
 // ---- acq64.hip: the fp64 engine behind the same context (compiled plans; it hands a
 // context on plan 3 to the generic engine below)

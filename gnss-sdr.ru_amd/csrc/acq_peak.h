@@ -1,6 +1,6 @@
 // acq_peak.h -- the row statistics of every acquisition engine, defined once.
 //
-// Every engine (acq.hip: fp32; acq64.hip: the compiled fp64 plans; acq64_gen.hip: the
+// Every engine (acq32.hip: fp32; acq64.hip: the compiled fp64 plans; acq64_gen.hip: the
 // generic passes, the four-step plans, chirp-z) reports per correlation row
 //   peak    the row maximum,
 //   argmax  its index,

@@ -1,6 +1,6 @@
 """GPU parity: multi-ms coherent acquisition (gnsscorr_acq_set_coherent) on every engine.
 
-The setter is implemented three times -- acq_fwd16_kernel (fp32, csrc/acq.hip),
+The setter is implemented three times -- acq_fwd16_kernel (fp32, csrc/acq32.hip),
 acq64_wipe_kernel<P> (the compiled fp64 plans) and g_wipe_kernel (the generic fp64
 engine: mixed-radix passes, four-step plan, chirp-z; csrc/acq64_gen.hip) -- and each folds
 coh code periods of a block into one N-point row with the carrier phase running on over

@@ -6,7 +6,7 @@ Reference: POSTPROCESSING_SCILAB_RECEIVERS/GLONASS/L1/acquisition.sci:52-72,
 coh*N-point FFTs, rows = first code period).  The oracle
 (oracle/acq_oracle.py, coh=) runs that literally in fp64 with 81 840-point
 transforms; the GPU folds the wiped-off block into one code period first (the
-coh*N spectrum is zero off multiples of coh, see acq.hip).  Tolerances as in
+coh*N spectrum is zero off multiples of coh, see acq32.hip).  Tolerances as in
 test_acq_gpu.py: fp64 -- 1e-6 relative everywhere, decisions exact; fp32 --
 powers 2e-5 of the row max, peaks 1e-4, decisions exact when the oracle's
 winner is clear.

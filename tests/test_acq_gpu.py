@@ -198,6 +198,40 @@ def test_zero_if_rows(gpu, acq):
     assert res[0]["code_phase"] == 1 and res[0]["bin"] == 0
 
 
+def test_two_precisions_in_one_process_do_not_disturb_each_other(gpu):
+    """The fp32 and the fp64 engine are separate code objects, each with its own constant
+    tables and its own lazy load (acq32_preload / acq64_preload at create).  Whatever order
+    the contexts are created in and however their searches interleave, each precision
+    returns byte for byte what it returned when it ran alone.  The code is compared with
+    itself only; the tests above hold both engines to the oracle."""
+    IF = gpu.ifgen(2 * N, [_sig(7, 100.5, 1000.0)], fs=FS, seed=5)
+    codes = np.stack([A.make_ca_table_row(p, FS) for p in (7, 9)])
+    freqs = 2.42e6 + np.array([0.0, 500.0, 1000.0])    # bins 0 and 2 share a spectrum class
+    gf = np.tile(np.arange(3), (2, 1))
+    modes = (gpu.ACQ_BEST_OF_BLOCKS, gpu.ACQ_NONCOHERENT)
+
+    def make(prec):
+        ctx = gpu.AcqCtx(FS, N, max_freqs=3, max_blocks=2, max_codes=2, precision=prec)
+        ctx.set_codes(codes)
+        return ctx
+
+    def run(ctx, mode):
+        res, rows = ctx.search(IF, 2, freqs, [0, 1], gf, spc=16, mode=mode)
+        return rows.tobytes(), res.tobytes()
+
+    c32, c64 = make(gpu.ACQ_F32), make(gpu.ACQ_F64)
+    alone = {(ctx.precision, m): run(ctx, m) for ctx in (c32, c64) for m in modes}
+    c32.close()
+    c64.close()
+    assert alone[gpu.ACQ_F32, modes[0]] != alone[gpu.ACQ_F32, modes[1]]   # the modes differ
+    c64, c32 = make(gpu.ACQ_F64), make(gpu.ACQ_F32)
+    for m in modes:
+        for ctx in (c32, c64):
+            assert run(ctx, m) == alone[ctx.precision, m], (ctx.precision, m)
+    c32.close()
+    c64.close()
+
+
 def test_bad_precision_or_size_rejected(gpu):
     with pytest.raises(gpu.GnssCorrError):
         gpu.AcqCtx(FS, N, precision=7)

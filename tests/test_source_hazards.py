@@ -13,8 +13,8 @@ on every product path, with its four environment switches, and the stream kernel
 seven compile-time switches that sat at their measured values and are constants now
 (the names: `gone` below; none is part of a surviving identifier --
 GNSSCORR_TRACK_XPF and GNSSCORR_TRACK_BALANCE stay).
-The acquisition side followed: acq.hip's phase-ablation mask (ACQ_SKIP), cache-policy
-sweep (ACQ_LOAD_AUX), plane stride (ACQ_PLANE) and load-group (ACQ_LDGROUP) switches,
+The acquisition side followed: the fp32 engine's (acq32.hip, then part of acq.hip)
+phase-ablation mask (ACQ_SKIP), cache-policy sweep (ACQ_LOAD_AUX), plane stride (ACQ_PLANE) and load-group (ACQ_LDGROUP) switches,
 the one-unit kernel's ACQ_STAMP hook (pinned with its parenthesis; ACQ_PSTAMP and
 ACQ64_STAMP stay) and GNSSCORR_ACQ_PIPE, which alone reached the best-of-blocks form
 of acq_corr_kernel; and acq64_gen.hip's generic-engine switches M4_COLS2_PLANE (the
@@ -56,7 +56,7 @@ def test_measured_out_switches_are_gone():
             # ... and osg_stream_kernel's settled compile-time switches
             "TRACK_NODUMP_COPY", "TRACK_IV4", "TRACK_ALIGNED", "TRACK_X2LUT", "TRACK_STREAM_CH",
             "TRACK_STREAM_WAVES", "TRACK_PF",
-            # acq.hip: the one-unit kernel's ablation and sweep switches, its stamp hook
+            # acq32.hip: the one-unit kernel's ablation and sweep switches, its stamp hook
             # (with the parenthesis: ACQ_PSTAMP stays) and the route past the pipelined kernel
             "ACQ_SKIP", "ACQ_LOAD_AUX", "ACQ_PLANE", "ACQ_LDGROUP", "ACQ_STAMP(",
             "GNSSCORR_ACQ_PIPE",

@@ -17,7 +17,7 @@ __device__ unsigned long long* g_stamps;
       g_stamps[((blockIdx.x * 16 + (it)) * 16 + (threadIdx.x >> 6)) * 8 + (i)] = _t; \
     }                                                                             \
   } while (0)
-#include "../gnss-sdr.ru_amd/csrc/acq.hip"
+#include "../gnss-sdr.ru_amd/csrc/acq32.hip"   // the engine alone; build_tile_order: acq_ctx.h
 
 int main() {
   const int G = 32, B = 41, R = G * B, NB = 2, U = R * NB, GRID = 256;
