@@ -63,5 +63,15 @@ void gnsscorr_sdr_post_dft(int16_t *out);
       return GNSSCORR_EDEVICE;                                                          \
     }                                                                                   \
   } while (0)
+
+/* XCD-aware channel order of the one-unit-per-channel kernels (track.hip,
+ * track_real.hip, sgt.hip): workgroup b of G runs on XCD b % 8, so every XCD
+ * gets a contiguous range of units -- the channels of one receiver (consecutive
+ * channels sharing an IF stream) then hit the same 4 MiB L2 and the stream is
+ * fetched from HBM once instead of once per XCD. */
+__device__ __forceinline__ int xcd_channel(int b, int G) {
+  const int q = G >> 3, r = G & 7, x = b & 7, slot = b >> 3;
+  return x * q + (x < r ? x : r) + slot;
+}
 #endif
 #endif

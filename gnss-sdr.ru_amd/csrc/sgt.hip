@@ -131,11 +131,6 @@ __device__ __forceinline__ gnsscorr_sgt_epoch sgt_epoch_end(const SgtParams& p,
   return r;
 }
 
-__device__ __forceinline__ int xcd_channel(int b, int G) {
-  const int q = G >> 3, r = G & 7, x = b & 7, slot = b >> 3;
-  return x * q + (x < r ? x : r) + slot;
-}
-
 // WAVE: one wavefront per channel (many-channel launches): the butterfly sums
 // leave the totals in every lane, so an epoch needs no LDS partials and no
 // barrier, and the loop filters run once per wave instead of once per wave of

@@ -15,26 +15,23 @@
 //    rollovers.  The E/P/L bits after the dump rollover are loaded from the
 //    PRE-reset index (>= 2046, the reference's row over-read) and half-chip 0
 //    of the new epoch keeps them (no reload), which hc_after() reproduces.
-//  * accumulation is int32 two's-complement, so per-thread partial sums can
-//    be combined in any order: each thread keeps at most two epochs' sums
-//    (a run of 64 samples can straddle at most one dump, D >= 2046), the
-//    wavefront reduces them with cross-lane shuffles and one lane per wave
-//    adds into an LDS slot per epoch.
+//  * accumulation is int32 two's-complement, so partial sums can be combined
+//    in any order: per epoch in LDS, from lanes (here) or threads
+//    (track_real.hip) that each hold the sums of the epoch they are in.
 //
-// Two kernels: osg_stream_kernel (one wavefront per channel, every interleaved
-// I,Q stream) and osg_track_kernel (thread groups of 64-sample runs, real-sample
-// streams).
+// Two kernels share that arithmetic (osg_chan.h): osg_stream_kernel in this
+// file, the IQ stream engine (one wavefront per channel, every interleaved I,Q
+// stream), and osg_track_kernel in track_real.hip (thread groups of 64-sample
+// runs, real-sample streams).  The context and the C ABI in front of both:
+// track_host.hip, through track_ctx.h.
 #include <hip/hip_runtime.h>
 #include <type_traits>
-#include <vector>
-#include <limits.h>
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 #include "gnsscorr_internal.h"
-#include "hostctx.h"
 #include "if2.h"
+#include "osg_chan.h"
 #include "osg_isr.h"
+#include "track_ctx.h"
 
 // Diagnostic hook of osg_stream_kernel (tools/trk_stream_stamps.hip; a no-op here)
 #ifndef STREAM_PSTAMP
@@ -44,117 +41,9 @@
 #endif
 
 namespace {
+using namespace osgchan;
 
-constexpr int kRun = 64;              // samples per thread
-constexpr int kMaxThreads = 1024;
-constexpr int kMaxNsamp = kRun * kMaxThreads;
-constexpr uint64_t kNever = ~0ull;
 constexpr int kPk8Stage = 3088;       // LDS bytes of the E/P/L row (D <= 3071: slew <= 1025) + 3 of misalignment
-constexpr int kMaxCpw = 4;            // channels per workgroup (32 waves/CU: two 1024-thread WGs)
-
-// 8-phase LO (correlator.c:203-204) as 4-bit two's-complement nibbles.
-constexpr uint32_t kLutI = 0xEEF1221Fu;  // i_lo = {-1, 1, 2, 2, 1,-1,-2,-2}
-constexpr uint32_t kLutQ = 0x1FEEF122u;  // q_lo = { 2, 2, 1,-1,-2,-2,-1, 1}
-
-struct Chan {
-  uint32_t P0, K0, cinc, kinc2, hc0, D;
-  uint64_t j1;       // rollover index of the first dump (kNever: none)
-  int base;          // prn * 2046 into the packed table
-};
-
-// Half-chip counter, table load index and epoch after r rollovers.
-__device__ __forceinline__ void hc_after(const Chan& c, uint64_t r, uint32_t& hc, uint32_t& ld,
-                                         uint32_t& epoch) {
-  if (r < c.j1) {
-    epoch = 0;
-    hc = (uint32_t)((c.hc0 + r) & 0xFFFFu);
-    ld = hc;
-  } else {
-    uint32_t m = (uint32_t)(r - c.j1);
-    epoch = 1 + m / c.D;
-    uint32_t q = m % c.D;
-    hc = q;
-    ld = q ? q : (m == 0 ? (uint32_t)((c.hc0 + c.j1) & 0xFFFFu) : c.D);
-  }
-}
-
-__device__ __forceinline__ uint32_t n_dumps_after(const Chan& c, uint64_t r) {
-  return r >= c.j1 ? 1 + (uint32_t)(r - c.j1) / c.D : 0u;
-}
-
-__device__ __forceinline__ void msbit_step(int& ms, int& bit) {
-  // correlator.c:275-280
-  ms++;
-  if (ms == 20) bit = (bit + 1) % 50;
-  ms %= 20;
-}
-
-// Wave-wide reductions without the LDS crossbar (ds_bpermute): a DPP
-// Hillis-Steele scan inside each 16-lane row (row_shr 1/2/4/8, identity
-// shifted in), then the four row results (lanes 15/31/47/63) combined in
-// scalar registers.  Every lane of the wave must be active.
-template <typename Op>
-__device__ __forceinline__ int wave_reduce(int v, int ident, Op op) {
-  v = op(v, __builtin_amdgcn_update_dpp(ident, v, 0x111, 0xF, 0xF, false));
-  v = op(v, __builtin_amdgcn_update_dpp(ident, v, 0x112, 0xF, 0xF, false));
-  v = op(v, __builtin_amdgcn_update_dpp(ident, v, 0x114, 0xF, 0xF, false));
-  v = op(v, __builtin_amdgcn_update_dpp(ident, v, 0x118, 0xF, 0xF, false));
-  const int a = __builtin_amdgcn_readlane(v, 15), b = __builtin_amdgcn_readlane(v, 31);
-  const int c = __builtin_amdgcn_readlane(v, 47), d = __builtin_amdgcn_readlane(v, 63);
-  return op(op(a, b), op(c, d));
-}
-__device__ __forceinline__ int wave_sum(int v) {
-  return wave_reduce(v, 0, [](int x, int y) { return (int)((uint32_t)x + (uint32_t)y); });
-}
-__device__ __forceinline__ int wave_max(int v) {
-  return wave_reduce(v, INT_MIN, [](int x, int y) { return max(x, y); });
-}
-__device__ __forceinline__ int wave_min(int v) {
-  return wave_reduce(v, INT_MAX, [](int x, int y) { return min(x, y); });
-}
-
-__device__ __forceinline__ int sbyte(int x, int b) { return __builtin_amdgcn_sbfe(x, 8 * b, 8); }
-
-struct Acc {
-  uint32_t a[6];
-};
-
-// one real sample of the reference recurrence (correlator.c:200-283) on a
-// thread's (first, cur) epoch sums
-__device__ __forceinline__ void corr_sample(int I, uint32_t& phase, uint32_t& kph, const Chan& c,
-                                            uint32_t& hc, int& lb, int& pb, int& eb, Acc& cur,
-                                            Acc& first, bool& switched,
-                                            const uint32_t* __restrict__ pk) {
-  const uint32_t off = (phase >> 27) & 0x1Cu;
-  const int il = __builtin_amdgcn_sbfe((int)kLutI, off, 4);
-  const int ql = __builtin_amdgcn_sbfe((int)kLutQ, off, 4);
-  const int ival = I * il;    // correlator.c:222-223
-  const int qval = I * ql;
-  cur.a[0] += (uint32_t)(lb * ival);
-  cur.a[1] += (uint32_t)(lb * qval);
-  cur.a[2] += (uint32_t)(pb * ival);
-  cur.a[3] += (uint32_t)(pb * qval);
-  cur.a[4] += (uint32_t)(eb * ival);
-  cur.a[5] += (uint32_t)(eb * qval);
-  phase += c.cinc;
-  const uint32_t nk = kph + c.kinc2;
-  const bool carry = nk < kph;
-  kph = nk;
-  if (carry) {
-    hc = (hc + 1u) & 0xFFFFu;
-    const uint32_t ld = hc;
-    if (hc >= c.D) {  // dump (correlator.c:251-281)
-#pragma unroll
-      for (int k = 0; k < 6; k++) { first.a[k] = cur.a[k]; cur.a[k] = 0; }
-      switched = true;
-      hc = 0;
-    }
-    const uint32_t w = pk[c.base + (int)ld];
-    lb = (int)(int8_t)(w & 0xFFu);
-    pb = (int)(int8_t)((w >> 8) & 0xFFu);
-    eb = (int)(int8_t)((w >> 16) & 0xFFu);
-  }
-}
 
 // ---- IQ streams (osg_stream_kernel): segment sums with v_dot4 ---------------
 // Between two code-NCO carries (one half-chip, ~8 samples) the E/P/L bits are
@@ -187,262 +76,6 @@ __device__ __forceinline__ void seg_flush(int si, int sq, int lb, int pb, int eb
   cur.a[3] = mad24(pb, sq, cur.a[3]);
   cur.a[4] = mad24(eb, si, cur.a[4]);
   cur.a[5] = mad24(eb, sq, cur.a[5]);
-}
-
-// E/P/L bits of one half-chip as three 2-bit two's-complement fields
-// (late | prompt << 2 | early << 4; values -1 / 0 / +1), see pack8_table()
-__device__ __forceinline__ void unpack8(uint32_t w, int& lb, int& pb, int& eb) {
-  lb = __builtin_amdgcn_sbfe((int)w, 0, 2);
-  pb = __builtin_amdgcn_sbfe((int)w, 2, 2);
-  eb = __builtin_amdgcn_sbfe((int)w, 4, 2);
-}
-
-// Per-channel epilogue of a call (one thread): dumps, ms/bit counters, TIC latch,
-// carrier cycles and the new channel state (correlator.c:243-316).  sum(i):
-// the call's epoch sums, word i = epoch * 6 + k (LDS or global).  st_out (if
-// given) receives the new state as well.
-template <typename SumAt>
-__device__ __forceinline__ gnsscorr_track_result channel_epilogue(
-    const Chan& c, const gnsscorr_nco_cmd& cmd, gnsscorr_chan_state st, int chn, bool active,
-    uint32_t ndump, uint64_t Rtot, int nsamp, int64_t tic_count, SumAt sum,
-    gnsscorr_track_result* __restrict__ res, gnsscorr_chan_state* __restrict__ state,
-    int32_t* __restrict__ all_dumps, int max_dumps, gnsscorr_chan_state* st_out = nullptr) {
-  if (!active) {   // idle channel: only the epoch load (correlator.c:177-185)
-    gnsscorr_track_result r;
-    memset(&r, 0, sizeof r);
-    r.n_dumps = cmd.prn > 32 ? -1 : 0;
-    r.msbit_reg = st.msbit_reg;
-    res[chn] = r;
-    state[chn] = st;
-    if (st_out) *st_out = st;
-    return r;
-  }
-  gnsscorr_track_result r;
-  memset(&r, 0, sizeof r);
-  r.n_dumps = (int)ndump;
-  int ms = st.ms_counter, bit = st.bit_counter, msbit = st.msbit_reg;
-
-  const bool tic_here = tic_count >= 0 && tic_count < nsamp;
-  uint32_t nd_tic = 0;
-  uint64_t Rt = 0;
-  if (tic_here) {
-    Rt = ((uint64_t)c.K0 + (uint64_t)(tic_count + 1) * c.kinc2) >> 32;
-    nd_tic = n_dumps_after(c, Rt);
-  }
-  int msbit_at_tic = msbit;
-  for (uint32_t d = 0; d < ndump; d++) {
-    uint32_t v[6];
-#pragma unroll
-    for (int k = 0; k < 6; k++)
-      v[k] = sum(d * 6 + k) + (d == 0 ? (uint32_t)st.acc[k] : 0u);
-    if (all_dumps && (int)d < max_dumps)
-      for (int k = 0; k < 6; k++) all_dumps[((int64_t)chn * max_dumps + d) * 6 + k] = (int32_t)v[k];
-    if (d + 1 == ndump)
-      for (int k = 0; k < 6; k++) r.dump[k] = (int32_t)v[k];
-    msbit_step(ms, bit);
-    msbit = ms + (bit << 8);
-    if (d + 1 == nd_tic) msbit_at_tic = msbit;
-  }
-  uint32_t nacc[6];
-  for (int k = 0; k < 6; k++)
-    nacc[k] = sum(ndump * 6 + k) + (ndump == 0 ? (uint32_t)st.acc[k] : 0u);
-
-  const uint64_t Wtot = ((uint64_t)c.P0 + (uint64_t)nsamp * c.cinc) >> 32;
-  uint32_t cycle_end;
-  if (tic_here) {  // TIC latch after sample tic_count (correlator.c:286-303)
-    const uint64_t t1 = (uint64_t)tic_count + 1;
-    const uint64_t Wt = ((uint64_t)c.P0 + t1 * c.cinc) >> 32;
-    const uint32_t cyc = st.carrier_cycle + (uint32_t)Wt;
-    uint32_t hct, ldt, ept;
-    hc_after(c, Rt, hct, ldt, ept);
-    r.tic = 1;
-    r.tic_regs[0] = (int32_t)hct;
-    r.tic_regs[1] = (int32_t)(cyc & 0xffffu);
-    r.tic_regs[2] = (int32_t)((c.P0 + (uint32_t)t1 * c.cinc) >> 22);
-    r.tic_regs[3] = msbit_at_tic;
-    r.tic_regs[4] = (int32_t)((uint32_t)((uint64_t)c.K0 + t1 * c.kinc2) >> 22);
-    r.tic_regs[5] = (int32_t)(cyc >> 16);
-    cycle_end = (uint32_t)(Wtot - Wt);
-  } else {
-    cycle_end = st.carrier_cycle + (uint32_t)Wtot;
-  }
-  uint32_t hce, lde, epe;
-  hc_after(c, Rtot, hce, lde, epe);
-
-  r.msbit_reg = msbit;
-  res[chn] = r;
-
-  st.carrier_phase = c.P0 + (uint32_t)nsamp * c.cinc;
-  st.carrier_cycle = cycle_end;
-  st.code_phase = (uint32_t)((uint64_t)c.K0 + (uint64_t)nsamp * c.kinc2);
-  st.half_chip = hce;
-  for (int k = 0; k < 6; k++) st.acc[k] = (int32_t)nacc[k];
-  st.ms_counter = ms;
-  st.bit_counter = bit;
-  st.msbit_reg = msbit;
-  state[chn] = st;
-  if (st_out) *st_out = st;
-  return r;
-}
-
-// Epoch-segmented reduction of the per-thread sums and the per-channel epilogue
-// (one thread per channel): dumps, ms/bit counters, TIC latch, carrier cycles and
-// the new channel state (correlator.c:243-316).  Every thread of the workgroup
-// calls it (it holds a barrier).
-__device__ __forceinline__ void finish_call(const Chan& c, const gnsscorr_nco_cmd& cmd,
-                                            gnsscorr_chan_state st, int chn, bool have,
-                                            bool active, int tid, bool runs, int e0,
-                                            bool switched, const Acc& first, const Acc& cur,
-                                            int32_t* s_sum, uint32_t ndump, uint64_t Rtot,
-                                            int nsamp, int64_t tic_count,
-                                            gnsscorr_track_result* __restrict__ res,
-                                            gnsscorr_chan_state* __restrict__ state,
-                                            int32_t* __restrict__ all_dumps, int max_dumps) {
-  // ---- epoch-segmented reduction ------------------------------------------
-  // thread contributes (e0, switched ? first : cur) and (e0+1, cur) if switched
-  // (a wave never spans two thread groups: T is a multiple of 64)
-  const int e_hi_mine = e0 + (switched ? 1 : 0);
-  const int e_lo = wave_min(runs ? e0 : 0x7fffffff);
-  const int e_hi = wave_max(runs ? e_hi_mine : -1);
-  const int lane = threadIdx.x & 63;
-  for (int e = e_lo; e <= e_hi; e++) {
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-      uint32_t v = 0;
-      if (e == e0) v += switched ? first.a[k] : cur.a[k];
-      if (switched && e == e0 + 1) v += cur.a[k];
-      const int s = wave_sum((int)v);
-      if (lane == 0) atomicAdd(&s_sum[e * 6 + k], s);
-    }
-  }
-  __syncthreads();
-
-  // ---- per-channel epilogue (one thread per channel) ------------------------
-  if (tid != 0 || !have) return;
-  channel_epilogue(c, cmd, st, chn, active, ndump, Rtot, nsamp, tic_count,
-                   [&](int i) { return (uint32_t)s_sum[i]; }, res, state, all_dumps, max_dumps);
-}
-
-__device__ __forceinline__ int xcd_channel(int b, int G) {
-  const int q = G >> 3, r = G & 7, x = b & 7, slot = b >> 3;
-  return x * q + (x < r ? x : r) + slot;
-}
-
-// channel state and NCO words of one call (correlator.c:177-189)
-__device__ __forceinline__ bool chan_setup(const gnsscorr_nco_cmd& cmd, gnsscorr_chan_state& st,
-                                           Chan& c) {
-  if (cmd.epoch_load >= 0) {  // epoch set, correlator.c:177-182
-    const int v = cmd.epoch_load & 0xFFFF;
-    st.msbit_reg = v;
-    st.ms_counter = v & 0xff;
-    st.bit_counter = v >> 8;
-  }
-  const bool active = cmd.prn > 0 && cmd.prn <= 32;   // correlator.c:185
-  c.P0 = st.carrier_phase;
-  c.K0 = st.code_phase;
-  c.cinc = cmd.carrier_incr;
-  c.kinc2 = cmd.code_incr << 1;
-  c.hc0 = st.half_chip & 0xFFFFu;
-  c.D = (cmd.slew & 0xFFFFu) + 2046u;
-  const uint32_t h1 = (c.hc0 + 1u) & 0xFFFFu;
-  if (h1 >= c.D) c.j1 = 1;
-  else if (c.D <= 0xFFFFu) c.j1 = 1ull + (c.D - h1);
-  else c.j1 = kNever;  // uint16 half-chip can never reach D
-  c.base = (active ? cmd.prn : 0) * GNSSCORR_OSG_ROW;
-  return active;
-}
-
-// ============================================================================
-// osg_track_kernel: real-sample (I-only) streams, int8 or 2-bit packed (PK:
-// GNSSCORR_IF_PACKED2, if2.h).  Interleaved I,Q streams run on
-// osg_stream_kernel below.
-//
-// One workgroup = cpw channels (cpw = 1024 / threads-per-channel, at most
-// kMaxCpw) x one call; thread group q = threadIdx.x / T runs channel
-// grp * cpw + q.  Every thread walks its own run of kRun samples with the
-// reference recurrence (corr_sample): 256 threads x 64 samples cover a 1-ms
-// chunk at 16.368 Msps.  Full int8 runs are read as 16-byte vector loads, tail
-// runs and packed runs element by element.
-// ============================================================================
-template <bool PK>
-__global__ __launch_bounds__(kMaxThreads, 8) void osg_track_kernel(
-    const int8_t* __restrict__ ifbuf, int64_t stream_stride, int nsamp, int n_channels, int cpw,
-    const gnsscorr_nco_cmd* __restrict__ cmds, gnsscorr_chan_state* __restrict__ state,
-    gnsscorr_track_result* __restrict__ res, int32_t* __restrict__ all_dumps, int max_dumps,
-    const uint32_t* __restrict__ pk, int64_t tic_count) {
-  // dynamic LDS: [cpw][ep_cap][6] epoch sums
-  extern __shared__ uint4 s_dyn[];
-  const int ep_cap = nsamp / GNSSCORR_OSG_ROW + 2;   // >= epochs of one call
-  const int T = (int)blockDim.x / cpw;
-  // wave-uniform (T is a multiple of 64): keeps the channel's command, state
-  // and NCO constants in scalar registers
-  const int q = __builtin_amdgcn_readfirstlane((int)threadIdx.x / T);
-  const int tid = (int)threadIdx.x - q * T;
-  int32_t* s_sum = reinterpret_cast<int32_t*>(s_dyn) + q * ep_cap * 6;
-  // XCD-aware order: workgroup b runs on XCD b % 8, so give every XCD a
-  // contiguous channel range -- the channels of one receiver (consecutive
-  // channels sharing an IF stream) then hit the same 4 MiB L2 and the stream
-  // is fetched from HBM once instead of once per XCD.
-  const int chn = xcd_channel(blockIdx.x, gridDim.x) * cpw + q;
-  const bool have = chn < n_channels;
-  gnsscorr_nco_cmd cmd = {};
-  gnsscorr_chan_state st = {};
-  if (have) {
-    cmd = cmds[chn];
-    st = state[chn];
-  }
-  Chan c;
-  const bool active = chan_setup(cmd, st, c) && have;
-  const uint64_t Rtot = ((uint64_t)c.K0 + (uint64_t)nsamp * c.kinc2) >> 32;
-  const uint32_t ndump = n_dumps_after(c, Rtot);
-  const int n_epochs = (int)ndump + 1;
-  if (active)
-    for (int i = tid; i < n_epochs * 6; i += T) s_sum[i] = 0;
-  __syncthreads();
-
-  // ---- per-thread run of kRun samples --------------------------------------
-  Acc cur, first;
-#pragma unroll
-  for (int k = 0; k < 6; k++) { cur.a[k] = 0; first.a[k] = 0; }
-  bool switched = false;
-  int e0 = 0;
-  const int n0 = tid * kRun;
-  const bool runs = active && n0 < nsamp;
-  if (runs) {
-    const uint64_t X = (uint64_t)c.K0 + (uint64_t)n0 * c.kinc2;
-    uint32_t kph = (uint32_t)X;
-    uint32_t phase = c.P0 + (uint32_t)n0 * c.cinc;
-    uint32_t hc, ld, ep;
-    hc_after(c, X >> 32, hc, ld, ep);
-    e0 = (int)ep;
-    const uint32_t w = pk[c.base + (int)ld];
-    int lb = (int)(int8_t)(w & 0xFFu);
-    int pb = (int)(int8_t)((w >> 8) & 0xFFu);
-    int eb = (int)(int8_t)((w >> 16) & 0xFFu);
-    // element offset of the run (a multiple of 64: n0 and the stream base are);
-    // src is its first byte in either format
-    const int64_t e_run = (int64_t)cmd.stream * stream_stride + n0;
-    const int8_t* src = PK ? ifbuf + (e_run >> 2) : ifbuf + e_run;
-    if (!PK && n0 + kRun <= nsamp) {
-      const int4* v = reinterpret_cast<const int4*>(src);
-#pragma unroll
-      for (int j = 0; j < kRun / 16; j++) {
-        const int4 u = v[j];
-        const int words[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int wd = 0; wd < 4; wd++)
-#pragma unroll
-          for (int b = 0; b < 4; b++)
-            corr_sample(sbyte(words[wd], b), phase, kph, c, hc, lb, pb, eb, cur, first, switched, pk);
-      }
-    } else {   // per sample (tail runs; every packed run)
-      const int L = min(kRun, nsamp - n0);
-      for (int k = 0; k < L; k++)
-        corr_sample(if_elem(src, k, PK), phase, kph, c, hc, lb, pb, eb, cur, first, switched, pk);
-    }
-  }
-  finish_call(c, cmd, st, chn, have, active, tid, runs, e0, switched, first, cur, s_sum, ndump, Rtot,
-              nsamp, tic_count, res, state, all_dumps, max_dumps);
 }
 
 // ============================================================================
@@ -486,22 +119,15 @@ constexpr uint32_t kFastKinc2 = 0xFFFFFFFFu / 6u;   // >= 6 samples per half-chi
 // hc_after without a 32-bit division (m < 2^24: fp32 reciprocal + one fix-up)
 __device__ __forceinline__ void hc_after_fast(const Chan& c, uint64_t r, float invD, uint32_t& hc,
                                               uint32_t& ld, uint32_t& epoch) {
-  if (r < c.j1) {
-    epoch = 0;
-    hc = (uint32_t)((c.hc0 + r) & 0xFFFFu);
-    ld = hc;
-  } else {
-    const uint32_t m = (uint32_t)(r - c.j1);
-    uint32_t e = (uint32_t)((float)m * invD);
+  hc_rule(c, r, hc, ld, epoch, [&](uint32_t m, uint32_t& e, uint32_t& qu) {
+    e = (uint32_t)((float)m * invD);
     // e < 2^14 and D < 2^17 (r counts the half-chips of one call): a full-rate
     // 24-bit multiply, not v_mul_lo_u32
     int q = (int)(m - __umul24(e, c.D));
     if (q < 0) { q += (int)c.D; e--; }
     if (q >= (int)c.D) { q -= (int)c.D; e++; }
-    epoch = 1 + e;
-    hc = (uint32_t)q;
-    ld = q ? (uint32_t)q : (m == 0 ? (uint32_t)((c.hc0 + c.j1) & 0xFFFFu) : c.D);
-  }
+    qu = (uint32_t)q;
+  });
 }
 
 // Lane state through its pieces.
@@ -513,20 +139,45 @@ struct Seg {
   bool carried;               // a code carry in the current interval
 };
 
-// one pair of samples (IF word x) in the branch-free interval form; ONE: the
-// word holds a single (last) sample, so no carry after a second one.  The LO
-// word pairs are two 256-byte tables (ival words, qval words): a ds_read_b32 of
-// 64 lanes then touches each bank at most once per distinct entry (64 entries
-// x 4 B = the 64 banks), where one 512-byte uint2 table would put entries e and
-// e + 32 on the same banks
+// lane a | b << 3 writes the LO words of the sample pair (a, b) into the table
+// lt: the ival word, and 64 entries on the qval word
+__device__ __forceinline__ void lo_words(int lane, uint32_t* lt) {
+  const int a = lane & 7, b = lane >> 3;
+  const uint32_t ia = (uint32_t)__builtin_amdgcn_sbfe((int)kLutI, 4 * a, 4) & 0xFFu;
+  const uint32_t qa = (uint32_t)__builtin_amdgcn_sbfe((int)kLutQ, 4 * a, 4) & 0xFFu;
+  const uint32_t ib = (uint32_t)__builtin_amdgcn_sbfe((int)kLutI, 4 * b, 4) & 0xFFu;
+  const uint32_t qb = (uint32_t)__builtin_amdgcn_sbfe((int)kLutQ, 4 * b, 4) & 0xFFu;
+  lt[lane] = ia | qa << 8 | ib << 16 | qb << 24;
+  lt[64 + lane] = qa | ((0u - ia) & 0xFFu) << 8 | qb << 16 | ((0u - ib) & 0xFFu) << 24;
+}
+
+// a pair's IF word x onto the interval sums: the whole word, and its part before
+// the carry (mask m)
+__device__ __forceinline__ void pair_dots(uint32_t x, uint32_t m, uint32_t lo_x, uint32_t lo_y,
+                                          Seg& g) {
+  const uint32_t xm = x & m;
+  g.ti = dot4(x, lo_x, g.ti);
+  g.tq = dot4(x, lo_y, g.tq);
+  g.pi = dot4(xm, lo_x, g.pi);
+  g.pq = dot4(xm, lo_y, g.pq);
+}
+
+// flush the part before the carry with the current bits and carry the rest into
+// the next segment (correlator.c:213-241)
+__device__ __forceinline__ void seg_carry(Seg& g, Acc& acc) {
+  seg_flush(g.pi, g.pq, g.lb, g.pb, g.eb, acc);
+  const int ri = g.ti - g.pi, rq = g.tq - g.pq;
+  g.ti = g.pi = ri;
+  g.tq = g.pq = rq;
+}
+
+// one pair of samples (IF word x, LO words lo_x / lo_y) in the branch-free
+// interval form; ONE: the word holds a single (last) sample, so no carry after
+// a second one.  (kPF: a piece's 16 LO word pairs are read from LDS before its
+// first interval)
 template <bool ONE>
-__device__ __forceinline__ void pair2s(uint32_t x, const Chan& c, Seg& g,
-                                       const uint32_t* __restrict__ lox,
-                                       const uint32_t* __restrict__ loy) {
-  const uint32_t p1 = g.p0 + c.cinc;
-  const uint32_t idx = (g.p0 >> 29) | ((p1 >> 26) & 0x38u);
-  const uint32_t lo_x = lox[idx], lo_y = loy[idx];
-  g.p0 = p1 + c.cinc;
+__device__ __forceinline__ void pair2r(uint32_t x, uint32_t lo_x, uint32_t lo_y, const Chan& c,
+                                       Seg& g) {
   const uint32_t k0 = g.kph + c.kinc2;
   const bool c0 = k0 < g.kph;
   uint32_t k1 = k0;
@@ -539,11 +190,32 @@ __device__ __forceinline__ void pair2s(uint32_t x, const Chan& c, Seg& g,
   uint32_t m = c0 ? 0xFFFFu : 0xFFFFFFFFu;
   m = g.carried ? 0u : m;
   g.carried = g.carried | c0 | c1;
-  const uint32_t xm = x & m;
-  g.ti = dot4(x, lo_x, g.ti);
-  g.tq = dot4(x, lo_y, g.tq);
-  g.pi = dot4(xm, lo_x, g.pi);
-  g.pq = dot4(xm, lo_y, g.pq);
+  pair_dots(x, m, lo_x, lo_y, g);
+}
+
+// the LO words of the pair at carrier phase g.p0, which moves on to the next
+// pair.  The LO word pairs are two 256-byte tables (ival words, qval words): a
+// ds_read_b32 of 64 lanes then touches each bank at most once per distinct entry
+// (64 entries x 4 B = the 64 banks), where one 512-byte uint2 table would put
+// entries e and e + 32 on the same banks.  (No __restrict__ of its own: what the
+// compiler may assume of the tables stays what each caller says.)
+__device__ __forceinline__ void pair_lo(const Chan& c, Seg& g, const uint32_t* lox,
+                                        const uint32_t* loy, uint32_t& lo_x, uint32_t& lo_y) {
+  const uint32_t p1 = g.p0 + c.cinc;
+  const uint32_t idx = (g.p0 >> 29) | ((p1 >> 26) & 0x38u);
+  lo_x = lox[idx];
+  lo_y = loy[idx];
+  g.p0 = p1 + c.cinc;
+}
+
+// pair2r with the pair's LO words looked up as it goes
+template <bool ONE>
+__device__ __forceinline__ void pair2s(uint32_t x, const Chan& c, Seg& g,
+                                       const uint32_t* __restrict__ lox,
+                                       const uint32_t* __restrict__ loy) {
+  uint32_t lo_x, lo_y;
+  pair_lo(c, g, lox, loy, lo_x, lo_y);
+  pair2r<ONE>(x, lo_x, lo_y, c, g);
 }
 
 // ============================================================================
@@ -648,7 +320,7 @@ __device__ __forceinline__ void flush_lanes(bool fl, Acc& acc, int e, int32_t* s
 
 // LDS per wavefront: [IF slot (int8)] [E/P/L row] [epoch sums] [64 LO word pairs]
 __host__ __device__ constexpr int stream_sum_bytes(int nsamp) {
-  return (((nsamp / GNSSCORR_OSG_ROW + 2) * 24 + 15) & ~15);
+  return ((epoch_cap(nsamp) * 24 + 15) & ~15);
 }
 __host__ __device__ constexpr int stream_wave_lds(bool pk, int nsamp) {
   return (pk ? 0 : kStage2Bytes) + kPk8Stage + stream_sum_bytes(nsamp) + 512;
@@ -683,10 +355,7 @@ struct StreamArgs {
 template <bool PF, bool DUMPS = true>
 __device__ __forceinline__ void interval_end_s(const Chan& c, Seg& g, Acc& acc, int& e,
                                                int32_t* s_sum, const uint8_t* __restrict__ row) {
-  seg_flush(g.pi, g.pq, g.lb, g.pb, g.eb, acc);
-  const int ri = g.ti - g.pi, rq = g.tq - g.pq;
-  g.ti = g.pi = ri;
-  g.tq = g.pq = rq;
+  seg_carry(g, acc);
   const bool cy = g.carried;
   g.hc += cy ? 1u : 0u;
   if constexpr (!PF) g.ld = cy ? g.hc : g.ld;
@@ -714,30 +383,6 @@ __device__ __forceinline__ void interval_end_s(const Chan& c, Seg& g, Acc& acc, 
   }
 }
 
-// pair2s with the pair's LO words already in registers (kPF: a piece's 16
-// LO word pairs are read from LDS before its first interval)
-template <bool ONE>
-__device__ __forceinline__ void pair2r(uint32_t x, uint32_t lo_x, uint32_t lo_y, const Chan& c,
-                                       Seg& g) {
-  const uint32_t k0 = g.kph + c.kinc2;
-  const bool c0 = k0 < g.kph;
-  uint32_t k1 = k0;
-  bool c1 = false;
-  if (!ONE) {
-    k1 = k0 + c.kinc2;
-    c1 = k1 < k0;
-  }
-  g.kph = k1;
-  uint32_t m = c0 ? 0xFFFFu : 0xFFFFFFFFu;
-  m = g.carried ? 0u : m;
-  g.carried = g.carried | c0 | c1;
-  const uint32_t xm = x & m;
-  g.ti = dot4(x, lo_x, g.ti);
-  g.tq = dot4(x, lo_y, g.tq);
-  g.pi = dot4(xm, lo_x, g.pi);
-  g.pq = dot4(xm, lo_y, g.pq);
-}
-
 // one sample of the reference recurrence (correlator.c:200-283) on the
 // running sums; ROW: the E/P/L bits from the LDS row, else the global table
 template <bool ROW>
@@ -745,22 +390,12 @@ __device__ __forceinline__ void corr_sample_s(int I, int Q, uint32_t& phase, uin
                                               const Chan& c, uint32_t& hc, int& lb, int& pb,
                                               int& eb, Acc& acc, int& e, int32_t* s_sum,
                                               const uint8_t* row, const uint32_t* __restrict__ pk) {
-  const uint32_t off = (phase >> 27) & 0x1Cu;
-  const int il = __builtin_amdgcn_sbfe((int)kLutI, off, 4);
-  const int ql = __builtin_amdgcn_sbfe((int)kLutQ, off, 4);
-  const int ival = il * I + ql * Q;   // correlator.c:215
-  const int qval = ql * I - il * Q;   // correlator.c:214
-  acc.a[0] += (uint32_t)(lb * ival);
-  acc.a[1] += (uint32_t)(lb * qval);
-  acc.a[2] += (uint32_t)(pb * ival);
-  acc.a[3] += (uint32_t)(pb * qval);
-  acc.a[4] += (uint32_t)(eb * ival);
-  acc.a[5] += (uint32_t)(eb * qval);
-  phase += c.cinc;
-  const uint32_t nk = kph + c.kinc2;
-  const bool carry = nk < kph;
-  kph = nk;
-  if (carry) {
+  int il, ql;
+  sample_lo(phase, il, ql);
+  sample_acc(il * I + ql * Q,   // correlator.c:215
+             ql * I - il * Q,   // correlator.c:214
+             lb, pb, eb, acc);
+  if (sample_nco(c, phase, kph)) {
     hc = (hc + 1u) & 0xFFFFu;
     const uint32_t ld = hc;
     if (hc >= c.D) {
@@ -771,10 +406,7 @@ __device__ __forceinline__ void corr_sample_s(int I, int Q, uint32_t& phase, uin
     if constexpr (ROW) {
       unpack8(row[ld], lb, pb, eb);
     } else {
-      const uint32_t w = pk[c.base + (int)ld];
-      lb = (int)(int8_t)(w & 0xFFu);
-      pb = (int)(int8_t)((w >> 8) & 0xFFu);
-      eb = (int)(int8_t)((w >> 16) & 0xFFu);
+      unpack_pk(pk[c.base + (int)ld], lb, pb, eb);
     }
   }
 }
@@ -794,7 +426,7 @@ __global__ __launch_bounds__(64 * kStreamCh, CLOSED ? 1 : 4) void osg_stream_ker
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int lane = (int)threadIdx.x & 63;
   const int nsamp = A.nsamp;
-  const int ep_cap = nsamp / GNSSCORR_OSG_ROW + 2;
+  const int ep_cap = epoch_cap(nsamp);
   // the 64 (a, b) LO word pairs as two 256-byte tables at a fixed LDS address,
   // shared by the workgroup's waves: a pair's words are one ds_read2_b32 whose
   // address is the byte index 4 (a | b << 3) itself (kPF); without the read-ahead
@@ -808,13 +440,7 @@ __global__ __launch_bounds__(64 * kStreamCh, CLOSED ? 1 : 4) void osg_stream_ker
     for (int i = threadIdx.x; i < 256; i += blockDim.x) s_x2[i] = if2_expand_byte((uint32_t)i);
   }
   if (kPF && threadIdx.x < 64) {
-    const int a = lane & 7, b = lane >> 3;
-    const uint32_t ia = (uint32_t)__builtin_amdgcn_sbfe((int)kLutI, 4 * a, 4) & 0xFFu;
-    const uint32_t qa = (uint32_t)__builtin_amdgcn_sbfe((int)kLutQ, 4 * a, 4) & 0xFFu;
-    const uint32_t ib = (uint32_t)__builtin_amdgcn_sbfe((int)kLutI, 4 * b, 4) & 0xFFu;
-    const uint32_t qb = (uint32_t)__builtin_amdgcn_sbfe((int)kLutQ, 4 * b, 4) & 0xFFu;
-    s_lot[lane] = ia | qa << 8 | ib << 16 | qb << 24;
-    s_lot[64 + lane] = qa | ((0u - ia) & 0xFFu) << 8 | qb << 16 | ((0u - ib) & 0xFFu) << 24;
+    lo_words(lane, s_lot);
   }
   if (kPF || kX2) __syncthreads();   // the only workgroup barrier: before any wave leaves
   uint8_t* wb = reinterpret_cast<uint8_t*>(s_dyn) + wave * stream_wave_lds(PK, nsamp);
@@ -827,14 +453,7 @@ __global__ __launch_bounds__(64 * kStreamCh, CLOSED ? 1 : 4) void osg_stream_ker
   const int chn = xcd_channel(blockIdx.x, gridDim.x) * kStreamCh + wave;
   if (chn >= C) return;   // wave-uniform; no workgroup barrier from here on
   if constexpr (!kPF) {
-    const int a = lane & 7, b = lane >> 3;   // LO words of the sample pair (a, b)
-    const uint32_t ia = (uint32_t)__builtin_amdgcn_sbfe((int)kLutI, 4 * a, 4) & 0xFFu;
-    const uint32_t qa = (uint32_t)__builtin_amdgcn_sbfe((int)kLutQ, 4 * a, 4) & 0xFFu;
-    const uint32_t ib = (uint32_t)__builtin_amdgcn_sbfe((int)kLutI, 4 * b, 4) & 0xFFu;
-    const uint32_t qb = (uint32_t)__builtin_amdgcn_sbfe((int)kLutQ, 4 * b, 4) & 0xFFu;
-    uint32_t* lt = reinterpret_cast<uint32_t*>(s_lo);
-    lt[lane] = ia | qa << 8 | ib << 16 | qb << 24;
-    lt[64 + lane] = qa | ((0u - ia) & 0xFFu) << 8 | qb << 16 | ((0u - ib) & 0xFFu) << 24;
+    lo_words(lane, reinterpret_cast<uint32_t*>(s_lo));
   }
   const uint32_t* lox = reinterpret_cast<const uint32_t*>(s_lo);
   const uint32_t* loy = lox + 64;
@@ -1097,22 +716,11 @@ __global__ __launch_bounds__(64 * kStreamCh, CLOSED ? 1 : 4) void osg_stream_ker
                 lo_x = lwx[4 * t + i];
                 lo_y = lwy[4 * t + i];
               } else {
-                const uint32_t p1 = g.p0 + c.cinc;
-                const uint32_t idx = (g.p0 >> 29) | ((p1 >> 26) & 0x38u);
-                lo_x = lox[idx];
-                lo_y = loy[idx];
-                g.p0 = p1 + c.cinc;
+                pair_lo(c, g, lox, loy, lo_x, lo_y);
               }
-              const uint32_t xm = words[i] & mq[i];
-              g.ti = dot4(words[i], lo_x, g.ti);
-              g.tq = dot4(words[i], lo_y, g.tq);
-              g.pi = dot4(xm, lo_x, g.pi);
-              g.pq = dot4(xm, lo_y, g.pq);
+              pair_dots(words[i], mq[i], lo_x, lo_y, g);
             }
-            seg_flush(g.pi, g.pq, g.lb, g.pb, g.eb, acc);
-            const int ri = g.ti - g.pi, rq = g.tq - g.pq;
-            g.ti = g.pi = ri;
-            g.tq = g.pq = rq;
+            seg_carry(g, acc);
             g.hc += 1u;   // no dump in the piece (the caller's ballot)
             if constexpr (kPF) {
               g.cb = g.nb;
@@ -1196,10 +804,7 @@ __global__ __launch_bounds__(64 * kStreamCh, CLOSED ? 1 : 4) void osg_stream_ker
         if (pk_lds) {
           unpack8(row[g.ld], lb, pb, eb);
         } else {
-          const uint32_t tw = A.pk[c.base + (int)g.ld];
-          lb = (int)(int8_t)(tw & 0xFFu);
-          pb = (int)(int8_t)((tw >> 8) & 0xFFu);
-          eb = (int)(int8_t)((tw >> 16) & 0xFFu);
+          unpack_pk(A.pk[c.base + (int)g.ld], lb, pb, eb);
         }
         uint32_t phase = g.p0, kph = g.kph;
         auto per_sample = [&](auto row_tag) {
@@ -1273,192 +878,15 @@ __global__ __launch_bounds__(64 * kStreamCh, CLOSED ? 1 : 4) void osg_stream_ker
 
 }  // namespace
 
-// ============================================================================
-// context / C ABI
-// ============================================================================
-struct gnsscorr_track_ctx {
-  gnsscorr_track_cfg cfg;
-  hipStream_t stream = nullptr;
-  uint32_t* d_pk = nullptr;
-  uint8_t* d_pk8 = nullptr;   // the same table as 2-bit E/P/L fields (unpack8)
-  gnsscorr_chan_state* d_state = nullptr;
-  gnsscorr_nco_cmd* d_cmds = nullptr;
-  gnsscorr_track_result* d_res = nullptr;
-  int32_t* d_dumps = nullptr;
-  hostctx::DevBuf<int8_t> d_if;   // gnsscorr_track's staging, in bytes
-  int max_dumps = 0;
-  int64_t tic = 0, tic_ref = 0;
-  int balance = 1;        // GNSSCORR_TRACK_BALANCE=0: no LDS padding for an even spread (A/B)
-  int xcall_prefetch = 1;  // GNSSCORR_TRACK_XPF=0: no cross-call piece prefetch (A/B)
-  int n_cu = 256;
-  size_t lds_max = 0;     // LDS bytes a workgroup may allocate (gnsscorr_device_lds_bytes)
-};
-
-extern "C" int gnsscorr_track_iq(const gnsscorr_track_ctx* ctx) { return ctx && (ctx->cfg.iq & GNSSCORR_IF_IQ); }
-static bool packed(const gnsscorr_track_ctx* c) { return (c->cfg.iq & GNSSCORR_IF_PACKED2) != 0; }
-static int bps_of(const gnsscorr_track_ctx* c) { return (c->cfg.iq & GNSSCORR_IF_IQ) ? 2 : 1; }
-// bytes of `samples` consecutive samples of one stream in the context's format
-extern "C" int64_t gnsscorr_track_if_bytes(const gnsscorr_track_ctx* c, int64_t samples) {
-  return if_bytes(samples * bps_of(c), packed(c));
-}
-
-static int set_dev(int dev) {
-  HIP_TRY(hipSetDevice(dev));
-  return GNSSCORR_OK;
-}
-
-// the stream, the device buffers and the code tables on them
-static int init_device(gnsscorr_track_ctx* c) {
-  const int C = c->cfg.n_channels;
-  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  HIP_TRY(hipMalloc(&c->d_pk, sizeof(uint32_t) * GNSSCORR_OSG_PK_LEN));
-  HIP_TRY(hipMalloc(&c->d_pk8, GNSSCORR_OSG_PK_LEN + 64));   // +64: whole-dword row staging
-  HIP_TRY(hipMalloc(&c->d_state, sizeof(gnsscorr_chan_state) * C));
-  HIP_TRY(hipMalloc(&c->d_cmds, sizeof(gnsscorr_nco_cmd) * C));
-  HIP_TRY(hipMalloc(&c->d_res, sizeof(gnsscorr_track_result) * C));
-  HIP_TRY(hipMalloc(&c->d_dumps, sizeof(int32_t) * 6 * (size_t)C * c->max_dumps));
-  std::vector<uint32_t> pk(GNSSCORR_OSG_PK_LEN);
-  gnsscorr_osg_packed_table(pk.data());
-  HIP_TRY(hipMemcpy(c->d_pk, pk.data(), sizeof(uint32_t) * GNSSCORR_OSG_PK_LEN,
-                    hipMemcpyHostToDevice));
-  // pack8: each int8 bit (-1 / 0 / +1) of {late, prompt, early} as a 2-bit field
-  std::vector<uint8_t> pk8(GNSSCORR_OSG_PK_LEN);
-  for (int i = 0; i < GNSSCORR_OSG_PK_LEN; i++) {
-    uint32_t b = 0;
-    for (int k = 0; k < 3; k++) b |= ((uint32_t)(int8_t)(pk[i] >> (8 * k)) & 3u) << (2 * k);
-    pk8[i] = (uint8_t)b;
-  }
-  HIP_TRY(hipMemset(c->d_pk8, 0, GNSSCORR_OSG_PK_LEN + 64));
-  HIP_TRY(hipMemcpy(c->d_pk8, pk8.data(), GNSSCORR_OSG_PK_LEN, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(c->d_state, 0, sizeof(gnsscorr_chan_state) * C));
-  return GNSSCORR_OK;
-}
-
-extern "C" int gnsscorr_track_create(gnsscorr_track_ctx** out, const gnsscorr_track_cfg* cfg) {
-  if (!out || !cfg || cfg->n_channels < 1 || cfg->max_nsamp < 1 || cfg->max_nsamp > kMaxNsamp ||
-      (cfg->iq & ~(GNSSCORR_IF_IQ | GNSSCORR_IF_PACKED2))) {
-    gnsscorr_set_error("gnsscorr_track_create: bad config (n_channels>=1, 1<=max_nsamp<=%d, "
-                       "iq = GNSSCORR_IF_* flags)", kMaxNsamp);
-    return GNSSCORR_EINVAL;
-  }
-  *out = nullptr;
-  int rc = hostctx::open_device(__func__, cfg->device);
-  if (rc) return rc;
-  auto* c = new gnsscorr_track_ctx();
-  c->cfg = *cfg;
-  c->lds_max = (size_t)gnsscorr_device_lds_bytes(cfg->device);
-  c->max_dumps = cfg->max_nsamp / GNSSCORR_OSG_ROW + 2;
-  c->tic_ref = (int64_t)(cfg->samp_rate * cfg->tic_period);
-  c->tic = c->tic_ref;
-  if (const char* e = getenv("GNSSCORR_TRACK_BALANCE")) c->balance = atoi(e) != 0;
-  if (const char* e = getenv("GNSSCORR_TRACK_XPF")) c->xcall_prefetch = atoi(e) != 0;
-  if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, cfg->device) !=
-          hipSuccess || c->n_cu < 1)
-    c->n_cu = 256;
-  rc = init_device(c);
-  if (rc) {
-    gnsscorr_track_destroy(c);
-    return rc;
-  }
-  *out = c;
-  return GNSSCORR_OK;
-}
-
-// Layout hint (round 2: per-channel LDS staging for one stream per channel).
-// Neither kernel needs it: osg_stream_kernel gives every channel its own
-// wavefront and IF pieces whatever the layout, and osg_track_kernel's threads
-// read their runs from global memory.  The hint is validated and has no effect.
-extern "C" int gnsscorr_track_set_layout(gnsscorr_track_ctx* c, int one_stream_per_channel) {
-  if (!c || one_stream_per_channel < 0 || one_stream_per_channel > 1) {
-    gnsscorr_set_error("gnsscorr_track_set_layout: bad arguments");
-    return GNSSCORR_EINVAL;
-  }
-  return GNSSCORR_OK;
-}
-
-extern "C" int gnsscorr_track_destroy(gnsscorr_track_ctx* c) {
-  return hostctx::destroy(c, [&] {
-    hostctx::release(c->d_pk, c->d_pk8, c->d_state, c->d_cmds, c->d_res, c->d_dumps, c->d_if);
-  });
-}
-
-extern "C" int gnsscorr_track_max_dumps(const gnsscorr_track_ctx* c) { return c ? c->max_dumps : 0; }
-
-extern "C" int64_t gnsscorr_track_next_tic(gnsscorr_track_ctx* c, int64_t nsamp) {
-  // correlator.c:155-165
-  if (c->tic < nsamp) {
-    const int64_t t = c->tic;
-    c->tic += c->tic_ref - nsamp;
-    return t;
-  }
-  c->tic -= nsamp;
-  return -1;
-}
-
-// nsamp and the IF alignment of one call (gnsscorr.h, "IF alignment of the
-// device calls"); launches nothing and changes nothing.  step: the call's index
-// in a multi-step request, named in the error text (-1: a single call).
-//   IQ int8      16-byte base and stream stride (LDS-DMA chunks of 16 bytes)
-//   IQ packed    8-byte base and stream stride (packed runs are read in 8-byte words)
-//   I-only int8  16-byte base and stream stride (osg_track_kernel's int4 loads)
-//   I-only packed any base, whole-byte stream stride (osg_track_kernel<true>
-//                reads its runs byte by byte, and a run starts on a multiple of
-//                64 elements of its stream)
-static int check_call(const gnsscorr_track_ctx* c, const int8_t* d_if, int64_t stride,
-                      int64_t nsamp, int step) {
-  if (nsamp < 1 || nsamp > c->cfg.max_nsamp) {
-    gnsscorr_set_error("nsamp %lld outside [1, max_nsamp=%d]", (long long)nsamp, c->cfg.max_nsamp);
-    return GNSSCORR_EINVAL;
-  }
-  const int bps = bps_of(c);
-  const bool pk = packed(c), iq = bps == 2;
-  const int base_al = pk ? (iq ? 8 : 1) : 16;
-  const int stride_al = base_al;   // bytes
-  const int64_t stride_elems = stride * bps;
-  // packed: four elements per byte, so the stride and a later step's offset
-  // must be whole bytes before their alignment means anything
-  const bool whole = !pk || (((stride_elems | (step > 0 ? step * nsamp * bps : 0)) & 3) == 0);
-  if (((uintptr_t)d_if & (uintptr_t)(base_al - 1)) || !whole ||
-      (if_bytes(stride_elems, pk) & (stride_al - 1))) {
-    char at[96] = "";
-    if (step >= 0) snprintf(at, sizeof at, "step %d (IF at element offset %lld): ", step,
-                            (long long)((int64_t)step * nsamp * bps));
-    gnsscorr_set_error("%s%s %s IF needs a %d-byte aligned base and a stream stride of whole "
-                       "%d-byte units%s", at, iq ? "IQ" : "I-only", pk ? "packed" : "int8", base_al,
-                       stride_al, pk ? " (4 elements per byte)" : "");
-    return GNSSCORR_EINVAL;
-  }
-  return GNSSCORR_OK;
-}
-
-// Every step of a multi-step request (step k reads the IF at + k * nsamp
-// samples) before any of them runs: a refused request leaves the channel
-// state, the TIC counter and the result arrays as they were.
-extern "C" int gnsscorr_track_check_steps(const gnsscorr_track_ctx* c, const int8_t* d_if,
-                                          int64_t stride, int64_t nsamp, int n_steps) {
-  for (int k = 0; k < n_steps; k++)
-    if (int rc = check_call(c, d_if + gnsscorr_track_if_bytes(c, (int64_t)k * nsamp), stride, nsamp,
-                            n_steps > 1 ? k : -1))
-      return rc;
-  return GNSSCORR_OK;
-}
-
-// osg_stream_kernel: n_calls consecutive calls of every channel in one launch
-// (call k reads the IF at + k * nsamp samples of each stream and the commands
-// at d_cmds + k * cmd_step; the results go to d_res + k * n_channels).  tic: the
-// first call's TIC sample (tic_explicit) or the TIC counter to step per call.
-// lcfg/d_loops: the closed loop, every channel's gpsisr step after each call.
-// Returns GNSSCORR_TRACK_NOT_FUSED when the kernel does not serve the context
-// (I-only streams) or the shape (alignment of the later calls of n_calls > 1);
-// a single call of an IQ context is always served.
-static int launch_stream(gnsscorr_track_ctx* c, const int8_t* d_if, int64_t stride, int64_t nsamp,
-                         int n_calls, gnsscorr_nco_cmd* d_cmds, int cmd_step,
-                         gnsscorr_track_result* d_res, int32_t* d_dumps, int64_t tic,
-                         int tic_explicit, const gnsscorr_osg_loop_cfg* lcfg,
-                         gnsscorr_osg_loop* d_loops, gnsscorr_osg_loop* d_hist) {
+// (track_ctx.h)
+int track_stream_launch(gnsscorr_track_ctx* c, const int8_t* d_if, int64_t stride, int64_t nsamp,
+                        int n_calls, gnsscorr_nco_cmd* d_cmds, int cmd_step,
+                        gnsscorr_track_result* d_res, int32_t* d_dumps, int64_t tic,
+                        int tic_explicit, const gnsscorr_osg_loop_cfg* lcfg,
+                        gnsscorr_osg_loop* d_loops, gnsscorr_osg_loop* d_hist) {
   const bool pk = packed(c), iq = bps_of(c) == 2;
   if (!iq) return GNSSCORR_TRACK_NOT_FUSED;
-  if (int rc = check_call(c, d_if, stride, nsamp, -1)) return rc;
+  if (int rc = gnsscorr_track_check_steps(c, d_if, stride, nsamp, 1)) return rc;
   // later calls start at + k * nsamp samples: the same alignment, and whole
   // 8-sample chunks (the partial-chunk path is for single calls)
   if (n_calls > 1 && ((nsamp * 2) & (pk ? 31 : 15))) return GNSSCORR_TRACK_NOT_FUSED;
@@ -1518,198 +946,4 @@ static int launch_stream(gnsscorr_track_ctx* c, const int8_t* d_if, int64_t stri
   else hipLaunchKernelGGL((osg_stream_kernel<false, false>), grid, block, dyn, c->stream, A);
   HIP_TRY(hipGetLastError());
   return GNSSCORR_OK;
-}
-
-static int launch(gnsscorr_track_ctx* c, const int8_t* d_if, int64_t stride, int64_t nsamp,
-                  const gnsscorr_nco_cmd* d_cmds, gnsscorr_track_result* d_res,
-                  int32_t* d_dumps, int64_t tic_count) {
-  if (int rc = check_call(c, d_if, stride, nsamp, -1)) return rc;
-  const bool pk = packed(c), iq = bps_of(c) == 2;
-  if (iq)   // (one call of an IQ context is never GNSSCORR_TRACK_NOT_FUSED)
-    return launch_stream(c, d_if, stride, nsamp, 1, const_cast<gnsscorr_nco_cmd*>(d_cmds), 0, d_res,
-                         d_dumps, tic_count, 1, nullptr, nullptr, nullptr);
-  // I-only: osg_track_kernel, one thread per 64-sample run, as many channels
-  // per workgroup as fit 1024 threads
-  const int C = c->cfg.n_channels;
-  const int threads = ((int)((nsamp + kRun - 1) / kRun) + 63) & ~63;
-  const int cpw = min(kMaxCpw, kMaxThreads / threads);
-  // dynamic LDS: the channels' epoch sums (under 1 KiB at every permitted nsamp)
-  const size_t dyn = (size_t)cpw * ((int)nsamp / GNSSCORR_OSG_ROW + 2) * 6 * sizeof(int32_t);
-  dim3 grid((C + cpw - 1) / cpw), block(threads * cpw);
-  if (pk)
-    hipLaunchKernelGGL((osg_track_kernel<true>), grid, block, dyn, c->stream, d_if, stride, (int)nsamp,
-                       C, cpw, d_cmds, c->d_state, d_res, d_dumps, c->max_dumps, c->d_pk, tic_count);
-  else
-    hipLaunchKernelGGL((osg_track_kernel<false>), grid, block, dyn, c->stream, d_if, stride, (int)nsamp,
-                       C, cpw, d_cmds, c->d_state, d_res, d_dumps, c->max_dumps, c->d_pk, tic_count);
-  HIP_TRY(hipGetLastError());
-  return GNSSCORR_OK;
-}
-
-extern "C" int gnsscorr_track(gnsscorr_track_ctx* c, const int8_t* h_if, int64_t stride,
-                              int n_streams, int64_t nsamp, const gnsscorr_nco_cmd* h_cmds,
-                              gnsscorr_track_result* h_res, int32_t* h_all_dumps, int* tic_fired) {
-  if (!c || !h_if || !h_cmds || !h_res || n_streams < 1 || nsamp < 1) {
-    gnsscorr_set_error("gnsscorr_track: bad arguments");
-    return GNSSCORR_EINVAL;
-  }
-  const int C = c->cfg.n_channels;
-  for (int i = 0; i < C; i++) {
-    if (h_cmds[i].prn < 0 || h_cmds[i].prn > 32 || h_cmds[i].stream < 0 ||
-        h_cmds[i].stream >= n_streams) {
-      gnsscorr_set_error("gnsscorr_track: channel %d: prn %d / stream %d invalid", i,
-                         h_cmds[i].prn, h_cmds[i].stream);
-      return GNSSCORR_EINVAL;
-    }
-  }
-  if (n_streams == 1) stride = 0;
-  if (n_streams > 1 && stride < nsamp) {
-    gnsscorr_set_error("gnsscorr_track: stream_stride < nsamp");
-    return GNSSCORR_EINVAL;
-  }
-  int rc = set_dev(c->cfg.device);
-  if (rc) return rc;
-  const int bps = bps_of(c);
-  const bool pk = packed(c);
-  if (pk && n_streams > 1 && (stride * bps) & 3) {
-    gnsscorr_set_error("gnsscorr_track: packed streams need a whole-byte stream stride");
-    return GNSSCORR_EINVAL;
-  }
-  // device copy with an aligned stride (16 int8 bytes / 8 packed bytes = 32 elements)
-  const int64_t al = pk ? 32 : 16;
-  const int64_t dstride = n_streams > 1 ? ((stride * bps + al - 1) & ~(al - 1)) / bps : 0;
-  const size_t need = (size_t)if_bytes((n_streams - 1) * dstride * bps + ((nsamp * bps + al - 1) & ~(al - 1)), pk);
-  if ((rc = hostctx::grow(c->d_if, need))) return rc;
-  if (n_streams == 1 || dstride == stride) {
-    HIP_TRY(hipMemcpyAsync(c->d_if.p, h_if, (size_t)if_bytes(((n_streams - 1) * stride + nsamp) * bps, pk),
-                           hipMemcpyHostToDevice, c->stream));
-  } else {
-    HIP_TRY(hipMemcpy2DAsync(c->d_if.p, if_bytes(dstride * bps, pk), h_if, if_bytes(stride * bps, pk),
-                             if_bytes(nsamp * bps, pk), n_streams, hipMemcpyHostToDevice, c->stream));
-  }
-  HIP_TRY(hipMemcpyAsync(c->d_cmds, h_cmds, sizeof(gnsscorr_nco_cmd) * C, hipMemcpyHostToDevice,
-                         c->stream));
-  const int64_t tic = gnsscorr_track_next_tic(c, nsamp);
-  rc = launch(c, c->d_if.p, dstride, nsamp, c->d_cmds, c->d_res, h_all_dumps ? c->d_dumps : nullptr,
-              tic);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h_res, c->d_res, sizeof(gnsscorr_track_result) * C,
-                         hipMemcpyDeviceToHost, c->stream));
-  if (h_all_dumps)
-    HIP_TRY(hipMemcpyAsync(h_all_dumps, c->d_dumps, sizeof(int32_t) * 6 * (size_t)C * c->max_dumps,
-                           hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (tic_fired) *tic_fired = tic >= 0;
-  return GNSSCORR_OK;
-}
-
-extern "C" int gnsscorr_track_dev(gnsscorr_track_ctx* c, const int8_t* d_if, int64_t stride,
-                                  int64_t nsamp, const gnsscorr_nco_cmd* d_cmds,
-                                  gnsscorr_track_result* d_res, int32_t* d_all_dumps,
-                                  int64_t tic_count) {
-  if (!c || !d_if || !d_cmds || !d_res) {
-    gnsscorr_set_error("gnsscorr_track_dev: bad arguments");
-    return GNSSCORR_EINVAL;
-  }
-  int rc = set_dev(c->cfg.device);
-  if (rc) return rc;
-  return launch(c, d_if, stride, nsamp, d_cmds, d_res, d_all_dumps, tic_count);
-}
-
-extern "C" int gnsscorr_track_dev_isr(gnsscorr_track_ctx* c, const int8_t* d_if, int64_t stride,
-                                      int64_t nsamp, int n_calls, gnsscorr_nco_cmd* d_cmds,
-                                      gnsscorr_track_result* d_res, int n_loops,
-                                      const gnsscorr_osg_loop_cfg* cfg, gnsscorr_osg_loop* d_loops,
-                                      gnsscorr_osg_loop* d_hist) {
-  if (!c || !d_if || !d_cmds || !d_res || !cfg || !d_loops || n_calls < 1) {
-    gnsscorr_set_error("gnsscorr_track_dev_isr: bad arguments");
-    return GNSSCORR_EINVAL;
-  }
-  if (n_loops != c->cfg.n_channels) return GNSSCORR_TRACK_NOT_FUSED;
-  int rc = set_dev(c->cfg.device);
-  if (rc) return rc;
-  rc = launch_stream(c, d_if, stride, nsamp, n_calls, d_cmds, 0, d_res, nullptr, c->tic, 0, cfg,
-                     d_loops, d_hist);
-  if (rc == GNSSCORR_OK)   // the kernel stepped the TIC counter once per call; so does the host
-    for (int k = 0; k < n_calls; k++) (void)gnsscorr_track_next_tic(c, nsamp);
-  return rc;
-}
-
-extern "C" int gnsscorr_track_replay_dev(gnsscorr_track_ctx* c, const int8_t* d_if, int64_t stride,
-                                         int64_t nsamp, int n_steps,
-                                         const gnsscorr_nco_cmd* d_cmds,
-                                         gnsscorr_track_result* d_res) {
-  if (!c || !d_if || !d_cmds || !d_res || n_steps < 1) {
-    gnsscorr_set_error("gnsscorr_track_replay_dev: bad arguments");
-    return GNSSCORR_EINVAL;
-  }
-  int rc = set_dev(c->cfg.device);
-  if (rc) return rc;
-  const int C = c->cfg.n_channels;
-  // every call in one osg_stream_kernel launch where it serves the context
-  rc = launch_stream(c, d_if, stride, nsamp, n_steps, const_cast<gnsscorr_nco_cmd*>(d_cmds), C,
-                     d_res, nullptr, c->tic, 0, nullptr, nullptr, nullptr);
-  if (rc == GNSSCORR_OK) {
-    for (int k = 0; k < n_steps; k++) (void)gnsscorr_track_next_tic(c, nsamp);
-    return GNSSCORR_OK;
-  }
-  if (rc != GNSSCORR_TRACK_NOT_FUSED) return rc;
-  // one launch per step (every I-only context; IQ steps that start off the
-  // fused kernel's alignment).  All or nothing: every step's IF is checked
-  // before the first launch and before the TIC counter moves.
-  if ((rc = gnsscorr_track_check_steps(c, d_if, stride, nsamp, n_steps))) return rc;
-  for (int k = 0; k < n_steps; k++) {
-    const int64_t tic = gnsscorr_track_next_tic(c, nsamp);
-    rc = launch(c, d_if + gnsscorr_track_if_bytes(c, (int64_t)k * nsamp), stride, nsamp,
-                d_cmds + (int64_t)k * C,
-                d_res + (int64_t)k * C, nullptr, tic);
-    if (rc) return rc;
-  }
-  return GNSSCORR_OK;
-}
-
-extern "C" int gnsscorr_track_get_state(gnsscorr_track_ctx* c, gnsscorr_chan_state* h) {
-  if (!c || !h) return GNSSCORR_EINVAL;
-  int rc = set_dev(c->cfg.device);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h, c->d_state, sizeof(gnsscorr_chan_state) * c->cfg.n_channels,
-                         hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GNSSCORR_OK;
-}
-
-extern "C" int gnsscorr_track_set_state(gnsscorr_track_ctx* c, const gnsscorr_chan_state* h) {
-  if (!c || !h) return GNSSCORR_EINVAL;
-  int rc = set_dev(c->cfg.device);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(c->d_state, h, sizeof(gnsscorr_chan_state) * c->cfg.n_channels,
-                         hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GNSSCORR_OK;
-}
-
-extern "C" int gnsscorr_track_sync(gnsscorr_track_ctx* c) { return hostctx::sync(c); }
-
-extern "C" void* gnsscorr_track_stream(gnsscorr_track_ctx* c) { return hostctx::stream(c); }
-
-extern "C" int gnsscorr_device_lds_bytes(int device) {
-  int blk = 0, cu = 0;
-  if (hipDeviceGetAttribute(&blk, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess)
-    blk = 0;
-  // gfx950 lets one workgroup allocate the CU's whole 160 KiB LDS, while the
-  // runtime's per-block attribute may report the older 64 KiB; elsewhere the
-  // per-block attribute is the limit
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) == hipSuccess &&
-      strncmp(prop.gcnArchName, "gfx950", 6) == 0 &&
-      hipDeviceGetAttribute(&cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device) ==
-          hipSuccess && cu > blk)
-    return cu;
-  return blk;
-}
-
-extern "C" int gnsscorr_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  return n;
 }

@@ -492,6 +492,93 @@ def test_replay_bench_receiver_shape(gpu, oracle):
             np.testing.assert_array_equal(st[key][j], ref_state[j][key][0], err_msg=f"{key} {j}")
 
 
+_TWO = dict(C=5, nsamp=4100, n_calls=2, n_streams=2)
+_TWO_ALONE = {}
+
+
+def _two_engines_case(kind):
+    """Streams, stride, commands and starting state of the IQ ("iq") or the I-only
+    ("real") context of test_iq_and_real_contexts_interleaved."""
+    C, nsamp, n_calls, n_streams = (_TWO[k] for k in ("C", "nsamp", "n_calls", "n_streams"))
+    iq = kind == "iq"
+    rng = np.random.default_rng(4100 + iq)
+    streams = [S.synth_if(nsamp * n_calls, 950 + 2 * i + iq, [(3, 40 * i, 0, 3)], iq=iq)
+               for i in range(n_streams)]
+    if iq:
+        buf, stride = _layout_streams(streams, nsamp, n_calls)
+    else:
+        stride = (nsamp * n_calls + 15) // 16 * 16
+        buf = np.ones(stride * n_streams, np.int8)
+        for i, s in enumerate(streams):
+            buf[i * stride: i * stride + len(s)] = s
+    cmds = _random_cmds(rng, n_calls, C, n_streams)
+    for k in range(n_calls):
+        cmds[k]["prn"] = [3, 0, 17, 32, 9]           # one idle channel
+        cmds[k]["slew"] = [30, 0, 500, 0, 7]
+    # stored half-chip counts that bring the dump (at D = 2046 + slew half-chips of about
+    # 8 samples) into these 4100-sample calls: channels 0 and 4 in the first (its second
+    # and first piece), channel 2 in the second
+    half_chip0 = np.array([1800, 1800, 1800, 0, 2040], np.uint32)
+    return buf, stride, cmds, half_chip0
+
+
+def _two_engines_ctx(gpu, kind):
+    buf, stride, cmds, half_chip0 = _two_engines_case(kind)
+    ctx = gpu.TrackCtx(_TWO["C"], iq=kind == "iq", max_nsamp=_TWO["nsamp"])
+    st = ctx.get_state()
+    st["half_chip"] = half_chip0
+    ctx.set_state(st)
+    return ctx
+
+
+def _two_engines_call(ctx, kind, k):
+    buf, stride, cmds, _ = _two_engines_case(kind)
+    bps = 2 if kind == "iq" else 1
+    res, _, d = ctx.track(buf[k * _TWO["nsamp"] * bps:], _TWO["nsamp"], cmds[k],
+                          n_streams=_TWO["n_streams"], stream_stride=stride, all_dumps=True)
+    # all_dumps rows from a channel's n_dumps on are not written by the call (the device
+    # buffer behind them is never initialised): only the rows the call reports count
+    d[np.arange(d.shape[1])[None, :] >= res["n_dumps"][:, None]] = 0
+    return res.tobytes(), d.tobytes(), res["n_dumps"].copy()
+
+
+def _two_engines_alone(gpu, kind):
+    """The two calls on a context of its own (once per kind): per call (results,
+    all_dumps, n_dumps), then the final state."""
+    if kind not in _TWO_ALONE:
+        ctx = _two_engines_ctx(gpu, kind)
+        calls = [_two_engines_call(ctx, kind, k) for k in range(_TWO["n_calls"])]
+        _TWO_ALONE[kind] = (calls, ctx.get_state().tobytes())
+    return _TWO_ALONE[kind]
+
+
+@pytest.mark.parametrize("first", ["iq", "real"])
+def test_iq_and_real_contexts_interleaved(gpu, first):
+    """osg_stream_kernel (track.hip) and osg_track_kernel (track_real.hip) are two code
+    objects behind one front (track_host.hip).  An IQ int8 and an I-only int8 context,
+    created in either order and alive together, 5 channels each (one full and one
+    part-filled stream workgroup; two I-only workgroups), two calls of 4100 samples each
+    (three 2048-sample pieces with a partial last one, and nsamp & 7 != 0: the
+    single-call partial-chunk path), interleaved IQ, I-only, IQ, I-only: results,
+    all_dumps (every row a call reports) and the final state are byte-identical to the
+    same two calls on each context alone.  (The alone runs are what the other tests hold
+    to the oracle.)"""
+    assert _TWO["nsamp"] & 7 and -(-_TWO["nsamp"] // 2048) == 3
+    second = "real" if first == "iq" else "iq"
+    alone = {kind: _two_engines_alone(gpu, kind) for kind in ("iq", "real")}
+    for kind in ("iq", "real"):     # a dump inside a call, on both engines
+        assert any((nd >= 1).any() for _, _, nd in alone[kind][0]), kind
+    ctx = {first: _two_engines_ctx(gpu, first)}
+    ctx[second] = _two_engines_ctx(gpu, second)
+    for k in range(_TWO["n_calls"]):
+        for kind in ("iq", "real"):
+            res, dumps, _ = _two_engines_call(ctx[kind], kind, k)
+            assert res == alone[kind][0][k][0], (kind, k, "results")
+            assert dumps == alone[kind][0][k][1], (kind, k, "all_dumps")
+    for kind in ("iq", "real"):
+        assert ctx[kind].get_state().tobytes() == alone[kind][1], (kind, "state")
+
+
 def test_track_rejects_bad_prn(gpu):
     ctx = gpu.TrackCtx(4, max_nsamp=1024)
     cm = _random_cmds(np.random.default_rng(0), 1, 4, 1)[0]

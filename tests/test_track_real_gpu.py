@@ -9,7 +9,7 @@ pinned to the compiled reference for I-only scenarios by test_oracle_osg.py), on
 instance per channel: every dump of every call (all_dumps against sim_dumps()), n_dumps,
 msbit_reg and the final channel state.
 
-(a) every threads / cpw / block combination launch() can pick, 37 channels (a last
+(a) every threads / cpw / block combination track_real_launch() can pick, 37 channels (a last
     workgroup with idle thread groups, 10..37 workgroups: a non-trivial XCD order) on 3
     streams at a stride the host call has to re-stride;
 (b) code words of about one and of half a half-chip per sample: many dumps per call,
@@ -99,7 +99,7 @@ def _run_host(gpu, ctx, buf, stride, n_streams, nsamp, cmds, packed):
 
 
 # ---------------------------------------------------------------- (a) launch shapes
-# launch() (track.hip): threads per channel T = ceil(nsamp / 64) rounded up to 64,
+# track_real_launch() (track_real.hip): threads per channel T = ceil(nsamp / 64) rounded up to 64,
 # cpw = min(kMaxCpw = 4, 1024 / T), block = T * cpw, grid = ceil(C / cpw):
 #   nsamp                 runs   T     cpw          block  grid (C = 37)
 #   1, 63, 64, 65         1-2    64    4 (16 -> 4)  256    10
@@ -119,7 +119,7 @@ _CASE_A = {}
 
 
 def test_shape_table_follows_launch():
-    """The table above is what launch() computes, and it holds every block size."""
+    """The table above is what track_real_launch() computes, and it holds every block size."""
     for nsamp, (T, cpw) in SHAPES.items():
         t = ((nsamp + 63) // 64 + 63) // 64 * 64
         assert (t, min(4, 1024 // t)) == (T, cpw), nsamp
