@@ -30,8 +30,11 @@
 #include "nav_host.h"
 
 #pragma clang fp contract(off)
+#include "nav_dev.h"
 
 namespace {
+
+using namespace navdev;
 
 constexpr int kGpsBits = 1500;
 constexpr double kGpsPi = 3.1415926535898;             // ephemeris.sci:65, satpos.sci:34
@@ -156,26 +159,8 @@ __global__ __launch_bounds__(64) void nav_gps_eph_kernel(
 struct FixArgs {
   double samples_per_code, start_offset, c, elevation_mask;
   int nav_sol_period, use_trop, max_meas, n_epochs;
-  // tropo.sci:34-56,94-96 for (hsta, p, tkel, hum, hp, htkel, hhum) =
-  // (0, 1013, 293, 50, 0, 0, 0): the two passes' htop and ref
-  double htop[2], ref[2];
+  double htop[2], ref[2];        // navdev::tropo_consts
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) v = v + __shfl_xor(v, d);
-  return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) v = fmin(v, __shfl_xor(v, d));
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) v = max(v, __shfl_xor(v, d));
-  return v;
-}
 
 __device__ __forceinline__ double check_t(double t) {          // check_t.sci:19-27
   const double half_week = 302400.0;
@@ -258,74 +243,6 @@ __device__ void togeod(double X, double Y, double Z, double* dphi_deg, double* d
     if (dP * dP + dZ * dZ < tolsq) break;
   }
   *dphi_deg = dphi * rtd;
-}
-
-// one pass of tropo.sci:59-86 with hsta = 0
-__device__ double tropo_pass(double sinel, double htop, double ref) {
-  const double a_e = 6378.137, b0 = 7.839257e-5;
-  double rtop = (a_e + htop) * (a_e + htop) - a_e * a_e * (1 - sinel * sinel);
-  if (rtop < 0) rtop = 0;
-  rtop = sqrt(rtop) - a_e * sinel;
-  const double a = -sinel / htop;
-  const double b = -b0 * (1 - sinel * sinel) / htop;
-  const double a2 = a * a, b2 = b * b;
-  double alpha[8] = {2 * a,
-                     2 * a2 + 4 * b / 3,
-                     a * (a2 + 3 * b),
-                     a2 * a2 / 5 + 2.4 * a2 * b + 1.2 * b2,
-                     2 * a * b * (a2 + 3 * b) / 3,
-                     b2 * (6 * a2 + 4 * b) * 1.428571e-1,
-                     0.0,
-                     0.0};
-  if (b2 > 1.0e-35) {
-    alpha[6] = a * (b2 * b) / 2;
-    alpha[7] = b2 * b2 / 9;
-  }
-  double rn = rtop * rtop, dot = 0.0;                          // rn(i) = rtop^(i + 1)
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    dot = dot + alpha[i] * rn;
-    rn = rn * rtop;
-  }
-  const double dr = rtop + dot;
-  return dr * ref * 1000;
-}
-
-// LDL' of the symmetric 4 x 4 N (lower triangle used), column order.  False when
-// a pivot is not above 1e-12 of its column's diagonal entry of N (the rank rule).
-struct Ldl { double l10, l20, l21, l30, l31, l32, d0, d1, d2, d3; };
-__device__ bool ldl_factor(const double (&N)[10], Ldl* f) {
-  // N: 00 10 11 20 21 22 30 31 32 33
-  const double tol = 1.e-12;
-  f->d0 = N[0];
-  if (!(f->d0 > tol * N[0])) return false;
-  f->l10 = N[1] / f->d0;
-  f->l20 = N[3] / f->d0;
-  f->l30 = N[6] / f->d0;
-  f->d1 = N[2] - f->l10 * f->l10 * f->d0;
-  if (!(f->d1 > tol * N[2])) return false;
-  f->l21 = (N[4] - f->l20 * f->l10 * f->d0) / f->d1;
-  f->l31 = (N[7] - f->l30 * f->l10 * f->d0) / f->d1;
-  f->d2 = N[5] - f->l20 * f->l20 * f->d0 - f->l21 * f->l21 * f->d1;
-  if (!(f->d2 > tol * N[5])) return false;
-  f->l32 = (N[8] - f->l30 * f->l20 * f->d0 - f->l31 * f->l21 * f->d1) / f->d2;
-  f->d3 = N[9] - f->l30 * f->l30 * f->d0 - f->l31 * f->l31 * f->d1 - f->l32 * f->l32 * f->d2;
-  if (!(f->d3 > tol * N[9])) return false;
-  return true;
-}
-__device__ void ldl_solve(const Ldl& f, double g0, double g1, double g2, double g3, double* x) {
-  const double z0 = g0;
-  const double z1 = g1 - f.l10 * z0;
-  const double z2 = g2 - f.l20 * z0 - f.l21 * z1;
-  const double z3 = g3 - f.l30 * z0 - f.l31 * z1 - f.l32 * z2;
-  const double x3 = z3 / f.d3;
-  const double x2 = z2 / f.d2 - f.l32 * x3;
-  const double x1 = z1 / f.d1 - f.l21 * x2 - f.l31 * x3;
-  const double x0 = z0 / f.d0 - f.l10 * x1 - f.l20 * x2 - f.l30 * x3;
-  x[0] = x0;
-  x[1] = x1;
-  x[2] = x2;
-  x[3] = x3;
 }
 
 // cart2geo.sci:22-53 with i = 5
@@ -636,25 +553,7 @@ extern "C" int gnsscorr_nav_gps_fix_dev(gnsscorr_nav_ctx* c, const gnsscorr_gps_
   p.use_trop = cfg->useTropCorr;
   p.max_meas = cfg->max_meas;
   p.n_epochs = n_epochs;
-  {                                                            // tropo.sci:34-56,94-96
-    const double tkel = 293.0, hum = 50.0, pr = 1013.0, tlapse = -6.5;
-    const double tkhum = tkel + tlapse * (0.0 - 0.0);
-    const double atkel = 7.5 * (tkhum - 273.15) / (237.3 + tkhum - 273.15);
-    const double e0 = 0.0611 * hum * pow(10.0, atkel);
-    const double tksea = tkel - tlapse * 0.0;
-    const double em = -978.77 / (2.8704e6 * tlapse * 1.0e-5);
-    const double tkelh = tksea + tlapse * 0.0;
-    const double e0sea = e0 * pow(tksea / tkelh, 4 * em);
-    const double tkelp = tksea + tlapse * 0.0;
-    const double psea = pr * pow(tksea / tkelp, em);
-    double refsea = 77.624e-6 / tksea;
-    p.htop[0] = 1.1385e-5 / refsea;
-    refsea = refsea * psea;
-    p.ref[0] = refsea * pow((p.htop[0] - 0.0) / p.htop[0], 4);
-    refsea = (371900.0e-6 / tksea - 12.92e-6) / tksea;
-    p.htop[1] = 1.1385e-5 * (1255 / tksea + 0.05) / refsea;
-    p.ref[1] = refsea * e0sea * pow((p.htop[1] - 0.0) / p.htop[1], 4);
-  }
+  navdev::tropo_consts(p.htop, p.ref);
   hipLaunchKernelGGL(nav_gps_fix_kernel, dim3(n_rx), dim3(64), 0, c->stream, d_eph,
                      d_first_subframe, (const char*)d_abs_sample, epoch_stride_bytes,
                      chan_stride_bytes, c->d_rx_first.p, p, d_n_meas, d_sol, d_chan);

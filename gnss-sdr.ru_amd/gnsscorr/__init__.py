@@ -129,6 +129,37 @@ GPS_FIX_SOL = np.dtype([("X", "<f8"), ("Y", "<f8"), ("Z", "<f8"), ("dt", "<f8"),
 GPS_FIX_CHAN = np.dtype([("el", "<f8"), ("az", "<f8"), ("rawP", "<f8"), ("corrP", "<f8"),
                          ("used", "<i4"), ("reserved", "<i4")])
 assert GPS_EPH.itemsize == 208 and GPS_FIX_SOL.itemsize == 104 and GPS_FIX_CHAN.itemsize == 40
+GLO_EPH_FIELDS = ("x", "y", "z", "xdot", "ydot", "zdot", "xdotdot", "ydotdot", "zdotdot",
+                  "gamman", "taun", "deltataun", "tauc", "tauGPS", "t")   # km, km/s, km/s^2; s
+GLO_EPH_INTS = ("P1", "tk_h", "tk_m", "tk_s", "Bn", "P2", "tb", "P3", "P", "In3", "En", "P4",
+                "Ft", "Nt", "n", "M", "NA", "N4", "In5", "string_1_pos", "have", "skipped",
+                "status", "reserved")
+GLO_EPH_OK, GLO_EPH_SHORT = 0, 1
+
+
+class GloEph(C.Structure):
+    """gnsscorr_glo_eph"""
+    _fields_ = [(f, C.c_double) for f in GLO_EPH_FIELDS] + [(f, C.c_int32) for f in GLO_EPH_INTS]
+
+
+class GloSat(C.Structure):
+    """gnsscorr_glo_sat"""
+    _fields_ = [("pos", C.c_double * 3), ("vel", C.c_double * 3), ("acc", C.c_double * 3),
+                ("clk", C.c_double), ("deltat", C.c_double), ("n10", C.c_int32),
+                ("n1", C.c_int32), ("n001", C.c_int32), ("ready", C.c_int32)]
+
+
+class GloFixCfg(C.Structure):
+    """gnsscorr_glo_fix_cfg"""
+    _fields_ = [("samplesPerCode", C.c_double), ("dataTypeSizeInBytes", C.c_double),
+                ("c", C.c_double), ("elevationMask", C.c_double), ("navSolPeriod", C.c_int32),
+                ("useTropCorr", C.c_int32), ("max_meas", C.c_int32), ("reserved", C.c_int32)]
+
+
+GLO_EPH = np.dtype(GloEph)
+GLO_SAT = np.dtype(GloSat)
+GLO_FIX_CFG = np.dtype(GloFixCfg)
+assert GLO_EPH.itemsize == 216 and GLO_SAT.itemsize == 104 and GLO_FIX_CFG.itemsize == 48
 SDR_CHAN = np.dtype([("code_phase", "<f8"), ("carrier_phase", "<f8"),
                      ("carrier_phase_prev", "<f8"), ("code_phase_mod", "<f8"),
                      ("carrier_phase_mod", "<f8"), ("code_nco", "<f8"), ("carrier_nco", "<f8"),
@@ -330,6 +361,13 @@ def _sig_table():
         "gnsscorr_nav_gps_fix_cfg_init": (None, [P]),
         "gnsscorr_nav_gps_fix_dev": (I, [P, P, P, P, I64, I64, I, I, P, P, P, P, P]),
         "gnsscorr_nav_gps_fix": (I, [P, P, P, P, I64, I64, I, I, P, P, P, P, P]),
+        "gnsscorr_nav_glo_ephemeris_dev": (I, [P, P, P, P, I, P]),
+        "gnsscorr_nav_glo_ephemeris": (I, [P, P, P, P, I, P]),
+        "gnsscorr_nav_glo_fix_cfg_init": (None, [P]),
+        "gnsscorr_nav_glo_satpos_dev": (I, [P, P, I, P, P]),
+        "gnsscorr_nav_glo_satpos": (I, [P, P, I, P, P]),
+        "gnsscorr_nav_glo_fix_dev": (I, [P, P, P, P, P, I64, I64, I, I, P, P, P, P, P]),
+        "gnsscorr_nav_glo_fix": (I, [P, P, P, P, P, I64, I64, I, I, P, P, P, P, P]),
         "gnsscorr_sdr_prn_codes": (I, [P]),
         "gnsscorr_sdr_sine_gen": (None, [P, D, D, I]),
         **_ctx_sig("gnsscorr_sdr_acq", C.POINTER(SdrAcqCfg)),
@@ -1162,7 +1200,10 @@ class NavCtx(_Handle):
     Viterbi decoder, one wave per stream; and frame synchronisation and data bits of GPS
     L1 C/A, GLONASS L1OF and BeiDou B1I (csrc/navbits.hip) from SgtCtx epoch records; and
     the rest of the GPS L1 receiver (csrc/navfix.hip): ephemeris fields and TOW from those
-    bits, then pseudoranges, satellite positions and least-squares positions.  The
+    bits, then pseudoranges, satellite positions and least-squares positions; and the rest
+    of the GLONASS L1OF receiver (csrc/navglo.hip): ephemeris fields and frame time from the
+    15 strings, the satellite states by Runge-Kutta integration, then the same loop with
+    one integration step per fix and PZ-90.02 -> WGS-84.  The
     *_dev calls are queued on the context's stream and read the trackers' epoch records in
     place (epoch_field)."""
 
@@ -1175,7 +1216,9 @@ class NavCtx(_Handle):
                                   "pattern_hits_dev", "gps_frames", "gps_frames_dev",
                                   "glo_strings", "glo_strings_dev", "b1_subframes",
                                   "b1_subframes_dev", "gps_ephemeris", "gps_ephemeris_dev",
-                                  "gps_fix", "gps_fix_dev"))
+                                  "gps_fix", "gps_fix_dev", "glo_ephemeris",
+                                  "glo_ephemeris_dev", "glo_satpos", "glo_satpos_dev",
+                                  "glo_fix", "glo_fix_dev"))
 
     conv_encode = staticmethod(nav_conv_encode)
 
@@ -1362,6 +1405,70 @@ class NavCtx(_Handle):
                                  C.addressof(cfg) if cfg is not None else None, d_n_meas, d_sol,
                                  d_chan), self._gps_fix_dev)
 
+    def glo_ephemeris(self, bits, n_strings, first_mark) -> np.ndarray:
+        """GLONASS L1OF: bits [n_ch, 15, 85], n_strings [n_ch] and first_mark [n_ch] as
+        glo_strings returns them -> GLO_EPH [n_ch] (ephemeris.sci:25-98; status GLO_EPH_*)."""
+        bits = np.ascontiguousarray(bits, np.uint8).reshape(-1, 15, 85)
+        n_ch = bits.shape[0]
+        n_strings = np.ascontiguousarray(n_strings, np.int32).reshape(n_ch)
+        first = np.ascontiguousarray(first_mark, np.int32).reshape(n_ch)
+        eph = np.zeros(n_ch, GLO_EPH)
+        _check(self._glo_ephemeris(self.h, _ptr(bits), _ptr(n_strings), _ptr(first), n_ch,
+                                   _ptr(eph)), self._glo_ephemeris)
+        return eph
+
+    def glo_ephemeris_dev(self, d_bits, d_n_strings, d_first_mark, n_ch, d_eph):
+        _check(self._glo_ephemeris_dev(self.h, d_bits, d_n_strings, d_first_mark, n_ch, d_eph),
+               self._glo_ephemeris_dev)
+
+    def glo_satpos(self, eph, cfg) -> np.ndarray:
+        """GLONASS L1OF: eph GLO_EPH [n_ch], cfg from glo_fix_cfg (its navSolPeriod) ->
+        GLO_SAT [n_ch]: the satellite states one navSolPeriod before each channel's frame
+        time (satposg.sci); zeros for a channel that is not ready."""
+        eph = np.ascontiguousarray(eph, GLO_EPH).ravel()
+        sat = np.zeros(eph.size, GLO_SAT)
+        _check(self._glo_satpos(self.h, _ptr(eph), eph.size, C.addressof(cfg), _ptr(sat)),
+               self._glo_satpos)
+        return sat
+
+    def glo_satpos_dev(self, d_eph, n_ch, cfg, d_sat):
+        _check(self._glo_satpos_dev(self.h, d_eph, n_ch,
+                                    C.addressof(cfg) if cfg is not None else None, d_sat),
+               self._glo_satpos_dev)
+
+    def glo_fix(self, eph, sat, first_mark, abs_sample, rx_first, cfg, n_meas=None, sol=None,
+                chan=None):
+        """GLONASS L1OF: eph GLO_EPH [n_ch], sat GLO_SAT [n_ch] from glo_satpos with the same
+        cfg, first_mark [n_ch], abs_sample [n_ch, n_epochs] fp64 (SGT_EPOCH absoluteSample),
+        rx_first [n_rx + 1] channel offsets.  Returns n_meas [n_rx], sol GPS_FIX_SOL
+        [n_rx, max_meas] and chan GPS_FIX_CHAN [n_ch, max_meas]; rows past n_meas keep what
+        sol and chan held (zeros by default)."""
+        eph = np.ascontiguousarray(eph, GLO_EPH).ravel()
+        n_ch = eph.size
+        sat = np.ascontiguousarray(sat, GLO_SAT).reshape(n_ch)
+        first = np.ascontiguousarray(first_mark, np.int32).reshape(n_ch)
+        series, cs, n_ep, _ = self._series(abs_sample)
+        assert series.shape[0] == n_ch
+        rx_first = np.ascontiguousarray(rx_first, np.int32).ravel()
+        n_rx = rx_first.size - 1
+        n_meas = np.zeros(n_rx, np.int32) if n_meas is None else n_meas
+        sol = np.zeros((n_rx, cfg.max_meas), GPS_FIX_SOL) if sol is None else sol
+        chan = np.zeros((n_ch, cfg.max_meas), GPS_FIX_CHAN) if chan is None else chan
+        _check(self._glo_fix(self.h, _ptr(eph), _ptr(sat), _ptr(first), _ptr(series), 8, cs,
+                             n_ep, n_rx, _ptr(rx_first), C.addressof(cfg), _ptr(n_meas),
+                             _ptr(sol), _ptr(chan)), self._glo_fix)
+        return n_meas, sol, chan
+
+    def glo_fix_dev(self, d_eph, d_sat, d_first_mark, d_abs_sample, epoch_stride_bytes,
+                    chan_stride_bytes, n_epochs, rx_first, cfg, d_n_meas, d_sol, d_chan):
+        """rx_first: a host int32 array of n_rx + 1 offsets (checked before the launch)."""
+        rx_first = np.ascontiguousarray(rx_first, np.int32).ravel()
+        _check(self._glo_fix_dev(self.h, d_eph, d_sat, d_first_mark, d_abs_sample,
+                                 epoch_stride_bytes, chan_stride_bytes, n_epochs,
+                                 rx_first.size - 1, _ptr(rx_first),
+                                 C.addressof(cfg) if cfg is not None else None, d_n_meas, d_sol,
+                                 d_chan), self._glo_fix_dev)
+
 
 def gps_fix_cfg(max_meas=1, **kw) -> GpsFixCfg:
     """GPS/L1/initSettings.sci:103-125 defaults (samplesPerCode 16000, startOffset 68.802,
@@ -1374,6 +1481,21 @@ def gps_fix_cfg(max_meas=1, **kw) -> GpsFixCfg:
         if k not in ("samplesPerCode", "startOffset", "c", "elevationMask", "navSolPeriod",
                      "useTropCorr"):
             raise GnssCorrError(f"gps_fix_cfg: unknown setting {k!r}")
+        setattr(cfg, k, v)
+    return cfg
+
+
+def glo_fix_cfg(max_meas=1, **kw) -> GloFixCfg:
+    """GLONASS/L1/initSettings.sci:59-136 defaults (samplesPerCode 16000, dataTypeSizeInBytes
+    1, c 299792458, navSolPeriod 500, elevationMask 0, useTropCorr 1); keyword overrides use
+    the Scilab names."""
+    cfg = GloFixCfg()
+    lib().gnsscorr_nav_glo_fix_cfg_init(C.byref(cfg))
+    cfg.max_meas = int(max_meas)
+    for k, v in kw.items():
+        if k not in ("samplesPerCode", "dataTypeSizeInBytes", "c", "elevationMask",
+                     "navSolPeriod", "useTropCorr"):
+            raise GnssCorrError(f"glo_fix_cfg: unknown setting {k!r}")
         setattr(cfg, k, v)
     return cfg
 

@@ -1049,8 +1049,9 @@ int gnsscorr_nav_l3_decode(gnsscorr_nav_ctx *ctx, const void *h_pilot, const voi
  * have 0.5 (a decision sum of exactly 0).  No field decoding, TOW, BCH or
  * Hamming checks, pseudoranges or PVT here; the files run no BCH or Hamming check
  * on these paths either.  GPS L1 goes on from these bits to a position in
- * gnsscorr_nav_gps_ephemeris and gnsscorr_nav_gps_fix below; GLONASS and BeiDou
- * stop here.  Bits and positions are exact.
+ * gnsscorr_nav_gps_ephemeris and gnsscorr_nav_gps_fix below, GLONASS L1OF in
+ * gnsscorr_nav_glo_ephemeris, gnsscorr_nav_glo_satpos and gnsscorr_nav_glo_fix;
+ * BeiDou stops here.  Bits and positions are exact.
  *
  * Pattern search, the files' convol(pattern, sign(x)) cut to its valid part:
  *   r[k] = sum_{i<T} pattern[i] sign(x[k + i]),  first_k <= k < n_epochs,
@@ -1152,7 +1153,8 @@ int gnsscorr_nav_b1_subframes(gnsscorr_nav_ctx *ctx, const void *h_series,
  *   leastSquarePos.sci:32-111, e_r_corr.sci, topocent.sci, togeod.sci, tropo.sci,
  *   cart2geo.sci
  * Same context as above.  UTM (findUtmZone, cart2utm) is presentation and is not
- * computed; the GLONASS, BeiDou and Galileo solutions are not part of the library.
+ * computed; the GLONASS L1OF solution follows this one, the BeiDou and Galileo
+ * solutions are not part of the library.
  *
  * Stage 1, gps_ephemeris: d_bits [n_ch][1500], d_n_bits and d_first_subframe as
  * gnsscorr_nav_gps_frames_dev writes them (bits already through checkPhase) ->
@@ -1277,6 +1279,167 @@ int gnsscorr_nav_gps_fix(gnsscorr_nav_ctx *ctx, const gnsscorr_gps_eph *h_eph,
                          const int32_t *h_first_subframe, const void *h_abs_sample,
                          int64_t epoch_stride_bytes, int64_t chan_stride_bytes, int n_epochs,
                          int n_rx, const int32_t *rx_first, const gnsscorr_gps_fix_cfg *cfg,
+                         int32_t *h_n_meas, gnsscorr_gps_fix_sol *h_sol,
+                         gnsscorr_gps_fix_chan *h_chan);
+
+/* ----------------------------------------------------------------------
+ * GLONASS L1OF position fix (csrc/navglo.hip): what the Scilab GLONASS receiver
+ * does after the data bits
+ *   GLONASS/L1/include/ephemeris.sci:25-98, postNavigation.sci:89-123,142-284,
+ *   calculatePseudoranges.sci:55-72, geoFunctions/satposg.sci:38-132,299-310,
+ *   deltasatposg.sci:66-137, leastSquarePos.sci:45-100, e_r_corr.sci, topocent.sci,
+ *   togeod.sci, tropo.sci, cart2geo.sci, initSettings.sci:59-136
+ * Same context as above.  Not a copy of the GPS fix: the ephemeris is a state
+ * vector, the satellite position comes from a Runge-Kutta integration, every
+ * channel has its own frame time, the least-squares rows are divided by the range,
+ * and the result goes through PZ-90.02 -> WGS-84.  topocent, togeod and cart2geo of
+ * this receiver call atan(y, x) directly (the GPS files go through atand).  UTM, the
+ * almanac strings 6-15, tauc / tauGPS handling and the L2 receiver (other text) are
+ * not computed.
+ *
+ * Stage 1, glo_ephemeris: d_bits [n_ch][15][85], d_n_strings and d_first_mark as
+ * gnsscorr_nav_glo_strings_dev writes them -> one gnsscorr_glo_eph per channel.
+ * decoded_str(k) of the file is bits[k - 1].
+ *  - string position i (1..15) is skipped when any of its 85 bits is above 1
+ *    (:38-41); bit i - 1 of `skipped` records it;
+ *  - str_num = value(bits 84..81).  Numbers 1..5 decode and set bit str_num - 1 of
+ *    `have`; others decode nothing.  A later string with the same number
+ *    overwrites an earlier one; string_1_pos is the last i with number 1, 0 when
+ *    there is none; fields of a string that is not there are 0;
+ *  - a field is the unsigned value of its bit range, MSB at the higher index, then
+ *    times (-1)^signbit, then times its scale, in the file's order (:49-90): a zero
+ *    magnitude with the sign bit set is -0.0.  tk_s, Bn and tb carry the file's
+ *    factors 30, 4 (of bit 80 alone) and 15.  Units are the file's: km, km/s, km/s^2;
+ *  - t = tk_h*3600 + tk_m*60 + tk_s - (string_1_pos - 1)*2 - 0.3 in fp64 in that
+ *    order (:95-98): 1.7 with no string 1, as in the file;
+ *  - n_strings < 15 or first_mark < 0: status SHORT and every field 0, t included
+ *    (the file drops such a channel, postNavigation.sci:89-93).
+ * Everything here is bit-exact.
+ * ---------------------------------------------------------------------- */
+#define GNSSCORR_GLO_EPH_OK    0
+#define GNSSCORR_GLO_EPH_SHORT 1
+
+typedef struct {          /* ephemeris.sci:49-98 */
+  double  x, y, z, xdot, ydot, zdot, xdotdot, ydotdot, zdotdot;
+  double  gamman, taun, deltataun, tauc, tauGPS;
+  double  t;              /* time of the first string's start [s of day]       */
+  int32_t P1, tk_h, tk_m, tk_s, Bn, P2, tb, P3, P, In3;
+  int32_t En, P4, Ft, Nt, n, M, NA, N4, In5;
+  int32_t string_1_pos;
+  int32_t have;
+  int32_t skipped;
+  int32_t status;
+  int32_t reserved;
+} gnsscorr_glo_eph;
+
+int gnsscorr_nav_glo_ephemeris_dev(gnsscorr_nav_ctx *ctx, const uint8_t *d_bits,
+                                   const int32_t *d_n_strings, const int32_t *d_first_mark,
+                                   int n_ch, gnsscorr_glo_eph *d_eph);
+int gnsscorr_nav_glo_ephemeris(gnsscorr_nav_ctx *ctx, const uint8_t *h_bits,
+                               const int32_t *h_n_strings, const int32_t *h_first_mark,
+                               int n_ch, gnsscorr_glo_eph *h_eph);
+
+/* Stage 2, glo_satpos (satposg.sci): the satellite state one navSolPeriod before
+ * the frame time, one lane per channel over all channels of all receivers.
+ *  - ready (postNavigation.sci:107-123): status OK, strings 1-4 decoded
+ *    (have & 15 == 15), Bn != 4, In3 != 1.  A channel that is not ready gets a
+ *    record of zeros;
+ *  - step = navSolPeriod / 1000; deltat = (t - step)*1000 - tb*60*1000 [ms] (:38);
+ *    deltat10 = fix(deltat/10000), remdeltat10 = deltat - deltat10*10000, deltat1 =
+ *    fix(remdeltat10/1000), deltat001 = remdeltat10 - deltat1*1000 (:40-44), each a
+ *    single IEEE operation; n10 = |deltat10|, n1 = |deltat1|, n001 =
+ *    floor(|deltat001|): Scilab runs 1:abs(x) floor(abs(x)) times.  t carries the
+ *    - 0.3, so deltat is usually a hair off a whole millisecond and n001 depends
+ *    on its last bit.  deltat and the three counts are outputs, bit-exact;
+ *  - from (x y z, xdot ydot zdot) * 1000: n10 steps of h = 10 sign(deltat), n1 of
+ *    1 sign(deltat), n001 of 0.001 sign(deltat), the classical Runge-Kutta step of
+ *    :67-132 with mu = 398600.44e9, C20 = -1082.63e-6, ae = 6378.136e3, we =
+ *    0.7292115e-4, r taken once per step and the accelerations * 1000 constant, as
+ *    the file has them.  Inside the step the compiler may contract, and r^3, r^5
+ *    are formed from 1 / r^2 and one more division: pos and vel are held to a
+ *    tolerance (tests/navglo_scenarios.py), not to bits;
+ *  - clk = taun - gamman*(deltat/1000) (:310), bit-exact.
+ * One widening: a record with |deltat| >= 2^27 ms is not ready.  Stage 1 writes
+ * none (tk_h <= 31 and tb <= 1905 min keep |deltat| below 1.2e8); the bound keeps
+ * the loop counts finite for any caller's record.
+ * Refused with GNSSCORR_EINVAL before any device call: a null pointer, n_ch < 1,
+ * navSolPeriod < 1. */
+typedef struct {
+  double  pos[3], vel[3], acc[3];   /* m, m/s, m/s^2 (PZ-90.02, rotating frame)  */
+  double  clk;                      /* satClkCorr [s]                            */
+  double  deltat;                   /* [ms]                                      */
+  int32_t n10, n1, n001;
+  int32_t ready;
+} gnsscorr_glo_sat;
+
+typedef struct {          /* initSettings.sci:59-136 */
+  double  samplesPerCode;       /* 16000 = round(16e6 / (0.511e6 / 511))          */
+  double  dataTypeSizeInBytes;  /* 1                                              */
+  double  c;                    /* 299792458                                      */
+  double  elevationMask;        /* 0 [deg]                                        */
+  int32_t navSolPeriod;         /* 500 [ms]                                       */
+  int32_t useTropCorr;          /* 1                                              */
+  int32_t max_meas;             /* rows of d_sol and d_chan per receiver / channel */
+  int32_t reserved;
+} gnsscorr_glo_fix_cfg;
+
+/* the defaults above, max_meas = 1 */
+void gnsscorr_nav_glo_fix_cfg_init(gnsscorr_glo_fix_cfg *cfg);
+int gnsscorr_nav_glo_satpos_dev(gnsscorr_nav_ctx *ctx, const gnsscorr_glo_eph *d_eph, int n_ch,
+                                const gnsscorr_glo_fix_cfg *cfg, gnsscorr_glo_sat *d_sat);
+int gnsscorr_nav_glo_satpos(gnsscorr_nav_ctx *ctx, const gnsscorr_glo_eph *h_eph, int n_ch,
+                            const gnsscorr_glo_fix_cfg *cfg, gnsscorr_glo_sat *h_sat);
+
+/* Stage 3, glo_fix: the measurement loop of postNavigation.sci:142-284, one wave
+ * per receiver.  rx_first, d_abs_sample, the outputs, the OK / FEW / RANK codes and
+ * the copy of rx_first are exactly as in gnsscorr_nav_gps_fix_dev.  d_eph and d_sat
+ * are read only, so a call can be repeated.  Indices below are 0-based.
+ *  - ready: d_sat[ch].ready and first_mark >= 0.  Fewer than 4 ready channels:
+ *    n_meas = 0 (:128).  Else n_meas = min(max_meas, fix((n_epochs - (max p + 1)) /
+ *    navSolPeriod)), the max over every channel of the receiver with first_mark =
+ *    p >= 0 (:167).  skipNumberOfFirstBits stays the caller's, as for glo_strings.
+ *    satElev starts at +inf;
+ *  - measurement m: active = ready and satElev >= elevationMask; el, az of every
+ *    channel NaN (an excluded satellite never returns: the file's known issue
+ *    :273-277); rawP = (absoluteSample[ch][p_ch + navSolPeriod m] / samplesPerCode /
+ *    dataTypeSizeInBytes - floor(min over active)) * (c / 1000), +inf for the
+ *    others (NaN for all when none is active): bit-exact, and no startOffset;
+ *  - every active channel takes one Runge-Kutta step of h = step from its own
+ *    state (deltasatposg.sci:66-126) and clk -= gamman * step (:137), so the first
+ *    measurement is at t;
+ *  - fewer than 4 active: X Y Z dt lat lon height NaN, DOP 0, status FEW, satElev
+ *    kept (:249-271);
+ *  - else leastSquarePos.sci: 7 iterations from 0; iteration 1 with dist =
+ *    |satpos| and trop = 0, later ones with e_r_corr, topocent / togeod (its D is
+ *    dist) and tropo(sin(el), 0, 1013, 293, 50, 0, 0, 0) when useTropCorr == 1;
+ *    obs = rawP - clk c, F = obs - pos(4) - dist - trop, rows of A divided by dist.
+ *    inv(A'A) A'F and Q = inv(A'A) go through the LDL' factorisation and the rank
+ *    rule of the GPS fix (above); status RANK is the one widening, the file has no
+ *    rank test.  Then X Y Z = [-1.1 -0.3 -0.9] + (1 - 0.12e-6) R xyz, R = [1
+ *    -0.82e-6 0; 0.82e-6 1 0; 0 0 1] (PZ-90.02 -> WGS-84, :206-208), corrP = rawP -
+ *    clk c + dt (:224-226), cart2geo(X, Y, Z, 5), satElev = el (NaN for channels
+ *    outside active).
+ * One deliberate departure: the file keeps the satellite states in columns
+ * ordered by position in the active list, and after the mask has excluded a
+ * channel it hands the remaining satellites their neighbours' states.  Here every
+ * channel keeps and advances its own state.  The two are identical until the
+ * first exclusion.
+ * Refused with GNSSCORR_EINVAL before any device call: as gnsscorr_nav_gps_fix_dev,
+ * and dataTypeSizeInBytes <= 0. */
+int gnsscorr_nav_glo_fix_dev(gnsscorr_nav_ctx *ctx, const gnsscorr_glo_eph *d_eph,
+                             const gnsscorr_glo_sat *d_sat, const int32_t *d_first_mark,
+                             const void *d_abs_sample, int64_t epoch_stride_bytes,
+                             int64_t chan_stride_bytes, int n_epochs, int n_rx,
+                             const int32_t *rx_first, const gnsscorr_glo_fix_cfg *cfg,
+                             int32_t *d_n_meas, gnsscorr_gps_fix_sol *d_sol,
+                             gnsscorr_gps_fix_chan *d_chan);
+/* Same with host arrays (synchronous); rows m >= n_meas of h_sol and h_chan keep
+ * what the caller put there. */
+int gnsscorr_nav_glo_fix(gnsscorr_nav_ctx *ctx, const gnsscorr_glo_eph *h_eph,
+                         const gnsscorr_glo_sat *h_sat, const int32_t *h_first_mark,
+                         const void *h_abs_sample, int64_t epoch_stride_bytes,
+                         int64_t chan_stride_bytes, int n_epochs, int n_rx,
+                         const int32_t *rx_first, const gnsscorr_glo_fix_cfg *cfg,
                          int32_t *h_n_meas, gnsscorr_gps_fix_sol *h_sol,
                          gnsscorr_gps_fix_chan *h_chan);
 
