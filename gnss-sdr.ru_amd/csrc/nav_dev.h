@@ -1,14 +1,18 @@
-// nav_dev.h -- device helpers that the GPS fix (navfix.hip) and the GLONASS fix
-// (navglo.hip) compute identically: the wave reductions, one pass of tropo.sci, the
-// LDL' factorisation of the normal equations with the library's rank rule, and on
-// the host the constants of tropo.sci's two passes.  Both files include it under
-// `#pragma clang fp contract(off)`: no operation here may be contracted.
+// nav_dev.h -- device helpers that the GPS fix (navfix.hip), the GLONASS fix (navglo.hip)
+// and the BeiDou fix (navb1.hip) compute identically: the wave reductions, one pass of
+// tropo.sci, the LDL' factorisation of the normal equations with the library's rank rule,
+// on the host the constants of tropo.sci's two passes; check_t and the reductions of the
+// Kepler propagation (GPS, BeiDou); togeod and cart2geo with plain atan(y, x) (GLONASS,
+// BeiDou).  Every file includes it under `#pragma clang fp contract(off)`: no operation
+// here may be contracted.
 #ifndef GNSSCORR_NAV_DEV_H
 #define GNSSCORR_NAV_DEV_H
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 namespace navdev {
+
+constexpr double kPi = 3.14159265358979323846;                 // %pi
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -114,6 +118,74 @@ static __device__ void ldl_solve(const Ldl& f, double g0, double g1, double g2, 
   x[1] = x1;
   x[2] = x2;
   x[3] = x3;
+}
+
+// the GPS L1 and COMPASS B1 satpos.sci share these (check_t.sci:19-27 is one text)
+__device__ __forceinline__ double check_t(double t) {          // check_t.sci:19-27
+  const double half_week = 302400.0;
+  if (t > half_week) return t - 2 * half_week;
+  if (t < -half_week) return t + 2 * half_week;
+  return t;
+}
+// x - fix(x ./ y) .* y
+__device__ __forceinline__ double rem_fix(double x, double y) { return x - trunc(x / y) * y; }
+// Scilab's two-argument atand, read as (180 / %pi) * atan(y, x)
+__device__ __forceinline__ double atand2(double y, double x) { return (180.0 / kPi) * atan2(y, x); }
+
+// GLONASS/L1 and COMPASS/B1 togeod.sci:31-110 (the same text, atan(y, x) called directly) for
+// a = 6378137, finv = 298.257223563: latitude and longitude in degrees
+inline __device__ void togeod_atan(double X, double Y, double Z, double* dphi_deg,
+                                   double* dlambda_deg) {
+  const double a = 6378137.0, finv = 298.257223563, tolsq = 1.e-10, rtd = 180 / kPi;
+  const double esq = (2 - 1 / finv) / finv, oneesq = 1 - esq;
+  const double P = sqrt(X * X + Y * Y);
+  double dlambda = P > 1.e-20 ? atan2(Y, X) * rtd : 0.0;       // :52-56
+  if (dlambda < 0) dlambda = dlambda + 360;
+  const double r = sqrt(P * P + Z * Z);
+  double sinphi = r > 1.e-20 ? Z / r : 0.0;
+  double dphi = asin(sinphi);
+  *dlambda_deg = dlambda;
+  if (r < 1.e-20) {                                            // :75-78, dphi is 0 here
+    *dphi_deg = dphi;
+    return;
+  }
+  double h = r - a * (1 - sinphi * sinphi / finv);
+  for (int i = 0; i < 10; i++) {
+    sinphi = sin(dphi);
+    const double cosphi = cos(dphi);
+    const double N_phi = a / sqrt(1 - esq * sinphi * sinphi);
+    const double dP = P - (N_phi + h) * cosphi;
+    const double dZ = Z - (N_phi * oneesq + h) * sinphi;
+    h = h + (sinphi * dZ + cosphi * dP);
+    dphi = dphi + (cosphi * dZ - sinphi * dP) / (N_phi + h);
+    if (dP * dP + dZ * dZ < tolsq) break;
+  }
+  *dphi_deg = dphi * rtd;
+}
+
+// GLONASS/L1 and COMPASS/B1 cart2geo.sci:20-45 with i = 5
+inline __device__ void cart2geo5_atan(double X, double Y, double Z, double* phi_deg,
+                                      double* lambda_deg, double* h_out) {
+  const double a = 6378137.0, f = 1 / 298.257223563;
+  const double lambda = atan2(Y, X);                           // :23
+  const double ex2 = (2 - f) * f / ((1 - f) * (1 - f));
+  const double c = a * sqrt(1 + ex2);
+  const double p = sqrt(X * X + Y * Y);
+  double phi = atan(Z / (p * (1 - (2 - f)) * f));
+  double h = 0.1, oldh = 0;
+  int iterations = 0;
+  while (fabs(h - oldh) > 1.e-12) {
+    oldh = h;
+    const double cp = cos(phi);
+    const double N = c / sqrt(1 + ex2 * (cp * cp));
+    phi = atan(Z / (p * (1 - (2 - f) * f * N / (N + h))));
+    h = p / cos(phi) - N;
+    iterations = iterations + 1;
+    if (iterations > 100) break;
+  }
+  *phi_deg = phi * 180 / kPi;
+  *lambda_deg = lambda * 180 / kPi;
+  *h_out = h;
 }
 
 }  // namespace navdev

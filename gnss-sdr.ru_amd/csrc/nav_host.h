@@ -1,4 +1,4 @@
-// nav_host.h -- what navsym.hip, navbits.hip, navfix.hip and navglo.hip share on the host: the "nav"
+// nav_host.h -- what navsym.hip, navbits.hip, navfix.hip, navglo.hip and navb1.hip share on the host: the "nav"
 // context, the refusal text and the checks of a series argument.  HIP only;
 // include after gnsscorr_internal.h and hostctx.h.
 #ifndef GNSSCORR_NAV_HOST_H
@@ -17,7 +17,7 @@ struct gnsscorr_nav_ctx {
   hostctx::DevBuf<int32_t> d_len;
   // navbits.hip: the hit bitmap of the GPS search, one bit per epoch
   hostctx::DevBuf<uint64_t> d_hitmap;
-  // navfix.hip, navglo.hip: the receivers' channel offsets of the last gps_fix / glo_fix call
+  // navfix.hip, navglo.hip, navb1.hip: the receivers' channel offsets of the last *_fix call
   hostctx::DevBuf<int32_t> d_rx_first;
 };
 

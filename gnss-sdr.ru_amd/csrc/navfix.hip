@@ -38,7 +38,6 @@ using namespace navdev;
 
 constexpr int kGpsBits = 1500;
 constexpr double kGpsPi = 3.1415926535898;             // ephemeris.sci:65, satpos.sci:34
-constexpr double kPi = 3.14159265358979323846;         // %pi
 
 // ---------------------------------------------------------------------------
 // ephemeris.sci:82-226.  Bit positions are the file's (1-based, inside a subframe).
@@ -161,17 +160,6 @@ struct FixArgs {
   int nav_sol_period, use_trop, max_meas, n_epochs;
   double htop[2], ref[2];        // navdev::tropo_consts
 };
-
-__device__ __forceinline__ double check_t(double t) {          // check_t.sci:19-27
-  const double half_week = 302400.0;
-  if (t > half_week) return t - 2 * half_week;
-  if (t < -half_week) return t + 2 * half_week;
-  return t;
-}
-// x - fix(x ./ y) .* y
-__device__ __forceinline__ double rem_fix(double x, double y) { return x - trunc(x / y) * y; }
-// Scilab's two-argument atand, read as (180 / %pi) * atan(y, x)
-__device__ __forceinline__ double atand2(double y, double x) { return (180.0 / kPi) * atan2(y, x); }
 
 struct SatPos { double x, y, z, clk; };
 

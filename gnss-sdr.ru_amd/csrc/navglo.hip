@@ -42,7 +42,6 @@ using namespace navdev;
 
 constexpr int kGloStrings = 15, kGloStringBits = 85;
 constexpr int kGloBits = kGloStrings * kGloStringBits;
-constexpr double kPi = 3.14159265358979323846;                 // %pi
 constexpr int kEphDoubles = 15, kEphInts = 24;
 
 // ---------------------------------------------------------------------------
@@ -292,60 +291,6 @@ struct GloFixArgs {
   double htop[2], ref[2];        // navdev::tropo_consts
 };
 
-// togeod.sci:31-110 for a = 6378137, finv = 298.257223563: latitude and longitude in degrees
-__device__ void glo_togeod(double X, double Y, double Z, double* dphi_deg, double* dlambda_deg) {
-  const double a = 6378137.0, finv = 298.257223563, tolsq = 1.e-10, rtd = 180 / kPi;
-  const double esq = (2 - 1 / finv) / finv, oneesq = 1 - esq;
-  const double P = sqrt(X * X + Y * Y);
-  double dlambda = P > 1.e-20 ? atan2(Y, X) * rtd : 0.0;       // :52-56
-  if (dlambda < 0) dlambda = dlambda + 360;
-  const double r = sqrt(P * P + Z * Z);
-  double sinphi = r > 1.e-20 ? Z / r : 0.0;
-  double dphi = asin(sinphi);
-  *dlambda_deg = dlambda;
-  if (r < 1.e-20) {                                            // :75-78, dphi is 0 here
-    *dphi_deg = dphi;
-    return;
-  }
-  double h = r - a * (1 - sinphi * sinphi / finv);
-  for (int i = 0; i < 10; i++) {
-    sinphi = sin(dphi);
-    const double cosphi = cos(dphi);
-    const double N_phi = a / sqrt(1 - esq * sinphi * sinphi);
-    const double dP = P - (N_phi + h) * cosphi;
-    const double dZ = Z - (N_phi * oneesq + h) * sinphi;
-    h = h + (sinphi * dZ + cosphi * dP);
-    dphi = dphi + (cosphi * dZ - sinphi * dP) / (N_phi + h);
-    if (dP * dP + dZ * dZ < tolsq) break;
-  }
-  *dphi_deg = dphi * rtd;
-}
-
-// cart2geo.sci:20-45 with i = 5
-__device__ void glo_cart2geo5(double X, double Y, double Z, double* phi_deg, double* lambda_deg,
-                              double* h_out) {
-  const double a = 6378137.0, f = 1 / 298.257223563;
-  const double lambda = atan2(Y, X);                           // :23
-  const double ex2 = (2 - f) * f / ((1 - f) * (1 - f));
-  const double c = a * sqrt(1 + ex2);
-  const double p = sqrt(X * X + Y * Y);
-  double phi = atan(Z / (p * (1 - (2 - f)) * f));
-  double h = 0.1, oldh = 0;
-  int iterations = 0;
-  while (fabs(h - oldh) > 1.e-12) {
-    oldh = h;
-    const double cp = cos(phi);
-    const double N = c / sqrt(1 + ex2 * (cp * cp));
-    phi = atan(Z / (p * (1 - (2 - f) * f * N / (N + h))));
-    h = p / cos(phi) - N;
-    iterations = iterations + 1;
-    if (iterations > 100) break;
-  }
-  *phi_deg = phi * 180 / kPi;
-  *lambda_deg = lambda * 180 / kPi;
-  *h_out = h;
-}
-
 __global__ __launch_bounds__(64) void nav_glo_fix_kernel(
     const gnsscorr_glo_eph* __restrict__ eph, const gnsscorr_glo_sat* __restrict__ sat,
     const int32_t* __restrict__ first_mark, const char* __restrict__ abs_sample,
@@ -420,7 +365,7 @@ __global__ __launch_bounds__(64) void nav_glo_fix_kernel(
           r0 = co * w.x + so * w.y;
           r1 = -so * w.x + co * w.y;
           double phi, lambda;                                  // topocent.sci:24-54
-          glo_togeod(pos0, pos1, pos2, &phi, &lambda);
+          togeod_atan(pos0, pos1, pos2, &phi, &lambda);
           const double cl = cos(lambda * dtr), sl = sin(lambda * dtr);
           const double cb = cos(phi * dtr), sb = sin(phi * dtr);
           const double d0 = r0 - pos0, d1 = r1 - pos1, d2 = r2 - pos2;
@@ -502,7 +447,7 @@ __global__ __launch_bounds__(64) void nav_glo_fix_kernel(
         if (!active) el = az_deg = nan;
         sat_elev = el;                                         // :221
         if (active) corr_p = raw_p - clk * p.c + pos3;         // :224-226
-        glo_cart2geo5(pos0, pos1, pos2, &lat, &lon, &height);  // :231-237
+        cart2geo5_atan(pos0, pos1, pos2, &lat, &lon, &height);  // :231-237
       }
     }
     if (valid) {

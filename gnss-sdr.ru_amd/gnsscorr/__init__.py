@@ -160,6 +160,29 @@ GLO_EPH = np.dtype(GloEph)
 GLO_SAT = np.dtype(GloSat)
 GLO_FIX_CFG = np.dtype(GloFixCfg)
 assert GLO_EPH.itemsize == 216 and GLO_SAT.itemsize == 104 and GLO_FIX_CFG.itemsize == 48
+B1_EPH_FIELDS = ("T_GD_1", "t_oc", "a2", "a0", "a1", "alpha0", "alpha1", "alpha2", "alpha3",
+                 "beta0", "beta1", "beta2", "beta3", "deltan", "C_uc", "M_0", "e", "C_us", "C_rc",
+                 "C_rs", "sqrtA", "t_oe_msb", "t_oe_lsb", "i_0", "C_ic", "omegaDot", "C_is",
+                 "iDot", "omega_0", "omega", "t_oe")   # ephemeris.sci:45-118
+B1_EPH_INTS = ("SatH1", "IODC", "URAI", "WN", "IODE", "SOW", "have", "status")
+B1_EPH_OK, B1_EPH_SHORT, B1_EPH_NO_SOW = 0, 1, 2
+
+
+class B1Eph(C.Structure):
+    """gnsscorr_b1_eph"""
+    _fields_ = [(f, C.c_double) for f in B1_EPH_FIELDS] + [(f, C.c_int32) for f in B1_EPH_INTS]
+
+
+class B1FixCfg(C.Structure):
+    """gnsscorr_b1_fix_cfg"""
+    _fields_ = [("samplesPerCode", C.c_double), ("dataTypeSizeInBytes", C.c_double),
+                ("c", C.c_double), ("navSolPeriod", C.c_int32), ("useTropCorr", C.c_int32),
+                ("max_meas", C.c_int32), ("reserved", C.c_int32)]
+
+
+B1_EPH = np.dtype(B1Eph)
+B1_FIX_CFG = np.dtype(B1FixCfg)
+assert B1_EPH.itemsize == 280 and B1_FIX_CFG.itemsize == 40
 SDR_CHAN = np.dtype([("code_phase", "<f8"), ("carrier_phase", "<f8"),
                      ("carrier_phase_prev", "<f8"), ("code_phase_mod", "<f8"),
                      ("carrier_phase_mod", "<f8"), ("code_nco", "<f8"), ("carrier_nco", "<f8"),
@@ -368,6 +391,11 @@ def _sig_table():
         "gnsscorr_nav_glo_satpos": (I, [P, P, I, P, P]),
         "gnsscorr_nav_glo_fix_dev": (I, [P, P, P, P, P, I64, I64, I, I, P, P, P, P, P]),
         "gnsscorr_nav_glo_fix": (I, [P, P, P, P, P, I64, I64, I, I, P, P, P, P, P]),
+        "gnsscorr_nav_b1_ephemeris_dev": (I, [P, P, P, P, I, P]),
+        "gnsscorr_nav_b1_ephemeris": (I, [P, P, P, P, I, P]),
+        "gnsscorr_nav_b1_fix_cfg_init": (None, [P]),
+        "gnsscorr_nav_b1_fix_dev": (I, [P, P, P, P, I64, I64, I, I, P, P, P, P, P]),
+        "gnsscorr_nav_b1_fix": (I, [P, P, P, P, I64, I64, I, I, P, P, P, P, P]),
         "gnsscorr_sdr_prn_codes": (I, [P]),
         "gnsscorr_sdr_sine_gen": (None, [P, D, D, I]),
         **_ctx_sig("gnsscorr_sdr_acq", C.POINTER(SdrAcqCfg)),
@@ -1203,7 +1231,9 @@ class NavCtx(_Handle):
     bits, then pseudoranges, satellite positions and least-squares positions; and the rest
     of the GLONASS L1OF receiver (csrc/navglo.hip): ephemeris fields and frame time from the
     15 strings, the satellite states by Runge-Kutta integration, then the same loop with
-    one integration step per fix and PZ-90.02 -> WGS-84.  The
+    one integration step per fix and PZ-90.02 -> WGS-84; and the rest of the BeiDou B1I
+    receiver (csrc/navb1.hip): ephemeris fields and SOW from the five subframes, then the
+    loop with Kepler satellite positions and no elevation mask.  The
     *_dev calls are queued on the context's stream and read the trackers' epoch records in
     place (epoch_field)."""
 
@@ -1218,7 +1248,8 @@ class NavCtx(_Handle):
                                   "b1_subframes_dev", "gps_ephemeris", "gps_ephemeris_dev",
                                   "gps_fix", "gps_fix_dev", "glo_ephemeris",
                                   "glo_ephemeris_dev", "glo_satpos", "glo_satpos_dev",
-                                  "glo_fix", "glo_fix_dev"))
+                                  "glo_fix", "glo_fix_dev", "b1_ephemeris", "b1_ephemeris_dev",
+                                  "b1_fix", "b1_fix_dev"))
 
     conv_encode = staticmethod(nav_conv_encode)
 
@@ -1469,6 +1500,51 @@ class NavCtx(_Handle):
                                  C.addressof(cfg) if cfg is not None else None, d_n_meas, d_sol,
                                  d_chan), self._glo_fix_dev)
 
+    def b1_ephemeris(self, bits, n_subframes, first) -> np.ndarray:
+        """BeiDou B1I: bits [n_ch, 5, 213], n_subframes [n_ch] and first [n_ch] as
+        b1_subframes returns them -> B1_EPH [n_ch] (ephemeris.sci:28-123; status B1_EPH_*)."""
+        bits = np.ascontiguousarray(bits, np.uint8).reshape(-1, 5, 213)
+        n_ch = bits.shape[0]
+        n_subframes = np.ascontiguousarray(n_subframes, np.int32).reshape(n_ch)
+        first = np.ascontiguousarray(first, np.int32).reshape(n_ch)
+        eph = np.zeros(n_ch, B1_EPH)
+        _check(self._b1_ephemeris(self.h, _ptr(bits), _ptr(n_subframes), _ptr(first), n_ch,
+                                  _ptr(eph)), self._b1_ephemeris)
+        return eph
+
+    def b1_ephemeris_dev(self, d_bits, d_n_subframes, d_first, n_ch, d_eph):
+        _check(self._b1_ephemeris_dev(self.h, d_bits, d_n_subframes, d_first, n_ch, d_eph),
+               self._b1_ephemeris_dev)
+
+    def b1_fix(self, eph, first, abs_sample, rx_first, cfg, n_meas=None, sol=None, chan=None):
+        """BeiDou B1I: eph B1_EPH [n_ch], first [n_ch], abs_sample [n_ch, n_epochs] fp64
+        (SGT_EPOCH absoluteSample), rx_first [n_rx + 1] channel offsets, cfg from b1_fix_cfg.
+        Returns n_meas [n_rx], sol GPS_FIX_SOL [n_rx, max_meas] and chan GPS_FIX_CHAN
+        [n_ch, max_meas]; rows past n_meas keep what sol and chan held (zeros by default)."""
+        eph = np.ascontiguousarray(eph, B1_EPH).ravel()
+        n_ch = eph.size
+        first = np.ascontiguousarray(first, np.int32).reshape(n_ch)
+        series, cs, n_ep, _ = self._series(abs_sample)
+        assert series.shape[0] == n_ch
+        rx_first = np.ascontiguousarray(rx_first, np.int32).ravel()
+        n_rx = rx_first.size - 1
+        n_meas = np.zeros(n_rx, np.int32) if n_meas is None else n_meas
+        sol = np.zeros((n_rx, cfg.max_meas), GPS_FIX_SOL) if sol is None else sol
+        chan = np.zeros((n_ch, cfg.max_meas), GPS_FIX_CHAN) if chan is None else chan
+        _check(self._b1_fix(self.h, _ptr(eph), _ptr(first), _ptr(series), 8, cs, n_ep, n_rx,
+                            _ptr(rx_first), C.addressof(cfg), _ptr(n_meas), _ptr(sol),
+                            _ptr(chan)), self._b1_fix)
+        return n_meas, sol, chan
+
+    def b1_fix_dev(self, d_eph, d_first, d_abs_sample, epoch_stride_bytes, chan_stride_bytes,
+                   n_epochs, rx_first, cfg, d_n_meas, d_sol, d_chan):
+        """rx_first: a host int32 array of n_rx + 1 offsets (checked before the launch)."""
+        rx_first = np.ascontiguousarray(rx_first, np.int32).ravel()
+        _check(self._b1_fix_dev(self.h, d_eph, d_first, d_abs_sample, epoch_stride_bytes,
+                                chan_stride_bytes, n_epochs, rx_first.size - 1, _ptr(rx_first),
+                                C.addressof(cfg) if cfg is not None else None, d_n_meas, d_sol,
+                                d_chan), self._b1_fix_dev)
+
 
 def gps_fix_cfg(max_meas=1, **kw) -> GpsFixCfg:
     """GPS/L1/initSettings.sci:103-125 defaults (samplesPerCode 16000, startOffset 68.802,
@@ -1496,6 +1572,21 @@ def glo_fix_cfg(max_meas=1, **kw) -> GloFixCfg:
         if k not in ("samplesPerCode", "dataTypeSizeInBytes", "c", "elevationMask",
                      "navSolPeriod", "useTropCorr"):
             raise GnssCorrError(f"glo_fix_cfg: unknown setting {k!r}")
+        setattr(cfg, k, v)
+    return cfg
+
+
+def b1_fix_cfg(max_meas=1, **kw) -> B1FixCfg:
+    """COMPASS/B1/initSettings.sci defaults (samplesPerCode 16000, dataTypeSizeInBytes 1,
+    c 299792458, navSolPeriod 500, useTropCorr 0; the receiver has no elevation mask);
+    keyword overrides use the Scilab names."""
+    cfg = B1FixCfg()
+    lib().gnsscorr_nav_b1_fix_cfg_init(C.byref(cfg))
+    cfg.max_meas = int(max_meas)
+    for k, v in kw.items():
+        if k not in ("samplesPerCode", "dataTypeSizeInBytes", "c", "navSolPeriod",
+                     "useTropCorr"):
+            raise GnssCorrError(f"b1_fix_cfg: unknown setting {k!r}")
         setattr(cfg, k, v)
     return cfg
 

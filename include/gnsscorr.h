@@ -1050,8 +1050,9 @@ int gnsscorr_nav_l3_decode(gnsscorr_nav_ctx *ctx, const void *h_pilot, const voi
  * Hamming checks, pseudoranges or PVT here; the files run no BCH or Hamming check
  * on these paths either.  GPS L1 goes on from these bits to a position in
  * gnsscorr_nav_gps_ephemeris and gnsscorr_nav_gps_fix below, GLONASS L1OF in
- * gnsscorr_nav_glo_ephemeris, gnsscorr_nav_glo_satpos and gnsscorr_nav_glo_fix;
- * BeiDou stops here.  Bits and positions are exact.
+ * gnsscorr_nav_glo_ephemeris, gnsscorr_nav_glo_satpos and gnsscorr_nav_glo_fix,
+ * BeiDou B1I in gnsscorr_nav_b1_ephemeris and gnsscorr_nav_b1_fix.  Bits and
+ * positions are exact.
  *
  * Pattern search, the files' convol(pattern, sign(x)) cut to its valid part:
  *   r[k] = sum_{i<T} pattern[i] sign(x[k + i]),  first_k <= k < n_epochs,
@@ -1153,8 +1154,8 @@ int gnsscorr_nav_b1_subframes(gnsscorr_nav_ctx *ctx, const void *h_series,
  *   leastSquarePos.sci:32-111, e_r_corr.sci, topocent.sci, togeod.sci, tropo.sci,
  *   cart2geo.sci
  * Same context as above.  UTM (findUtmZone, cart2utm) is presentation and is not
- * computed; the GLONASS L1OF solution follows this one, the BeiDou and Galileo
- * solutions are not part of the library.
+ * computed; the GLONASS L1OF and BeiDou B1I solutions follow this one, and the
+ * Galileo solution is not part of the library (the reference has none).
  *
  * Stage 1, gps_ephemeris: d_bits [n_ch][1500], d_n_bits and d_first_subframe as
  * gnsscorr_nav_gps_frames_dev writes them (bits already through checkPhase) ->
@@ -1442,6 +1443,135 @@ int gnsscorr_nav_glo_fix(gnsscorr_nav_ctx *ctx, const gnsscorr_glo_eph *h_eph,
                          const int32_t *rx_first, const gnsscorr_glo_fix_cfg *cfg,
                          int32_t *h_n_meas, gnsscorr_gps_fix_sol *h_sol,
                          gnsscorr_gps_fix_chan *h_chan);
+
+/* ----------------------------------------------------------------------
+ * BeiDou B1I position fix (csrc/navb1.hip): what the Scilab COMPASS receiver does
+ * after the data bits
+ *   COMPASS/B1/include/ephemeris.sci:28-123, postNavigation.sci:129-272,
+ *   calculatePseudoranges.sci, geoFunctions/satpos.sci:45-137, check_t.sci,
+ *   leastSquarePos.sci, e_r_corr.sci, topocent.sci, togeod.sci, tropo.sci,
+ *   cart2geo.sci, initSettings.sci
+ * Same context as above.  The ephemeris is Keplerian and satpos.sci is the GPS
+ * propagation with BeiDou's constants; leastSquarePos and the geo functions it
+ * calls are the GLONASS L1 text (rows divided by the range, atan(y, x) called
+ * directly).  There is no elevation mask, no startOffset and no datum transform.
+ * UTM, the ionosphere terms (decoded, not applied by the file) and the almanac
+ * subframes 4 and 5 are not computed; the file has no branch for the GEO
+ * satellites' D2 message and orbit rotation, and neither has this.
+ *
+ * Stage 1, b1_ephemeris: d_bits [n_ch][5][213], d_n_subframes and d_first as
+ * gnsscorr_nav_b1_subframes_dev writes them -> one gnsscorr_b1_eph per channel.
+ * decoded_sbfrm(k) of the file is bits[k - 1]; positions below are the file's.
+ *  - slot i (1..5) is skipped whole when any of its 213 values is 2 (the file's
+ *    `continue` on a 0.5, :36-39).  Else the subframe ID is the value of bits 5..7.
+ *    IDs 1, 2, 3 decode the fields of :45-107 and set bit 0, 1, 2 of `have`; IDs 0,
+ *    4, 5, 6, 7 decode nothing.  A later slot with the same ID overwrites an earlier
+ *    one; fields of a subframe that is not there are 0;
+ *  - a field is the unsigned value of its bit range, minus bit(first) * 2^length
+ *    where the file subtracts, times its factors in the file's left-to-right order
+ *    (* 2^k * BDPi, BDPi = 3.1415926535898): bit-exact.  The file's quirks are kept:
+ *    alpha3 (bits 112..119) subtracts bit(88) * 2^8 and beta1 (128..135) subtracts
+ *    bit(120) * 2^8, not their own sign bits; e (94..125) is read signed, sqrtA
+ *    (180..211) unsigned; T_GD_1 = ((v - bit(68) * 2^10) * 0.1) * 1e-9, the file's
+ *    10^-9 being read as the double 1e-9; t_oe_msb = v * 2^15 * 2^3, t_oe_lsb =
+ *    v * 2^3, and t_oe = t_oe_msb + t_oe_lsb (:118) only when subframes 2 and 3 were
+ *    both decoded, else 0;
+ *  - SOW = value(bits 8..27 of slot 5) - 24 (:123).  The file keeps decoded_sbfrm
+ *    across the `continue`, so SOW is taken whenever those 20 values are all 0 or
+ *    1, even if slot 5 was skipped for a 2 elsewhere.
+ * The reference stops with an error in these cases; here they are statuses, the
+ * widenings of this stage:
+ *  - SHORT: n_subframes < 5 or first < 0.  have = 0 and every field is 0;
+ *  - NO_SOW: one of bits 8..27 of slot 5 is 2.  Fields and have stay as decoded,
+ *    SOW = 0, and the channel is not ready for stage 2.
+ * ---------------------------------------------------------------------- */
+#define GNSSCORR_B1_EPH_OK     0
+#define GNSSCORR_B1_EPH_SHORT  1
+#define GNSSCORR_B1_EPH_NO_SOW 2
+
+typedef struct {          /* ephemeris.sci:45-118: 31 doubles, 8 int32, 280 bytes */
+  double  T_GD_1, t_oc, a2, a0, a1;
+  double  alpha0, alpha1, alpha2, alpha3, beta0, beta1, beta2, beta3;
+  double  deltan, C_uc, M_0, e, C_us, C_rc, C_rs, sqrtA, t_oe_msb;
+  double  t_oe_lsb, i_0, C_ic, omegaDot, C_is, iDot, omega_0, omega;
+  double  t_oe;
+  int32_t SatH1, IODC, URAI, WN, IODE;
+  int32_t SOW;            /* start of the first subframe [s of week]           */
+  int32_t have;
+  int32_t status;
+} gnsscorr_b1_eph;
+
+int gnsscorr_nav_b1_ephemeris_dev(gnsscorr_nav_ctx *ctx, const uint8_t *d_bits,
+                                  const int32_t *d_n_subframes, const int32_t *d_first,
+                                  int n_ch, gnsscorr_b1_eph *d_eph);
+int gnsscorr_nav_b1_ephemeris(gnsscorr_nav_ctx *ctx, const uint8_t *h_bits,
+                              const int32_t *h_n_subframes, const int32_t *h_first,
+                              int n_ch, gnsscorr_b1_eph *h_eph);
+
+/* Stage 2, b1_fix: the measurement loop of postNavigation.sci:129-272, one wave
+ * per receiver, one lane per channel.  rx_first, d_abs_sample, the outputs
+ * d_n_meas, d_sol and d_chan, the OK / FEW / RANK codes and the queued copy of
+ * rx_first are exactly as in gnsscorr_nav_gps_fix_dev.  Indices below are 0-based.
+ *  - ready: first >= 0, status OK and have == 7.  The file has its own exclusion
+ *    lines disabled (:117-118) and then stops, or reads unset entries, when a found
+ *    channel lacks an ephemeris; dropping such channels is the one widening, and
+ *    gives the file's result whenever the file runs to the end.  Fewer than 4
+ *    ready channels: n_meas = 0.  Else n_meas = min(max_meas, fix((n_epochs -
+ *    (max p + 1)) / navSolPeriod)), the max over every channel of the receiver
+ *    with first = p >= 0 (:152).  skipNumberOfFirstBits stays the caller's, as for
+ *    b1_subframes;
+ *  - transmitTime is one value per receiver: it starts at the SOW of the
+ *    receiver's lowest-numbered ready channel (:145) and advances by navSolPeriod /
+ *    1000 through repeated addition (:270);
+ *  - there is no elevation mask (the file has it commented out, :156-157): every
+ *    ready channel is used at every measurement, so status FEW does not occur; el
+ *    and az are NaN for the other channels;
+ *  - rawP = (absoluteSample[ch][p_ch + navSolPeriod m] / samplesPerCode /
+ *    dataTypeSizeInBytes - floor(min over used)) * (c / 1000), +inf for the other
+ *    channels: bit-exact, and no startOffset;
+ *  - satpos.sci per used channel from its own ephemeris at the shared
+ *    transmitTime: Omegae_dot = 7.2921150e-5, GM = 3.986004418e14, F =
+ *    -4.442807633e-10 (not the GPS values), the clock term from a2, a1, a0 and
+ *    T_GD_1, check_t, the x - fix(x / y) y reductions and the ten-step Kepler loop
+ *    with its 1e-12 exit as in the file; its two-argument atand(..) / 180 * %pi is
+ *    read as in the GPS fix;
+ *  - leastSquarePos.sci as in gnsscorr_nav_glo_fix_dev: 7 iterations from 0;
+ *    iteration 1 with dist = |satpos| and trop = 0, later ones with e_r_corr,
+ *    topocent / togeod with plain atan(y, x) and tropo when useTropCorr == 1; F =
+ *    obs - pos(4) - dist - trop, rows of A divided by dist; the LDL' factorisation
+ *    and the rank rule of the GPS fix, status RANK as the widening;
+ *  - obs = rawP + satClkCorr c (:187-188) and corrP = rawP - satClkCorr c + dt
+ *    (:212-214): the two disagree in the file, and are kept as written;
+ *  - no PZ-90 transform (commented out in the file); cart2geo(X, Y, Z, 5).
+ * d_eph is read only, so a call can be repeated.
+ * Refused with GNSSCORR_EINVAL before any device call: as gnsscorr_nav_gps_fix_dev,
+ * and dataTypeSizeInBytes <= 0. */
+typedef struct {          /* COMPASS/B1/initSettings.sci */
+  double  samplesPerCode;       /* 16000 = 16e6 / (2.046e6 / 2046)                */
+  double  dataTypeSizeInBytes;  /* 1                                              */
+  double  c;                    /* 299792458                                      */
+  int32_t navSolPeriod;         /* 500 [ms]                                       */
+  int32_t useTropCorr;          /* 0                                              */
+  int32_t max_meas;             /* rows of d_sol and d_chan per receiver / channel */
+  int32_t reserved;
+} gnsscorr_b1_fix_cfg;
+
+/* the defaults above, max_meas = 1 */
+void gnsscorr_nav_b1_fix_cfg_init(gnsscorr_b1_fix_cfg *cfg);
+int gnsscorr_nav_b1_fix_dev(gnsscorr_nav_ctx *ctx, const gnsscorr_b1_eph *d_eph,
+                            const int32_t *d_first, const void *d_abs_sample,
+                            int64_t epoch_stride_bytes, int64_t chan_stride_bytes,
+                            int n_epochs, int n_rx, const int32_t *rx_first,
+                            const gnsscorr_b1_fix_cfg *cfg, int32_t *d_n_meas,
+                            gnsscorr_gps_fix_sol *d_sol, gnsscorr_gps_fix_chan *d_chan);
+/* Same with host arrays (synchronous); rows m >= n_meas of h_sol and h_chan keep
+ * what the caller put there. */
+int gnsscorr_nav_b1_fix(gnsscorr_nav_ctx *ctx, const gnsscorr_b1_eph *h_eph,
+                        const int32_t *h_first, const void *h_abs_sample,
+                        int64_t epoch_stride_bytes, int64_t chan_stride_bytes, int n_epochs,
+                        int n_rx, const int32_t *rx_first, const gnsscorr_b1_fix_cfg *cfg,
+                        int32_t *h_n_meas, gnsscorr_gps_fix_sol *h_sol,
+                        gnsscorr_gps_fix_chan *h_chan);
 
 /* ======================================================================
  * GPS-SDR integer strong acquisition ("sdr"), bit-exact with the real-time
