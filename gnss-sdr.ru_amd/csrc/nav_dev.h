@@ -1,14 +1,16 @@
 // nav_dev.h -- device helpers that the GPS fix (navfix.hip), the GLONASS fix (navglo.hip)
 // and the BeiDou fix (navb1.hip) compute identically: the wave reductions, one pass of
 // tropo.sci, the LDL' factorisation of the normal equations with the library's rank rule,
-// on the host the constants of tropo.sci's two passes; check_t and the reductions of the
-// Kepler propagation (GPS, BeiDou); togeod and cart2geo with plain atan(y, x) (GLONASS,
-// BeiDou).  Every file includes it under `#pragma clang fp contract(off)`: no operation
-// here may be contracted.
+// on the host the constants of tropo.sci's two passes; togeod and cart2geo in their two texts
+// (Fix); the Kepler propagation of satpos.sci with check_t and its reductions (GPS, BeiDou);
+// bin2dec of an ephemeris field.  The measurement loop built from them is nav_fix.h.  Every
+// file includes it under `#pragma clang fp contract(off)`: no operation here may be
+// contracted.
 #ifndef GNSSCORR_NAV_DEV_H
 #define GNSSCORR_NAV_DEV_H
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stdint.h>
 
 namespace navdev {
 
@@ -132,20 +134,33 @@ __device__ __forceinline__ double rem_fix(double x, double y) { return x - trunc
 // Scilab's two-argument atand, read as (180 / %pi) * atan(y, x)
 __device__ __forceinline__ double atand2(double y, double x) { return (180.0 / kPi) * atan2(y, x); }
 
-// GLONASS/L1 and COMPASS/B1 togeod.sci:31-110 (the same text, atan(y, x) called directly) for
-// a = 6378137, finv = 298.257223563: latitude and longitude in degrees
-inline __device__ void togeod_atan(double X, double Y, double Z, double* dphi_deg,
-                                   double* dlambda_deg) {
+// The two texts of the shared geoFunctions.  kGps: GPS/L1 takes every angle of two arguments
+// through atand and converts back; its leastSquarePos.sci starts the troposphere term at 2 m,
+// divides the rows of A by the observation and forms omc as obs - range - dt - trop.
+// kGloB1: GLONASS/L1 and COMPASS/B1 call atan(y, x) directly, start the term at 0, divide by
+// the geometric range and form obs - dt - range - trop.
+enum class Fix { kGps, kGloB1 };
+
+template <Fix F>
+__device__ __forceinline__ double atan_yx(double y, double x) {
+  if constexpr (F == Fix::kGps) return atand2(y, x) / 180 * kPi;
+  else return atan2(y, x);
+}
+
+// togeod.sci (GPS/L1 :32-113, GLONASS/L1 and COMPASS/B1 :31-110) for a = 6378137,
+// finv = 298.257223563: latitude and longitude in degrees
+template <Fix F>
+__device__ void togeod(double X, double Y, double Z, double* dphi_deg, double* dlambda_deg) {
   const double a = 6378137.0, finv = 298.257223563, tolsq = 1.e-10, rtd = 180 / kPi;
   const double esq = (2 - 1 / finv) / finv, oneesq = 1 - esq;
   const double P = sqrt(X * X + Y * Y);
-  double dlambda = P > 1.e-20 ? atan2(Y, X) * rtd : 0.0;       // :52-56
+  double dlambda = P > 1.e-20 ? atan_yx<F>(Y, X) * rtd : 0.0;
   if (dlambda < 0) dlambda = dlambda + 360;
   const double r = sqrt(P * P + Z * Z);
   double sinphi = r > 1.e-20 ? Z / r : 0.0;
   double dphi = asin(sinphi);
   *dlambda_deg = dlambda;
-  if (r < 1.e-20) {                                            // :75-78, dphi is 0 here
+  if (r < 1.e-20) {                                            // dphi is 0 here
     *dphi_deg = dphi;
     return;
   }
@@ -163,11 +178,12 @@ inline __device__ void togeod_atan(double X, double Y, double Z, double* dphi_de
   *dphi_deg = dphi * rtd;
 }
 
-// GLONASS/L1 and COMPASS/B1 cart2geo.sci:20-45 with i = 5
-inline __device__ void cart2geo5_atan(double X, double Y, double Z, double* phi_deg,
-                                      double* lambda_deg, double* h_out) {
+// cart2geo.sci (GPS/L1 :22-53, GLONASS/L1 and COMPASS/B1 :20-45) with i = 5
+template <Fix F>
+__device__ void cart2geo5(double X, double Y, double Z, double* phi_deg, double* lambda_deg,
+                          double* h_out) {
   const double a = 6378137.0, f = 1 / 298.257223563;
-  const double lambda = atan2(Y, X);                           // :23
+  const double lambda = atan_yx<F>(Y, X);
   const double ex2 = (2 - f) * f / ((1 - f) * (1 - f));
   const double c = a * sqrt(1 + ex2);
   const double p = sqrt(X * X + Y * Y);
@@ -186,6 +202,74 @@ inline __device__ void cart2geo5_atan(double X, double Y, double Z, double* phi_
   *phi_deg = phi * 180 / kPi;
   *lambda_deg = lambda * 180 / kPi;
   *h_out = h;
+}
+
+// GPS/L1 and COMPASS/B1 satpos.sci (:56-145, :53-136) are one text but for two constants and
+// the names of four fields.  The elements as the file names them, a2 / a1 / a0 / T_GD for
+// GPS's a_f2 / a_f1 / a_f0 / T_GD and BeiDou's a2 / a1 / a0 / T_GD_1.
+constexpr double kEphPi = 3.1415926535898;     // gpsPi, BDPi: ephemeris.sci, satpos.sci
+struct Kepler {
+  double t_oc, a2, a1, a0, T_GD;
+  double sqrtA, t_oe, deltan, M_0, e, omega, C_uc, C_us, C_rc, C_rs, i_0, iDot, C_ic, C_is;
+  double omega_0, omegaDot;
+};
+// from a record E that names the orbit as the file does, and its own clock terms
+template <class E>
+__device__ __forceinline__ Kepler kepler_of(const E& e, double a2, double a1, double a0,
+                                            double T_GD) {
+  return {e.t_oc, a2, a1, a0, T_GD, e.sqrtA, e.t_oe, e.deltan, e.M_0, e.e, e.omega,
+          e.C_uc, e.C_us, e.C_rc, e.C_rs, e.i_0, e.iDot, e.C_ic, e.C_is, e.omega_0, e.omegaDot};
+}
+
+struct SatPos { double x, y, z, clk; };
+
+// satpos.sci for one satellite: ECEF position and clock correction at transmit_time
+__device__ inline SatPos sat_pos(const Kepler& e, double Omegae_dot, double GM,
+                                 double transmit_time) {
+  const double F = -4.442807633e-10;
+  const double two_pi = 2 * kEphPi;
+  const double dt = check_t(transmit_time - e.t_oc);
+  const double clk0 = ((e.a2 * dt + e.a1) * dt + e.a0) - e.T_GD;
+  const double time = transmit_time - clk0;
+  const double a = e.sqrtA * e.sqrtA;
+  const double tk = check_t(time - e.t_oe);
+  const double n0 = sqrt(GM / (a * a * a));
+  const double n = n0 + e.deltan;
+  double M = e.M_0 + n * tk;
+  M = rem_fix(M + two_pi, two_pi);
+  double E = M;
+  for (int ii = 0; ii < 10; ii++) {
+    const double E_old = E;
+    E = M + e.e * sin(E);
+    const double dE = rem_fix(E - E_old, two_pi);
+    if (fabs(dE) < 1.e-12) break;
+  }
+  E = rem_fix(E + two_pi, two_pi);
+  const double sinE = sin(E), cosE = cos(E);
+  const double dtr = F * e.e * e.sqrtA * sinE;
+  const double nu = atand2(sqrt(1 - e.e * e.e) * sinE, cosE - e.e) / 180 * kPi;
+  double phi = nu + e.omega;
+  phi = rem_fix(phi, two_pi);
+  const double c2 = cos(2 * phi), s2 = sin(2 * phi);
+  const double u = phi + e.C_uc * c2 + e.C_us * s2;
+  const double r = a * (1 - e.e * cosE) + e.C_rc * c2 + e.C_rs * s2;
+  const double i = e.i_0 + e.iDot * tk + e.C_ic * c2 + e.C_is * s2;
+  double Omega = e.omega_0 + (e.omegaDot - Omegae_dot) * tk - Omegae_dot * e.t_oe;
+  Omega = rem_fix(Omega + two_pi, two_pi);
+  const double cu = cos(u), su = sin(u), cO = cos(Omega), sO = sin(Omega);
+  SatPos s;
+  s.x = cu * r * cO - su * r * cos(i) * sO;
+  s.y = cu * r * sO + su * r * cos(i) * cO;
+  s.z = su * r * sin(i);
+  s.clk = ((e.a2 * dt + e.a1) * dt + e.a0) - e.T_GD + dtr;
+  return s;
+}
+
+// the unsigned value of n values from 1-based position s of a subframe (bin2dec)
+__device__ __forceinline__ uint64_t bits_value(const uint8_t* sub, int s, int n) {
+  uint64_t v = 0;
+  for (int i = 0; i < n; i++) v = v << 1 | sub[s - 1 + i];
+  return v;
 }
 
 }  // namespace navdev

@@ -23,8 +23,9 @@
 // sizes, so the step's code is there once.
 //
 // nav_glo_fix_kernel: one wave64 per receiver, lane = channel, the measurement loop inside
-// the kernel, as nav_gps_fix_kernel (navfix.hip).  Every lane keeps and advances its own
-// satellite state.
+// the kernel, out of the steps of nav_fix.h with the GLONASS/L1 text of the least squares
+// (Fix::kGloB1).  Every lane keeps and advances its own satellite state; the solution goes
+// from PZ-90.02 to WGS-84 before it is written.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -34,7 +35,7 @@
 #include "nav_host.h"
 
 #pragma clang fp contract(off)
-#include "nav_dev.h"
+#include "nav_fix.h"
 
 namespace {
 
@@ -288,7 +289,7 @@ __global__ __launch_bounds__(64) void nav_glo_satpos_kernel(
 struct GloFixArgs {
   double samples_per_code, data_size, c, elevation_mask, step;
   int nav_sol_period, use_trop, max_meas, n_epochs;
-  double htop[2], ref[2];        // navdev::tropo_consts
+  Tropo trop;
 };
 
 __global__ __launch_bounds__(64) void nav_glo_fix_kernel(
@@ -297,47 +298,31 @@ __global__ __launch_bounds__(64) void nav_glo_fix_kernel(
     int64_t epoch_stride, int64_t chan_stride, const int32_t* __restrict__ rx_first,
     GloFixArgs p, int32_t* __restrict__ n_meas_out, gnsscorr_gps_fix_sol* __restrict__ sol,
     gnsscorr_gps_fix_chan* __restrict__ chan) {
-  const int rx = blockIdx.x, lane = threadIdx.x;
-  const int c0 = rx_first[rx], n_ch = rx_first[rx + 1] - c0;
-  const bool valid = lane < n_ch;
-  const int ch = c0 + (valid ? lane : 0);
-  const int fs = valid ? first_mark[ch] : -1;
-  const gnsscorr_glo_sat* my_sat = sat + ch;
-  const bool ready = valid && fs >= 0 && my_sat->ready == 1;   // postNavigation.sci:107-123
+  const FixLane l = fix_lane(rx_first);
+  const int fs = l.valid ? first_mark[l.ch] : -1;
+  const gnsscorr_glo_sat* my_sat = sat + l.ch;
+  const bool ready = l.valid && fs >= 0 && my_sat->ready == 1;   // postNavigation.sci:107-123
   const int n_ready = __popcll(__ballot(ready));
-  const int p_max = wave_max(fs);
-  int64_t n_meas = 0;
-  if (n_ready >= 4)                                            // :128, :167
-    n_meas = min((int64_t)p.max_meas, ((int64_t)p.n_epochs - (p_max + 1)) / p.nav_sol_period);
-  if (n_meas < 0) n_meas = 0;
-  if (lane == 0) n_meas_out[rx] = (int32_t)n_meas;
-  if (n_meas == 0) return;
+  const FixRows r = fix_rows(l, fs, n_ready, p.max_meas, p.n_epochs, p.nav_sol_period,   // :128, :167
+                             abs_sample, chan_stride, n_meas_out, sol, chan);
+  if (r.n_meas == 0) return;
 
   GloState w = {my_sat->pos[0], my_sat->pos[1], my_sat->pos[2],
                 my_sat->vel[0], my_sat->vel[1], my_sat->vel[2]};
   const double ax = my_sat->acc[0], ay = my_sat->acc[1], az = my_sat->acc[2];
   double clk = my_sat->clk;
-  const double gamman = eph[ch].gamman;
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  const double inf = __longlong_as_double(0x7ff0000000000000ll);
-  const double dtr = kPi / 180;
-  double sat_elev = inf;                                       // :142
-  const char* my_abs = abs_sample + (int64_t)ch * chan_stride;
-  gnsscorr_gps_fix_chan* my_chan = chan + (int64_t)ch * p.max_meas;
-  gnsscorr_gps_fix_sol* my_sol = sol + (int64_t)rx * p.max_meas;
-
-  for (int m = 0; m < (int)n_meas; m++) {
+  const double gamman = eph[l.ch].gamman;
+  const double nan = quiet_nan();
+  double sat_elev = infinity();                                // :142
+  for (int m = 0; m < (int)r.n_meas; m++) {
     const bool active = ready && sat_elev >= p.elevation_mask;  // :170
     const int n_act = __popcll(__ballot(active));
-    double el = nan, az_deg = nan;                             // :179-180
 
-    // calculatePseudoranges.sci:55-72
-    double travel = inf;
+    double travel = infinity();                                // calculatePseudoranges.sci:55-72
     if (active)
-      travel = *(const double*)(my_abs + ((int64_t)fs + (int64_t)p.nav_sol_period * m) *
-                                             epoch_stride) / p.samples_per_code / p.data_size;
-    const double minimum = floor(wave_min(travel));
-    const double raw_p = (travel - minimum) * (p.c / 1000);
+      travel = code_periods(r.my_abs, fs, p.nav_sol_period, m, epoch_stride,
+                            p.samples_per_code) / p.data_size;
+    const double raw_p = since_earliest(travel) * (p.c / 1000);
 
     if (active) {                                              // deltasatposg.sci:66-137
       rk4_step(w, ax, ay, az, p.step);
@@ -345,135 +330,32 @@ __global__ __launch_bounds__(64) void nav_glo_fix_kernel(
     }
     const double obs = raw_p - clk * p.c;                      // postNavigation.sci:202-203
 
-    int status = GNSSCORR_GPS_FIX_OK;
-    double pos0 = 0, pos1 = 0, pos2 = 0, pos3 = 0;
+    int status = GNSSCORR_GPS_FIX_FEW;
+    double pos[4] = {nan, nan, nan, nan}, el = nan, az_deg = nan;   // :179-180
     double dop[5] = {0, 0, 0, 0, 0};
     double lat = nan, lon = nan, height = nan, corr_p = 0.0;
-    if (n_act < 4) {                                           // :249-271
-      status = GNSSCORR_GPS_FIX_FEW;
-      pos0 = pos1 = pos2 = pos3 = nan;
-    } else {                                                   // leastSquarePos.sci:45-100
-      double N[10];
-      Ldl f;
-      for (int iter = 0; iter < 7; iter++) {
-        double r0 = w.x, r1 = w.y, r2 = w.z, trop = 0;
-        if (iter > 0) {
-          const double rho2 = (w.x - pos0) * (w.x - pos0) + (w.y - pos1) * (w.y - pos1) +
-                              (w.z - pos2) * (w.z - pos2);
-          const double omegatau = 7.292115147e-5 * (sqrt(rho2) / p.c);   // e_r_corr.sci:20-23
-          const double co = cos(omegatau), so = sin(omegatau);
-          r0 = co * w.x + so * w.y;
-          r1 = -so * w.x + co * w.y;
-          double phi, lambda;                                  // topocent.sci:24-54
-          togeod_atan(pos0, pos1, pos2, &phi, &lambda);
-          const double cl = cos(lambda * dtr), sl = sin(lambda * dtr);
-          const double cb = cos(phi * dtr), sb = sin(phi * dtr);
-          const double d0 = r0 - pos0, d1 = r1 - pos1, d2 = r2 - pos2;
-          const double E = -sl * d0 + cl * d1 + 0 * d2;
-          const double Nn = -sb * cl * d0 + -sb * sl * d1 + cb * d2;
-          const double U = cb * cl * d0 + cb * sl * d1 + sb * d2;
-          const double hor_dis = sqrt(E * E + Nn * Nn);
-          if (hor_dis < 1.e-20) {
-            az_deg = 0;
-            el = 90;
-          } else {
-            az_deg = atan2(E, Nn) / dtr;
-            el = atan2(U, hor_dis) / dtr;
-          }
-          if (az_deg < 0) az_deg = az_deg + 360;
-          if (p.use_trop == 1) {                               // tropo.sci:45-47,56-95
-            double sinel = sin(el * dtr);
-            if (sinel < 0) sinel = 0;
-            trop = 0 + tropo_pass(sinel, p.htop[0], p.ref[0]);
-            trop = trop + tropo_pass(sinel, p.htop[1], p.ref[1]);
-          }
-        }
-        const double d0 = r0 - pos0, d1 = r1 - pos1, d2 = r2 - pos2;
-        const double dist = sqrt(d0 * d0 + d1 * d1 + d2 * d2);  // :51-53, topocent.sci:54
-        const double F = active ? obs - pos3 - dist - trop : 0.0;
-        const double a0 = active ? -d0 / dist : 0.0;
-        const double a1 = active ? -d1 / dist : 0.0;
-        const double a2 = active ? -d2 / dist : 0.0;
-        const double a3 = active ? 1.0 : 0.0;
-        N[0] = wave_sum(a0 * a0);
-        N[1] = wave_sum(a1 * a0);
-        N[2] = wave_sum(a1 * a1);
-        N[3] = wave_sum(a2 * a0);
-        N[4] = wave_sum(a2 * a1);
-        N[5] = wave_sum(a2 * a2);
-        N[6] = wave_sum(a3 * a0);
-        N[7] = wave_sum(a3 * a1);
-        N[8] = wave_sum(a3 * a2);
-        N[9] = wave_sum(a3 * a3);
-        const double g0 = wave_sum(a0 * F), g1 = wave_sum(a1 * F);
-        const double g2 = wave_sum(a2 * F), g3 = wave_sum(a3 * F);
-        if (!ldl_factor(N, &f)) {                              // the library's rank rule
-          status = GNSSCORR_GPS_FIX_RANK;
-          break;
-        }
-        double x[4];
-        ldl_solve(f, g0, g1, g2, g3, x);                       // :83
-        pos0 = pos0 + x[0];
-        pos1 = pos1 + x[1];
-        pos2 = pos2 + x[2];
-        pos3 = pos3 + x[3];
-      }
+    if (n_act >= 4) {                                          // else :249-271
+      Ldl f;                                                   // leastSquarePos.sci:45-100
+      status = least_squares<Fix::kGloB1>(w.x, w.y, w.z, obs, active, p.c, p.use_trop, p.trop,
+                                          pos, f, el, az_deg);
       if (status == GNSSCORR_GPS_FIX_RANK) {
-        pos0 = pos1 = pos2 = pos3 = 0;
         lat = lon = height = 0;
-        el = az_deg = nan;
       } else {
-        double q[4], Q00, Q11, Q22, Q33;                       // :94-100
-        ldl_solve(f, 1, 0, 0, 0, q);
-        Q00 = q[0];
-        ldl_solve(f, 0, 1, 0, 0, q);
-        Q11 = q[1];
-        ldl_solve(f, 0, 0, 1, 0, q);
-        Q22 = q[2];
-        ldl_solve(f, 0, 0, 0, 1, q);
-        Q33 = q[3];
-        dop[0] = sqrt(Q00 + Q11 + Q22 + Q33);
-        dop[1] = sqrt(Q00 + Q11 + Q22);
-        dop[2] = sqrt(Q00 + Q11);
-        dop[3] = sqrt(Q22);
-        dop[4] = sqrt(Q33);
+        dop_from(f, dop);                                      // :94-100
         // PZ-90.02 -> WGS-84, postNavigation.sci:206-208
-        const double t0 = 1 * pos0 + -0.82e-6 * pos1 + 0 * pos2;
-        const double t1 = 0.82e-6 * pos0 + 1 * pos1 + 0 * pos2;
-        const double t2 = 0 * pos0 + 0 * pos1 + 1 * pos2;
-        pos0 = -1.1 + (1 - 0.12e-6) * t0;
-        pos1 = -0.3 + (1 - 0.12e-6) * t1;
-        pos2 = -0.9 + (1 - 0.12e-6) * t2;
-        if (!active) el = az_deg = nan;
+        const double t0 = 1 * pos[0] + -0.82e-6 * pos[1] + 0 * pos[2];
+        const double t1 = 0.82e-6 * pos[0] + 1 * pos[1] + 0 * pos[2];
+        const double t2 = 0 * pos[0] + 0 * pos[1] + 1 * pos[2];
+        pos[0] = -1.1 + (1 - 0.12e-6) * t0;
+        pos[1] = -0.3 + (1 - 0.12e-6) * t1;
+        pos[2] = -0.9 + (1 - 0.12e-6) * t2;
         sat_elev = el;                                         // :221
-        if (active) corr_p = raw_p - clk * p.c + pos3;         // :224-226
-        cart2geo5_atan(pos0, pos1, pos2, &lat, &lon, &height);  // :231-237
+        if (active) corr_p = raw_p - clk * p.c + pos[3];       // :224-226
+        cart2geo5<Fix::kGloB1>(pos[0], pos[1], pos[2], &lat, &lon, &height);   // :231-237
       }
     }
-    if (valid) {
-      gnsscorr_gps_fix_chan o;
-      o.el = el;
-      o.az = az_deg;
-      o.rawP = raw_p;
-      o.corrP = corr_p;
-      o.used = active;
-      o.reserved = 0;
-      my_chan[m] = o;
-    }
-    if (lane == 0) {
-      gnsscorr_gps_fix_sol o;
-      o.X = pos0;
-      o.Y = pos1;
-      o.Z = pos2;
-      o.dt = pos3;
-      for (int k = 0; k < 5; k++) o.DOP[k] = dop[k];
-      o.lat = lat;
-      o.lon = lon;
-      o.height = height;
-      o.status = status;
-      o.n_used = n_act;
-      my_sol[m] = o;
-    }
+    write_fix_records(l.valid, r.my_chan + m, r.my_sol + m, el, az_deg, raw_p, corr_p, active,
+                      pos, dop, lat, lon, height, status, n_act);
   }
 }
 
@@ -483,8 +365,6 @@ __global__ __launch_bounds__(64) void nav_glo_fix_kernel(
 // host side
 // ============================================================================
 using navhost::bad_arguments;
-using navhost::check_series;
-using navhost::series_bytes;
 
 extern "C" void gnsscorr_nav_glo_fix_cfg_init(gnsscorr_glo_fix_cfg* cfg) {
   if (!cfg) return;
@@ -498,42 +378,20 @@ extern "C" void gnsscorr_nav_glo_fix_cfg_init(gnsscorr_glo_fix_cfg* cfg) {
   cfg->max_meas = 1;
 }
 
-static int check_eph(const char* fn, const gnsscorr_nav_ctx* c, const void* bits,
-                     const void* n_strings, const void* first, int n_ch, const void* eph) {
-  if (!c || !bits || !n_strings || !first || !eph) return bad_arguments(fn, "null pointer");
-  if (n_ch < 1) return bad_arguments(fn, "n_ch >= 1");
-  return GNSSCORR_OK;
-}
-
 extern "C" int gnsscorr_nav_glo_ephemeris_dev(gnsscorr_nav_ctx* c, const uint8_t* d_bits,
                                               const int32_t* d_n_strings,
                                               const int32_t* d_first_mark, int n_ch,
                                               gnsscorr_glo_eph* d_eph) {
-  int rc = check_eph(__func__, c, d_bits, d_n_strings, d_first_mark, n_ch, d_eph);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  hipLaunchKernelGGL(nav_glo_eph_kernel, dim3(n_ch), dim3(64), 0, c->stream, d_bits, d_n_strings,
-                     d_first_mark, d_eph);
-  HIP_TRY(hipGetLastError());
-  return GNSSCORR_OK;
+  return navhost::ephemeris_dev(__func__, c, nav_glo_eph_kernel, d_bits, d_n_strings,
+                                d_first_mark, n_ch, d_eph);
 }
 
 extern "C" int gnsscorr_nav_glo_ephemeris(gnsscorr_nav_ctx* c, const uint8_t* h_bits,
                                           const int32_t* h_n_strings,
                                           const int32_t* h_first_mark, int n_ch,
                                           gnsscorr_glo_eph* h_eph) {
-  int rc = check_eph(__func__, c, h_bits, h_n_strings, h_first_mark, n_ch, h_eph);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  const size_t n = (size_t)n_ch;
-  hostctx::Staging st(c->stream);
-  const uint8_t* d_bits = st.in(h_bits, n * kGloBits);
-  const int32_t* d_n_strings = st.in(h_n_strings, n);
-  const int32_t* d_first_mark = st.in(h_first_mark, n);
-  gnsscorr_glo_eph* d_eph = st.out(h_eph, n);
-  if (st.status()) return st.status();
-  rc = gnsscorr_nav_glo_ephemeris_dev(c, d_bits, d_n_strings, d_first_mark, n_ch, d_eph);
-  return rc ? rc : st.finish();
+  return navhost::ephemeris_host(__func__, c, nav_glo_eph_kernel, kGloBits, h_bits, h_n_strings,
+                                 h_first_mark, n_ch, h_eph);
 }
 
 static int check_satpos(const char* fn, const gnsscorr_nav_ctx* c, const void* eph, int n_ch,
@@ -571,30 +429,6 @@ extern "C" int gnsscorr_nav_glo_satpos(gnsscorr_nav_ctx* c, const gnsscorr_glo_e
   return rc ? rc : st.finish();
 }
 
-static int check_fix(const char* fn, const gnsscorr_nav_ctx* c, const void* eph, const void* sat,
-                     const void* first, const void* abs_sample, int64_t epoch_stride,
-                     int64_t chan_stride, int n_epochs, int n_rx, const int32_t* rx_first,
-                     const gnsscorr_glo_fix_cfg* cfg, const void* n_meas, const void* sol,
-                     const void* chan) {
-  if (!c || !eph || !sat || !first || !abs_sample || !rx_first || !cfg || !n_meas || !sol ||
-      !chan)
-    return bad_arguments(fn, "null pointer");
-  if (n_rx < 1) return bad_arguments(fn, "n_rx >= 1");
-  if (rx_first[0] != 0) return bad_arguments(fn, "rx_first[0] == 0");
-  for (int i = 0; i < n_rx; i++) {
-    const int64_t n = (int64_t)rx_first[i + 1] - rx_first[i];
-    if (n < 1) return bad_arguments(fn, "rx_first ascending");
-    if (n > 64) return bad_arguments(fn, "at most 64 channels in a receiver");
-  }
-  int rc = check_series(fn, c, abs_sample, epoch_stride, chan_stride, n_epochs, rx_first[n_rx]);
-  if (rc) return rc;
-  if (cfg->navSolPeriod < 1) return bad_arguments(fn, "navSolPeriod >= 1");
-  if (!(cfg->samplesPerCode > 0)) return bad_arguments(fn, "samplesPerCode > 0");
-  if (!(cfg->dataTypeSizeInBytes > 0)) return bad_arguments(fn, "dataTypeSizeInBytes > 0");
-  if (cfg->max_meas < 1) return bad_arguments(fn, "max_meas >= 1");
-  return GNSSCORR_OK;
-}
-
 extern "C" int gnsscorr_nav_glo_fix_dev(gnsscorr_nav_ctx* c, const gnsscorr_glo_eph* d_eph,
                                         const gnsscorr_glo_sat* d_sat,
                                         const int32_t* d_first_mark, const void* d_abs_sample,
@@ -603,14 +437,14 @@ extern "C" int gnsscorr_nav_glo_fix_dev(gnsscorr_nav_ctx* c, const gnsscorr_glo_
                                         const gnsscorr_glo_fix_cfg* cfg, int32_t* d_n_meas,
                                         gnsscorr_gps_fix_sol* d_sol,
                                         gnsscorr_gps_fix_chan* d_chan) {
-  int rc = check_fix(__func__, c, d_eph, d_sat, d_first_mark, d_abs_sample, epoch_stride_bytes,
-                     chan_stride_bytes, n_epochs, n_rx, rx_first, cfg, d_n_meas, d_sol, d_chan);
+  int rc = navhost::check_fix_common(__func__, c, {d_eph, d_sat}, d_first_mark, d_abs_sample,
+                                     epoch_stride_bytes, chan_stride_bytes, n_epochs, n_rx,
+                                     rx_first, cfg, &gnsscorr_glo_fix_cfg::dataTypeSizeInBytes,
+                                     d_n_meas, d_sol, d_chan);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->cfg.device));
-  rc = hostctx::grow(c->d_rx_first, (size_t)n_rx + 1);
+  rc = navhost::upload_rx_first(c, rx_first, n_rx);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(c->d_rx_first.p, rx_first, ((size_t)n_rx + 1) * sizeof(int32_t),
-                         hipMemcpyHostToDevice, c->stream));
   GloFixArgs p;
   p.samples_per_code = cfg->samplesPerCode;
   p.data_size = cfg->dataTypeSizeInBytes;
@@ -621,7 +455,7 @@ extern "C" int gnsscorr_nav_glo_fix_dev(gnsscorr_nav_ctx* c, const gnsscorr_glo_
   p.use_trop = cfg->useTropCorr;
   p.max_meas = cfg->max_meas;
   p.n_epochs = n_epochs;
-  navdev::tropo_consts(p.htop, p.ref);
+  navdev::tropo_consts(p.trop.htop, p.trop.ref);
   hipLaunchKernelGGL(nav_glo_fix_kernel, dim3(n_rx), dim3(64), 0, c->stream, d_eph, d_sat,
                      d_first_mark, (const char*)d_abs_sample, epoch_stride_bytes,
                      chan_stride_bytes, c->d_rx_first.p, p, d_n_meas, d_sol, d_chan);
@@ -636,24 +470,21 @@ extern "C" int gnsscorr_nav_glo_fix(gnsscorr_nav_ctx* c, const gnsscorr_glo_eph*
                                     const int32_t* rx_first, const gnsscorr_glo_fix_cfg* cfg,
                                     int32_t* h_n_meas, gnsscorr_gps_fix_sol* h_sol,
                                     gnsscorr_gps_fix_chan* h_chan) {
-  int rc = check_fix(__func__, c, h_eph, h_sat, h_first_mark, h_abs_sample, epoch_stride_bytes,
-                     chan_stride_bytes, n_epochs, n_rx, rx_first, cfg, h_n_meas, h_sol, h_chan);
+  int rc = navhost::check_fix_common(__func__, c, {h_eph, h_sat}, h_first_mark, h_abs_sample,
+                                     epoch_stride_bytes, chan_stride_bytes, n_epochs, n_rx,
+                                     rx_first, cfg, &gnsscorr_glo_fix_cfg::dataTypeSizeInBytes,
+                                     h_n_meas, h_sol, h_chan);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->cfg.device));
-  const size_t n_ch = (size_t)rx_first[n_rx], mm = (size_t)cfg->max_meas;
-  const size_t n_in = series_bytes(epoch_stride_bytes, chan_stride_bytes, n_epochs, (int)n_ch);
   hostctx::Staging st(c->stream);
-  const gnsscorr_glo_eph* d_eph = st.in(h_eph, n_ch);
-  const gnsscorr_glo_sat* d_sat = st.in(h_sat, n_ch);
-  const int32_t* d_first_mark = st.in(h_first_mark, n_ch);
-  int32_t* d_n_meas = st.out(h_n_meas, (size_t)n_rx);
-  const char* d_abs_sample = st.in((const char*)h_abs_sample, n_in);
-  // uploaded too: rows past n_meas stay as the caller has them
-  gnsscorr_gps_fix_sol* d_sol = st.inout(h_sol, (size_t)n_rx * mm);
-  gnsscorr_gps_fix_chan* d_chan = st.inout(h_chan, n_ch * mm);
+  const gnsscorr_glo_eph* d_eph = st.in(h_eph, (size_t)rx_first[n_rx]);
+  const gnsscorr_glo_sat* d_sat = st.in(h_sat, (size_t)rx_first[n_rx]);
+  const navhost::FixStaged d =
+      navhost::stage_fix(st, h_first_mark, h_abs_sample, epoch_stride_bytes, chan_stride_bytes,
+                         n_epochs, n_rx, rx_first, cfg->max_meas, h_n_meas, h_sol, h_chan);
   if (st.status()) return st.status();
-  rc = gnsscorr_nav_glo_fix_dev(c, d_eph, d_sat, d_first_mark, d_abs_sample, epoch_stride_bytes,
-                                chan_stride_bytes, n_epochs, n_rx, rx_first, cfg, d_n_meas, d_sol,
-                                d_chan);
+  rc = gnsscorr_nav_glo_fix_dev(c, d_eph, d_sat, d.first, d.abs_sample, epoch_stride_bytes,
+                                chan_stride_bytes, n_epochs, n_rx, rx_first, cfg, d.n_meas, d.sol,
+                                d.chan);
   return rc ? rc : st.finish();
 }

@@ -1389,17 +1389,46 @@ class NavCtx(_Handle):
                                       n_epochs, n_ch, max_subframes, d_first, d_n_subframes,
                                       d_bits), self._b1_subframes_dev)
 
+    def _ephemeris(self, fn, shape, dtype, bits, n_units, first) -> np.ndarray:
+        bits = np.ascontiguousarray(bits, np.uint8).reshape(-1, *shape)
+        n_ch = bits.shape[0]
+        n_units = np.ascontiguousarray(n_units, np.int32).reshape(n_ch)
+        first = np.ascontiguousarray(first, np.int32).reshape(n_ch)
+        eph = np.zeros(n_ch, dtype)
+        _check(fn(self.h, _ptr(bits), _ptr(n_units), _ptr(first), n_ch, _ptr(eph)), fn)
+        return eph
+
+    def _fix_host(self, fn, eph_dtype, eph, extra_inputs, first, abs_sample, rx_first, cfg,
+                  n_meas, sol, chan):
+        """extra_inputs: (array, dtype) of each per-channel input between eph and first"""
+        eph = np.ascontiguousarray(eph, eph_dtype).ravel()
+        n_ch = eph.size
+        extra = [np.ascontiguousarray(x, dt).reshape(n_ch) for x, dt in extra_inputs]
+        first = np.ascontiguousarray(first, np.int32).reshape(n_ch)
+        series, cs, n_ep, _ = self._series(abs_sample)
+        assert series.shape[0] == n_ch
+        rx_first = np.ascontiguousarray(rx_first, np.int32).ravel()
+        n_rx = rx_first.size - 1
+        n_meas = np.zeros(n_rx, np.int32) if n_meas is None else n_meas
+        sol = np.zeros((n_rx, cfg.max_meas), GPS_FIX_SOL) if sol is None else sol
+        chan = np.zeros((n_ch, cfg.max_meas), GPS_FIX_CHAN) if chan is None else chan
+        _check(fn(self.h, _ptr(eph), *[_ptr(x) for x in extra], _ptr(first), _ptr(series), 8, cs,
+                  n_ep, n_rx, _ptr(rx_first), C.addressof(cfg), _ptr(n_meas), _ptr(sol),
+                  _ptr(chan)), fn)
+        return n_meas, sol, chan
+
+    def _fix_dev(self, fn, d_inputs, d_abs_sample, epoch_stride_bytes, chan_stride_bytes,
+                 n_epochs, rx_first, cfg, d_n_meas, d_sol, d_chan):
+        rx_first = np.ascontiguousarray(rx_first, np.int32).ravel()
+        _check(fn(self.h, *d_inputs, d_abs_sample, epoch_stride_bytes, chan_stride_bytes,
+                  n_epochs, rx_first.size - 1, _ptr(rx_first),
+                  C.addressof(cfg) if cfg is not None else None, d_n_meas, d_sol, d_chan), fn)
+
     def gps_ephemeris(self, bits, n_bits, first_subframe) -> np.ndarray:
         """GPS L1: bits [n_ch, 1500], n_bits [n_ch] and first_subframe [n_ch] as gps_frames
         returns them -> GPS_EPH [n_ch] (ephemeris.sci:82-226; status GPS_EPH_*)."""
-        bits = np.ascontiguousarray(bits, np.uint8).reshape(-1, 1500)
-        n_ch = bits.shape[0]
-        n_bits = np.ascontiguousarray(n_bits, np.int32).reshape(n_ch)
-        first = np.ascontiguousarray(first_subframe, np.int32).reshape(n_ch)
-        eph = np.zeros(n_ch, GPS_EPH)
-        _check(self._gps_ephemeris(self.h, _ptr(bits), _ptr(n_bits), _ptr(first), n_ch,
-                                   _ptr(eph)), self._gps_ephemeris)
-        return eph
+        return self._ephemeris(self._gps_ephemeris, (1500,), GPS_EPH, bits, n_bits,
+                               first_subframe)
 
     def gps_ephemeris_dev(self, d_bits, d_n_bits, d_first_subframe, n_ch, d_eph):
         _check(self._gps_ephemeris_dev(self.h, d_bits, d_n_bits, d_first_subframe, n_ch, d_eph),
@@ -1411,42 +1440,21 @@ class NavCtx(_Handle):
         (SGT_EPOCH absoluteSample), rx_first [n_rx + 1] channel offsets, cfg from gps_fix_cfg.
         Returns n_meas [n_rx], sol GPS_FIX_SOL [n_rx, max_meas] and chan GPS_FIX_CHAN
         [n_ch, max_meas]; rows past n_meas keep what sol and chan held (zeros by default)."""
-        eph = np.ascontiguousarray(eph, GPS_EPH).ravel()
-        n_ch = eph.size
-        first = np.ascontiguousarray(first_subframe, np.int32).reshape(n_ch)
-        series, cs, n_ep, _ = self._series(abs_sample)
-        assert series.shape[0] == n_ch
-        rx_first = np.ascontiguousarray(rx_first, np.int32).ravel()
-        n_rx = rx_first.size - 1
-        n_meas = np.zeros(n_rx, np.int32) if n_meas is None else n_meas
-        sol = np.zeros((n_rx, cfg.max_meas), GPS_FIX_SOL) if sol is None else sol
-        chan = np.zeros((n_ch, cfg.max_meas), GPS_FIX_CHAN) if chan is None else chan
-        _check(self._gps_fix(self.h, _ptr(eph), _ptr(first), _ptr(series), 8, cs, n_ep, n_rx,
-                             _ptr(rx_first), C.addressof(cfg), _ptr(n_meas), _ptr(sol),
-                             _ptr(chan)), self._gps_fix)
-        return n_meas, sol, chan
+        return self._fix_host(self._gps_fix, GPS_EPH, eph, (), first_subframe, abs_sample,
+                              rx_first, cfg, n_meas, sol, chan)
 
     def gps_fix_dev(self, d_eph, d_first_subframe, d_abs_sample, epoch_stride_bytes,
                     chan_stride_bytes, n_epochs, rx_first, cfg, d_n_meas, d_sol, d_chan):
         """rx_first: a host int32 array of n_rx + 1 offsets (checked before the launch)."""
-        rx_first = np.ascontiguousarray(rx_first, np.int32).ravel()
-        _check(self._gps_fix_dev(self.h, d_eph, d_first_subframe, d_abs_sample,
-                                 epoch_stride_bytes, chan_stride_bytes, n_epochs,
-                                 rx_first.size - 1, _ptr(rx_first),
-                                 C.addressof(cfg) if cfg is not None else None, d_n_meas, d_sol,
-                                 d_chan), self._gps_fix_dev)
+        self._fix_dev(self._gps_fix_dev, (d_eph, d_first_subframe), d_abs_sample,
+                      epoch_stride_bytes, chan_stride_bytes, n_epochs, rx_first, cfg, d_n_meas,
+                      d_sol, d_chan)
 
     def glo_ephemeris(self, bits, n_strings, first_mark) -> np.ndarray:
         """GLONASS L1OF: bits [n_ch, 15, 85], n_strings [n_ch] and first_mark [n_ch] as
         glo_strings returns them -> GLO_EPH [n_ch] (ephemeris.sci:25-98; status GLO_EPH_*)."""
-        bits = np.ascontiguousarray(bits, np.uint8).reshape(-1, 15, 85)
-        n_ch = bits.shape[0]
-        n_strings = np.ascontiguousarray(n_strings, np.int32).reshape(n_ch)
-        first = np.ascontiguousarray(first_mark, np.int32).reshape(n_ch)
-        eph = np.zeros(n_ch, GLO_EPH)
-        _check(self._glo_ephemeris(self.h, _ptr(bits), _ptr(n_strings), _ptr(first), n_ch,
-                                   _ptr(eph)), self._glo_ephemeris)
-        return eph
+        return self._ephemeris(self._glo_ephemeris, (15, 85), GLO_EPH, bits, n_strings,
+                               first_mark)
 
     def glo_ephemeris_dev(self, d_bits, d_n_strings, d_first_mark, n_ch, d_eph):
         _check(self._glo_ephemeris_dev(self.h, d_bits, d_n_strings, d_first_mark, n_ch, d_eph),
@@ -1474,43 +1482,20 @@ class NavCtx(_Handle):
         rx_first [n_rx + 1] channel offsets.  Returns n_meas [n_rx], sol GPS_FIX_SOL
         [n_rx, max_meas] and chan GPS_FIX_CHAN [n_ch, max_meas]; rows past n_meas keep what
         sol and chan held (zeros by default)."""
-        eph = np.ascontiguousarray(eph, GLO_EPH).ravel()
-        n_ch = eph.size
-        sat = np.ascontiguousarray(sat, GLO_SAT).reshape(n_ch)
-        first = np.ascontiguousarray(first_mark, np.int32).reshape(n_ch)
-        series, cs, n_ep, _ = self._series(abs_sample)
-        assert series.shape[0] == n_ch
-        rx_first = np.ascontiguousarray(rx_first, np.int32).ravel()
-        n_rx = rx_first.size - 1
-        n_meas = np.zeros(n_rx, np.int32) if n_meas is None else n_meas
-        sol = np.zeros((n_rx, cfg.max_meas), GPS_FIX_SOL) if sol is None else sol
-        chan = np.zeros((n_ch, cfg.max_meas), GPS_FIX_CHAN) if chan is None else chan
-        _check(self._glo_fix(self.h, _ptr(eph), _ptr(sat), _ptr(first), _ptr(series), 8, cs,
-                             n_ep, n_rx, _ptr(rx_first), C.addressof(cfg), _ptr(n_meas),
-                             _ptr(sol), _ptr(chan)), self._glo_fix)
-        return n_meas, sol, chan
+        return self._fix_host(self._glo_fix, GLO_EPH, eph, ((sat, GLO_SAT),), first_mark,
+                              abs_sample, rx_first, cfg, n_meas, sol, chan)
 
     def glo_fix_dev(self, d_eph, d_sat, d_first_mark, d_abs_sample, epoch_stride_bytes,
                     chan_stride_bytes, n_epochs, rx_first, cfg, d_n_meas, d_sol, d_chan):
         """rx_first: a host int32 array of n_rx + 1 offsets (checked before the launch)."""
-        rx_first = np.ascontiguousarray(rx_first, np.int32).ravel()
-        _check(self._glo_fix_dev(self.h, d_eph, d_sat, d_first_mark, d_abs_sample,
-                                 epoch_stride_bytes, chan_stride_bytes, n_epochs,
-                                 rx_first.size - 1, _ptr(rx_first),
-                                 C.addressof(cfg) if cfg is not None else None, d_n_meas, d_sol,
-                                 d_chan), self._glo_fix_dev)
+        self._fix_dev(self._glo_fix_dev, (d_eph, d_sat, d_first_mark), d_abs_sample,
+                      epoch_stride_bytes, chan_stride_bytes, n_epochs, rx_first, cfg, d_n_meas,
+                      d_sol, d_chan)
 
     def b1_ephemeris(self, bits, n_subframes, first) -> np.ndarray:
         """BeiDou B1I: bits [n_ch, 5, 213], n_subframes [n_ch] and first [n_ch] as
         b1_subframes returns them -> B1_EPH [n_ch] (ephemeris.sci:28-123; status B1_EPH_*)."""
-        bits = np.ascontiguousarray(bits, np.uint8).reshape(-1, 5, 213)
-        n_ch = bits.shape[0]
-        n_subframes = np.ascontiguousarray(n_subframes, np.int32).reshape(n_ch)
-        first = np.ascontiguousarray(first, np.int32).reshape(n_ch)
-        eph = np.zeros(n_ch, B1_EPH)
-        _check(self._b1_ephemeris(self.h, _ptr(bits), _ptr(n_subframes), _ptr(first), n_ch,
-                                  _ptr(eph)), self._b1_ephemeris)
-        return eph
+        return self._ephemeris(self._b1_ephemeris, (5, 213), B1_EPH, bits, n_subframes, first)
 
     def b1_ephemeris_dev(self, d_bits, d_n_subframes, d_first, n_ch, d_eph):
         _check(self._b1_ephemeris_dev(self.h, d_bits, d_n_subframes, d_first, n_ch, d_eph),
@@ -1521,74 +1506,51 @@ class NavCtx(_Handle):
         (SGT_EPOCH absoluteSample), rx_first [n_rx + 1] channel offsets, cfg from b1_fix_cfg.
         Returns n_meas [n_rx], sol GPS_FIX_SOL [n_rx, max_meas] and chan GPS_FIX_CHAN
         [n_ch, max_meas]; rows past n_meas keep what sol and chan held (zeros by default)."""
-        eph = np.ascontiguousarray(eph, B1_EPH).ravel()
-        n_ch = eph.size
-        first = np.ascontiguousarray(first, np.int32).reshape(n_ch)
-        series, cs, n_ep, _ = self._series(abs_sample)
-        assert series.shape[0] == n_ch
-        rx_first = np.ascontiguousarray(rx_first, np.int32).ravel()
-        n_rx = rx_first.size - 1
-        n_meas = np.zeros(n_rx, np.int32) if n_meas is None else n_meas
-        sol = np.zeros((n_rx, cfg.max_meas), GPS_FIX_SOL) if sol is None else sol
-        chan = np.zeros((n_ch, cfg.max_meas), GPS_FIX_CHAN) if chan is None else chan
-        _check(self._b1_fix(self.h, _ptr(eph), _ptr(first), _ptr(series), 8, cs, n_ep, n_rx,
-                            _ptr(rx_first), C.addressof(cfg), _ptr(n_meas), _ptr(sol),
-                            _ptr(chan)), self._b1_fix)
-        return n_meas, sol, chan
+        return self._fix_host(self._b1_fix, B1_EPH, eph, (), first, abs_sample, rx_first, cfg,
+                              n_meas, sol, chan)
 
     def b1_fix_dev(self, d_eph, d_first, d_abs_sample, epoch_stride_bytes, chan_stride_bytes,
                    n_epochs, rx_first, cfg, d_n_meas, d_sol, d_chan):
         """rx_first: a host int32 array of n_rx + 1 offsets (checked before the launch)."""
-        rx_first = np.ascontiguousarray(rx_first, np.int32).ravel()
-        _check(self._b1_fix_dev(self.h, d_eph, d_first, d_abs_sample, epoch_stride_bytes,
-                                chan_stride_bytes, n_epochs, rx_first.size - 1, _ptr(rx_first),
-                                C.addressof(cfg) if cfg is not None else None, d_n_meas, d_sol,
-                                d_chan), self._b1_fix_dev)
+        self._fix_dev(self._b1_fix_dev, (d_eph, d_first), d_abs_sample, epoch_stride_bytes,
+                      chan_stride_bytes, n_epochs, rx_first, cfg, d_n_meas, d_sol, d_chan)
+
+
+def _fix_cfg(name, struct, allowed, max_meas, kw):
+    cfg = struct()
+    getattr(lib(), f"gnsscorr_nav_{name}_init")(C.byref(cfg))
+    cfg.max_meas = int(max_meas)
+    for k, v in kw.items():
+        if k not in allowed:
+            raise GnssCorrError(f"{name}: unknown setting {k!r}")
+        setattr(cfg, k, v)
+    return cfg
 
 
 def gps_fix_cfg(max_meas=1, **kw) -> GpsFixCfg:
     """GPS/L1/initSettings.sci:103-125 defaults (samplesPerCode 16000, startOffset 68.802,
     c 299792458, navSolPeriod 500, elevationMask 10, useTropCorr 1); keyword overrides use
     the Scilab names."""
-    cfg = GpsFixCfg()
-    lib().gnsscorr_nav_gps_fix_cfg_init(C.byref(cfg))
-    cfg.max_meas = int(max_meas)
-    for k, v in kw.items():
-        if k not in ("samplesPerCode", "startOffset", "c", "elevationMask", "navSolPeriod",
-                     "useTropCorr"):
-            raise GnssCorrError(f"gps_fix_cfg: unknown setting {k!r}")
-        setattr(cfg, k, v)
-    return cfg
+    return _fix_cfg("gps_fix_cfg", GpsFixCfg, ("samplesPerCode", "startOffset", "c",
+                                               "elevationMask", "navSolPeriod", "useTropCorr"),
+                    max_meas, kw)
 
 
 def glo_fix_cfg(max_meas=1, **kw) -> GloFixCfg:
     """GLONASS/L1/initSettings.sci:59-136 defaults (samplesPerCode 16000, dataTypeSizeInBytes
     1, c 299792458, navSolPeriod 500, elevationMask 0, useTropCorr 1); keyword overrides use
     the Scilab names."""
-    cfg = GloFixCfg()
-    lib().gnsscorr_nav_glo_fix_cfg_init(C.byref(cfg))
-    cfg.max_meas = int(max_meas)
-    for k, v in kw.items():
-        if k not in ("samplesPerCode", "dataTypeSizeInBytes", "c", "elevationMask",
-                     "navSolPeriod", "useTropCorr"):
-            raise GnssCorrError(f"glo_fix_cfg: unknown setting {k!r}")
-        setattr(cfg, k, v)
-    return cfg
+    return _fix_cfg("glo_fix_cfg", GloFixCfg, ("samplesPerCode", "dataTypeSizeInBytes", "c",
+                                               "elevationMask", "navSolPeriod", "useTropCorr"),
+                    max_meas, kw)
 
 
 def b1_fix_cfg(max_meas=1, **kw) -> B1FixCfg:
     """COMPASS/B1/initSettings.sci defaults (samplesPerCode 16000, dataTypeSizeInBytes 1,
     c 299792458, navSolPeriod 500, useTropCorr 0; the receiver has no elevation mask);
     keyword overrides use the Scilab names."""
-    cfg = B1FixCfg()
-    lib().gnsscorr_nav_b1_fix_cfg_init(C.byref(cfg))
-    cfg.max_meas = int(max_meas)
-    for k, v in kw.items():
-        if k not in ("samplesPerCode", "dataTypeSizeInBytes", "c", "navSolPeriod",
-                     "useTropCorr"):
-            raise GnssCorrError(f"b1_fix_cfg: unknown setting {k!r}")
-        setattr(cfg, k, v)
-    return cfg
+    return _fix_cfg("b1_fix_cfg", B1FixCfg, ("samplesPerCode", "dataTypeSizeInBytes", "c",
+                                             "navSolPeriod", "useTropCorr"), max_meas, kw)
 
 
 # ---------------------------------------------------------------- GPS-SDR integer acquisition

@@ -7,13 +7,9 @@ import numpy as np
 import pytest
 
 import navglo_scenarios as S
+from nav_fix_gpu_util import check_records, fix_dev, poison as _poison
 
 pytestmark = pytest.mark.gpu
-PAD = 3              # epochs of padding after every channel's absoluteSample: NaN, never read
-
-
-def _poison(n, dtype):
-    return np.full(n * np.dtype(dtype).itemsize, 0xAA, np.uint8)
 
 
 # ------------------------------------------------------------------ stage 1
@@ -73,58 +69,23 @@ def test_satpos_equals_the_restatement(gpu, period, n_ch):
 # ------------------------------------------------------------------ stage 3
 def _fix_dev(gc, nav, s, in_place=False):
     """-> sat, n_meas, sol, chan and the poisoned arrays they started from"""
-    n_ch, n_ep = s["abs_sample"].shape
-    n_rx, mm = len(s["rx_first"]) - 1, s["cfg"]["max_meas"]
-    if in_place:                                               # gnsscorr_sgt_epoch records
-        ep = np.zeros((n_ch, n_ep), gc.SGT_EPOCH)
-        for f in gc.SGT_EPOCH.names:
-            if gc.SGT_EPOCH[f].kind == "f":
-                ep[f] = np.nan
-        ep["absoluteSample"] = s["abs_sample"]
-        d_x = gc.DevBuf.from_array(ep)
-        off, es = gc.epoch_field(gc.SGT_EPOCH, "absoluteSample")
-        ptr, cs = d_x.ptr + off, n_ep * es
-    else:
-        padded = np.full((n_ch, n_ep + PAD), np.nan)
-        padded[:, :n_ep] = s["abs_sample"]
-        d_x = gc.DevBuf.from_array(padded)
-        ptr, es, cs = d_x.ptr, 8, padded.strides[0]
-    d_eph = gc.DevBuf.from_array(s["eph"])
-    d_first = gc.DevBuf.from_array(s["first"])
+    n_ch = len(s["eph"])
     d_sat = gc.DevBuf.from_array(_poison(n_ch, gc.GLO_SAT))
-    p_n, p_sol, p_chan = _poison(n_rx, np.int32), _poison(n_rx * mm, gc.GPS_FIX_SOL), \
-        _poison(n_ch * mm, gc.GPS_FIX_CHAN)
-    d_n, d_sol, d_chan = (gc.DevBuf.from_array(a) for a in (p_n, p_sol, p_chan))
     cfg = gc.glo_fix_cfg(**s["cfg"])
-    nav.glo_satpos_dev(d_eph.ptr, n_ch, cfg, d_sat.ptr)
-    nav.glo_fix_dev(d_eph.ptr, d_sat.ptr, d_first.ptr, ptr, es, cs, n_ep, s["rx_first"], cfg,
-                    d_n.ptr, d_sol.ptr, d_chan.ptr)
-    nav.sync()
-    return (d_sat.download(gc.GLO_SAT), d_n.download(np.int32),
-            d_sol.download(gc.GPS_FIX_SOL).reshape(n_rx, mm),
-            d_chan.download(gc.GPS_FIX_CHAN).reshape(n_ch, mm),
-            p_sol.view(gc.GPS_FIX_SOL).reshape(n_rx, mm), p_chan.view(gc.GPS_FIX_CHAN).reshape(n_ch, mm))
 
-
-def _check_records(name, want, n_meas, sol, chan, p_sol):
-    w_n, want_sol, want_chan, written = want
-    assert n_meas.tolist() == w_n.tolist(), name
-    for k in ("status", "n_used"):
-        assert np.array_equal(sol[k], want_sol[k]), (name, k)
-    assert np.array_equal(chan["used"], want_chan["used"]), name
-    assert chan["rawP"].tobytes() == want_chan["rawP"].tobytes(), name
-    assert sol[~written].tobytes() == p_sol[~written].tobytes(), name     # rows past n_meas
-    for g in S.GROUPS:
-        dist = S.group_distance((sol, chan), (want_sol, want_chan), g)
-        print(name, g, dist, S.TOL[g])
-        assert dist <= S.TOL[g], (name, g, dist, S.TOL[g])
+    def launch(d_eph, d_first, *series_and_outputs):
+        nav.glo_satpos_dev(d_eph, n_ch, cfg, d_sat.ptr)
+        nav.glo_fix_dev(d_eph, d_sat.ptr, d_first, *series_and_outputs[:4], s["rx_first"], cfg,
+                        *series_and_outputs[4:])
+    out = fix_dev(gc, nav, s, launch, in_place)
+    return (d_sat.download(gc.GLO_SAT), *out)
 
 
 def _check_fix(name, s, sat, n_meas, sol, chan, p_sol, p_chan):
     _check_sat(sat, S.scene_sat(name), name)
     w_n, Sx, Cx = S.literal_result(name)
     want_sol, want_chan = S.G.as_records(w_n, Sx, Cx, p_sol, p_chan)
-    _check_records(name, (w_n, want_sol, want_chan, Sx["written"]), n_meas, sol, chan, p_sol)
+    check_records(S, name, (w_n, want_sol, want_chan, Sx["written"]), n_meas, sol, chan, p_sol)
     unwritten = np.repeat(~Sx["written"], np.diff(s["rx_first"]), axis=0)
     assert chan[unwritten].tobytes() == p_chan[unwritten].tobytes(), name
 
@@ -191,7 +152,7 @@ def test_strings_to_fix_chain_on_device_buffers(gpu):
     w_n, Sx, Cx = S.fix_literal(w_eph, first, s["abs_sample"], s["rx_first"], s["cfg"], sat=lit_sat)
     want_sol, want_chan = S.G.as_records(w_n, Sx, Cx, p_sol, p_chan)
     assert n_meas.tolist() == [mm] and not sol["status"].any()
-    _check_records("chain", (w_n, want_sol, want_chan, Sx["written"]), n_meas, sol, chan, p_sol)
+    check_records(S, "chain", (w_n, want_sol, want_chan, Sx["written"]), n_meas, sol, chan, p_sol)
     err = np.linalg.norm(np.array([sol["X"][0], sol["Y"][0], sol["Z"][0]]).T - s["planted"][0],
                          axis=1)
     print("chain: distance to the planted receiver", err)
