@@ -45,9 +45,10 @@ def fix_dev(gc, nav, s, launch, in_place=False):
             p_sol.view(gc.GPS_FIX_SOL).reshape(n_rx, mm), p_chan.view(gc.GPS_FIX_CHAN).reshape(n_ch, mm))
 
 
-def check_records(S, name, want, n_meas, sol, chan, p_sol):
-    """S: the scenario module whose GROUPS, TOL and group_distance hold the records to
-    want = (n_meas, sol, chan, written)"""
+def check_records(S, name, want, n_meas, sol, chan, p_sol, tol=None):
+    """S: the scenario module whose GROUPS, TOL (or the table tol) and group_distance hold the
+    records to want = (n_meas, sol, chan, written)"""
+    tol = S.TOL if tol is None else tol
     w_n, want_sol, want_chan, written = want
     assert n_meas.tolist() == w_n.tolist(), name
     for k in ("status", "n_used"):
@@ -57,5 +58,5 @@ def check_records(S, name, want, n_meas, sol, chan, p_sol):
     assert sol[~written].tobytes() == p_sol[~written].tobytes(), name     # rows past n_meas
     for g in S.GROUPS:
         dist = S.group_distance((sol, chan), (want_sol, want_chan), g)
-        print(name, g, dist, S.TOL[g])
-        assert dist <= S.TOL[g], (name, g, dist, S.TOL[g])
+        print(name, g, dist, tol[g])
+        assert dist <= tol[g], (name, g, dist, tol[g])

@@ -24,6 +24,10 @@ mutant= switches plant one mistake each, a mistake a kernel could plausibly make
     "mask"         the elevation mask of 10 degrees applied as the GPS receiver does
     "alpha3_own_sign", "beta1_own_sign"   the fields' own sign bits instead of bits 88 / 120
     "e_unsigned"   e read without the subtraction
+    "togeod_abs_z", "cart2geo_abs_z", "cart2geo_atan_y_over_x"   fabs(Z) for Z, and atan(Y / X)
+                   for atan(Y, X) in the longitude (the world scene)
+    "check_t_identity"   check_t returning its argument (the week scenes)
+    "kepler_20"    the Kepler loop capped at 20 steps in place of 10 (the eccentric scene)
 
 Tolerances.  SPREAD is the largest |literal in float64 - literal in longdouble| per output
 group over every scene and measurement of SCENES and of many_rx_scene(); TOL = 16 * SPREAD.
@@ -78,6 +82,7 @@ FIELDS = {
 SIGNED = tuple(k for k, v in FIELDS.items() if v[3])
 EPH_MUTANTS = ("alpha3_own_sign", "beta1_own_sign", "e_unsigned")
 FIX_MUTANTS = ("gps_consts", "start_offset", "obs_sign", "mask")
+GEO_MUTANTS = ("togeod_abs_z", "cart2geo_abs_z", "cart2geo_atan_y_over_x")
 
 
 def field_len(name):
@@ -180,26 +185,30 @@ def settings(**kw):
 check_t, _rem, _atand = G.check_t, G._rem, G._atand
 
 
-def satpos_literal(T, transmitTime, e, mutant=None):
+def satpos_literal(T, transmitTime, e, mutant=None, trace=None):
     """satpos.sci:53-136 for one satellite; e: a mapping of float64 fields.
-    Returns (x, y, z, satClkCorr) and the |dE| of every step of the Kepler loop."""
+    Returns (x, y, z, satClkCorr) and the |dE| of every step of the Kepler loop.  trace: a
+    list that receives (time - t_oe, tk), the argument and the value of check_t at :69."""
     BDPi = T(BD_PI)
+    chk = (lambda T, t: t) if mutant == "check_t_identity" else check_t
     Omegae_dot, GM, F = T(7.2921150e-5), T(3.986004418e14), T(-4.442807633e-10)   # :34-37
     if mutant == "gps_consts":
         Omegae_dot, GM = T(7.2921151467e-5), T(3.986005e14)
     g = lambda k: T(e[k])
-    dt = check_t(T, transmitTime - g("t_oc"))                  # :53
+    dt = chk(T, transmitTime - g("t_oc"))                      # :53
     satClkCorr = (g("a2") * dt + g("a1")) * dt + g("a0") - g("T_GD_1")   # :56-58
     time = transmitTime - satClkCorr                           # :61
     a = g("sqrtA") * g("sqrtA")                                # :66
-    tk = check_t(T, time - g("t_oe"))                          # :69
+    tk = chk(T, time - g("t_oe"))                              # :69
+    if trace is not None:
+        trace.append((time - g("t_oe"), tk))
     n0 = np.sqrt(GM / (a * a * a))                             # :72
     n = n0 + g("deltan")                                       # :74
     M = g("M_0") + n * tk                                      # :77
     M = _rem(T, M + 2 * BDPi, 2 * BDPi)                        # :79
     E = M                                                      # :82
     steps = []
-    for ii in range(10):                                       # :85-93
+    for ii in range(20 if mutant == "kepler_20" else 10):      # :85-93
         E_old = E
         E = M + g("e") * np.sin(E)
         dE = _rem(T, E - E_old, 2 * BDPi)
@@ -283,10 +292,12 @@ def fix_literal(eph, first, abs_sample, rx_first, cfg, T=np.float64, mutant=None
                 sp = []
                 for ch in active:                              # :175-177
                     s, dE = satpos_literal(T, transmitTime, {k: eph[k][ch] for k in SAT_FIELDS},
-                                           mutant)
+                                           mutant,
+                                           None if diag is None else diag.setdefault("tk", []))
                     sp.append(s)
                     if diag is not None:
                         diag["dE"].extend(dE)
+                        diag.setdefault("kepler", []).append((len(dE), float(dE[-1])))
                 S["written"][rx, m] = True
                 S["n_used"][rx, m] = len(active)
                 if len(active) > 3:                            # :183
@@ -294,7 +305,8 @@ def fix_literal(eph, first, abs_sample, rx_first, cfg, T=np.float64, mutant=None
                     obs = [Cn["rawP"][ch, m] + sign * (s[3] * c) for ch, s in zip(active, sp)]
                     if diag is not None:
                         diag["togeod"] = []
-                    r = GL.lsq_literal(T, sp, obs, c, cfg["useTropCorr"], None, 7, diag)   # :186
+                    geo = mutant if mutant in GEO_MUTANTS else None
+                    r = GL.lsq_literal(T, sp, obs, c, cfg["useTropCorr"], geo, 7, diag)   # :186
                     if r is None:                              # the library's widening
                         S["status"][rx, m] = FIX_RANK
                         for k in ("X", "Y", "Z", "dt", "lat", "lon", "height"):
@@ -311,7 +323,7 @@ def fix_literal(eph, first, abs_sample, rx_first, cfg, T=np.float64, mutant=None
                         for ch, s in zip(active, sp):          # :212-214
                             Cn["corrP"][ch, m] = Cn["rawP"][ch, m] - s[3] * c + pos[3]
                         S["lat"][rx, m], S["lon"][rx, m], S["height"][rx, m] = \
-                            GL.cart2geo_literal(T, pos[0], pos[1], pos[2])     # :219-225
+                            GL.cart2geo_literal(T, pos[0], pos[1], pos[2], geo)   # :219-225
                         if diag is not None:
                             diag.setdefault("elev", []).extend(el)
                             diag.setdefault("togeod_all", []).extend(diag["togeod"])
@@ -635,15 +647,22 @@ _elevation, _near, _gdop = G._elevation, G._near, G._gdop
 WEEK = 604800
 
 
-def draw_satellite(rng, tow, toe, pos, el_lo, el_hi, span=4.0):
+def draw_satellite(rng, tow, toe, pos, el_lo, el_hi, span=4.0, e=(0.001, 0.01), i_0=None,
+                   geo=False):
     """a BeiDou-like orbit, MEO (sqrtA near 5282) or IGSO (near 6493), on the message's grid,
     whose elevation from pos at tow lies in [el_lo, el_hi] and whose Kepler loop, at tow and
-    `span` seconds on, takes no step with |dE| within a factor 4 of its 1e-12 exit.  Returns
-    the raw integers and the position at tow."""
+    `span` seconds on, takes no step with |dE| within a factor 4 of its 1e-12 exit.  e, i_0:
+    the ranges the eccentricity and the inclination [rad] are drawn from (i_0 None: 0.96 +-
+    0.03); from e = 0.1 on only orbits whose loop runs all 10 steps are kept.  geo: a GEO-like
+    orbit, sqrtA near 6493.4 with i_0 in 0 .. 0.1 rad and e below 0.001.  Returns the raw
+    integers and the position at tow."""
+    if geo:
+        e, i_0 = (0.0001, 0.001), (0.0, 0.1)
     while True:
-        igso = bool(rng.integers(0, 2))
+        igso = bool(rng.integers(0, 2)) or geo
         vals = dict(sqrtA=(6493.4 if igso else 5282.6) + rng.uniform(-0.5, 0.5),
-                    e=rng.uniform(0.001, 0.01), i_0=0.96 + rng.uniform(-0.03, 0.03),
+                    e=rng.uniform(*e),
+                    i_0=0.96 + rng.uniform(-0.03, 0.03) if i_0 is None else rng.uniform(*i_0),
                     omega_0=rng.uniform(-PI, PI), omega=rng.uniform(-PI, PI),
                     M_0=rng.uniform(-PI, PI), deltan=rng.uniform(1e-9, 4e-9),
                     omegaDot=rng.uniform(-8e-9, -2e-9), iDot=rng.uniform(-5e-10, 5e-10),
@@ -655,6 +674,8 @@ def draw_satellite(rng, tow, toe, pos, el_lo, el_hi, span=4.0):
         v = raw_to_values(raw)
         s, dE = satpos_literal(np.float64, np.float64(tow), v)
         dE2 = satpos_literal(np.float64, np.float64(tow + span), v)[1]
+        if e[0] >= 0.1 and not (G.full_kepler_loop(dE) and G.full_kepler_loop(dE2)):
+            continue
         if el_lo <= _elevation(pos, s) <= el_hi and not _near(dE + dE2, 1e-12):
             return raw, s
 
@@ -691,7 +712,7 @@ def plant_abs_samples(eph, first, chans, tow, pos, cfg, n_epochs, n_meas, trop, 
 
 def make_fix_scene(seed, sizes, n_epochs=200, period=20, max_meas=7, trop=0, low=(), no_sf=(),
                    no_sow=(), not_ready=(), odd_sow=(), clone=(), first_lo=0, first_hi=15,
-                   week=None):
+                   week=None, sites=None, e=(0.001, 0.01), i_0=None, geo=(), rx_seeds=None):
     """sizes: channels per receiver.  low: {receiver: number of satellites between 3 and 7
     degrees} (its last lanes; used all the same, the receiver has no mask).  no_sf: (receiver,
     lane, ID) whose frame lacks the subframe with that ID; no_sow / not_ready: (receiver, lane)
@@ -699,7 +720,11 @@ def make_fix_scene(seed, sizes, n_epochs=200, period=20, max_meas=7, trop=0, low
     600 s off the others'; clone: receivers in which every channel carries channel 0's
     ephemeris and absoluteSample (rank 1).  week: "start" puts SOW near the start of the week
     with t_oe and t_oc at the end of the week before (check_t adds a week), "end" the other way
-    round (check_t subtracts one)."""
+    round (check_t subtracts one).  sites: (latitude, longitude) in degrees per receiver, in
+    place of RX_ECEF; the 200 km of jitter and the rescaling to 6371 km stay.  e, i_0:
+    draw_satellite's ranges.  geo: {receiver: number of GEO-like satellites}, its first lanes.  rx_seeds: a seed per receiver for its own
+    generator (jitter, satellites, frame filler) in place of the scene's, so that one
+    receiver's draw can be searched with the others kept."""
     rng = np.random.default_rng(seed)
     cfg = settings(navSolPeriod=period, max_meas=max_meas, useTropCorr=trop)
     rx_first = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
@@ -715,15 +740,19 @@ def make_fix_scene(seed, sizes, n_epochs=200, period=20, max_meas=7, trop=0, low
         sow = 6 * int(rng.integers(2000, 90000))
         toe = sow - sow % 3600 + (3600 if rng.integers(0, 2) else 0)
     missing = {(r, l): i for r, l, i in no_sf}
+    scene_rng = rng
     for rx, size in enumerate(sizes):
-        pos = np.array(RX_ECEF) + rng.uniform(-2e5, 2e5, 3)
+        rng = scene_rng if rx_seeds is None else np.random.default_rng(rx_seeds[rx])
+        pos = (np.array(RX_ECEF) if sites is None else G.site_ecef(sites[rx])) + \
+            rng.uniform(-2e5, 2e5, 3)
         pos *= 6371000.0 / np.linalg.norm(pos)
         planted.append(pos)
-        n_low = dict(low).get(rx, 0)
+        n_low, n_geo = dict(low).get(rx, 0), dict(geo).get(rx, 0)
         bad = [(r, l) for r, l in (*missing, *no_sow, *not_ready) if r == rx]
         while True:                                            # a geometry with GDOP < 5
             drawn = [draw_satellite(rng, sow, toe, pos, *((3.0, 7.0) if lane >= size - n_low
-                                                          else (18.0, 85.0))) for lane in range(size)]
+                                                          else (18.0, 85.0)), e=e, i_0=i_0,
+                                    geo=lane < n_geo) for lane in range(size)]
             use = [lane for lane in range(size) if (rx, lane) not in bad]
             if len(use) < 4 or rx in clone:
                 break
@@ -781,9 +810,31 @@ SCENES = {
 }
 
 
+# the scenes that reach what SCENES does not: one receiver at every site of
+# navfix_scenarios.SITES in one launch, Kepler loops that leave by the cap, and GEO-like orbits
+# among MEO and IGSO ones seen from (20 N, 110 E).  eccentric and geo: the seed is the first
+# tried; the scene passes conditions_hold and shows what it is named for
+# (navfix_scenarios.search_seed).  world: in this least-squares text the first togeod call of a
+# fix, on the position after one step from the origin, leaves its loop at 3e-11 to 1e-10 at
+# sites between 12 and 22 degrees of latitude unless the geometry makes it take one step more,
+# about one draw in three; so every receiver has a seed of its own, the first of 1000 rx + 0,
+# 1, .. at which it passes alone (navfix_scenarios.search_rx_seeds: the second for S-E, the
+# fourth for the western side of the 180 degree meridian, the first for the rest).  No site
+# was moved.  useTropCorr is one setting per launch: on for all eleven.  e stops at 0.24
+# where the GPS scene goes to 0.3: the file reads the 32-bit field as signed, which ends at 0.25.
+WORLD_SCENES = {
+    "world": (dict(seed=100, sizes=G.WORLD_SIZES, max_meas=2, trop=1, sites=G.world_sites(),
+                   rx_seeds=(0, 1001, 2000, 3000, 4003, 5000, 6000, 7000, 8000, 9000, 10000)),
+              True),
+    "eccentric": (dict(seed=400, sizes=(6,), max_meas=2, e=(0.1, 0.24)), True),
+    "geo": (dict(seed=600, sizes=(8,), max_meas=2, trop=1, sites=((20.0, 110.0),), geo={0: 3}),
+            True),
+}
+
+
 @functools.lru_cache(None)
 def fix_scene(name):
-    return make_fix_scene(**SCENES[name][0])
+    return make_fix_scene(**(SCENES.get(name) or WORLD_SCENES[name])[0])
 
 
 @functools.lru_cache(None)
@@ -794,7 +845,7 @@ def many_rx_scene(n_rx=65, seed=21):
 
 
 def _scene(name):
-    return fix_scene(name) if name in SCENES else many_rx_scene()
+    return many_rx_scene() if name == "many" else fix_scene(name)
 
 
 @functools.lru_cache(None)
@@ -813,7 +864,7 @@ def scene_diagnostics(s):
     diag = {"dE": []}
     fix_literal(s["eph"], s["first"], s["abs_sample"], s["rx_first"], s["cfg"], diag=diag)
     return {k: np.array(diag.get(k, []), np.float64)
-            for k in ("cond", "gdop", "elev", "dE", "togeod_all")}
+            for k in ("cond", "gdop", "elev", "dE", "togeod_all", "tk", "kepler")}
 
 
 def conditions_hold(s, full_rank=True):
@@ -878,12 +929,17 @@ SPREAD = {"xyz": 2.044e-07, "dt": 1.258e-07, "dop": 1.332e-13, "latlon": 1.561e-
           "height": 1.932e-07, "elaz": 4.399e-12, "corrP": 1.570e-07}
 TOL = {k: 16 * v for k, v in SPREAD.items()}
 
+# the same over WORLD_SCENES alone, from `python tests/navb1_scenarios.py world`
+SPREAD_WORLD = {"xyz": 1.001e-07, "dt": 6.779e-08, "dop": 4.881e-14, "latlon": 1.813e-12,
+                "height": 9.244e-08, "elaz": 1.820e-12, "corrP": 1.033e-07}
+TOL_WORLD = {k: 16 * v for k, v in SPREAD_WORLD.items()}
+
 group_distance = G.group_distance
 
 
-def measure_spread():
+def measure_spread(names=tuple(SCENES) + ("many",)):
     out = {g: 0.0 for g in GROUPS}
-    for name in tuple(SCENES) + ("many",):
+    for name in names:
         _, S64, C64 = literal_result(name, np.float64)
         _, SL, CL = literal_result(name, np.longdouble)
         for g in GROUPS:
@@ -891,6 +947,37 @@ def measure_spread():
     return out
 
 
+def named_for_missed(name, s):
+    """what the scene `name` of WORLD_SCENES is named for and s does not show, from the literal
+    restatement in float64 (an empty list: it shows all of it).  Every receiver is solved at
+    every measurement; no check_t wraps; world: navfix_scenarios.site_classes_missed;
+    eccentric: every Kepler loop ran 10 steps and left by the cap with |dE| > 4e-12; geo: three
+    orbits with sqrtA above 6000, i_0 below 0.1 rad and e below 0.001, a MEO and an IGSO one"""
+    diag = {"dE": []}
+    n, Sx, Cx = fix_literal(s["eph"], s["first"], s["abs_sample"], s["rx_first"], s["cfg"],
+                            diag=diag)
+    missed = []
+    if not (n == s["cfg"]["max_meas"]).all() or Sx["status"].any() or not Cx["used"].all():
+        missed.append("solved")
+    tk = np.array(diag["tk"], np.float64)
+    if not (tk[:, 1] == tk[:, 0]).all():
+        missed.append("check_t")
+    kep = np.array(diag["kepler"], np.float64)
+    if name == "eccentric" and not ((kep[:, 0] == 10) & (kep[:, 1] > 4e-12)).all():
+        missed.append("kepler")
+    if name == "geo":
+        e = s["eph"]
+        is_geo = (e["sqrtA"] > 6000) & (np.abs(e["i_0"]) < 0.1) & (e["e"] < 0.001)
+        igso = (e["sqrtA"] > 6000) & (e["i_0"] > 0.9)
+        if not (is_geo.sum() == 3 and igso.any() and (e["sqrtA"] < 6000).any()):
+            missed.append("orbits")
+    if name == "world":
+        missed += G.site_classes_missed(Sx["lat"], Sx["lon"])
+    return missed
+
+
 if __name__ == "__main__":
-    for g, v in measure_spread().items():
+    import sys
+    world = sys.argv[1:] == ["world"]
+    for g, v in (measure_spread(tuple(WORLD_SCENES)) if world else measure_spread()).items():
         print(f'"{g}": {v:.3e},')

@@ -19,6 +19,8 @@ Tolerances (fp64 outputs behind transcendental functions).  SPREAD is the larges
 measurement of SCENES and of many_rx_scene(); TOL = 16 * SPREAD.  Produced by
     python tests/navfix_scenarios.py
 and copied here; test_navfix_cpu.py asserts that a fresh measurement does not exceed them.
+SPREAD_WORLD and TOL_WORLD are the same over the scenes of WORLD_SCENES alone
+(`python tests/navfix_scenarios.py world`): other sites, the week's edges, other orbit shapes.
 """
 import functools
 
@@ -208,25 +210,29 @@ def _atand(T, y, x):
     return (T(180) / T(PI)) * np.arctan2(y, x)
 
 
-def satpos_literal(T, transmitTime, e, mutant=None):
+def satpos_literal(T, transmitTime, e, mutant=None, trace=None):
     """satpos.sci:56-145 for one satellite; e: a mapping of float64 fields.
-    Returns (x, y, z, satClkCorr) and the |dE| of every step of the Kepler loop."""
+    Returns (x, y, z, satClkCorr) and the |dE| of every step of the Kepler loop.  trace: a
+    list that receives (time - t_oe, tk), the argument and the value of check_t at :71."""
     gpsPi = T(GPS_PI)
+    chk = (lambda T, t: t) if mutant == "check_t_identity" else check_t
     Omegae_dot, GM, F = T(7.2921151467e-5), T(3.986005e14), T(-4.442807633e-10)
     g = lambda k: T(e[k])
     T_GD = T(0) if mutant == "no_tgd" else g("T_GD")
-    dt = check_t(T, transmitTime - g("t_oc"))                  # :56
+    dt = chk(T, transmitTime - g("t_oc"))                      # :56
     satClkCorr = (g("a_f2") * dt + g("a_f1")) * dt + g("a_f0") - T_GD   # :59-61
     time = transmitTime - satClkCorr                           # :63
     a = g("sqrtA") * g("sqrtA")                                # :68
-    tk = check_t(T, time - g("t_oe"))                          # :71
+    tk = chk(T, time - g("t_oe"))                              # :71
+    if trace is not None:
+        trace.append((time - g("t_oe"), tk))
     n0 = np.sqrt(GM / (a * a * a))                             # :74
     n = n0 + g("deltan")                                       # :76
     M = g("M_0") + n * tk                                      # :79
     M = _rem(T, M + 2 * gpsPi, 2 * gpsPi)                      # :82
     E = M                                                      # :85
     steps = []
-    for ii in range(10):                                       # :88-97
+    for ii in range(20 if mutant == "kepler_20" else 10):      # :88-97
         E_old = E
         E = M + g("e") * np.sin(E)
         dE = _rem(T, E - E_old, 2 * gpsPi)
@@ -252,10 +258,12 @@ def satpos_literal(T, transmitTime, e, mutant=None):
     return (x, y, z, satClkCorr), steps
 
 
-def togeod_literal(T, X, Y, Z):
+def togeod_literal(T, X, Y, Z, mutant=None):
     """togeod.sci:32-113 with a = 6378137, finv = 298.257223563 -> (dphi, dlambda) in degrees
     and the residual dP^2 + dZ^2 at the loop's exit"""
     a, finv, tolsq = T(6378137), T(298.257223563), T(1.e-10)
+    if mutant == "togeod_abs_z":
+        Z = abs(Z)
     rtd = T(180) / T(PI)                                       # :37
     esq = (2 - 1 / finv) / finv                                # :43
     oneesq = 1 - esq
@@ -376,10 +384,20 @@ def ldl_solve(T, f, g):
     return x
 
 
-def cart2geo_literal(T, X, Y, Z):
+def one_argument_atan(T, Y, X):
+    """(Y, X) as the "cart2geo_atan_y_over_x" mutant passes them on to the two-argument form:
+    the quadrant-blind angle atan(Y / X), written as atan(-Y, -X) where X < 0 so that where
+    X > 0 it is the file's own operation, bit for bit"""
+    return (-Y, -X) if X < 0 else (Y, X)
+
+
+def cart2geo_literal(T, X, Y, Z, mutant=None):
     """cart2geo.sci:22-53 with i = 5"""
     a, f = T(6378137), 1 / T(298.257223563)
-    lam = _atand(T, Y, X) / 180 * T(PI)                        # :26
+    if mutant == "cart2geo_abs_z":
+        Z = abs(Z)
+    ly, lx = one_argument_atan(T, Y, X) if mutant == "cart2geo_atan_y_over_x" else (Y, X)
+    lam = _atand(T, ly, lx) / 180 * T(PI)                      # :26
     ex2 = (2 - f) * f / ((1 - f) * (1 - f))
     c = a * np.sqrt(1 + ex2)
     p = np.sqrt(X * X + Y * Y)
@@ -409,7 +427,7 @@ def lsq_literal(T, satpos, obs, c, useTropCorr, mutant=None, n_iter=7, diag=None
         A = [None] * n
         omc = [T(0)] * n
         if it > 1:
-            phi, lam, res = togeod_literal(T, pos[0], pos[1], pos[2])   # topocent.sci:26
+            phi, lam, res = togeod_literal(T, pos[0], pos[1], pos[2], mutant)   # topocent.sci:26
             if diag is not None:
                 diag["togeod"].append(res)
         for i in range(n):                                     # :47
@@ -515,10 +533,12 @@ def fix_literal(eph, first, abs_sample, rx_first, cfg, T=np.float64, mutant=None
                 sp = []
                 for ch in active:                              # :189-191
                     e = {k: eph[k][ch] for k in EPH_FIELDS}
-                    s, dE = satpos_literal(T, transmitTime, e, mutant)
+                    s, dE = satpos_literal(T, transmitTime, e, mutant,
+                                           None if diag is None else diag.setdefault("tk", []))
                     sp.append(s)
                     if diag is not None:
                         diag["dE"].extend(dE)
+                        diag.setdefault("kepler", []).append((len(dE), float(dE[-1])))
                 S["written"][rx, m] = True
                 S["n_used"][rx, m] = len(active)
                 if len(active) > 3:                            # :197
@@ -542,7 +562,7 @@ def fix_literal(eph, first, abs_sample, rx_first, cfg, T=np.float64, mutant=None
                         for ch, s in zip(active, sp):          # :220-222
                             Cn["corrP"][ch, m] = Cn["rawP"][ch, m] + s[3] * c + pos[3]
                         S["lat"][rx, m], S["lon"][rx, m], S["height"][rx, m] = \
-                            cart2geo_literal(T, pos[0], pos[1], pos[2])        # :227-233
+                            cart2geo_literal(T, pos[0], pos[1], pos[2], mutant)   # :227-233
                         if diag is not None:
                             diag.setdefault("elev", []).extend(el)
                             diag.setdefault("togeod_all", []).extend(diag["togeod"])
@@ -991,17 +1011,34 @@ def _gdop(pos, sats):
     return float(np.sqrt(np.trace(np.linalg.inv(A.T @ A))))
 
 
-def draw_satellite(rng, tow, pos, el_lo, el_hi, span=4.0):
+def site_ecef(site):
+    """(latitude, longitude) in degrees -> the point of the 6371 km sphere there"""
+    lat, lon = np.radians(site[0]), np.radians(site[1])
+    return 6371000.0 * np.array([np.cos(lat) * np.cos(lon), np.cos(lat) * np.sin(lon),
+                                 np.sin(lat)])
+
+
+def full_kepler_loop(steps):
+    """the loop ran its 10 steps and left by the cap, its last |dE| a factor 4 above the exit"""
+    return len(steps) == 10 and steps[-1] > 4e-12
+
+
+def draw_satellite(rng, tow, pos, el_lo, el_hi, span=4.0, e=(0.001, 0.02), i_0=None, toe=None):
     """a GPS-like orbit on the ICD grid whose elevation from pos at tow lies in [el_lo, el_hi]
     and whose Kepler loop, at tow and `span` seconds on, takes no step with |dE| within a
-    factor 4 of its 1e-12 exit.  Returns the raw integers and the position at tow."""
+    factor 4 of its 1e-12 exit.  e, i_0: the ranges the eccentricity and the inclination [rad]
+    are drawn from (i_0 None: 0.96 +- 0.03); from e = 0.1 on only orbits whose loop runs all
+    10 steps are kept.  toe: t_oe = t_oc (None: the next 2-hour boundary).  Returns the raw
+    integers and the position at tow."""
+    toe = tow - tow % 7200 + 7200 if toe is None else toe
     while True:
-        vals = dict(sqrtA=5153.6 + rng.uniform(-0.5, 0.5), e=rng.uniform(0.001, 0.02),
-                    i_0=0.96 + rng.uniform(-0.03, 0.03), omega_0=rng.uniform(-PI, PI),
+        vals = dict(sqrtA=5153.6 + rng.uniform(-0.5, 0.5), e=rng.uniform(*e),
+                    i_0=0.96 + rng.uniform(-0.03, 0.03) if i_0 is None else rng.uniform(*i_0),
+                    omega_0=rng.uniform(-PI, PI),
                     omega=rng.uniform(-PI, PI), M_0=rng.uniform(-PI, PI),
                     deltan=rng.uniform(3e-9, 6e-9), omegaDot=rng.uniform(-9e-9, -7e-9),
-                    iDot=rng.uniform(-5e-10, 5e-10), t_oe=tow - tow % 7200 + 7200,
-                    t_oc=tow - tow % 7200 + 7200, a_f0=rng.uniform(-5e-4, 5e-4),
+                    iDot=rng.uniform(-5e-10, 5e-10), t_oe=toe,
+                    t_oc=toe, a_f0=rng.uniform(-5e-4, 5e-4),
                     a_f1=rng.uniform(-1e-11, 1e-11), a_f2=0.0, T_GD=rng.uniform(-2e-8, 2e-8),
                     weekNumber=1024 + int(rng.integers(0, 1024)), IODC=int(rng.integers(0, 1024)),
                     IODE_sf2=int(rng.integers(0, 256)), IODE_sf3=int(rng.integers(0, 256)),
@@ -1010,6 +1047,8 @@ def draw_satellite(rng, tow, pos, el_lo, el_hi, span=4.0):
         raw = values_to_raw(vals)
         s, dE = satpos_literal(np.float64, np.float64(tow), raw_to_values(raw))
         dE2 = satpos_literal(np.float64, np.float64(tow + span), raw_to_values(raw))[1]
+        if e[0] >= 0.1 and not (full_kepler_loop(dE) and full_kepler_loop(dE2)):
+            continue
         if el_lo <= _elevation(pos, s) <= el_hi and not _near(dE + dE2, 1e-12):
             return raw, s
 
@@ -1041,12 +1080,20 @@ def plant_abs_samples(eph, first, chans, tow, pos, cfg, n_epochs, n_meas, trop, 
     return out
 
 
+WEEK = 604800
+
+
 def make_fix_scene(seed, sizes, n_epochs=200, period=20, max_meas=7, trop=1, low=(), no_sf2=(),
-                   not_ready=(), clone=(), first_lo=40, first_hi=55):
+                   not_ready=(), clone=(), first_lo=40, first_hi=55, sites=None, week=None,
+                   e=(0.001, 0.02), i_0=None):
     """sizes: channels per receiver.  low: {receiver: number of satellites between 3 and 7
     degrees}: in the first fix, then out.  no_sf2 / not_ready: (receiver, lane) pairs whose
     frame has no subframe 2 / whose first_subframe is -1.  clone: receivers in which every
-    channel carries channel 0's ephemeris and absoluteSample (rank 1)."""
+    channel carries channel 0's ephemeris and absoluteSample (rank 1).  sites: (latitude,
+    longitude) in degrees per receiver, in place of RX_ECEF; the 200 km of jitter and the
+    rescaling to 6371 km stay.  week: "end" puts TOW into the last 15 minutes of the week with
+    t_oe = t_oc = 0 (check_t subtracts a week), "start" into the first 15 minutes with
+    t_oe = t_oc = 597600 (check_t adds one).  e, i_0: draw_satellite's ranges."""
     rng = np.random.default_rng(seed)
     cfg = settings(navSolPeriod=period, max_meas=max_meas, useTropCorr=trop)
     rx_first = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
@@ -1054,16 +1101,24 @@ def make_fix_scene(seed, sizes, n_epochs=200, period=20, max_meas=7, trop=1, low
     bits = np.zeros((n_ch, 1500), np.uint8)
     first = rng.integers(first_lo, first_hi, n_ch).astype(np.int32)
     planted = []
-    tow_count = int(rng.integers(1000, 90000))
+    toe = None
+    if week == "end":                                          # TOW = 6 count - 6 below
+        tow_count, toe = WEEK // 6 + 1 - int(rng.integers(10, 150)), 0
+    elif week == "start":
+        tow_count, toe = 1 + int(rng.integers(10, 150)), WEEK - 7200
+    else:
+        tow_count = int(rng.integers(1000, 90000))
     tow = tow_count * 6 - 30 + 24                              # the fifth subframe's count is + 4
     for rx, size in enumerate(sizes):
-        pos = np.array(RX_ECEF) + rng.uniform(-2e5, 2e5, 3)
+        pos = (np.array(RX_ECEF) if sites is None else site_ecef(sites[rx])) + \
+            rng.uniform(-2e5, 2e5, 3)
         pos *= 6371000.0 / np.linalg.norm(pos)
         planted.append(pos)
         n_low = dict(low).get(rx, 0)
         while True:                                            # a geometry with GDOP < 5
             drawn = [draw_satellite(rng, tow, pos, *((3.0, 7.0) if lane >= size - n_low
-                                                     else (18.0, 85.0))) for lane in range(size)]
+                                                     else (18.0, 85.0)), e=e, i_0=i_0, toe=toe)
+                     for lane in range(size)]
             use = [lane for lane in range(size)
                    if (rx, lane) not in no_sf2 and (rx, lane) not in not_ready]
             high = [lane for lane in use if lane < size - n_low]
@@ -1119,9 +1174,58 @@ SCENES = {
 }
 
 
+# name: (latitude, longitude) the receiver starts from, what its solved latitude and longitude
+# must show.  The two meridians hold two receivers each, and the seed is one whose jitter puts
+# them on either side.  The southern sites stand at 17 S: between 33 S and 37 S togeod's exit
+# residual lies at 0.5 to 1 times its 1e-10 threshold, so one last bit of sin / cos decides
+# the number of its steps there, in the reference itself.
+SITES = {
+    "north_east": ((48.0, 11.0), lambda lat, lon: lat > 0 and lon > 0),
+    "south_east": ((-17.0, 150.0), lambda lat, lon: lat < 0 and lon > 0),
+    "south_west": ((-17.0, -70.0), lambda lat, lon: lat < 0 and lon < 0),
+    "meridian_180_east": ((-17.0, 179.2), lambda lat, lon: lat < 0 and lon > 177),
+    "meridian_180_west": ((-17.0, 179.2), lambda lat, lon: lat < 0 and lon < -177),
+    "meridian_0_west": ((51.0, -0.3), lambda lat, lon: lat > 0 and -3 < lon < 0),
+    "meridian_0_east": ((51.0, -0.3), lambda lat, lon: lat > 0 and 0 < lon < 3),
+    "equator": ((0.4, 101.0), lambda lat, lon: abs(lat) < 2.5 and lon > 0),
+    "arctic": ((84.0, -30.0), lambda lat, lon: lat > 80 and lon < 0),
+    "antarctic": ((-82.0, 70.0), lambda lat, lon: lat < -80 and lon > 0),
+    "control": ((60.0, -53.0), lambda lat, lon: lat > 0 and lon < 0),
+}
+WORLD_SIZES = (6, 5, 7, 4, 5, 8, 5, 6, 4, 7, 5)                # one receiver per site, in order
+
+
+def world_sites(moved=None):
+    """the (latitude, longitude) of SITES in order, with those of `moved` in their place"""
+    return tuple(dict(moved or {}).get(k, v[0]) for k, v in SITES.items())
+
+
+# the scenes that reach what SCENES does not: sites in every quadrant in one launch, the
+# week's two edges, Kepler loops that leave by the cap, inclinations from 0.3 to 1.4 rad.  Every
+# seed is the first, counting up from the hundred it starts with, at which the scene passes
+# conditions_hold and shows what it is named for (search_seed: world took 36 seeds, most of them
+# for the jitter to put the meridians' receivers on either side; inclined 2); no site was moved.
+# useTropCorr is one setting per launch: the troposphere is on for all eleven receivers, and
+# SCENES' "notrop" stays the case without it.
+WORLD_SCENES = {
+    "world": (dict(seed=135, sizes=WORLD_SIZES, max_meas=2, sites=world_sites()), True),
+    "week_end": (dict(seed=200, sizes=(6,), max_meas=2, trop=0, week="end"), True),
+    "week_start": (dict(seed=300, sizes=(5,), max_meas=2, trop=0, week="start"), True),
+    "eccentric": (dict(seed=400, sizes=(6,), max_meas=2, e=(0.1, 0.3)), True),
+    "inclined": (dict(seed=501, sizes=(8,), max_meas=2, i_0=(0.3, 1.4)), True),
+}
+
+
 @functools.lru_cache(None)
 def fix_scene(name):
-    return make_fix_scene(**SCENES[name][0])
+    return make_fix_scene(**(SCENES.get(name) or WORLD_SCENES[name])[0])
+
+
+def site_classes_missed(lat, lon):
+    """the sites of SITES whose class a solved (lat, lon) [n_rx, max_meas] of a world scene
+    does not show"""
+    return [k for (k, (_, rule)), las, los in zip(SITES.items(), lat, lon)
+            if not all(rule(la, lo) for la, lo in zip(las, los))]
 
 
 @functools.lru_cache(None)
@@ -1132,9 +1236,10 @@ def many_rx_scene(n_rx=65, seed=21):
 
 
 @functools.lru_cache(None)
-def literal_result(name, T=np.float64):
-    s = fix_scene(name) if name in SCENES else many_rx_scene()
-    n_meas, S, Cn = fix_literal(s["eph"], s["first"], s["abs_sample"], s["rx_first"], s["cfg"], T)
+def literal_result(name, T=np.float64, mutant=None):
+    s = many_rx_scene() if name == "many" else fix_scene(name)
+    n_meas, S, Cn = fix_literal(s["eph"], s["first"], s["abs_sample"], s["rx_first"], s["cfg"], T,
+                                mutant)
     S["rx_first"] = s["rx_first"]
     return n_meas, S, Cn
 
@@ -1146,7 +1251,7 @@ def scene_diagnostics(s):
     diag = {"dE": []}
     fix_literal(s["eph"], s["first"], s["abs_sample"], s["rx_first"], s["cfg"], diag=diag)
     return {k: np.array(diag.get(k, []), np.float64)
-            for k in ("cond", "gdop", "elev", "dE", "togeod_all")}
+            for k in ("cond", "gdop", "elev", "dE", "togeod_all", "tk", "kepler")}
 
 
 def conditions_hold(s, full_rank=True, mask=10.0):
@@ -1202,6 +1307,11 @@ SPREAD = {"xyz": 2.882e-07, "dt": 1.476e-07, "dop": 1.518e-13, "latlon": 1.843e-
           "height": 2.517e-07, "elaz": 5.777e-12, "corrP": 1.691e-07}
 TOL = {k: 16 * v for k, v in SPREAD.items()}
 
+# the same over WORLD_SCENES alone, from `python tests/navfix_scenarios.py world`
+SPREAD_WORLD = {"xyz": 8.624e-08, "dt": 6.939e-08, "dop": 4.391e-14, "latlon": 1.467e-12,
+                "height": 9.391e-08, "elaz": 2.247e-12, "corrP": 9.004e-08}
+TOL_WORLD = {k: 16 * v for k, v in SPREAD_WORLD.items()}
+
 
 def group_distance(a, b, group):
     """largest |a - b| over a group's fields, NaN and inf patterns required equal; a and b are
@@ -1219,9 +1329,9 @@ def group_distance(a, b, group):
     return worst
 
 
-def measure_spread():
+def measure_spread(names=tuple(SCENES) + ("many",)):
     out = {g: 0.0 for g in GROUPS}
-    for name in tuple(SCENES) + ("many",):
+    for name in names:
         _, S64, C64 = literal_result(name, np.float64)
         _, SL, CL = literal_result(name, np.longdouble)
         for g in GROUPS:
@@ -1229,6 +1339,76 @@ def measure_spread():
     return out
 
 
+def named_for_missed(name, s):
+    """what the scene `name` of WORLD_SCENES is named for and s does not show, from the literal
+    restatement in float64 (an empty list: it shows all of it).  Every receiver is solved at
+    every measurement; world: site_classes_missed; week_end / week_start: check_t took every
+    used channel's time - t_oe down / up by a week; eccentric: every Kepler loop ran 10 steps
+    and left by the cap with |dE| > 4e-12; inclined: inclinations below 0.6 and above 1.2 rad"""
+    diag = {"dE": []}
+    n, Sx, Cx = fix_literal(s["eph"], s["first"], s["abs_sample"], s["rx_first"], s["cfg"],
+                            diag=diag)
+    missed = []
+    if not (n == s["cfg"]["max_meas"]).all() or Sx["status"].any() or not Cx["used"].all():
+        missed.append("solved")
+    tk = np.array(diag["tk"], np.float64)
+    wrap = {"week_end": -WEEK, "week_start": WEEK}.get(name, 0)
+    if not (tk[:, 1] - tk[:, 0] == wrap).all():
+        missed.append("check_t")
+    kep = np.array(diag["kepler"], np.float64)
+    if name == "eccentric" and not ((kep[:, 0] == 10) & (kep[:, 1] > 4e-12)).all():
+        missed.append("kepler")
+    if name == "inclined" and not (s["eph"]["i_0"].min() < 0.6 and s["eph"]["i_0"].max() > 1.2):
+        missed.append("i_0")
+    if name == "world":
+        missed += site_classes_missed(Sx["lat"], Sx["lon"])
+    return missed
+
+
+def search_seed(S, name, start, tries=400, **kw):
+    """S: a scenario module.  The first seed from `start` on at which the scene `name` of
+    S.WORLD_SCENES, with kw in place of its arguments, passes S.conditions_hold and
+    S.named_for_missed is empty"""
+    for seed in range(start, start + tries):
+        s = S.make_fix_scene(**dict(S.WORLD_SCENES[name][0], seed=seed, **kw))
+        if S.conditions_hold(s, full_rank=True) and not S.named_for_missed(name, s):
+            return seed
+    return None
+
+
+def receiver_scene(s, rx):
+    """the scene s cut down to its receiver rx: receivers do not see each other"""
+    a, b = s["rx_first"][rx], s["rx_first"][rx + 1]
+    return dict(s, eph=s["eph"][a:b], first=s["first"][a:b], abs_sample=s["abs_sample"][a:b],
+                rx_first=np.array([0, b - a], np.int32), sizes=(int(b - a),))
+
+
+def search_rx_seeds(S, tries=200, **kw):
+    """for the world scene of a module whose builder takes rx_seeds: per receiver rx the first
+    seed 1000 rx + t, t = 0, 1, .., at which that receiver alone passes S.conditions_hold, is
+    solved at every measurement with every channel used and shows its site's class.  A
+    receiver's draw depends on the scene's seed and its own only, so the seeds found together
+    give the receivers found one by one."""
+    rules = [rule for _, rule in SITES.values()]
+    found = [None] * len(rules)
+    for t in range(tries):
+        s = S.make_fix_scene(**dict(S.WORLD_SCENES["world"][0], **kw,
+                                    rx_seeds=tuple(1000 * rx + t for rx in range(len(rules)))))
+        for rx in (rx for rx in range(len(rules)) if found[rx] is None):
+            sub = receiver_scene(s, rx)
+            n, Sx, Cx = S.fix_literal(sub["eph"], sub["first"], sub["abs_sample"],
+                                      sub["rx_first"], sub["cfg"])
+            if (n == sub["cfg"]["max_meas"]).all() and not Sx["status"].any() and \
+                    Cx["used"].all() and S.conditions_hold(sub, full_rank=True) and \
+                    all(rules[rx](la, lo) for la, lo in zip(Sx["lat"][0], Sx["lon"][0])):
+                found[rx] = 1000 * rx + t
+        if None not in found:
+            break
+    return tuple(found)
+
+
 if __name__ == "__main__":
-    for g, v in measure_spread().items():
+    import sys
+    world = sys.argv[1:] == ["world"]
+    for g, v in (measure_spread(tuple(WORLD_SCENES)) if world else measure_spread()).items():
         print(f'"{g}": {v:.3e},')

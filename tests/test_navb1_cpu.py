@@ -11,6 +11,7 @@ import pytest
 import navb1_scenarios as S
 
 ALL = tuple(S.SCENES) + ("many",)
+WORLD = tuple(S.WORLD_SCENES)
 EXACT_SOL, EXACT_CHAN = ("status", "n_used", "written"), ("used", "rawP")
 
 
@@ -59,9 +60,10 @@ def test_field_mutants_change_the_record(mutant):
     assert all((a[k] == b[k]).all() for k in S.EPH.names if k != field)
 
 
-@pytest.mark.parametrize("name", ALL)
+@pytest.mark.parametrize("name", ALL + WORLD)
 def test_literal_equals_fast(name):
     s = S._scene(name)
+    tol = S.TOL_WORLD if name in WORLD else S.TOL
     n_l, Sl, Cl = S.literal_result(name)
     n_f, Sf, Cf = S.fix_fast(s["eph"], s["first"], s["abs_sample"], s["rx_first"], s["cfg"])
     assert n_l.tolist() == n_f.tolist()
@@ -71,15 +73,15 @@ def test_literal_equals_fast(name):
         assert np.asarray(Cl[k], np.float64).tobytes() == np.asarray(Cf[k], np.float64).tobytes(), k
     for g in S.GROUPS:
         dist = S.group_distance((Sl, Cl), (Sf, Cf), g)
-        assert dist <= S.TOL[g], (name, g, dist, S.TOL[g])
+        assert dist <= tol[g], (name, g, dist, tol[g])
 
 
-@pytest.mark.parametrize("name", ALL)
+@pytest.mark.parametrize("name", ALL + WORLD)
 def test_scene_conditions(name):
     """cond(A) < 1e6 and GDOP < 6 wherever a receiver is solved, on every scene a tolerance is
     measured on; no Kepler or togeod exit within a factor 4 of its threshold"""
     s = S._scene(name)
-    full = S.SCENES[name][1] if name in S.SCENES else True
+    full = S.SCENES[name][1] if name in S.SCENES else True     # WORLD_SCENES: all full rank
     d = S.scene_diagnostics(s)
     assert S.conditions_hold(s, full_rank=full), {k: (v.min(), v.max()) for k, v in d.items()
                                                    if len(v)}
@@ -203,3 +205,103 @@ def test_struct_sizes_and_field_names_match_the_library(gc):
     for fn in ("ephemeris", "fix"):
         assert hasattr(gc.lib(), f"gnsscorr_nav_b1_{fn}_dev") and hasattr(gc.lib(), f"gnsscorr_nav_b1_{fn}")
     assert hasattr(gc.lib(), "gnsscorr_nav_b1_fix_cfg_init")
+
+
+# ------------------------------------------------------------------ the scenes of WORLD_SCENES
+@pytest.mark.parametrize("name", WORLD)
+def test_world_scenes_show_what_they_are_named_for(name):
+    """every receiver solved at every measurement and no check_t wrap; world: each receiver's
+    solved latitude and longitude in its site's class, both sides of both meridians; eccentric: every Kepler
+    loop ran its 10 steps and left by the cap with |dE| > 4e-12; geo: three GEO-like orbits
+    (sqrtA near 6493.4, i_0 below 0.1 rad, e below 0.001) beside MEO and IGSO ones, seen from
+    near (20 N, 110 E) with GDOP below 5"""
+    s = S.fix_scene(name)
+    assert S.named_for_missed(name, s) == []
+    d = S.scene_diagnostics(s)
+    n_calls = int(s["rx_first"][-1]) * s["cfg"]["max_meas"]
+    assert len(d["tk"]) == len(d["kepler"]) == n_calls
+    if name == "world":
+        n, Sx, Cx = S.literal_result(name)
+        assert len(n) == len(S.G.SITES) == 11 and s["sizes"] == S.G.WORLD_SIZES
+        assert (Sx["Z"] < 0).sum() >= 2 * 5 and (Sx["X"] < 0).any() and (Sx["Y"] > 0).any()
+    if name == "eccentric":
+        assert d["kepler"][:, 0].sum() == 10 * n_calls and (d["kepler"][:, 1] > 4e-12).all()
+        assert (s["eph"]["e"] >= 0.1).all() and (s["eph"]["e"] < 0.25).all()
+    if name == "geo":
+        n, Sx, Cx = S.literal_result(name)
+        assert abs(Sx["lat"][0, 0] - 20) < 2.5 and abs(Sx["lon"][0, 0] - 110) < 2.5
+        assert (np.abs(s["eph"]["sqrtA"][:3] - 6493.4) < 0.5).all() and (d["gdop"] < 5).all()
+        assert (np.abs(s["eph"]["i_0"][:3]) < 0.1).all() and (s["eph"]["e"][:3] < 0.001).all()
+        assert (Cx["el"][:3] > 18).all()                       # high in the sky, and used
+
+
+def test_world_tolerances_are_the_measured_spread_times_16():
+    got = S.measure_spread(WORLD)
+    print(got)
+    for g, v in got.items():
+        assert v <= S.SPREAD_WORLD[g] * 1.001, (g, v)          # the constants are what is measured
+        assert v >= S.SPREAD_WORLD[g] * 0.5, (g, v)
+        assert S.TOL_WORLD[g] == 16 * S.SPREAD_WORLD[g]
+
+
+def _xyz_move(name, mutant):
+    n0, S0, C0 = S.literal_result(name)
+    n1, S1, C1 = S.literal_result(name, mutant=mutant)
+    assert not S0["status"].any() and not S1["status"].any() and S0["written"].all()
+    return np.max([np.abs(S1[k] - S0[k]) for k in "XYZ"], axis=0)
+
+
+def test_kepler_cap_mutant_moves_the_eccentric_scene():
+    """20 steps in place of 10 move X Y Z of every measurement by more than 100 tolerances"""
+    move = _xyz_move("eccentric", "kepler_20")
+    print(move, 100 * S.TOL_WORLD["xyz"])
+    assert (move > 100 * S.TOL_WORLD["xyz"]).all()
+
+
+def test_check_t_mutant_moves_the_week_scenes():
+    """the week scenes of SCENES catch a check_t that returns its argument: X Y Z of every
+    measurement by more than 100 tolerances"""
+    for name in ("week_start", "week_end"):
+        move = _xyz_move(name, "check_t_identity")
+        print(name, move, 100 * S.TOL["xyz"])
+        assert (move > 100 * S.TOL["xyz"]).all()
+
+
+@pytest.mark.parametrize("mutant", ["kepler_20", "check_t_identity"] + list(S.GEO_MUTANTS))
+@pytest.mark.parametrize("name", ALL)
+def test_world_mutants_leave_every_earlier_scene_as_it_was(name, mutant):
+    """bit for bit, but for check_t in the two week scenes: no other scene of SCENES, and not
+    many_rx_scene, reaches what these mutants change"""
+    if mutant == "check_t_identity" and name.startswith("week"):
+        return
+    a, b = S.literal_result(name), S.literal_result(name, mutant=mutant)
+    assert a[0].tolist() == b[0].tolist()
+    ra, rb = S.as_records(*a), S.as_records(*b)
+    assert ra[0].tobytes() == rb[0].tobytes() and ra[1].tobytes() == rb[1].tobytes()
+
+
+# mutant: (the outputs that must move, their tolerance group, which receivers: sign of Z or X)
+GEO_MUTANTS = {"togeod_abs_z": (("el", "az"), "elaz", "Z"), "cart2geo_abs_z": (("lat",), "latlon", "Z"),
+               "cart2geo_atan_y_over_x": (("lon",), "latlon", "X")}
+
+
+@pytest.mark.parametrize("mutant", GEO_MUTANTS)
+def test_geo_mutants_move_the_world_scene(mutant):
+    """fabs(Z) in togeod and in cart2geo and atan(Y / X) for the longitude move the named
+    outputs of every measurement of the receivers they concern, the southern ones and those
+    with X < 0, by more than 100 tolerances, and no output of any other receiver"""
+    keys, group, axis = GEO_MUTANTS[mutant]
+    s = S.fix_scene("world")
+    n0, S0, C0 = S.literal_result("world")
+    n1, S1, C1 = S.literal_result("world", mutant=mutant)
+    assert not S0["status"].any() and not S1["status"].any()   # no mask: nothing drops out
+    if keys[0] in C0:
+        per_ch = np.max([np.abs(C1[k] - C0[k]) for k in keys], axis=0)
+        move = np.array([per_ch[a:b].max(axis=0) for a, b in zip(s["rx_first"], s["rx_first"][1:])])
+    else:
+        move = np.max([np.abs(S1[k] - S0[k]) for k in keys], axis=0)
+    hit = S0[axis] < 0
+    print(mutant, move[hit].min(), 100 * S.TOL_WORLD[group])
+    assert hit.any() and (~hit).any()
+    assert (move[hit] > 100 * S.TOL_WORLD[group]).all(), (mutant, move[hit].min())
+    assert not move[~hit].any(), (mutant, move[~hit].max())

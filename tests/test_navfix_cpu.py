@@ -9,6 +9,7 @@ import pytest
 import navfix_scenarios as S
 
 ALL = tuple(S.SCENES) + ("many",)
+WORLD = tuple(S.WORLD_SCENES)
 MULTI = tuple(k for k, (_, multi) in S.SCENES.items() if multi)
 
 
@@ -37,7 +38,7 @@ def test_field_decode_literal_equals_fast_and_what_was_planted(n_ch):
         assert set(neg) == set(S.SIGNED)                       # every signed field went negative
 
 
-@pytest.mark.parametrize("name", ALL)
+@pytest.mark.parametrize("name", ALL + WORLD)
 def test_fix_literal_equals_fast(name):
     s = _scene(name)
     n1, S1, C1 = S.literal_result(name)
@@ -47,7 +48,7 @@ def test_fix_literal_equals_fast(name):
     assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
 
 
-@pytest.mark.parametrize("name", ALL)
+@pytest.mark.parametrize("name", ALL + WORLD)
 def test_scene_conditions(name):
     """cond(A) < 1e6 and GDOP < 6 where a receiver is full rank; no elevation within 1e-6
     degrees of the mask; no Kepler step and no togeod exit within a factor 4 of its threshold"""
@@ -131,3 +132,113 @@ def test_first_iteration_troposphere_constant_discriminates():
     print(move)
     assert (move > 100 * S.TOL["dt"]).all()
     assert abs(move[0] - 2.0) < 1e-6
+
+
+# ------------------------------------------------------------------ the scenes of WORLD_SCENES
+@pytest.mark.parametrize("name", WORLD)
+def test_world_scenes_show_what_they_are_named_for(name):
+    """every receiver solved at every measurement; world: each receiver's solved latitude and
+    longitude in its site's class; week_end / week_start: check_t moved every used channel's
+    time - t_oe by a week, down / up, and nowhere else; eccentric: every Kepler loop ran its 10
+    steps and left by the cap with |dE| > 4e-12; inclined: i_0 below 0.6 and above 1.2 rad"""
+    s = S.fix_scene(name)
+    assert S.named_for_missed(name, s) == []
+    d = S.scene_diagnostics(s)
+    n_calls = int(s["rx_first"][-1]) * s["cfg"]["max_meas"]
+    assert len(d["tk"]) == len(d["kepler"]) == n_calls
+    if name == "world":
+        n, Sx, Cx = S.literal_result(name)
+        assert len(n) == len(S.SITES) == 11 and s["sizes"] == S.WORLD_SIZES
+        assert (Sx["Z"] < 0).sum() >= 2 * 5 and (Sx["X"] < 0).any() and (Sx["Y"] > 0).any()
+        for k in ("meridian_180", "meridian_0"):               # both sides of both meridians
+            i = list(S.SITES).index(k + "_east")
+            assert Sx["lon"][i, 0] * Sx["lon"][i - 1 if k == "meridian_0" else i + 1, 0] < 0
+    if name.startswith("week"):
+        tow = int(s["eph"]["TOW"][0])
+        assert (tow > S.WEEK - 900 and tow + 1 < S.WEEK) if name == "week_end" else 0 < tow < 900
+        assert (s["eph"]["t_oe"] == (0 if name == "week_end" else 597600)).all()
+        assert (s["eph"]["t_oc"] == s["eph"]["t_oe"]).all()
+        assert (np.abs(d["tk"][:, 1] - d["tk"][:, 0]) == S.WEEK).all()
+    if name == "eccentric":
+        assert d["kepler"][:, 0].sum() == 10 * n_calls and (d["kepler"][:, 1] > 4e-12).all()
+        assert (s["eph"]["e"] >= 0.1).all() and (s["eph"]["e"] <= 0.3).all()
+
+
+def test_planted_position_is_recovered_at_the_week_edges():
+    """troposphere off in both.  Seven iterations with rows divided by obs stop a geometry's
+    own distance short (printed: 2.5e-2 m at the end, 1.1e-3 m at the start), so the check runs
+    the same restatement to 14 iterations, where only the planting's rounding is left: 8e-6 m.
+    The bound is 1e-4 m, ten times the 1e-5 m a float64 probe of the scene's kind recovered; a
+    week lost in tk moves the satellites by thousands of kilometres."""
+    for name in ("week_end", "week_start"):
+        s = S.fix_scene(name)
+        for n_iter in (7, 14):
+            n, Sx, Cx = S.fix_literal(s["eph"], s["first"], s["abs_sample"], s["rx_first"],
+                                      s["cfg"], n_iter=n_iter)
+            err = [float(np.linalg.norm(np.array([Sx[k][0, m] for k in "XYZ"]) - s["planted"][0]))
+                   for m in range(n[0])]
+            print(name, n_iter, "iterations: planted position recovered to", err, "m")
+        assert len(err) == 2 and max(err) < 1e-4
+
+
+def test_world_tolerances_are_the_measured_spread_times_16():
+    got = S.measure_spread(WORLD)
+    print(got)
+    for g, v in got.items():
+        assert v <= S.SPREAD_WORLD[g] * 1.001, (g, v)          # the constants are what is measured
+        assert v >= S.SPREAD_WORLD[g] * 0.5, (g, v)
+        assert S.TOL_WORLD[g] == 16 * S.SPREAD_WORLD[g]
+
+
+def _world_move(name, mutant, keys):
+    """|mutant - restatement| per receiver and measurement [n_rx, max_meas], the largest over
+    keys (sol) or over keys and the receiver's channels (chan); infinite where the mutant has no
+    value (fabs(Z) in togeod turns the southern sky over: satellites fall below the mask)"""
+    s = S.fix_scene(name)
+    n0, S0, C0 = S.literal_result(name)
+    n1, S1, C1 = S.literal_result(name, mutant=mutant)
+    assert not S0["status"].any()
+    far = lambda x, y: np.nan_to_num(np.abs(x - y), nan=np.inf)   # a value gone: moved
+    if keys[0] in C0:
+        per_ch = np.max([far(C1[k], C0[k]) for k in keys], axis=0)
+        return np.array([per_ch[a:b].max(axis=0) for a, b in zip(s["rx_first"], s["rx_first"][1:])])
+    return np.max([far(S1[k], S0[k]) for k in keys], axis=0)
+
+
+# mutant: (its scenes, the outputs that must move, their tolerance group)
+WORLD_MUTANTS = {
+    "check_t_identity": (("week_end", "week_start"), ("X", "Y", "Z"), "xyz"),
+    "kepler_20": (("eccentric",), ("X", "Y", "Z"), "xyz"),
+    "togeod_abs_z": (("world",), ("el", "az"), "elaz"),
+    "cart2geo_abs_z": (("world",), ("lat",), "latlon"),
+    "cart2geo_atan_y_over_x": (("world",), ("lon",), "latlon"),
+}
+
+
+@pytest.mark.parametrize("mutant", WORLD_MUTANTS)
+def test_world_mutants_move_the_scene_named_for_them(mutant):
+    """each mistake that only the new scenes reach moves the named outputs of every solved
+    measurement by more than 100 tolerances; in the world scene of the receivers it concerns,
+    the southern ones for fabs(Z) and those with X < 0 for atan(Y / X), and of no other"""
+    scenes, keys, group = WORLD_MUTANTS[mutant]
+    for name in scenes:
+        move = _world_move(name, mutant, keys)
+        print(mutant, name, move.min(), move.max(), 100 * S.TOL_WORLD[group])
+        if name != "world":
+            assert (move > 100 * S.TOL_WORLD[group]).all(), (mutant, name, move.min())
+            continue
+        n, Sx, Cx = S.literal_result(name)
+        hit = (Sx["X"] < 0) if mutant == "cart2geo_atan_y_over_x" else (Sx["Z"] < 0)
+        assert hit.any() and (~hit).any()
+        assert (move[hit] > 100 * S.TOL_WORLD[group]).all(), (mutant, move[hit].min())
+        assert not move[~hit].any(), (mutant, move[~hit].max())
+
+
+@pytest.mark.parametrize("mutant", WORLD_MUTANTS)
+@pytest.mark.parametrize("name", ALL)
+def test_world_mutants_leave_every_earlier_scene_as_it_was(name, mutant):
+    """bit for bit: what these mutants change, no scene of SCENES and not many_rx_scene reaches"""
+    a = S.as_records(*S.literal_result(name))
+    b = S.as_records(*S.literal_result(name, mutant=mutant))
+    assert S.literal_result(name)[0].tolist() == S.literal_result(name, mutant=mutant)[0].tolist()
+    assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()

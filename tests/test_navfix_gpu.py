@@ -44,10 +44,11 @@ def _fix_dev(gc, nav, s, in_place=False):
     return fix_dev(gc, nav, s, launch, in_place)
 
 
-def _check_fix(name, s, n_meas, sol, chan, p_sol, p_chan):
+def _check_fix(name, s, n_meas, sol, chan, p_sol, p_chan, tol=None):
     w_n, Sx, Cx = S.literal_result(name)
     want_sol, want_chan = S.as_records(w_n, Sx, Cx, p_sol, p_chan)
-    check_records(S, name, (w_n, want_sol, want_chan, Sx["written"]), n_meas, sol, chan, p_sol)
+    check_records(S, name, (w_n, want_sol, want_chan, Sx["written"]), n_meas, sol, chan, p_sol,
+                  tol)
 
 
 @pytest.mark.parametrize("name", tuple(S.SCENES) + ("many",))
@@ -59,6 +60,27 @@ def test_fix_equals_the_literal_restatement(gpu, name):
     s = S.many_rx_scene() if name == "many" else S.fix_scene(name)
     nav = gpu.NavCtx()
     _check_fix(name, s, *_fix_dev(gpu, nav, s))
+
+
+@pytest.mark.parametrize("name", tuple(S.WORLD_SCENES))
+def test_fix_equals_the_literal_restatement_on_the_world_scenes(gpu, name):
+    """11 receivers in one launch in every quadrant, south of the equator, on either side of
+    the 0 and 180 degree meridians, at the equator and above 80 degrees north and south; TOW
+    in the week's last and first minutes with check_t wrapping either way; Kepler loops that
+    run all 10 steps at e from 0.1 to 0.3; inclinations from 0.3 to 1.4 rad.  Held to
+    TOL_WORLD, measured on these scenes alone; poisoned outputs, padded strides; in the world
+    scene the host twin gives the device form's bytes."""
+    s = S.fix_scene(name)
+    nav = gpu.NavCtx()
+    n_meas, sol, chan, p_sol, p_chan = _fix_dev(gpu, nav, s)
+    _check_fix(name, s, n_meas, sol, chan, p_sol, p_chan, S.TOL_WORLD)
+    assert not sol["status"].any() and chan["used"].all()
+    if name == "world":
+        h_n, h_sol, h_chan = nav.gps_fix(s["eph"], s["first"], s["abs_sample"], s["rx_first"],
+                                         gpu.gps_fix_cfg(**s["cfg"]), sol=p_sol.copy(),
+                                         chan=p_chan.copy())
+        assert h_n.tobytes() == n_meas.tobytes()
+        assert h_sol.tobytes() == sol.tobytes() and h_chan.tobytes() == chan.tobytes()
 
 
 def test_absolute_sample_is_read_in_place_from_epoch_records(gpu):

@@ -11,6 +11,7 @@ import pytest
 import navglo_scenarios as S
 
 ALL = tuple(S.SCENES) + ("many",)
+WORLD = tuple(S.WORLD_SCENES)
 MULTI = tuple(k for k, (_, multi) in S.SCENES.items() if multi)
 
 
@@ -78,7 +79,7 @@ def test_integration_follows_the_orbit():
     assert (S.sat_literal(700)["deltat"] == 0).any()
 
 
-@pytest.mark.parametrize("name", ALL)
+@pytest.mark.parametrize("name", ALL + WORLD)
 def test_scene_conditions(name):
     """cond(A) < 1e6 and GDOP < 6 where a receiver is full rank; no elevation within 1e-6
     degrees of the mask; no togeod exit within a factor 4 of its threshold"""
@@ -214,3 +215,62 @@ def test_struct_sizes_and_field_names_match_the_library(gc):
     assert ctypes.sizeof(gc.GloEph) == 216 and ctypes.sizeof(gc.GloFixCfg) == 48
     for fn in ("ephemeris", "satpos", "fix"):
         assert hasattr(gc.lib(), f"gnsscorr_nav_glo_{fn}_dev") and hasattr(gc.lib(), f"gnsscorr_nav_glo_{fn}")
+
+
+# ------------------------------------------------------------------ the world scene
+def test_world_scene_shows_every_site_class():
+    """every receiver solved at both measurements with every channel used, its solved
+    latitude and longitude in its site's class; both sides of both meridians"""
+    s = S.fix_scene("world")
+    assert S.named_for_missed("world", s) == []
+    n, Sx, Cx = S.literal_result("world")
+    assert len(n) == len(S.G.SITES) == 11 and s["sizes"] == S.G.WORLD_SIZES
+    assert (Sx["Z"] < 0).sum() >= 2 * 5 and (Sx["X"] < 0).any() and (Sx["Y"] > 0).any()
+
+
+def test_world_tolerances_are_the_measured_spread_times_16():
+    got = S.measure_spread(WORLD, ())
+    print(got)
+    for g, v in got.items():
+        assert v <= S.SPREAD_WORLD[g] * 1.001, (g, v)          # the constants are what is measured
+        assert v >= S.SPREAD_WORLD[g] * 0.5, (g, v)
+        assert S.TOL_WORLD[g] == 16 * S.SPREAD_WORLD[g]
+
+
+# mutant: (the outputs that must move, their tolerance group, which receivers: sign of Z or X)
+GEO_MUTANTS = {"togeod_abs_z": (("el", "az"), "elaz", "Z"), "cart2geo_abs_z": (("lat",), "latlon", "Z"),
+               "cart2geo_atan_y_over_x": (("lon",), "latlon", "X")}
+
+
+@pytest.mark.parametrize("mutant", GEO_MUTANTS)
+def test_geo_mutants_move_the_world_scene(mutant):
+    """fabs(Z) in togeod and in cart2geo and atan(Y / X) for the longitude move the named
+    outputs of every measurement of the receivers they concern, the southern ones and those
+    with X < 0, by more than 100 tolerances (a satellite that falls below the mask counts as
+    moved), and no output of any other receiver"""
+    keys, group, axis = GEO_MUTANTS[mutant]
+    s = S.fix_scene("world")
+    n0, S0, C0 = S.literal_result("world")
+    n1, S1, C1 = S.literal_result("world", mutant=mutant)
+    assert not S0["status"].any()
+    far = lambda x, y: np.nan_to_num(np.abs(x - y), nan=np.inf)
+    if keys[0] in C0:
+        per_ch = np.max([far(C1[k], C0[k]) for k in keys], axis=0)
+        move = np.array([per_ch[a:b].max(axis=0) for a, b in zip(s["rx_first"], s["rx_first"][1:])])
+    else:
+        move = np.max([far(S1[k], S0[k]) for k in keys], axis=0)
+    hit = S0[axis] < 0
+    print(mutant, move[hit].min(), 100 * S.TOL_WORLD[group])
+    assert hit.any() and (~hit).any()
+    assert (move[hit] > 100 * S.TOL_WORLD[group]).all(), (mutant, move[hit].min())
+    assert not move[~hit].any(), (mutant, move[~hit].max())
+
+
+@pytest.mark.parametrize("mutant", GEO_MUTANTS)
+@pytest.mark.parametrize("name", ALL)
+def test_geo_mutants_leave_every_earlier_scene_as_it_was(name, mutant):
+    """bit for bit: no scene of SCENES and not many_rx_scene reaches what they change"""
+    a, b = S.literal_result(name), S.literal_result(name, mutant=mutant)
+    assert a[0].tolist() == b[0].tolist()
+    ra, rb = S.G.as_records(*a), S.G.as_records(*b)
+    assert ra[0].tobytes() == rb[0].tobytes() and ra[1].tobytes() == rb[1].tobytes()
